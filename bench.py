@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- frames/sec of the ORB extract + match front-end on N MI355X (one process per GPU).
 
-    python bench.py                                   # N=1, all three workloads, a few minutes
+    python bench.py --gpus 1 --steps K --warmup W     # the headline figure only: set up, warm up, K timed steps
+    python bench.py --full                            # N=1, every workload, host inputs, roofline, CPU baseline: minutes
     python bench.py --gpus N --steps K --warmup W     # N>1 without a launcher: spawns torch.distributed.run itself
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W     # the driver's form
+    python bench.py --steps K --dump-outputs DIR      # + what the last timed step delivered, as DIR/<name>.npy
 
 A "step" = one pass of the hot path over one batch of synthetic frames per rank: `--batch` images go through
 extraction (pyramid, FAST+NMS per cell, quadtree, orientation, blur, rBRIEF) and every frame is matched (mono:
@@ -16,12 +18,16 @@ step (mono workload, N>1: vslam_exchange_ring = ncclSend/ncclRecv on the extract
 Rank 0 prints ONE JSON line on stdout:
   value                = headline workload (BASELINE configs[1], KITTI-00 mono 1241x376, 1000 features), input frames
                          resident in HBM when the timed region starts (the contract's definition of `value`)
+  ms_per_step          = milliseconds of one timed step; the timed region is exactly K = --steps steps, after at least
+                         W = --warmup untimed steps that last 0.5 s or more (Pipeline.warm_up)
+With --full, beside it:
   value_host_inputs    = the same workload with the frames in pinned HOST memory: H2D over PCIe inside the timed
                          region (SURVEY.md 8(d): the span frame.cpp:103-116 + :124-132 starts from a host cv::Mat)
   extra_workloads[]    = KITTI-00 stereo N=2000 (north_star's >=5x target) and 1920x1080 stereo N=4000, each with its
                          own value / value_host_inputs / roofline / cpu_baseline
-The timed region is K steps repeated R times back to back (R chosen so that it lasts >= --min-seconds; `timed_repeats`).
-A second JSON line with per-stage details goes to STDERR.
+  roofline, roofline_pcie, cpu_baseline, and for N>1 the exchange alone and its GPU-side proof
+and every timed region is K steps repeated R times back to back (R chosen so that it lasts >= --min-seconds;
+`timed_repeats`).  A second JSON line with per-stage details goes to STDERR.
 """
 import argparse
 import json
@@ -55,7 +61,7 @@ WORKLOADS = {
     "kitti00_stereo_1241x376_n2000": dict(w=1241, h=376, nf=2000, stereo=True),
     # configs[4]: synthetic 1920x1080 stream, 4000 features/frame
     "synthetic_stereo_1920x1080_n4000": dict(w=1920, h=1080, nf=4000, stereo=True),
-    # SURVEY.md 8(d) "real-image sanity point": the reference's own hut_stereo PNGs (752x480; tests/golden/real_images.npz),
+    # SURVEY.md 8(d) "real-image sanity point": the reference's own hut_stereo PNGs (752x480; tests/golden/real_images*.npz),
     # pairs (01,02) (03,04) (04,05) cycled; fx from hut_stereo.json, the baseline is a bench parameter
     "hut_stereo_752x480_n1200_real": dict(w=752, h=480, nf=1200, stereo=True, real="hut", bf=822.5 * 0.4, fx=822.5),
     # SURVEY.md 8(f) rank 1, the per-frame tracking front-end of TrackWithMotionModel: stereo frame construction +
@@ -69,6 +75,7 @@ EXTRAS = ["kitti00_mono_1241x376_n2000", "kitti00_stereo_1241x376_n2000", "synth
 BF, FX = 386.1448, 718.856  # config/KITTI00-Stereo.yaml Camera.bf, Camera.fx
 FY, CX, CY = 718.856, 607.1928, 185.2157
 TRACK_Z = 12.0  # the synthetic scene moves (+3,+1) px per frame; as a camera translation at this depth
+WARMUP_SECONDS = 0.5  # shortest warm-up before an exactly --steps long region (Pipeline.warm_up)
 KERNEL_OF = {"pyramid": "k_pyramid", "fast": "k_fast_cells_v3", "blur": "k_blur7_v2", "describe": "k_orient_describe_dev"}
 PROF_KEY = {"pyramid": "pyramid_ms", "fast": "fast_ms", "blur": "blur_ms", "describe": "describe_ms"}
 
@@ -104,9 +111,11 @@ def self_launch(args):
 
 
 def real_frames(cfg):
-    """the hut_stereo frames as L,R,L,R,... (three pairs; the generator of the fixture is tests/golden/make_golden.py)"""
+    """the hut_stereo frames as L,R,L,R,... (three pairs; the generator of the fixtures is tests/golden/make_golden.py)"""
     import numpy as np
-    z = np.load(os.path.join(ROOT, "tests", "golden", "real_images.npz"))
+    z = {}
+    for f in ("real_images.npz", "real_images_hut4_5.npz"):
+        z.update(np.load(os.path.join(ROOT, "tests", "golden", f)))
     out = []
     for a, b in (("hut1", "hut2"), ("hut3", "hut4"), ("hut4", "hut5")):
         out += [np.ascontiguousarray(z[a]), np.ascontiguousarray(z[b])]
@@ -344,6 +353,7 @@ class Pipeline:
         self.state = {"matches": 0}
         self.stamps = None  # timed(): host time at which every step's results were delivered
         self.step_trace = None
+        self.last = None  # collect(): (step, features, stereo, matcher outputs) of the last step delivered
         self.job_cache = {}
         self.track_Twc = [np.hstack([np.eye(3), np.zeros((3, 1))]).astype(np.float32)] * (B // 2)
         self.track_cam = (CX, CY, float(np.float32(1.0) / np.float32(FX)), float(np.float32(1.0) / np.float32(FY)))
@@ -494,6 +504,7 @@ class Pipeline:
         st, B = self.state, self.B
         c = self.ctxs[t % self.NCTX]
         t_a = time.perf_counter()
+        out = []
         if self.stereo:
             feats, stv = c.frame_stereo_wait()
             st["matches"] = sum(int((u >= 0).sum()) for u, _ in stv)
@@ -504,12 +515,14 @@ class Pipeline:
                 out = self.matchers[t % self.NCTX].search_by_projection_dev_wait(ncur)
                 st["track_matches"] = sum(o[0] for o in out)
         else:
-            c.wait()
+            feats, stv = c.wait(), None
             t_b = time.perf_counter()
             nj = st["njobs"].pop(t)
             if nj:
                 out = self.matchers[t % self.NCTX].search_init_dev_wait([self.fe.cap] * nj)
                 st["matches"] = sum(o[0] for o in out)
+        # what the step delivered (views into the context's staging, valid until its next wait): --dump-outputs
+        self.last = (t, feats, stv, out)
         hs = st.setdefault("host_s", [0.0, 0.0])
         hs[0] += t_b - t_a
         hs[1] += time.perf_counter() - t_b
@@ -591,45 +604,61 @@ class Pipeline:
         return res
 
     # -------------------------------------------------------------------------------------------- timing
-    def timed(self, steps, warmup, min_seconds):
-        """W warmup steps, then R x K steps bracketed by barrier + synchronize; max over ranks.  R is agreed by all ranks
-        BEFORE the timed region (every rank must issue the same number of exchanges)."""
-        env = self.env
+    def warm_up(self, warmup):
+        """At least `warmup` untimed steps, then more in blocks until the warm-up has lasted WARMUP_SECONDS: a GPU that comes
+        out of the set-up idle runs its first steps slowly (5 warmup steps alone left 20 timed mono steps at 0.92 instead of
+        0.16 ms each; 20 left 4 ms of 495 in a region of 3000 steps).  All ranks agree on every further block (exchanges)."""
+        t_end = time.perf_counter() + WARMUP_SECONDS
         self.run(max(warmup, 1))
-        self.run(steps)  # first calibration block: still warming up (first DMA copies, clocks) -- not used
-        self.torch.cuda.synchronize()
-        env["barrier"]()
-        t0 = time.perf_counter()
-        self.run(steps)  # second calibration block, untimed but clocked: how many repeats make min_seconds
-        self.torch.cuda.synchronize()
-        block = env["max_over_ranks"](time.perf_counter() - t0)
-        reps = max(1, min(int(math.ceil(1.25 * min_seconds / max(block, 1e-6))), 100000 // max(steps, 1) + 1))
+        while self.env["max_over_ranks"](1.0 if time.perf_counter() < t_end else 0.0) > 0:
+            self.run(50)
+
+    def timed(self, steps, warmup, min_seconds, profile=False, outputs=False):
+        """W warmup steps, then the timed region bracketed by barrier + synchronize; max over ranks.  min_seconds = 0: the
+        region is exactly K = `steps` steps.  min_seconds > 0 (--full): R x K steps, R measured on calibration blocks and
+        agreed by all ranks BEFORE the region (every rank must issue the same number of exchanges).  profile: per-stage
+        event spans from a run of their own after the region.  outputs: what the region's last step delivered
+        (last_outputs)."""
+        env = self.env
+        import gc
+        gc_was = gc.isenabled()
+        reps = 1
+        if min_seconds > 0:
+            self.run(max(warmup, 1))
+            self.run(steps)  # first calibration block: still warming up (first DMA copies, clocks) -- not used
+            self.torch.cuda.synchronize()
+            env["barrier"]()
+            t0 = time.perf_counter()
+            self.run(steps)  # second calibration block, untimed but clocked: how many repeats make min_seconds
+            self.torch.cuda.synchronize()
+            block = env["max_over_ranks"](time.perf_counter() - t0)
+            reps = max(1, min(int(math.ceil(1.25 * min_seconds / max(block, 1e-6))), 100000 // max(steps, 1) + 1))
+        # The harness is Python; the product's host side is C++.  A collection of the cyclic garbage collector inside the
+        # timed region stalls the one host thread for a few hundred microseconds -- two or three steps' worth -- which is what
+        # the blocks well below the median were (DESIGN section 7); the collector is switched off for the region (--gc keeps it)
+        if not self.args.gc:
+            gc.collect()
+            gc.disable()
+        # the collection above left the GPU idle for tens of milliseconds; the first blocks of the region then ran 10-13 %
+        # below the rest (profiles/r04_slow_blocks.txt): fill the pipeline, untimed, before the bracket (the warmup steps
+        # themselves when there is no calibration)
+        if min_seconds > 0:
+            self.run(steps)
+        else:
+            self.warm_up(warmup)
         for k in ("host_s", "enq_s"):
             self.state.pop(k, None)
         env["barrier"]()
         self.stamps = []
         self.step_trace = [] if self.args.stamp_dump else None
         sent0 = [c.delivery_stats() for c in self.ctxs]
-        # The harness is Python; the product's host side is C++.  A collection of the cyclic garbage collector inside the
-        # timed region stalls the one host thread for a few hundred microseconds -- two or three steps' worth -- which is what
-        # the blocks well below the median were (DESIGN section 7); the collector is switched off for the region (--gc keeps it)
-        import gc
-        gc_was = gc.isenabled()
-        if not self.args.gc:
-            gc.collect()
-            gc.disable()
-            # the collection above left the GPU idle for tens of milliseconds; the first blocks of the region then ran 10-13 %
-            # below the rest (profiles/r04_slow_blocks.txt): refill the pipeline, untimed, before the bracket
-            self.stamps = None
-            self.run(steps)
-            env["barrier"]()
-            self.stamps = []
         t0 = time.perf_counter()
         self.run(steps * reps)  # the timed region: the product path as a caller runs it (no per-stage events)
         env["barrier"]()
         dt = env["max_over_ranks"](time.perf_counter() - t0)
         if gc_was:
             gc.enable()
+        delivered = self.last_outputs() if outputs else None
         if self.step_trace is not None:
             with open("%s.%s.%s.json" % (self.args.stamp_dump, self.name, "pinned" if self.where == self.V.IMGS_PINNED else "device"), "w") as f:
                 json.dump({"workload": self.name, "steps": steps, "reps": reps, "t0": t0, "dt": dt, "gc": bool(self.args.gc),
@@ -640,15 +669,16 @@ class Pipeline:
         host_times = {k: self.state.get(k) for k in ("host_s", "enq_s")}
         # per-stage event spans inside the pipeline: a short run of its own with the contexts' stage events switched on
         # (they cost launches of their own and keep the pass out of its captured graph), after the timed region
-        for c in self.ctxs:
-            c.set_profiling(True)
-        self.run(steps * min(reps, 10))
-        self.torch.cuda.synchronize()
         prof = {}
-        for c in self.ctxs:
-            for k, v in c.get_profile().items():
-                prof[k] = prof.get(k, 0) + v
-            c.set_profiling(False)
+        if profile:
+            for c in self.ctxs:
+                c.set_profiling(True)
+            self.run(steps * min(reps, 10))
+            self.torch.cuda.synchronize()
+            for c in self.ctxs:
+                for k, v in c.get_profile().items():
+                    prof[k] = prof.get(k, 0) + v
+                c.set_profiling(False)
         for k, v in host_times.items():
             if v is not None:
                 self.state[k] = v
@@ -667,11 +697,48 @@ class Pipeline:
         spread = ({"min": blocks[0], "median": blocks[len(blocks) // 2], "max": blocks[-1], "blocks": len(blocks), "block_steps": bs}
                   if blocks else None)
         return {"value": frames_per_step * n / dt, "ms_per_step": dt / n * 1e3, "reps": reps, "seconds": dt, "prof": prof,
-                "spread": spread,
+                "spread": spread, "outputs": delivered,
                 # result deliveries of this rank's contexts: copy operations towards the host per step, and their bytes
                 "result_transfers_per_step": sum(a for a, _ in sent) / n, "result_bytes_per_step": sum(b for _, b in sent) / n,
                 "host_ms_per_step": {k: v / n * 1e3 for k, v in zip(("enqueue", "wait_step", "fetch_matches"),
                                                                    [self.state.get("enq_s", 0.0)] + self.state.get("host_s", [0, 0]))}}
+
+    def last_outputs(self):
+        """What the last collected step delivered to its caller, as float32 arrays (--dump-outputs): every image's keypoints
+        (x, y, size, angle, response, octave, class_id) and descriptors, concatenated in slot order, with the per-image counts;
+        mono: monoIndex and, per matcher job, SearchForInitialization's nmatches and vnMatches12 (over the predecessor's
+        keypoints); stereo: mvuRight / mvDepth of every left image; tracking: SearchByProjection's nmatches and matches."""
+        np, B = self.np, self.B
+        t, feats, stv, out = self.last
+        f32 = lambda a: np.asarray(a, np.float32)
+        counts = [len(f[0]) for f in feats]
+        res = {"keypoint_counts": f32(counts),
+               "keypoints": np.concatenate([np.stack([f[0][n].astype(np.float32) for n in f[0].dtype.names], 1) for f in feats]),
+               "descriptors": np.concatenate([f32(f[1]).reshape(-1, 32) for f in feats])}
+        if self.stereo:
+            res["u_right"] = np.concatenate([f32(u) for u, _ in stv])
+            res["depth"] = np.concatenate([f32(d) for _, d in stv])
+            if self.track:
+                res["track_nmatches"] = f32([o[0] for o in out])
+                res["track_matches"] = np.concatenate([f32(o[1]) for o in out] or [f32([])])
+            return res
+        res["mono_index"] = f32([f[2] for f in feats])
+        # job j matched query slot B - njobs + j (slot 0 has no job in a run's first step) against its predecessor
+        rank, world = self.env["rank"], self.env["world"]
+        m12 = []
+        for j, (_, m, _) in enumerate(out):
+            s = B - len(out) + j
+            _, ps, prev_step = self.vd.predecessor(rank, s, world, B)
+            if s > 0:
+                n1 = counts[ps]
+            else:  # the left neighbour's last frame, carried or exchanged: its count heads the packed slot
+                kk = (t - 1) % self.NCTX if prev_step else t % self.NCTX
+                buf = self.xchg.left_block(self.recv[kk]) if self.multi else self.carry[kk]
+                n1 = int(buf[:4].cpu().numpy().view(np.int32)[0])
+            m12.append(f32(m[:n1]))
+        res["init_nmatches"] = f32([o[0] for o in out])
+        res["init_matches12"] = np.concatenate(m12 or [f32([])])
+        return res
 
     def single_context_stage_ms(self, passes=30):
         """The extraction pass alone on the GPU (one context, device-resident frames, no matcher, nothing else in flight):
@@ -780,25 +847,30 @@ def link_probe(nbytes):
     return nbytes / (min(ts) * 1e-3) / 1e9
 
 
-def run_workload(name, args, env, want_cpu, cpu_seconds):
+def run_workload(name, args, env, want_cpu, cpu_seconds, headline):
+    """headline: the workload of the line's `value`; --dump-outputs writes what its main region (device inputs, unless
+    --inputs pinned) delivered last."""
     pl = Pipeline(name, args, env)
     try:
         inputs = args.inputs
         res = {}
-        if inputs in ("device", "both"):
-            pl.use_inputs("device")
-            res["device"] = pl.timed(args.steps, args.warmup, args.min_seconds)
-        if inputs in ("pinned", "both"):
-            pl.use_inputs("pinned")
-            res["pinned"] = pl.timed(args.steps, args.warmup, args.min_seconds)
+        main_mode = "device" if inputs in ("device", "both") else "pinned"
+        for mode in ("device", "pinned"):
+            if inputs in (mode, "both"):
+                pl.use_inputs(mode)
+                res[mode] = pl.timed(args.steps, args.warmup, args.min_seconds if args.full else 0.0,
+                                     profile=args.full and mode == main_mode,
+                                     outputs=headline and mode == main_mode and bool(args.dump_outputs))
         pl.use_inputs("device")
-        main = res.get("device") or res["pinned"]
+        main = res[main_mode]
+        if main["outputs"] is not None and env["rank"] == 0:
+            dump_outputs(args.dump_outputs, main["outputs"])
         out = {"workload": name, "value": main["value"] if "device" in res else None,
                "value_host_inputs": res["pinned"]["value"] if "pinned" in res else None,
                "ms_per_step": main["ms_per_step"], "timed_repeats": main["reps"], "timed_seconds": main["seconds"],
                "result_transfers_per_step": main["result_transfers_per_step"], "result_bytes_per_step": main["result_bytes_per_step"],
                "spread": main.get("spread"), "spread_host_inputs": res["pinned"].get("spread") if "pinned" in res else None}
-        if "pinned" in res and env["rank"] == 0:
+        if args.full and "pinned" in res and env["rank"] == 0:
             # the PCIe roofline of the host-input figure: image bytes that cross the link per second against what one
             # hipMemcpyAsync of a step's images achieves alone on this box, measured here
             img_bytes = pl.cfg["w"] * pl.cfg["h"] * (2 if pl.stereo else 1)
@@ -807,7 +879,7 @@ def run_workload(name, args, env, want_cpu, cpu_seconds):
             ach = res["pinned"]["value"] / env["world"] * img_bytes / 1e9
             out["roofline_pcie"] = {"bound": "pcie_h2d", "achieved": ach, "peak": peak, "unit": "GB/s", "frac": ach / peak,
                                     "bytes_per_frame": img_bytes, "peak_source": "best of 9 hipMemcpyAsync of one step's images from vslam_host_alloc memory, idle GPU, this run"}
-        if pl.multi:  # the exchange step alone: every rank enqueues the same 50 shifts of its last packed slot and waits once
+        if args.full and pl.multi:  # the exchange step alone: every rank enqueues the same 50 shifts of its last packed slot and waits once
             pl.torch.cuda.synchronize()
             env["barrier"]()
             t0 = time.perf_counter()
@@ -850,7 +922,7 @@ def run_workload(name, args, env, want_cpu, cpu_seconds):
                   "track_matches_last_step_rank0": pl.state.get("track_matches"),
                   "host_ms_per_step": main["host_ms_per_step"],
                   "ms_per_step_host_inputs": res["pinned"]["ms_per_step"] if "pinned" in res else None}
-        if env["rank"] == 0:
+        if args.full and env["rank"] == 0:
             prof = main["prof"]
             nb = max(prof.get("batches", 0), 1)
             stage_pipe = {k: prof[v] / nb for k, v in PROF_KEY.items()} | {"octree": prof["octree_ms"] / nb}
@@ -873,16 +945,37 @@ def run_workload(name, args, env, want_cpu, cpu_seconds):
     return out, detail
 
 
+def dump_outputs(folder, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array (float32), 64 MB at most in all."""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > 64 << 20:
+        raise RuntimeError("--dump-outputs: %d bytes of outputs exceed 64 MB" % total)
+    os.makedirs(folder, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(folder, name + ".npy"), np.ascontiguousarray(a, np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (with --full: steps per block, see --min-seconds)")
+    ap.add_argument("--warmup", type=int, default=5,
+                    help="untimed steps before the region (without --full: at least that many, and %.1f s of them)" % WARMUP_SECONDS)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: host inputs, the extra workloads, CPU baselines, roofline and per-stage "
+                         "figures, the PCIe roofline, and for N>1 the exchange alone and its GPU-side proof; every timed region "
+                         "then repeats its --steps steps until it lasts --min-seconds")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the headline region's last step delivered as DIR/<name>.npy (float32)")
     ap.add_argument("--workload", default="all", choices=["all"] + sorted(WORKLOADS),
-                    help="'all' = the headline workload plus the two extra workloads in one line")
-    ap.add_argument("--inputs", default="both", choices=["device", "pinned", "both"],
-                    help="where the frames are when the timed region starts: HBM, pinned host memory, or both (two timed regions)")
-    ap.add_argument("--min-seconds", type=float, default=1.0, help="minimum length of every timed region")
+                    help="'all' = the headline workload (with --full: plus the extra workloads in one line)")
+    ap.add_argument("--inputs", default=None, choices=["device", "pinned", "both"],
+                    help="where the frames are when the timed region starts: HBM, pinned host memory, or both (two timed regions); "
+                         "default device, with --full both")
+    ap.add_argument("--min-seconds", type=float, default=1.0,
+                    help="with --full: every timed region repeats its --steps steps until it lasts this long (without --full "
+                         "the timed region is exactly --steps steps)")
     ap.add_argument("--batch", type=int, default=32, help="images (stereo: L,R,L,R..) per rank per step")
     ap.add_argument("--inflight", type=int, default=4, help="extractor contexts (HIP streams) in flight per GPU")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -917,6 +1010,8 @@ def main():
     ap.add_argument("--launch-check", action="store_true",
                     help="spawned ranks only rendezvous (gloo, no GPU touched), all-reduce and exit: tests the self-launch")
     args = ap.parse_args()
+    if args.inputs is None:
+        args.inputs = "both" if args.full else "device"
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -986,11 +1081,11 @@ def main():
                                              transport="rccl" if args.dist_backend == "nccl" else "gloo",
                                              lanes=max(3, args.inflight))  # one communicator per context in flight
 
-    names = [HEADLINE] + ([] if args.no_extras else EXTRAS) if args.workload == "all" else [args.workload]
+    names = [HEADLINE] + ([] if args.no_extras or not args.full else EXTRAS) if args.workload == "all" else [args.workload]
     results, details = [], []
     for i, name in enumerate(names):
-        want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
-        out, det = run_workload(name, args, env, want_cpu, 12.0 if i == 0 else 6.0)  # bounded CPU samples: five workloads in one run
+        want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
+        out, det = run_workload(name, args, env, want_cpu, 12.0 if i == 0 else 6.0, i == 0)  # bounded CPU samples: five workloads in one run
         results.append(out)
         details.append(det)
         barrier()

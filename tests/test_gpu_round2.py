@@ -176,7 +176,7 @@ def test_bench_verify_exchange_world1_collective_path():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--force-collective", "--workload",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--force-collective", "--workload",
                         "kitti00_mono_1241x376_n1000", "--inputs", "device", "--no-cpu-baseline", "--steps", "4", "--warmup", "1",
                         "--min-seconds", "0.05"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -189,6 +189,45 @@ def test_bench_verify_exchange_world1_collective_path():
     for mode, v in ver.items():
         assert v["verified"] and v["keypoints_compared_rank0"] > 500 and v["matches_rank0"] > 20, (mode, v)
     assert d["exchange"]["transport"] == "rccl"
+
+
+def test_bench_plain_run_times_steps_and_dumps_what_the_last_step_delivered(tmp_path):
+    """bench.py without --full: the headline figure only, its timed region exactly --steps steps, and --dump-outputs writes
+    the last timed step's keypoints, descriptors and SearchForInitialization results, which equal the oracle's"""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
+    assert len(line) == 1, r.stdout[-2000:]
+    d = json.loads(line[0])
+    assert d["steps"] == 7 and d["timed_repeats"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "u8"
+    assert not any(k in d for k in ("extra_workloads", "cpu_baseline", "roofline_pcie")) and not d["roofline"]
+    a = {p.stem: np.load(p) for p in out.glob("*.npy")}
+    assert all(v.dtype == np.float32 for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64 << 20
+    B, W, H = 32, 1241, 376
+    counts = a["keypoint_counts"].astype(int)
+    assert len(counts) == B and a["keypoints"].shape == (counts.sum(), 7) and a["descriptors"].shape == (counts.sum(), 32)
+    e = orbo.Extractor(1000)
+    want = [e.compute(synth.make_frame(W, H, step=s), lap=(0, 1000)) for s in range(B)]
+    off = np.concatenate([[0], np.cumsum(counts)])
+    for s, (k, dsc, mono) in enumerate(want):
+        got = a["keypoints"][off[s]:off[s + 1]]
+        assert counts[s] == len(k) and a["mono_index"][s] == mono, s
+        assert np.array_equal(got, np.stack([k[f].astype(np.float32) for f in k.dtype.names], 1)), s
+        assert np.array_equal(a["descriptors"][off[s]:off[s + 1]], dsc.astype(np.float32)), s
+    # step 6 > 0: every slot was matched against its predecessor (slot 0 against the previous step's last frame)
+    assert len(a["init_nmatches"]) == B and len(a["init_matches12"]) == counts.sum()
+    m_off = np.concatenate([[0], np.cumsum([counts[(s - 1) % B] for s in range(B)])])
+    for s in range(B):
+        p = want[(s - 1) % B]
+        wn, wm, _ = orbo.search_for_initialization(p[0], p[1], want[s][0], want[s][1], W, H, window=100, nnratio=0.9)
+        assert a["init_nmatches"][s] == wn and np.array_equal(a["init_matches12"][m_off[s]:m_off[s + 1]], wm), s
 
 
 def test_rccl_ring_and_allgather_world1_on_context_stream():

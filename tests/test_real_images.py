@@ -1,6 +1,6 @@
 """The reference's own test images at FULL size (hut_stereo/01-05.png 752x480, lenna.png 512x512, chessboard_798_798.png --
 the tie-heavy one) through the whole path: extraction at N in {1200, 2000, 5 x 1000}, ComputeStereoMatches and
-SearchForInitialization.  tests/golden/real_images.npz holds the gray images, real_expected.npz the oracle's outputs
+SearchForInitialization.  tests/golden/real_images*.npz hold the gray images, real_expected.npz the oracle's outputs
 (generator: tests/golden/make_golden.py real; the reference's PNGs exist only in the build container).
 
 CPU (-m "not gpu"): the oracle reproduces the committed outputs.
@@ -30,9 +30,12 @@ def _key(name, nf, lap):
 
 @pytest.fixture(scope="module")
 def real():
-    ims = np.load(os.path.join(HERE, "golden", "real_images.npz"))
+    ims = {}
+    for f in ("real_images.npz", "real_images_hut4_5.npz"):  # two files: each stays under the 1 MiB a committed file may hold
+        z = np.load(os.path.join(HERE, "golden", f))
+        ims.update({k: z[k] for k in z.files})
     exp = np.load(os.path.join(HERE, "golden", "real_expected.npz"))
-    return {k: ims[k] for k in ims.files}, exp
+    return ims, exp
 
 
 def _sha(d):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """cProfile of the host side of bench.py's mono step (GPU box)."""
 import cProfile, pstats, sys, io, os
-sys.argv = ["bench.py", "--steps", "60", "--warmup", "5", "--no-cpu-baseline"]
+sys.argv = ["bench.py", "--full", "--steps", "60", "--warmup", "5", "--no-cpu-baseline"]
 sys.path.insert(0, "/root/repo")
 import bench
 pr = cProfile.Profile()

@@ -9,12 +9,12 @@ echo "== gpu tests"; timeout -k 10 900 python -m pytest tests -m gpu -x -q > $O/
 if [ $rc -ne 0 ]; then exit 1; fi
 echo "== smoke"; timeout -k 10 300 python __graft_entry__.py smoke 2>&1 | tail -2
 echo "== multi-rank rehearsal"; bash tools/rehearse_multi.sh > $O/final/rehearse_multi.txt 2>&1; tail -6 $O/final/rehearse_multi.txt
-echo "== bench default"; timeout -k 10 900 python bench.py > $O/final/default_bench.json 2> $O/final/default_bench.err; echo rc=$?; wc -c $O/final/default_bench.json
+echo "== bench default"; timeout -k 10 900 python bench.py --full > $O/final/default_bench.json 2> $O/final/default_bench.err; echo rc=$?; wc -c $O/final/default_bench.json
 echo "== replay rounds"; timeout -k 10 300 python tools/replay_stats.py 2>&1 | grep -v amdgpu > $O/final/replay_stats.txt; cat $O/final/replay_stats.txt
 echo "== latency"; timeout -k 10 300 python tools/latency_batch1.py 2>&1 | grep -v amdgpu > $O/final/latency_batch1.txt; cat $O/final/latency_batch1.txt
 cd /tmp && export TMPDIR=/tmp
 for wl in kitti00_mono_1241x376_n1000 kitti00_stereo_1241x376_n2000; do
-  timeout -k 10 300 rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv -d $R/$O/final/prof_$wl -o t -- python3 $R/bench.py --workload $wl --inputs device --no-cpu-baseline --steps 20 > $R/$O/final/prof_$wl.json 2> $R/$O/final/prof_$wl.err
+  timeout -k 10 300 rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv -d $R/$O/final/prof_$wl -o t -- python3 $R/bench.py --full --workload $wl --inputs device --no-cpu-baseline --steps 20 > $R/$O/final/prof_$wl.json 2> $R/$O/final/prof_$wl.err
   echo "-- $wl rc=$?"
   find $R/$O/final/prof_$wl -name "*_trace.csv" -delete
 done

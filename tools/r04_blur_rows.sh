@@ -10,7 +10,7 @@ for r in 24 32 48 64 96; do
 done | tee $O/stage_times.txt
 for wl in kitti00_mono_1241x376_n1000 kitti00_stereo_1241x376_n2000 synthetic_stereo_1920x1080_n4000 hut_stereo_752x480_n1200_real; do
   for r in 32 48 64 32 64; do
-    VSLAM_BLUR_ROWS=$r timeout -k 10 300 python bench.py --workload $wl --no-cpu-baseline --inputs device > $O/${wl}_r$r.json 2> $O/${wl}_r$r.err
+    VSLAM_BLUR_ROWS=$r timeout -k 10 300 python bench.py --full --workload $wl --no-cpu-baseline --inputs device > $O/${wl}_r$r.json 2> $O/${wl}_r$r.err
     echo "$wl blur_rows=$r rc=$? $(python3 -c "
 import json
 d=json.load(open('$O/${wl}_r$r.json'))

@@ -8,7 +8,7 @@ for rep in 1 2; do
 for ch in chain nochain; do
   flag=""; [ $ch = nochain ] && flag="--no-fast-chain"
   for wl in $WLS; do
-    timeout -k 10 240 python bench.py --workload $wl --no-cpu-baseline $flag > $O/b_${wl}_${ch}_r$rep.json 2> $O/b_${wl}_${ch}_r$rep.err
+    timeout -k 10 240 python bench.py --full --workload $wl --no-cpu-baseline $flag > $O/b_${wl}_${ch}_r$rep.json 2> $O/b_${wl}_${ch}_r$rep.err
     echo "$ch rep=$rep $wl rc=$? $(python3 -c "import json; d=json.load(open('$O/b_${wl}_${ch}_r$rep.json')); print(d['value'], d['value_host_inputs'], d.get('spread'), d.get('spread_host_inputs'))" 2>/dev/null)"
   done
 done

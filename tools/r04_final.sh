@@ -15,7 +15,7 @@ tests)
   if [ $rc -ne 0 ]; then exit 1; fi
   echo "== smoke"; timeout -k 10 300 python __graft_entry__.py smoke 2>&1 | tail -2;;
 bench)
-  echo "== bench default"; timeout -k 10 900 python bench.py > $O/final/default_bench.json 2> $O/final/default_bench.err; echo rc=$?; wc -c $O/final/default_bench.json
+  echo "== bench default"; timeout -k 10 900 python bench.py --full > $O/final/default_bench.json 2> $O/final/default_bench.err; echo rc=$?; wc -c $O/final/default_bench.json
   python3 -c "
 import json; d=json.load(open('$O/final/default_bench.json'))
 print(d['value'], d['value_host_inputs'], d['spread'], d['roofline'].get('kernel'), d['roofline'].get('avg_launch_ms'), d['roofline'].get('frac'))
@@ -23,7 +23,7 @@ for e in d.get('extra_workloads', []): print(e['workload'], e['value'], e['value
 prof)
   cd /tmp && export TMPDIR=/tmp
   for wl in kitti00_mono_1241x376_n1000 kitti00_stereo_1241x376_n2000; do
-    timeout -k 10 300 rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv -d $R/$O/final/prof_$wl -o t -- python3 $R/bench.py --workload $wl --inputs device --no-cpu-baseline --steps 20 > $R/$O/final/prof_$wl.json 2> $R/$O/final/prof_$wl.err
+    timeout -k 10 300 rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv -d $R/$O/final/prof_$wl -o t -- python3 $R/bench.py --full --workload $wl --inputs device --no-cpu-baseline --steps 20 > $R/$O/final/prof_$wl.json 2> $R/$O/final/prof_$wl.err
     echo "-- $wl rc=$?"
     find $R/$O/final/prof_$wl -name "*_trace.csv" -delete
   done

@@ -7,7 +7,7 @@ mkdir -p $O
 for wl in kitti00_mono_1241x376_n1000 kitti00_stereo_1241x376_n2000 synthetic_stereo_1920x1080_n4000 hut_stereo_752x480_n1200_real; do
   for cfg in "4 4" "8 4" "8 6" "8 8" "16 8" "4 4" "8 6"; do
     set -- $cfg
-    GPU_MAX_HW_QUEUES=$1 timeout -k 10 300 python bench.py --workload $wl --no-cpu-baseline --inputs device --inflight $2 > $O/${wl}_q$1_i$2.json 2> $O/${wl}_q$1_i$2.err
+    GPU_MAX_HW_QUEUES=$1 timeout -k 10 300 python bench.py --full --workload $wl --no-cpu-baseline --inputs device --inflight $2 > $O/${wl}_q$1_i$2.json 2> $O/${wl}_q$1_i$2.err
     echo "$wl hwq=$1 inflight=$2 rc=$? $(python3 -c "
 import json
 d=json.load(open('$O/${wl}_q$1_i$2.json'))

@@ -5,7 +5,7 @@ O=gpurun_out/inflight
 mkdir -p $O
 for wl in kitti00_mono_1241x376_n1000 kitti00_stereo_1241x376_n2000 synthetic_stereo_1920x1080_n4000 hut_stereo_752x480_n1200_real; do
   for n in 3 4 5 6 8; do
-    timeout -k 10 300 python bench.py --workload $wl --no-cpu-baseline --inputs device --inflight $n > $O/${wl}_i$n.json 2> $O/${wl}_i$n.err
+    timeout -k 10 300 python bench.py --full --workload $wl --no-cpu-baseline --inputs device --inflight $n > $O/${wl}_i$n.json 2> $O/${wl}_i$n.err
     echo "$wl inflight=$n rc=$? $(python3 -c "
 import json
 d=json.load(open('$O/${wl}_i$n.json'))

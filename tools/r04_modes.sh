@@ -5,7 +5,7 @@ set -o pipefail
 O=gpurun_out/modes
 mkdir -p $O
 WL=kitti00_mono_1241x376_n1000
-run() { name=$1; shift; timeout -k 10 240 env "$@" python bench.py --workload $WL --inputs device --no-cpu-baseline --min-seconds 1.5 --stamp-dump $O/st_$name ${EXTRA[@]} > $O/b_$name.json 2> $O/b_$name.err; echo "$name rc=$? $(python3 -c "import json; d=json.load(open('$O/b_$name.json')); print(d['value'], d.get('spread'))" 2>/dev/null)"; }
+run() { name=$1; shift; timeout -k 10 240 env "$@" python bench.py --full --workload $WL --inputs device --no-cpu-baseline --min-seconds 1.5 --stamp-dump $O/st_$name ${EXTRA[@]} > $O/b_$name.json 2> $O/b_$name.err; echo "$name rc=$? $(python3 -c "import json; d=json.load(open('$O/b_$name.json')); print(d['value'], d.get('spread'))" 2>/dev/null)"; }
 EXTRA=(); run default A=1
 EXTRA=(--fast-chain); run chain A=1
 EXTRA=(--fast-chain); run chain2 A=1

@@ -13,7 +13,7 @@ for rep in 1 2; do
 for cfg in $CFGS; do
   k=${cfg:1:1}; prio=${cfg:3}
   for wl in $WLS; do
-    timeout -k 10 240 python bench.py --workload $wl --inputs device --no-cpu-baseline --fast-kernel $k --wave-prio $prio > $O/b_${wl}_${cfg}_r${rep}.json 2> $O/b_${wl}_${cfg}_r${rep}.err
+    timeout -k 10 240 python bench.py --full --workload $wl --inputs device --no-cpu-baseline --fast-kernel $k --wave-prio $prio > $O/b_${wl}_${cfg}_r${rep}.json 2> $O/b_${wl}_${cfg}_r${rep}.err
     echo "cfg=$cfg rep=$rep $wl rc=$? $(python3 -c "import json,sys; d=json.load(open('$O/b_${wl}_${cfg}_r${rep}.json')); print(d['value'], d.get('spread'))" 2>/dev/null)"
   done
 done
@@ -22,7 +22,7 @@ cd /tmp && export TMPDIR=/tmp
 for cfg in k4p0 k4p7; do
   k=${cfg:1:1}; prio=${cfg:3}
   for wl in kitti00_mono_1241x376_n1000 kitti00_stereo_1241x376_n2000; do
-    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof_${wl}_${cfg} -o t -- python3 $R/bench.py --workload $wl --inputs device --no-cpu-baseline --steps 20 --fast-kernel $k --wave-prio $prio > $R/$O/prof_${wl}_${cfg}.json 2> $R/$O/prof_${wl}_${cfg}.err
+    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof_${wl}_${cfg} -o t -- python3 $R/bench.py --full --workload $wl --inputs device --no-cpu-baseline --steps 20 --fast-kernel $k --wave-prio $prio > $R/$O/prof_${wl}_${cfg}.json 2> $R/$O/prof_${wl}_${cfg}.err
     echo "-- trace $wl $cfg rc=$?"
     find $R/$O/prof_${wl}_${cfg} -name "*_trace.csv" -delete
   done

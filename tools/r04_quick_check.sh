@@ -18,7 +18,7 @@ for n,e in d.items():
     print(n[:30].ljust(30), {c: (round(e[c]/1e6,3) if isinstance(e.get(c),(int,float)) else e.get(c)) for c in ("SQ_INSTS_VALU","SQ_INSTS_SALU","SQ_BUSY_CYCLES")})
 PY
 for wl in kitti00_mono_1241x376_n1000 kitti00_stereo_1241x376_n2000 synthetic_stereo_1920x1080_n4000 hut_stereo_752x480_n1200_real; do
-  timeout -k 10 300 python bench.py --workload $wl --no-cpu-baseline --inputs device > $O/$wl.json 2> $O/$wl.err
+  timeout -k 10 300 python bench.py --full --workload $wl --no-cpu-baseline --inputs device > $O/$wl.json 2> $O/$wl.err
   echo "$wl rc=$? $(python3 -c "
 import json
 d=json.load(open('$O/$wl.json'))

@@ -8,7 +8,7 @@ WLS="kitti00_mono_1241x376_n1000 kitti00_stereo_1241x376_n2000 synthetic_stereo_
 for gc in gcon gcoff; do
   flag=""; [ $gc = gcon ] && flag="--gc"
   for wl in $WLS; do
-    timeout -k 10 240 python bench.py --workload $wl --inputs device --no-cpu-baseline $flag --stamp-dump $O/st_$gc > $O/b_${wl}_$gc.json 2> $O/b_${wl}_$gc.err
+    timeout -k 10 240 python bench.py --full --workload $wl --inputs device --no-cpu-baseline $flag --stamp-dump $O/st_$gc > $O/b_${wl}_$gc.json 2> $O/b_${wl}_$gc.err
     echo "$gc $wl rc=$? $(python3 -c "import json; d=json.load(open('$O/b_${wl}_$gc.json')); print(d['value'], d.get('spread'))" 2>/dev/null)"
   done
 done

@@ -39,6 +39,8 @@ def run(tag, frames, nf, w, h):
 if __name__ == "__main__":
     for nf in (1000, 2000):
         run("kitti synthetic N=%d" % nf, [synth.make_frame(1241, 376, seed=5, step=s) for s in range(32)], nf, 1241, 376)
-    g = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "real_images.npz")
-    ims = np.load(g)
+    g = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
+    ims = {}
+    for f in ("real_images.npz", "real_images_hut4_5.npz"):
+        ims.update(np.load(os.path.join(g, f)))
     run("hut real N=1200", [ims["hut%d" % i] for i in (1, 2, 3, 4, 5)], 1200, 752, 480)
