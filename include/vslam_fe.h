@@ -380,6 +380,56 @@ int vslam_search_init_dev_wait(vslam_fe* fe, const int* n1, int32_t* const* matc
 /* device address of a slot's keypoint count (int32), valid for the life of the context */
 int vslam_fe_slot_count_ptr(vslam_fe* fe, int slot, const int32_t** dev_n);
 
+/* ---------------------------------------------------------------- distorted pinhole cameras (Frame::ukeypoints_)
+ *
+ * Frame::UndistortKeyPoints (frame.cpp:758-790) runs cv::undistortPoints(mat, mat, mK, mDistCoef, cv::Mat(), mK) on
+ * the keypoints right after extraction, and Frame::ComputeImageBounds (:793-821) undistorts the image corners into the
+ * float grid bounds mnMinX/mnMaxX/mnMinY/mnMaxY.  With a camera set, every extraction pass of the context
+ * (vslam_fe_extract*, the async/wait forms, vslam_frame_stereo_batch_async) also writes the undistorted keypoints of
+ * each slot to the device (one small launch behind the descriptors; captured graphs include it).  The reference only
+ * tests k1: with k1 == 0 ukeypoints_ = keypoints_ even if k2, p1, p2 or k3 are not zero, and so does this library (no
+ * launch; the slot's keypoint array doubles as its undistorted one).  Contexts without a camera launch nothing extra. */
+typedef struct vslam_camera {
+    float fx, fy, cx, cy; /* Pinhole::toK (CV_32F) */
+    float dist[5];        /* mDistCoef: k1, k2, p1, p2[, k3] */
+    int32_t ndist;        /* 4 or 5 */
+} vslam_camera;
+/* NULL = no camera (the default).  Drops the context's captured graph, so the next pass captures with the new one. */
+int vslam_fe_set_camera(vslam_fe* fe, const vslam_camera* cam);
+/* Device address of a slot's ukeypoints_ (vslam_kp[cap], n = the slot's count; valid until the next extraction, fixed
+ * for the life of the context): the slot's keypoint array itself when k1 == 0.  VSLAM_ERR_INVALID without a camera. */
+int vslam_fe_slot_ukps(vslam_fe* fe, int slot, const vslam_kp** dev_ukps);
+/* Waits for fe's stream, then copies the slot's ukeypoints_ (*n entries) to dst; VSLAM_ERR_CAPACITY if cap < *n. */
+int vslam_fe_ukps_copy(vslam_fe* fe, int slot, vslam_kp* dst, int cap, int* n);
+/* cv::undistortPoints with the context's camera (k1 == 0: unchanged) of n points, xy / out_xy interleaved host arrays;
+ * evaluated on the device by the arithmetic of the keypoint kernel.  VSLAM_ERR_INVALID without a camera. */
+int vslam_undistort_points(vslam_fe* fe, const float* xy, int n, float* out_xy);
+/* Frame::ComputeImageBounds on level 0: bounds = minX, maxX, minY, maxY; {0, width, 0, height} without a camera or
+ * with k1 == 0. */
+int vslam_fe_image_bounds(vslam_fe* fe, float bounds[4]);
+
+/* The three SearchForInitialization entry points over frame 2's float grid bounds (vslam_fe_image_bounds) instead of
+ * img_w / img_h: mfGridElementWidthInv = (float)64 / (maxX - minX), PosInGrid = round((x - minX) * inv), window cells
+ * floor((x - minX - r) * inv) .. ceil((x - minX + r) * inv) (frame.cpp:322-323, 678-756).  The img_w / img_h forms are
+ * these with {0, img_w, 0, img_h}.  Keypoints are typically ukeypoints_ (vslam_fe_slot_ukps / vslam_fe_ukps_copy);
+ * in a device job dev_prev_matched == NULL then means frame 1's undistorted positions (tracking.cpp:2286-2288).
+ * The bounds must be finite with max > min (VSLAM_ERR_INVALID otherwise). */
+typedef struct vslam_bounds {
+    float min_x, max_x, min_y, max_y;
+} vslam_bounds;
+int vslam_search_for_initialization_ex(vslam_fe* fe, const vslam_kp* kps1_host, const uint8_t* dev_desc1, int n1,
+                                       const vslam_kp* kps2_host, const uint8_t* dev_desc2, int n2, const vslam_bounds* b,
+                                       float* prev_matched, int32_t* matches12, int window, float nnratio,
+                                       int check_orientation, int* nmatches);
+int vslam_search_for_initialization_batch_ex(vslam_fe* fe, int npairs, const vslam_kp* const* kps1_host,
+                                             const uint8_t* const* dev_desc1, const int* n1,
+                                             const vslam_kp* const* kps2_host, const uint8_t* const* dev_desc2,
+                                             const int* n2, const vslam_bounds* b, float* const* prev_matched,
+                                             int32_t* const* matches12, int window, float nnratio, int check_orientation,
+                                             int* nmatches);
+int vslam_search_init_dev_async_ex(vslam_fe* fe, int npairs, const vslam_init_job* jobs, const vslam_bounds* b,
+                                   int window, float nnratio, int check_orientation);
+
 /* ---------------------------------------------------------------- diagnostics */
 
 /* FMatcher::SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, th, bMono)

@@ -169,6 +169,26 @@ public:
     /* the device context (NULL before the first compute): device-side consumers -- FMatcher, stereo -- use it */
     vslam_fe* context() const { return fe_; }
 
+    /* The Frame's camera (Pinhole::toK, mDistCoef: 4 or 5 coefficients).  Set it BEFORE compute(): every later pass then
+     * also writes the undistorted keypoints on the device (UndistortKeyPoints below reads them).  Kept across the
+     * re-creation of the context when the image size changes.  An empty dist removes the camera. */
+    void SetCamera(float fx, float fy, float cx, float cy, const std::vector<float>& dist) {
+        has_cam_ = !dist.empty();
+        if (has_cam_) {
+            if (dist.size() != 4 && dist.size() != 5) throw std::invalid_argument("mDistCoef needs 4 or 5 coefficients");
+            std::memset(&cam_, 0, sizeof(cam_));
+            cam_.fx = fx;
+            cam_.fy = fy;
+            cam_.cx = cx;
+            cam_.cy = cy;
+            for (size_t i = 0; i < dist.size(); i++) cam_.dist[i] = dist[i];
+            cam_.ndist = (int32_t)dist.size();
+        }
+        if (fe_) check(vslam_fe_set_camera(fe_, has_cam_ ? &cam_ : nullptr));
+    }
+    bool HasCamera() const { return has_cam_; }
+    float DistortionK1() const { return has_cam_ ? cam_.dist[0] : 0.0f; }
+
 protected:
     int run(const uint8_t* data, int cols, int rows, size_t step, std::vector<KeyPoint>& keypoints,
             std::vector<uint8_t>& desc, std::vector<int>& vLappingArea, int* n_out) {
@@ -189,6 +209,7 @@ protected:
             check(vslam_fe_create(&p, &fe_));
             w_ = cols;
             h_ = rows;
+            if (has_cam_) check(vslam_fe_set_camera(fe_, &cam_));
         }
         const int cap = vslam_fe_capacity(fe_); /* quota + the quadtree's overshoot, see vslam_fe.h */
         keypoints.resize(cap);
@@ -211,7 +232,40 @@ protected:
     std::vector<float> mvScaleFactor, mvInvScaleFactor, mvLevelSigma2, mvInvLevelSigma2;
     vslam_fe* fe_ = nullptr;
     int w_ = 0, h_ = 0;
+    bool has_cam_ = false;
+    vslam_camera cam_;
 };
+
+/* Frame::UndistortKeyPoints (frame.cpp:758-790) for the keypoints the extractor's last compute() returned: with
+ * mDistCoef.at<float>(0) == 0 (or no camera) ukeypoints_ = keypoints_, otherwise the device's cv::undistortPoints of
+ * them (vslam_fe_ukps_copy). */
+inline void UndistortKeyPoints(const FExtractor& extractor, const std::vector<KeyPoint>& keypoints,
+                               std::vector<KeyPoint>& ukeypoints) {
+    if (!extractor.HasCamera() || extractor.DistortionK1() == 0.0f || keypoints.empty()) {
+        ukeypoints = keypoints;
+        return;
+    }
+    if (!extractor.context()) throw std::runtime_error("UndistortKeyPoints: no image has been processed yet");
+    ukeypoints.resize(keypoints.size());
+    int n = 0;
+    const int rc = vslam_fe_ukps_copy(extractor.context(), 0, reinterpret_cast<vslam_kp*>(ukeypoints.data()),
+                                      (int)ukeypoints.size(), &n);
+    if (rc != VSLAM_OK || n != (int)keypoints.size())
+        throw std::runtime_error(rc != VSLAM_OK ? vslam_last_error()
+                                                : "UndistortKeyPoints: the extractor's slot no longer holds these keypoints");
+}
+
+/* Frame::ComputeImageBounds (frame.cpp:793-821): {0, cols, 0, rows} without distortion (k1 == 0), else the undistorted
+ * corners.  Needs the extractor's context (after its first compute()). */
+inline void ComputeImageBounds(const FExtractor& extractor, float& mnMinX, float& mnMaxX, float& mnMinY, float& mnMaxY) {
+    if (!extractor.context()) throw std::runtime_error("ComputeImageBounds: no image has been processed yet");
+    float b[4];
+    if (vslam_fe_image_bounds(extractor.context(), b) != VSLAM_OK) throw std::runtime_error(vslam_last_error());
+    mnMinX = b[0];
+    mnMaxX = b[1];
+    mnMinY = b[2];
+    mnMaxY = b[3];
+}
 
 /* What the matchers read of a Frame (frame.h:71-91): undistorted keypoints, the image bounds of its grid,
  * and where its descriptors are in HBM (the extractor that produced them still holds them). */
@@ -219,6 +273,10 @@ struct FrameView {
     const std::vector<KeyPoint>* ukeypoints = nullptr; /* Frame::ukeypoints_ */
     const FExtractor* extractor = nullptr;             /* descriptors_ live in its slot 0 */
     int mnMaxX = 0, mnMaxY = 0;                        /* image bounds (no distortion: cols, rows) */
+    /* float grid bounds of a distorted camera (ComputeImageBounds); unset = {0, mnMaxX, 0, mnMaxY}.  Used by
+     * SearchForInitialization only (the other matchers take integer bounds). */
+    bool has_bounds = false;
+    vslam_bounds bounds = {0.0f, 0.0f, 0.0f, 0.0f};
 };
 
 /* ---------------------------------------------------------------------------------------------------
@@ -256,6 +314,14 @@ public:
         check(vslam_fe_slot_buffers(F2.extractor->context(), 0, nullptr, &d2, &n2));
         if (n1 != (int)k1.size() || n2 != (int)k2.size())
             throw std::runtime_error("FMatcher: the extractor's slot no longer holds this frame's descriptors");
+        if (F2.has_bounds) {
+            check(vslam_search_for_initialization_ex(F2.extractor->context(), reinterpret_cast<const vslam_kp*>(k1.data()),
+                                                     d1, n1, reinterpret_cast<const vslam_kp*>(k2.data()), d2, n2,
+                                                     &F2.bounds, reinterpret_cast<float*>(vbPrevMatched.data()),
+                                                     vnMatches12.data(), windowSize, mfNNratio, mbCheckOrientation ? 1 : 0,
+                                                     &nm));
+            return nm;
+        }
         check(vslam_search_for_initialization(F2.extractor->context(), reinterpret_cast<const vslam_kp*>(k1.data()), d1,
                                               n1, reinterpret_cast<const vslam_kp*>(k2.data()), d2, n2, F2.mnMaxX,
                                               F2.mnMaxY, reinterpret_cast<float*>(vbPrevMatched.data()),

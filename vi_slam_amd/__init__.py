@@ -51,6 +51,8 @@ ABI_SYMBOLS = [
     "vslam_fe_stage_images_async", "vslam_fe_octree_stats", "vslam_fe_delivery_stats", "vslam_dbg_search_init_replay_stats", "vslam_tuning_init", "vslam_fe_set_tuning", "vslam_stereo_fisheye_candidates", "vslam_hamming_top2_batch", "vslam_hamming_top2_batch_dev_async", "vslam_fe_set_fast_gate",
     "vslam_voc_load", "vslam_voc_file_open", "vslam_voc_file_close", "vslam_voc_file_info", "vslam_voc_file_arrays",
     "vslam_voc_file_last_error", "vslam_dbg_qlz_decode",
+    "vslam_fe_set_camera", "vslam_fe_slot_ukps", "vslam_fe_ukps_copy", "vslam_undistort_points", "vslam_fe_image_bounds",
+    "vslam_search_for_initialization_ex", "vslam_search_for_initialization_batch_ex", "vslam_search_init_dev_async_ex",
 ]
 
 
@@ -130,6 +132,20 @@ class _InitJob(C.Structure):  # vslam_init_job
     _fields_ = [("dev_kps1", C.c_void_p), ("dev_desc1", C.c_void_p), ("dev_n1", C.c_void_p),
                 ("dev_kps2", C.c_void_p), ("dev_desc2", C.c_void_p), ("dev_n2", C.c_void_p),
                 ("dev_prev_matched", C.c_void_p)]
+
+
+class _Camera(C.Structure):  # vslam_camera
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("dist", C.c_float * 5),
+                ("ndist", C.c_int32)]
+
+
+class _Bounds(C.Structure):  # vslam_bounds
+    _fields_ = [("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float)]
+
+
+def _bounds(b):
+    """(min_x, max_x, min_y, max_y) -> vslam_bounds (FExtractor.image_bounds() order)"""
+    return _Bounds(*[float(v) for v in b])
 
 
 def bind_voc_file(L):
@@ -259,6 +275,15 @@ def lib():
         L.vslam_host_free.argtypes = [vp]
         L.vslam_host_free.restype = None
         L.vslam_fe_stage_images_async.argtypes = [vp, i, vp, C.c_size_t, i]
+        L.vslam_fe_set_camera.argtypes = [vp, C.POINTER(_Camera)]
+        L.vslam_fe_slot_ukps.argtypes = [vp, i, C.POINTER(vp)]
+        L.vslam_fe_ukps_copy.argtypes = [vp, i, vp, i, C.POINTER(i)]
+        L.vslam_undistort_points.argtypes = [vp, vp, i, vp]
+        L.vslam_fe_image_bounds.argtypes = [vp, vp]
+        L.vslam_search_for_initialization_ex.argtypes = [vp, vp, vp, i, vp, vp, i, C.POINTER(_Bounds), vp, vp, i, f, i, vp]
+        L.vslam_search_for_initialization_batch_ex.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, C.POINTER(_Bounds), vp, vp, i,
+                                                               f, i, vp]
+        L.vslam_search_init_dev_async_ex.argtypes = [vp, i, vp, C.POINTER(_Bounds), i, f, i]
         _lib = L
     return _lib
 
@@ -555,6 +580,38 @@ class FExtractor:
                 self._slot_ptrs.append((k.value, d.value, c.value))
         return self._slot_ptrs[slot]
 
+    # ---- distorted pinhole camera: Frame::UndistortKeyPoints / ComputeImageBounds (frame.cpp:758-821)
+    def set_camera(self, fx, fy=None, cx=None, cy=None, dist=None):
+        """Pinhole intrinsics and mDistCoef (k1, k2, p1, p2[, k3]); every later pass also writes the slots' ukeypoints_.
+        set_camera(None) removes the camera (the default)."""
+        if fx is None:
+            _check(lib().vslam_fe_set_camera(self._h, None))
+            return
+        d = [float(v) for v in dist]
+        if len(d) not in (4, 5):
+            raise VslamError(ERR_INVALID, "dist must hold 4 or 5 coefficients")
+        cam = _Camera(fx, fy, cx, cy, (C.c_float * 5)(*(d + [0.0] * (5 - len(d)))), len(d))
+        _check(lib().vslam_fe_set_camera(self._h, C.byref(cam)))
+
+    def slot_ukps_ptr(self, slot=0):
+        """device address of the slot's ukeypoints_ (the keypoint array itself when k1 == 0)"""
+        k = C.c_void_p()
+        _check(lib().vslam_fe_slot_ukps(self._h, slot, C.byref(k)))
+        return k.value
+
+    def ukeypoints(self, slot=0):
+        """ukeypoints_ of the slot's last pass as a host KP_DTYPE array (waits for the context's stream)"""
+        out = np.zeros(self.cap, KP_DTYPE)
+        n = C.c_int()
+        _check(lib().vslam_fe_ukps_copy(self._h, slot, _p(out), self.cap, C.byref(n)))
+        return out[:n.value].copy()
+
+    def image_bounds(self):
+        """Frame::ComputeImageBounds: (mnMinX, mnMaxX, mnMinY, mnMaxY) as float32"""
+        b = np.zeros(4, np.float32)
+        _check(lib().vslam_fe_image_bounds(self._h, _p(b)))
+        return b
+
     def wait_for(self, other):
         """GPU-side: work enqueued on this context from now on runs after everything enqueued on `other`."""
         _check(lib().vslam_fe_wait_for(self._h, other._h))
@@ -694,16 +751,23 @@ class FMatcher:
         return out[:nq, :nt]
 
     def SearchForInitialization(self, kps1, dev_desc1, kps2, dev_desc2, vbPrevMatched, windowSize=10,
-                                img_size=None):
+                                img_size=None, bounds=None):
         """FMatcher::SearchForInitialization (fmatcher.cpp:983-1098).
 
         kps1/kps2: host keypoint arrays; dev_desc1/2: device addresses of their descriptors.
-        Returns (nmatches, vnMatches12, updated vbPrevMatched)."""
+        bounds: frame 2's grid bounds (min_x, max_x, min_y, max_y), e.g. FExtractor.image_bounds() of a distorted
+        camera; None = (0, W, 0, H).  Returns (nmatches, vnMatches12, updated vbPrevMatched)."""
         kps1 = np.ascontiguousarray(kps1, KP_DTYPE)
         kps2 = np.ascontiguousarray(kps2, KP_DTYPE)
         pm = np.ascontiguousarray(vbPrevMatched, np.float32).copy()
         m = np.full(max(len(kps1), 1), -1, np.int32)
         nm = C.c_int(0)
+        if bounds is not None:
+            _check(lib().vslam_search_for_initialization_ex(self.fe._h, _p(kps1), dev_desc1, len(kps1), _p(kps2),
+                                                            dev_desc2, len(kps2), C.byref(_bounds(bounds)), _p(pm), _p(m),
+                                                            windowSize, self.mfNNratio, int(self.mbCheckOrientation),
+                                                            C.byref(nm)))
+            return nm.value, m[:len(kps1)], pm
         w, h = img_size or (self.fe.width, self.fe.height)
         _check(lib().vslam_search_for_initialization(self.fe._h, _p(kps1), dev_desc1, len(kps1), _p(kps2),
                                                      dev_desc2, len(kps2), w, h, _p(pm), _p(m), windowSize,
@@ -712,13 +776,18 @@ class FMatcher:
         return nm.value, m[:len(kps1)], pm
 
     # ---- device-resident form: nothing but device pointers go in, one kernel, results later
-    def search_init_dev_async(self, jobs, windowSize=10, img_size=None):
+    def search_init_dev_async(self, jobs, windowSize=10, img_size=None, bounds=None):
         """jobs: list of (dev_kps1, dev_desc1, dev_n1, dev_kps2, dev_desc2, dev_n2, dev_prev_or_0) device
-        addresses.  Enqueues the whole matcher for all pairs on the extractor's stream and returns."""
+        addresses.  Enqueues the whole matcher for all pairs on the extractor's stream and returns.
+        bounds: (min_x, max_x, min_y, max_y) of frame 2's grid (None = (0, W, 0, H))."""
         n = len(jobs)
         arr = jobs if isinstance(jobs, C.Array) else self.make_init_jobs(jobs)
-        w, h = img_size or (self.fe.width, self.fe.height)
         self._init_n = n
+        if bounds is not None:
+            _check(lib().vslam_search_init_dev_async_ex(self.fe._h, n, arr, C.byref(_bounds(bounds)), windowSize,
+                                                        self.mfNNratio, int(self.mbCheckOrientation)))
+            return
+        w, h = img_size or (self.fe.width, self.fe.height)
         _check(lib().vslam_search_init_dev_async(self.fe._h, n, arr, w, h, windowSize, self.mfNNratio,
                                                  int(self.mbCheckOrientation)))
 
@@ -1018,10 +1087,10 @@ class FMatcher:
         _check(lib().vslam_dbg_search_init_replay_stats(self.fe._h, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
 
-    def SearchForInitializationBatch(self, pairs, windowSize=10, img_size=None):
+    def SearchForInitializationBatch(self, pairs, windowSize=10, img_size=None, bounds=None):
         """Several independent SearchForInitialization problems in one pass of the kernels.
-        pairs: list of (kps1, dev_desc1, kps2, dev_desc2, vbPrevMatched).  Returns a list of
-        (nmatches, vnMatches12, vbPrevMatched)."""
+        pairs: list of (kps1, dev_desc1, kps2, dev_desc2, vbPrevMatched); bounds as in SearchForInitialization (one
+        set for all pairs).  Returns a list of (nmatches, vnMatches12, vbPrevMatched)."""
         npairs = len(pairs)
         k1 = [np.ascontiguousarray(p[0], KP_DTYPE) for p in pairs]
         k2 = [np.ascontiguousarray(p[2], KP_DTYPE) for p in pairs]
@@ -1035,13 +1104,16 @@ class FMatcher:
         nm = ia()
         w, h = img_size or (self.fe.width, self.fe.height)
         dummy = np.zeros(1, KP_DTYPE)
-        _check(lib().vslam_search_for_initialization_batch(
-            self.fe._h, npairs, vpa(*[(k if len(k) else dummy).ctypes.data for k in k1]),
-            vpa(*[(p[1] or dummy.ctypes.data) for p in pairs]), ia(*[len(k) for k in k1]),
-            vpa(*[(k if len(k) else dummy).ctypes.data for k in k2]),
-            vpa(*[(p[3] or dummy.ctypes.data) for p in pairs]), ia(*[len(k) for k in k2]), w, h,
-            vpa(*[a.ctypes.data for a in pm]), vpa(*[a.ctypes.data for a in m]), windowSize, self.mfNNratio,
-            int(self.mbCheckOrientation), nm))
+        common = (self.fe._h, npairs, vpa(*[(k if len(k) else dummy).ctypes.data for k in k1]),
+                  vpa(*[(p[1] or dummy.ctypes.data) for p in pairs]), ia(*[len(k) for k in k1]),
+                  vpa(*[(k if len(k) else dummy).ctypes.data for k in k2]),
+                  vpa(*[(p[3] or dummy.ctypes.data) for p in pairs]), ia(*[len(k) for k in k2]))
+        tail = (vpa(*[a.ctypes.data for a in pm]), vpa(*[a.ctypes.data for a in m]), windowSize, self.mfNNratio,
+                int(self.mbCheckOrientation), nm)
+        if bounds is not None:
+            _check(lib().vslam_search_for_initialization_batch_ex(*common, C.byref(_bounds(bounds)), *tail))
+        else:
+            _check(lib().vslam_search_for_initialization_batch(*common, w, h, *tail))
         return [(nm[j], m[j][:len(k1[j])], pm[j][:len(k1[j])]) for j in range(npairs)]
 
 
@@ -1179,6 +1251,15 @@ def ComputeDistinctiveDescriptors(fe, desc, offsets):
     best = np.full(max(len(off) - 1, 1), -1, np.int32)
     _check(lib().vslam_distinctive_descriptors(fe._h, _p(desc) if len(desc) else None, _p(off), len(off) - 1, _p(best)))
     return best[:len(off) - 1]
+
+
+def undistort_points(fe, pts):
+    """cv::undistortPoints(pts, K, D, noArray(), K) with fe's camera (vslam_fe_set_camera; k1 == 0: unchanged),
+    evaluated on the device: pts [n, 2] -> float32 [n, 2]"""
+    xy = np.ascontiguousarray(np.asarray(pts, np.float32).reshape(-1, 2))
+    out = np.zeros_like(xy)
+    _check(lib().vslam_undistort_points(fe._h, _p(xy), len(xy), _p(out)))
+    return out
 
 
 def ComputeStereoMatches(feL, slotL, feR, slotR, bf, fx):

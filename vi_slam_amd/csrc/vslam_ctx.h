@@ -136,6 +136,10 @@ struct vslam_fe {
     size_t h_init_bytes = 0;
     int init_pairs = 0;
     bool init_lds_set = false;
+    /* vslam_fe_set_camera: Frame::UndistortKeyPoints behind every pass when has_cam && ud.dist[0] != 0 */
+    bool has_cam = false;
+    UdCam ud;
+    vslam_kp* d_ukps = nullptr; /* B x cap, allocated by the first camera with k1 != 0 */
     uint8_t* d_init_scratch = nullptr; /* k_si_topm -> k_si_replay: compacted octave-0 lists + sorted prefixes */
     size_t init_scratch_bytes = 0;
     int* d_init_fb = nullptr; /* number of full re-scans in k_si_replay / k_sbp_replay (diagnostics) */
@@ -210,6 +214,8 @@ int vslam_pinned_alloc(void** p, size_t bytes);                  /* hipHostMallo
 int vslam_enqueue_extract(vslam_fe* fe, int nimg, const uint8_t* const* imgs, size_t pitch, int on_device,
                           int lap0, int lap1, int want_host);
 int vslam_finish_extract(vslam_fe* fe, int nimg);
+/* k_undistort_kps behind the descriptors of a pass, if the context has a camera with k1 != 0 (vslam_undistort.hip) */
+int vslam_enqueue_undistort(vslam_fe* fe, int nimg);
 int vslam_deliver(vslam_fe* fe, int nimg, vslam_kp* const* kps, uint8_t* const* desc, int cap, int* n,
                   int* mono_index);
 

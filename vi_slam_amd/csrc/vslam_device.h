@@ -287,5 +287,14 @@ struct InitJob {
 struct InitJobs {
     InitJob job[VSLAM_MAX_MAT_JOBS];
 };
+/* Frame 2's grid bounds mnMinX, mnMaxX, mnMinY, mnMaxY (frame.cpp:793-821): {0, cols, 0, rows} without distortion */
+struct SiBounds {
+    float minX, maxX, minY, maxY;
+};
+/* the camera of vslam_fe_set_camera as k_undistort_kps takes it: fx, fy, cx, cy | k1, k2, p1, p2, k3 */
+struct UdCam {
+    float cam[4];
+    float dist[5];
+};
 
 #endif

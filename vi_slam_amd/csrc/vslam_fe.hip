@@ -83,6 +83,7 @@ static void free_ctx(vslam_fe* fe) {
     if (fe->h_stereo) hipHostFree(fe->h_stereo);
     if (!fe->init_in_block) hipFree(fe->d_init);
     hipFree(fe->d_init_scratch);
+    hipFree(fe->d_ukps);
     hipFree(fe->d_proj);
     hipFree(fe->d_sbp);
     if (fe->h_sbp) hipHostFree(fe->h_sbp);
@@ -1121,6 +1122,7 @@ static int enqueue_back_host(vslam_fe* fe, int nimg, int lap0, int lap1) {
         if (prof) HIPCHK(hipEventRecord(fe->ev_prof[5], st));
         vk_orient_describe(st, fe->d_pyr, fe->d_blur, fe->slot_stride, fe->src, fe->geom, fe->d_sel, nsel,
                            fe->d_pattern, fe->d_kps, fe->d_desc, fe->cap, (p.flags & VSLAM_FLAG_ATAN_FMA) ? 1 : 0);
+        if ((rc = vslam_enqueue_undistort(fe, nimg))) return rc;
         if (prof) HIPCHK(hipEventRecord(fe->ev_prof[6], st));
     } else if (prof) {
         HIPCHK(hipEventRecord(fe->ev_prof[5], st));
@@ -1157,6 +1159,8 @@ static int enqueue_back_dev(vslam_fe* fe, int nimg, int lap0, int lap1) {
     vk_orient_describe_dev(st, fe->d_pyr, fe->d_blur, fe->slot_stride, fe->src, fe->geom, fe->d_sel, fe->d_counts,
                            fe->d_pattern, fe->d_kps, fe->d_desc, fe->cap, (p.flags & VSLAM_FLAG_ATAN_FMA) ? 1 : 0,
                            nimg, wave_prio_on(fe->tune, 2), fe->tune.desc_kpw >= 0 ? fe->tune.desc_kpw : fe->desc_kpw_hint);
+    const int rc = vslam_enqueue_undistort(fe, nimg); /* Frame::UndistortKeyPoints, if a camera asks for it */
+    if (rc) return rc;
     if (prof) HIPCHK(hipEventRecord(fe->ev_prof[6], st));
     HIPCHK(hipGetLastError());
     return VSLAM_OK; /* counts travel to the host with the results (vslam_enqueue_extract) */

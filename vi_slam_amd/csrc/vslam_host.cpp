@@ -1,5 +1,6 @@
 /* vslam_host.cpp -- see vslam_host.h.  Reference lines are cited per function. */
 #include "vslam_host.h"
+#include "vslam_undistort.h"
 
 #include <algorithm>
 #include <climits>
@@ -602,9 +603,14 @@ void compute_three_maxima(const int* hs, int L, int& ind1, int& ind2, int& ind3)
 }
 
 void FrameGrid::build(const vslam_kp* k, int n_, int imgW, int imgH) {
+    const float b[4] = {0.0f, (float)imgW, 0.0f, (float)imgH}; /* frame.cpp:814-820 */
+    build(k, n_, b);
+}
+
+void FrameGrid::build(const vslam_kp* k, int n_, const float bounds[4]) {
     kps = k;
     n = n_;
-    minX = 0.0f; maxX = (float)imgW; minY = 0.0f; maxY = (float)imgH; /* frame.cpp:814-820 */
+    minX = bounds[0]; maxX = bounds[1]; minY = bounds[2]; maxY = bounds[3]; /* frame.cpp:793-821 */
     invW = (float)COLS / (maxX - minX);                                /* frame.cpp:322-323 */
     invH = (float)ROWS / (maxY - minY);
     std::vector<int> cellOf(n, -1);
@@ -652,7 +658,7 @@ void FrameGrid::query(float x, float y, float r, int minLevel, int maxLevel, std
 
 int search_for_initialization_replay(const vslam_kp* kps1, int n1, const vslam_kp* kps2, int n2,
                                      const uint8_t* dmat, const int* row_of_i1, const int* col_of_i2,
-                                     int ncols, int imgW, int imgH, float* prevMatched, int32_t* vnMatches12,
+                                     int ncols, const float bounds[4], float* prevMatched, int32_t* vnMatches12,
                                      int windowSize, float mfNNratio, bool checkOri) {
     /* fmatcher.cpp:983-1098 */
     const int TH_LOW = 50, HISTO_LENGTH = 30;
@@ -662,7 +668,7 @@ int search_for_initialization_replay(const vslam_kp* kps1, int n1, const vslam_k
     const float factor = 1.0f / HISTO_LENGTH;
     std::vector<int> vMatchedDistance(n2, INT_MAX), vnMatches21(n2, -1);
     FrameGrid grid2;
-    grid2.build(kps2, n2, imgW, imgH);
+    grid2.build(kps2, n2, bounds);
     std::vector<int> vIndices2;
     for (int i1 = 0; i1 < n1; i1++) {
         const int level1 = kps1[i1].octave;
@@ -875,8 +881,39 @@ int vslamh_search_init(const vslam_kp* kps1, int n1, const vslam_kp* kps2, int n
     std::vector<int> rows(n1), cols(n2);
     for (int i = 0; i < n1; i++) rows[i] = i;
     for (int i = 0; i < n2; i++) cols[i] = i;
+    const float b[4] = {0.0f, (float)W, 0.0f, (float)H};
     return vslam::search_for_initialization_replay(kps1, n1, kps2, n2, dmat_full, rows.data(), cols.data(), n2,
-                                                   W, H, prevMatched, matches12, window, nnratio, checkOri != 0);
+                                                   b, prevMatched, matches12, window, nnratio, checkOri != 0);
+}
+
+/* the same over float grid bounds (minX, maxX, minY, maxY): the host replay of the _ex entry points */
+int vslamh_search_init_bounds(const vslam_kp* kps1, int n1, const vslam_kp* kps2, int n2, const uint8_t* dmat_full,
+                              const float* bounds, float* prevMatched, int32_t* matches12, int window, float nnratio,
+                              int checkOri) {
+    std::vector<int> rows(n1), cols(n2);
+    for (int i = 0; i < n1; i++) rows[i] = i;
+    for (int i = 0; i < n2; i++) cols[i] = i;
+    return vslam::search_for_initialization_replay(kps1, n1, kps2, n2, dmat_full, rows.data(), cols.data(), n2,
+                                                   bounds, prevMatched, matches12, window, nnratio, checkOri != 0);
+}
+
+/* cv::undistortPoints as Frame::UndistortKeyPoints applies it (k1 == 0: unchanged), the shared vslam_undistort.h code:
+ * cam = fx, fy, cx, cy; dist = ndist (4 or 5) coefficients; xy / out = n interleaved points */
+int vslamh_undistort_points(const float* cam, const float* dist, int ndist, const float* xy, int n, float* out) {
+    if (ndist != 4 && ndist != 5) return -1;
+    float d[5] = {0, 0, 0, 0, 0};
+    for (int i = 0; i < ndist; i++) d[i] = dist[i];
+    for (int i = 0; i < n; i++) vslam_ud::frame_undistort(xy[2 * i], xy[2 * i + 1], cam, d, &out[2 * i], &out[2 * i + 1]);
+    return 0;
+}
+
+/* Frame::ComputeImageBounds of a cols x rows image: minX, maxX, minY, maxY */
+int vslamh_image_bounds(const float* cam, const float* dist, int ndist, int cols, int rows, float* b) {
+    if (ndist != 4 && ndist != 5) return -1;
+    float d[5] = {0, 0, 0, 0, 0};
+    for (int i = 0; i < ndist; i++) d[i] = dist[i];
+    vslam_ud::image_bounds(cam, d, cols, rows, b);
+    return 0;
 }
 
 /* quadtree path tables of k_octree_v4 against the literal halvings: returns the number of (x, y) whose table path differs */

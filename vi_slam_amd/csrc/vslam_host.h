@@ -134,16 +134,18 @@ struct FrameGrid {
     std::vector<int> cell_items;
     const vslam_kp* kps;
     int n;
-    void build(const vslam_kp* k, int n_, int imgW, int imgH);
+    void build(const vslam_kp* k, int n_, int imgW, int imgH); /* bounds {0, imgW, 0, imgH} */
+    void build(const vslam_kp* k, int n_, const float bounds[4]); /* minX, maxX, minY, maxY (ComputeImageBounds) */
     void query(float x, float y, float r, int minLevel, int maxLevel, std::vector<int>& out) const;
 };
 
-/* FMatcher::SearchForInitialization (fmatcher.cpp:983-1098) sequential replay.  dist(i1,i2) is read
+/* FMatcher::SearchForInitialization (fmatcher.cpp:983-1098) sequential replay over frame 2's grid with the float
+ * bounds minX, maxX, minY, maxY (vslam_bounds order).  dist(i1,i2) is read
  * from a dense matrix over the octave-0 keypoints of both frames: row r of `dmat` belongs to l0_1[r],
  * column c to l0_2[c] (map2[i2] = column or -1). */
 int search_for_initialization_replay(const vslam_kp* kps1, int n1, const vslam_kp* kps2, int n2,
                                      const uint8_t* dmat, const int* row_of_i1, const int* col_of_i2,
-                                     int ncols, int imgW, int imgH, float* prevMatched, int32_t* matches12,
+                                     int ncols, const float bounds[4], float* prevMatched, int32_t* matches12,
                                      int windowSize, float nnratio, bool checkOri);
 
 } // namespace vslam

@@ -69,6 +69,19 @@ __device__ __forceinline__ SiWindow si_window(float px, float py, float r, float
     w.empty = w.minX >= SI_GRID_COLS || w.maxX < 0 || w.minY >= SI_GRID_ROWS || w.maxY < 0;
     return w;
 }
+/* the same with float grid bounds (frame.cpp:686-708 with mnMinX / mnMinY): floor((x - minX - r) * inv), left to right.
+ * With minX = minY = 0 every value equals si_window's bit for bit (x - 0.0f == x), which the SearchByProjection / Fuse /
+ * Sim3 kernels keep using. */
+__device__ __forceinline__ SiWindow si_window_b(float px, float py, float r, const SiBounds& b, float invW, float invH) {
+    SiWindow w;
+    const float dx = __fsub_rn(px, b.minX), dy = __fsub_rn(py, b.minY);
+    w.minX = max(0, (int)floorf(__fmul_rn(__fsub_rn(dx, r), invW)));
+    w.maxX = min(SI_GRID_COLS - 1, (int)ceilf(__fmul_rn(__fadd_rn(dx, r), invW)));
+    w.minY = max(0, (int)floorf(__fmul_rn(__fsub_rn(dy, r), invH)));
+    w.maxY = min(SI_GRID_ROWS - 1, (int)ceilf(__fmul_rn(__fadd_rn(dy, r), invH)));
+    w.empty = w.minX >= SI_GRID_COLS || w.maxX < 0 || w.minY >= SI_GRID_ROWS || w.maxY < 0;
+    return w;
+}
 __device__ __forceinline__ bool si_in_window(const SiCand& cd, const SiWindow& w, float px, float py, float r) {
     const int gx = cd.cell >> 6, gy = cd.cell & 63;
     if (gx < w.minX || gx > w.maxX || gy < w.minY || gy > w.maxY) return false;
@@ -92,7 +105,7 @@ __device__ __forceinline__ uint32_t si_hamming(const uint4& da, const uint4& db,
  * candidates of its own queries.  Chunk 0 also publishes the compacted candidate list and the counts.
  * ---------------------------------------------------------------------------------------------- */
 __global__ void __launch_bounds__(256)
-k_si_topm(InitJobs jobs, int cap, int imgW, int imgH, int window, int max_c2, int M, uint8_t* scratch, int SI_QPB, int prio) {
+k_si_topm(InitJobs jobs, int cap, SiBounds bnd, int window, int max_c2, int M, uint8_t* scratch, int SI_QPB, int prio) {
     extern __shared__ __align__(16) uint8_t sism[];
     wave_prio_raise(prio);
     SiCandL* cand = (SiCandL*)sism;                  /* max_c2, sorted by grid column */
@@ -115,9 +128,10 @@ k_si_topm(InitJobs jobs, int cap, int imgW, int imgH, int window, int max_c2, in
     uint32_t* topm = (uint32_t*)(gqry + max_c2);
     const int q0 = blockIdx.x * SI_QPB;
 
-    /* Frame grid of frame 2 (frame.cpp:322-323, 746-756): mnMinX = 0, mnMaxX = cols (no distortion) */
-    const float invW = __fdiv_rn((float)SI_GRID_COLS, (float)imgW);
-    const float invH = __fdiv_rn((float)SI_GRID_ROWS, (float)imgH);
+    /* Frame grid of frame 2 (frame.cpp:322-323, 746-756): (float)64 / (mnMaxX - mnMinX); {0, cols, 0, rows} without
+     * distortion, where (float)cols - 0.0f == (float)cols */
+    const float invW = __fdiv_rn((float)SI_GRID_COLS, __fsub_rn(bnd.maxX, bnd.minX));
+    const float invH = __fdiv_rn((float)SI_GRID_ROWS, __fsub_rn(bnd.maxY, bnd.minY));
 
     int c2 = 0;
     for (int b = 0; b < n2; b += 256) {
@@ -128,9 +142,11 @@ k_si_topm(InitJobs jobs, int cap, int imgW, int imgH, int window, int max_c2, in
         if (i < n2) {
             k = jb.k2[i];
             if (k.octave == 0) {
-                gx = (int)roundf(__fmul_rn(k.x, invW));
-                gy = (int)roundf(__fmul_rn(k.y, invH));
-                take = !(gx < 0 || gx >= SI_GRID_COLS || gy < 0 || gy >= SI_GRID_ROWS); /* PosInGrid */
+                /* PosInGrid: undistorted keypoints may lie left of / above the image or beyond it; they are rejected here,
+                 * before anything is packed into the u16 cell or the 12-bit key field */
+                gx = (int)roundf(__fmul_rn(__fsub_rn(k.x, bnd.minX), invW));
+                gy = (int)roundf(__fmul_rn(__fsub_rn(k.y, bnd.minY), invH));
+                take = !(gx < 0 || gx >= SI_GRID_COLS || gy < 0 || gy >= SI_GRID_ROWS);
             }
         }
         const unsigned long long m = __ballot(take);
@@ -220,7 +236,7 @@ k_si_topm(InitJobs jobs, int cap, int imgW, int imgH, int window, int max_c2, in
     uint32_t* wk = wkeys + (size_t)wave * max_c2;
     for (int t = q0 + wave; t < min(c1, q0 + SI_QPB); t += 4) {
         const SiQuery qq = s_q[t - q0];
-        const SiWindow win = si_window(qq.px, qq.py, r, invW, invH);
+        const SiWindow win = si_window_b(qq.px, qq.py, r, bnd, invW, invH);
         uint32_t mine = 0xFFFFFFFFu; /* lane j < M ends up with the j-th smallest key */
         if (!win.empty) {
             const uint4 da = ((const uint4*)jb.d1)[(size_t)qq.idx * 2];
@@ -278,8 +294,9 @@ __device__ __forceinline__ uint32_t sir_od_eff(const uint4 L, uint32_t q) {
 /* Full re-scan of one query's window (the reference loop body, fmatcher.cpp:1003-1035) by ONE wave: used when the query's
  * sorted prefix ran out.  Returns the best key; *second_out = bestDist2 (0x7FFFFFFF if none). */
 __device__ uint32_t si_full_scan(const InitJob& jb, const SiCand* gcand, const uint4* slotlog, int c2, int lane,
-                                 const SiQuery& qq, uint32_t qpos, float r, float invW, float invH, uint32_t* second_out) {
-    const SiWindow win = si_window(qq.px, qq.py, r, invW, invH);
+                                 const SiQuery& qq, uint32_t qpos, float r, const SiBounds& bnd, float invW, float invH,
+                                 uint32_t* second_out) {
+    const SiWindow win = si_window_b(qq.px, qq.py, r, bnd, invW, invH);
     uint32_t bestKey = 0xFFFFFFFFu, second = 0x7FFFFFFFu; /* per lane: best key, smallest other distance */
     if (!win.empty) {
         const uint4 da = ((const uint4*)jb.d1)[(size_t)qq.idx * 2];
@@ -357,7 +374,7 @@ __device__ __forceinline__ bool sir_slot_append(uint4* slotlog, uint32_t slot, u
 #define SIR_SCAN 4u
 template <int MAXM> /* unrolled length of a query's sorted prefix: 8 (the default M) or SI_MAX_M */
 __global__ void __launch_bounds__(SIR_NT)
-k_si_replay(InitJobs jobs, int cap, int imgW, int imgH, int window, float nnratio, int checkOri,
+k_si_replay(InitJobs jobs, int cap, SiBounds bnd, int window, float nnratio, int checkOri,
             int32_t* matches_out /* [pair][cap] */, float* prev_out /* [pair][2*cap] */,
             int32_t* nmatch_out /* [pair] */, int max_c2, int M, const uint8_t* scratch, int* fallbacks, int keys_lds_bytes,
             int prio) {
@@ -393,8 +410,8 @@ k_si_replay(InitJobs jobs, int cap, int imgW, int imgH, int window, float nnrati
 
     int32_t* mo = matches_out + (size_t)blockIdx.x * cap;
     float* po = prev_out + (size_t)blockIdx.x * cap * 2;
-    const float invW = __fdiv_rn((float)SI_GRID_COLS, (float)imgW);
-    const float invH = __fdiv_rn((float)SI_GRID_ROWS, (float)imgH);
+    const float invW = __fdiv_rn((float)SI_GRID_COLS, __fsub_rn(bnd.maxX, bnd.minX));
+    const float invH = __fdiv_rn((float)SI_GRID_ROWS, __fsub_rn(bnd.maxY, bnd.minY));
     const float r = (float)window;
 
     for (int c = tid; c < c2; c += SIR_NT) {
@@ -501,7 +518,7 @@ k_si_replay(InitJobs jobs, int cap, int imgW, int imgH, int window, float nnrati
         if (sq >= 0) { /* block-uniform */
             if (tid < 64) {
                 uint32_t d2;
-                const uint32_t gb = si_full_scan(jb, gcand, slotlog, c2, lane, gqry[sq], (uint32_t)sq, r, invW, invH, &d2);
+                const uint32_t gb = si_full_scan(jb, gcand, slotlog, c2, lane, gqry[sq], (uint32_t)sq, r, bnd, invW, invH, &d2);
                 if (tid == 0) {
                     if (gb != 0xFFFFFFFFu && (gb >> 24) <= SI_TH_LOW && (float)(int)(gb >> 24) < __fmul_rn((float)(int)d2, nnratio)) {
                         sir_slot_append(slotlog, gb & 0xFFFu, (uint32_t)sq, gb >> 24, true);
@@ -630,7 +647,7 @@ int vk_search_init_set_max_lds(size_t bytes) {
     return (int)hipFuncSetAttribute((const void*)k_si_replay<SI_MAX_M>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
-void vk_search_init(hipStream_t st, const InitJobs& jobs, int npairs, int cap, int imgW, int imgH, int window,
+void vk_search_init(hipStream_t st, const InitJobs& jobs, int npairs, int cap, const SiBounds& bounds, int window,
                     float nnratio, int checkOri, int32_t* matches_out, float* prev_out, int32_t* nmatch_out,
                     int max_c2, int M, uint8_t* scratch, int* fallbacks, const vslam_tuning& T) {
     if (npairs <= 0) return;
@@ -640,17 +657,17 @@ void vk_search_init(hipStream_t st, const InitJobs& jobs, int npairs, int cap, i
     const int qpb = (qv == 8 || qv == 16 || qv == 32) ? qv : 16;
     const int chunks = (max_c2 + qpb - 1) / qpb;
     const int prio = T.wave_prio > 0 && (T.wave_prio & 4) ? 1 : 0;
-    hipLaunchKernelGGL(k_si_topm, dim3(chunks, npairs), dim3(256), si_topm_lds(max_c2), st, jobs, cap, imgW, imgH,
+    hipLaunchKernelGGL(k_si_topm, dim3(chunks, npairs), dim3(256), si_topm_lds(max_c2), st, jobs, cap, bounds,
                        window, max_c2, M, scratch, qpb, prio);
     /* the key cache only if the whole allocation stays within what vk_search_init_set_max_lds allowed (150 KB) */
     int keys_lds = (int)si_replay_keys_lds(max_c2, M);
     if (si_replay_lds(cap, max_c2, M) > (150u << 10)) keys_lds = 0;
     const size_t rlds = keys_lds ? si_replay_lds(cap, max_c2, M) : si_replay_lds(cap, max_c2);
     if (M <= 8)
-        hipLaunchKernelGGL(k_si_replay<8>, dim3(npairs), dim3(SIR_NT), rlds, st, jobs, cap, imgW, imgH,
+        hipLaunchKernelGGL(k_si_replay<8>, dim3(npairs), dim3(SIR_NT), rlds, st, jobs, cap, bounds,
                            window, nnratio, checkOri, matches_out, prev_out, nmatch_out, max_c2, M, scratch, fallbacks, keys_lds, prio);
     else
-        hipLaunchKernelGGL(k_si_replay<SI_MAX_M>, dim3(npairs), dim3(SIR_NT), rlds, st, jobs, cap, imgW, imgH,
+        hipLaunchKernelGGL(k_si_replay<SI_MAX_M>, dim3(npairs), dim3(SIR_NT), rlds, st, jobs, cap, bounds,
                            window, nnratio, checkOri, matches_out, prev_out, nmatch_out, max_c2, M, scratch, fallbacks, keys_lds, prio);
 }
 

@@ -79,7 +79,7 @@ size_t vk_search_init_lds(int cap, int max_c2);
 size_t vk_search_init_scratch_bytes(int npairs, int max_c2, int M);
 int vk_search_init_set_max_lds(size_t bytes);
 /* k_si_topm + k_si_replay; scratch = vk_search_init_scratch_bytes(); fallbacks (nullable) counts full re-scans */
-void vk_search_init(hipStream_t st, const InitJobs& jobs, int npairs, int cap, int imgW, int imgH, int window,
+void vk_search_init(hipStream_t st, const InitJobs& jobs, int npairs, int cap, const SiBounds& bounds, int window,
                     float nnratio, int checkOri, int32_t* matches_out, float* prev_out, int32_t* nmatch_out,
                     int max_c2, int M, uint8_t* scratch, int* fallbacks, const vslam_tuning& T);
 /* FMatcher::SearchByProjection(CurrentFrame, LastFrame): k_sbp_rank + k_sbp_replay over up to
@@ -99,6 +99,12 @@ void vk_reset_headers(hipStream_t st, uint8_t* d_cand, size_t cand_stride_bytes,
 /* device -> pinned host (or device) range copies / zero fills in one launch; see k_copy_ranges */
 /* returns the number of copy operations put on the stream (runtime copies or one kernel launch) */
 int vk_copy_ranges(hipStream_t st, const CopyRanges& R, const vslam_tuning& T = vslam_process_tuning());
+/* cv::undistortPoints of every keypoint of slots 0..nimg-1 (counts[s*4] keypoints each, cap apart): full vslam_kp copies
+ * with x, y replaced (vslam_undistort.hip) */
+void vk_undistort_kps(hipStream_t st, const vslam_kp* kps, const int32_t* counts, vslam_kp* ukps, int cap, int nimg,
+                      const UdCam& cam);
+/* the same arithmetic on n loose points (x, y interleaved) */
+void vk_undistort_xy(hipStream_t st, const float* xy, int n, float* out, const UdCam& cam);
 /* host (pinned) images -> level 0 of the slots, one launch; src.l0 / src.pitch0 describe the host rows */
 void vk_pull_images(hipStream_t st, const BatchSrc& src, uint8_t* pyr, size_t slot_stride, uint32_t off0, int dpitch,
                     int w, int h, int nimg, int from_host, const vslam_tuning& T);

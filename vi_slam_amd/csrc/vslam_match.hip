@@ -212,8 +212,18 @@ static int init_scratch(vslam_fe* fe, int npairs) {
     return VSLAM_OK;
 }
 
-extern "C" int vslam_search_init_dev_async(vslam_fe* fe, int npairs, const vslam_init_job* jobs, int img_w,
-                                           int img_h, int window, float nnratio, int check_orientation) {
+/* the grid bounds of the _ex entry points: finite, non-empty (the reference divides by mnMaxX - mnMinX) */
+static bool bounds_ok(const vslam_bounds* b) {
+    return b && std::isfinite(b->min_x) && std::isfinite(b->max_x) && std::isfinite(b->min_y) && std::isfinite(b->max_y) &&
+           b->max_x > b->min_x && b->max_y > b->min_y;
+}
+/* The img_w / img_h entry points pass {0, (float)img_w, 0, (float)img_h}: with mnMinX = mnMinY = 0 every expression of
+ * the float-bounds matcher -- x - 0.0f, (float)W - 0.0f, the window and PosInGrid -- equals the integer-bounds one bit for
+ * bit, so their results do not change. */
+static SiBounds int_bounds(int img_w, int img_h) { return SiBounds{0.0f, (float)img_w, 0.0f, (float)img_h}; }
+
+static int search_init_dev_async_b(vslam_fe* fe, int npairs, const vslam_init_job* jobs, const SiBounds& bnd, int window,
+                                   float nnratio, int check_orientation) {
     if (!fe || npairs < 1 || npairs > VSLAM_MAX_MAT_JOBS || !jobs) {
         g_err = "invalid arguments";
         return VSLAM_ERR_INVALID;
@@ -273,7 +283,7 @@ extern "C" int vslam_search_init_dev_async(vslam_fe* fe, int npairs, const vslam
     int32_t* d_m = (int32_t*)fe->d_init;
     float* d_p = (float*)(d_m + nm);
     int32_t* d_n = (int32_t*)(d_p + 2 * nm);
-    vk_search_init(fe->stream, J, npairs, fe->cap, img_w, img_h, window, nnratio, check_orientation, d_m, d_p, d_n,
+    vk_search_init(fe->stream, J, npairs, fe->cap, bnd, window, nnratio, check_orientation, d_m, d_p, d_n,
                    max_c2, M, fe->d_init_scratch, fe->d_init_fb, fe->tune);
     HIPCHK(hipGetLastError());
     CopyRanges R;
@@ -295,6 +305,21 @@ extern "C" int vslam_search_init_dev_async(vslam_fe* fe, int npairs, const vslam
     HIPCHK(hipGetLastError());
     fe->init_pairs = npairs;
     return VSLAM_OK;
+}
+
+extern "C" int vslam_search_init_dev_async(vslam_fe* fe, int npairs, const vslam_init_job* jobs, int img_w,
+                                           int img_h, int window, float nnratio, int check_orientation) {
+    return search_init_dev_async_b(fe, npairs, jobs, int_bounds(img_w, img_h), window, nnratio, check_orientation);
+}
+
+extern "C" int vslam_search_init_dev_async_ex(vslam_fe* fe, int npairs, const vslam_init_job* jobs, const vslam_bounds* b,
+                                              int window, float nnratio, int check_orientation) {
+    if (!bounds_ok(b)) {
+        g_err = "invalid image bounds";
+        return VSLAM_ERR_INVALID;
+    }
+    return search_init_dev_async_b(fe, npairs, jobs, SiBounds{b->min_x, b->max_x, b->min_y, b->max_y}, window, nnratio,
+                                   check_orientation);
 }
 
 extern "C" int vslam_search_init_dev_wait(vslam_fe* fe, const int* n1, int32_t* const* matches12,
@@ -326,13 +351,10 @@ extern "C" int vslam_search_init_dev_wait(vslam_fe* fe, const int* n1, int32_t* 
 }
 
 /* ------------------------------------------------------------------ SearchForInitialization */
-extern "C" int vslam_search_for_initialization_batch(vslam_fe* fe, int npairs, const vslam_kp* const* kps1,
-                                                     const uint8_t* const* dev_desc1, const int* n1,
-                                                     const vslam_kp* const* kps2, const uint8_t* const* dev_desc2,
-                                                     const int* n2, int img_w, int img_h,
-                                                     float* const* prev_matched, int32_t* const* matches12,
-                                                     int window, float nnratio, int check_orientation,
-                                                     int* nmatches) {
+static int search_init_batch_b(vslam_fe* fe, int npairs, const vslam_kp* const* kps1, const uint8_t* const* dev_desc1,
+                               const int* n1, const vslam_kp* const* kps2, const uint8_t* const* dev_desc2, const int* n2,
+                               const SiBounds& bnd, float* const* prev_matched, int32_t* const* matches12, int window,
+                               float nnratio, int check_orientation, int* nmatches) {
     if (!fe || npairs < 1 || npairs > VSLAM_MAX_MAT_JOBS || !kps1 || !dev_desc1 || !n1 || !kps2 || !dev_desc2 ||
         !n2 || !prev_matched || !matches12 || !nmatches) {
         g_err = "invalid arguments";
@@ -390,7 +412,7 @@ extern "C" int vslam_search_for_initialization_batch(vslam_fe* fe, int npairs, c
             }
             HIPCHK(hipMemcpyAsync(fe->d_tmp_desc[1], stage.data(), off, hipMemcpyHostToDevice, fe->stream));
             HIPCHK(vslam_stream_wait(fe->stream)); /* stage is pageable and goes out of scope */
-            rc = vslam_search_init_dev_async(fe, npairs, jobs.data(), img_w, img_h, window, nnratio, check_orientation);
+            rc = search_init_dev_async_b(fe, npairs, jobs.data(), bnd, window, nnratio, check_orientation);
             if (rc) return rc;
             return vslam_search_init_dev_wait(fe, n1, matches12, prev_matched, nmatches);
         }
@@ -443,20 +465,45 @@ extern "C" int vslam_search_for_initialization_batch(vslam_fe* fe, int npairs, c
     }
     /* the stealing / ratio / rotation-histogram logic is order dependent: replayed on the host, one
      * pair per worker */
+    const float hb[4] = {bnd.minX, bnd.maxX, bnd.minY, bnd.maxY};
     fe->pool->parallel_for(npairs, [&](int j) {
         const MatJob& jb = jobs.job[j];
         nmatches[j] = vslam::search_for_initialization_replay(
             kps1[j], n1[j], kps2[j], n2[j], dmat.data() + jb.out_off, row_of[j].data(), col_of[j].data(),
-            std::max(jb.nc, 1), img_w, img_h, prev_matched[j], matches12[j], window, nnratio, check_orientation != 0);
+            std::max(jb.nc, 1), hb, prev_matched[j], matches12[j], window, nnratio, check_orientation != 0);
     });
     return VSLAM_OK;
 }
 
-extern "C" int vslam_search_for_initialization(vslam_fe* fe, const vslam_kp* kps1, const uint8_t* dev_desc1,
-                                               int n1, const vslam_kp* kps2, const uint8_t* dev_desc2, int n2,
-                                               int img_w, int img_h, float* prev_matched, int32_t* matches12,
-                                               int window, float nnratio, int check_orientation,
-                                               int* nmatches) {
+extern "C" int vslam_search_for_initialization_batch(vslam_fe* fe, int npairs, const vslam_kp* const* kps1,
+                                                     const uint8_t* const* dev_desc1, const int* n1,
+                                                     const vslam_kp* const* kps2, const uint8_t* const* dev_desc2,
+                                                     const int* n2, int img_w, int img_h,
+                                                     float* const* prev_matched, int32_t* const* matches12,
+                                                     int window, float nnratio, int check_orientation,
+                                                     int* nmatches) {
+    return search_init_batch_b(fe, npairs, kps1, dev_desc1, n1, kps2, dev_desc2, n2, int_bounds(img_w, img_h), prev_matched,
+                               matches12, window, nnratio, check_orientation, nmatches);
+}
+
+extern "C" int vslam_search_for_initialization_batch_ex(vslam_fe* fe, int npairs, const vslam_kp* const* kps1,
+                                                        const uint8_t* const* dev_desc1, const int* n1,
+                                                        const vslam_kp* const* kps2, const uint8_t* const* dev_desc2,
+                                                        const int* n2, const vslam_bounds* b, float* const* prev_matched,
+                                                        int32_t* const* matches12, int window, float nnratio,
+                                                        int check_orientation, int* nmatches) {
+    if (!bounds_ok(b)) {
+        g_err = "invalid image bounds";
+        return VSLAM_ERR_INVALID;
+    }
+    return search_init_batch_b(fe, npairs, kps1, dev_desc1, n1, kps2, dev_desc2, n2,
+                               SiBounds{b->min_x, b->max_x, b->min_y, b->max_y}, prev_matched, matches12, window, nnratio,
+                               check_orientation, nmatches);
+}
+
+static int search_init_single_b(vslam_fe* fe, const vslam_kp* kps1, const uint8_t* dev_desc1, int n1, const vslam_kp* kps2,
+                                const uint8_t* dev_desc2, int n2, const SiBounds& bnd, float* prev_matched,
+                                int32_t* matches12, int window, float nnratio, int check_orientation, int* nmatches) {
     /* the reference tolerates empty frames: nothing to match */
     static const vslam_kp no_kp = {0, 0, 0, 0, 0, 0, 0};
     static const uint8_t* no_desc = (const uint8_t*)&no_kp;
@@ -468,8 +515,29 @@ extern "C" int vslam_search_for_initialization(vslam_fe* fe, const vslam_kp* kps
     const uint8_t* d2 = n2 ? dev_desc2 : no_desc;
     float* pm = n1 ? prev_matched : no_prev;
     int32_t* m = n1 ? matches12 : no_match;
-    return vslam_search_for_initialization_batch(fe, 1, &k1, &d1, &n1, &k2, &d2, &n2, img_w, img_h, &pm, &m, window,
-                                                 nnratio, check_orientation, nmatches);
+    return search_init_batch_b(fe, 1, &k1, &d1, &n1, &k2, &d2, &n2, bnd, &pm, &m, window, nnratio, check_orientation,
+                               nmatches);
+}
+
+extern "C" int vslam_search_for_initialization(vslam_fe* fe, const vslam_kp* kps1, const uint8_t* dev_desc1,
+                                               int n1, const vslam_kp* kps2, const uint8_t* dev_desc2, int n2,
+                                               int img_w, int img_h, float* prev_matched, int32_t* matches12,
+                                               int window, float nnratio, int check_orientation,
+                                               int* nmatches) {
+    return search_init_single_b(fe, kps1, dev_desc1, n1, kps2, dev_desc2, n2, int_bounds(img_w, img_h), prev_matched,
+                                matches12, window, nnratio, check_orientation, nmatches);
+}
+
+extern "C" int vslam_search_for_initialization_ex(vslam_fe* fe, const vslam_kp* kps1, const uint8_t* dev_desc1, int n1,
+                                                  const vslam_kp* kps2, const uint8_t* dev_desc2, int n2,
+                                                  const vslam_bounds* b, float* prev_matched, int32_t* matches12,
+                                                  int window, float nnratio, int check_orientation, int* nmatches) {
+    if (!bounds_ok(b)) {
+        g_err = "invalid image bounds";
+        return VSLAM_ERR_INVALID;
+    }
+    return search_init_single_b(fe, kps1, dev_desc1, n1, kps2, dev_desc2, n2, SiBounds{b->min_x, b->max_x, b->min_y, b->max_y},
+                                prev_matched, matches12, window, nnratio, check_orientation, nmatches);
 }
 
 /* ------------------------------------------------------------------ diagnostics */

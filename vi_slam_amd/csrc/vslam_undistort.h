@@ -1,0 +1,129 @@
+/* vslam_undistort.h -- cv::undistortPoints(src, dst, K, D, noArray(), K) of OpenCV 4.2 for one point, written once for
+ * the device (k_undistort_kps, vslam_undistort.hip) and the host (vslam_host.cpp, image bounds, CPU tests).
+ *
+ * What the reference calls (frame.cpp:758-790 UndistortKeyPoints, :793-821 ComputeImageBounds) lands in
+ * cvUndistortPointsInternal with TermCriteria(MAX_ITER, 5, 0.01): exactly five fixed-point iterations, no EPS test,
+ * everything in double.  K is CV_32F (Pinhole::toK), D is CV_32F k1,k2,p1,p2[,k3]; both are converted to double first.
+ * The tilt matrix is the identity, R is empty and P = K, so the final projection is fx*x + 0*y + cx over 0*x + 0*y + 1.
+ * The expressions below keep OpenCV's literal order (including the terms of the 14-coefficient model that are zero
+ * here), so a host build and a device build round identically.
+ *
+ * Contraction: on the device every operation goes through the _rn intrinsics, which the compiler may not fuse;
+ * host builds rely on -ffp-contract=off (vi_slam_amd/csrc/Makefile).  No reciprocal approximations: 1./fx is a
+ * correctly rounded division on both sides.
+ *
+ * The sequence is OpenCV 4.2 as recalled, not pinned against a real OpenCV build (oracle section;
+ * tools/dump_opencv_undistort.cpp settles it).
+ */
+#ifndef VSLAM_UNDISTORT_H
+#define VSLAM_UNDISTORT_H
+
+#if defined(__HIPCC__)
+#define VSLAM_UD_HD __host__ __device__ inline __attribute__((always_inline))
+#else
+#define VSLAM_UD_HD static inline
+#endif
+
+namespace vslam_ud {
+
+VSLAM_UD_HD double mul(double a, double b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __dmul_rn(a, b);
+#else
+    return a * b;
+#endif
+}
+VSLAM_UD_HD double add(double a, double b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __dadd_rn(a, b);
+#else
+    return a + b;
+#endif
+}
+VSLAM_UD_HD double sub(double a, double b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __dsub_rn(a, b);
+#else
+    return a - b;
+#endif
+}
+VSLAM_UD_HD double dvd(double a, double b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __ddiv_rn(a, b);
+#else
+    return a / b;
+#endif
+}
+
+/* cv::undistortPoints of one point: cam = fx, fy, cx, cy (float, as in the CV_32F K); dist = 5 coefficients
+ * k1, k2, p1, p2, k3 (k3 = 0 for a 4-coefficient model) */
+VSLAM_UD_HD void undistort_point(float px, float py, const float* cam, const float* dist, float* ox, float* oy) {
+    const double fx = (double)cam[0], fy = (double)cam[1], cx = (double)cam[2], cy = (double)cam[3];
+    const double ifx = dvd(1., fx), ify = dvd(1., fy);
+    double k[14];
+    for (int i = 0; i < 14; i++) k[i] = 0.;
+    for (int i = 0; i < 5; i++) k[i] = (double)dist[i];
+    const double u = (double)px, v = (double)py;
+    double x = u, y = v;
+    x = mul(sub(x, cx), ifx);
+    y = mul(sub(y, cy), ify);
+    const double x0 = x, y0 = y; /* tilt compensation with the identity */
+    for (int j = 0; j < 5; j++) {
+        const double r2 = add(mul(x, x), mul(y, y));
+        const double icdist = dvd(add(1., mul(add(mul(add(mul(k[7], r2), k[6]), r2), k[5]), r2)),
+                                  add(1., mul(add(mul(add(mul(k[4], r2), k[1]), r2), k[0]), r2)));
+        if (icdist < 0) { /* OpenCV issue 14583 (4.1.1+): give up, keep the undistorted-by-nothing point */
+            x = mul(sub(u, cx), ifx);
+            y = mul(sub(v, cy), ify);
+            break;
+        }
+        /* 2*k[2]*x*y + k[3]*(r2 + 2*x*x) + k[8]*r2 + k[9]*r2*r2 */
+        const double deltaX = add(add(add(mul(mul(mul(2., k[2]), x), y), mul(k[3], add(r2, mul(mul(2., x), x)))),
+                                      mul(k[8], r2)),
+                                  mul(mul(k[9], r2), r2));
+        /* k[2]*(r2 + 2*y*y) + 2*k[3]*x*y + k[10]*r2 + k[11]*r2*r2 */
+        const double deltaY = add(add(add(mul(k[2], add(r2, mul(mul(2., y), y))), mul(mul(mul(2., k[3]), x), y)),
+                                      mul(k[10], r2)),
+                                  mul(mul(k[11], r2), r2));
+        x = mul(sub(x0, deltaX), icdist);
+        y = mul(sub(y0, deltaY), icdist);
+    }
+    /* R = I, P = K: RR = K */
+    const double xx = add(add(mul(fx, x), mul(0., y)), cx);
+    const double yy = add(add(mul(0., x), mul(fy, y)), cy);
+    const double ww = dvd(1., add(add(mul(0., x), mul(0., y)), 1.));
+    *ox = (float)mul(xx, ww);
+    *oy = (float)mul(yy, ww);
+}
+
+/* Frame::UndistortKeyPoints' test (frame.cpp:762): only k1 decides.  k1 == 0 -> ukeypoints_ = keypoints_, whatever
+ * k2, p1, p2, k3 hold. */
+VSLAM_UD_HD void frame_undistort(float px, float py, const float* cam, const float* dist, float* ox, float* oy) {
+    if (dist[0] == 0.0f) {
+        *ox = px;
+        *oy = py;
+        return;
+    }
+    undistort_point(px, py, cam, dist, ox, oy);
+}
+
+/* Frame::ComputeImageBounds (frame.cpp:793-821) for a cols x rows image: b = minX, maxX, minY, maxY */
+VSLAM_UD_HD void image_bounds(const float* cam, const float* dist, int cols, int rows, float* b) {
+    if (dist[0] == 0.0f) {
+        b[0] = 0.0f;
+        b[1] = (float)cols;
+        b[2] = 0.0f;
+        b[3] = (float)rows;
+        return;
+    }
+    const float px[4] = {0.0f, (float)cols, 0.0f, (float)cols}, py[4] = {0.0f, 0.0f, (float)rows, (float)rows};
+    float ux[4], uy[4];
+    for (int i = 0; i < 4; i++) undistort_point(px[i], py[i], cam, dist, &ux[i], &uy[i]);
+    b[0] = ux[2] < ux[0] ? ux[2] : ux[0]; /* std::min(a, b): b < a ? b : a */
+    b[1] = ux[1] < ux[3] ? ux[3] : ux[1]; /* std::max(a, b): a < b ? b : a */
+    b[2] = uy[1] < uy[0] ? uy[1] : uy[0];
+    b[3] = uy[2] < uy[3] ? uy[3] : uy[2];
+}
+
+} // namespace vslam_ud
+#endif
