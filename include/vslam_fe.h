@@ -61,12 +61,12 @@ typedef struct vslam_kp {
 typedef struct vslam_tuning {
     int32_t pyramid_per_level;    /* VSLAM_PYRAMID=levels: 1 = one launch per pyramid level instead of the fused groups */
     int32_t pyr_rows;             /* VSLAM_PYR_ROWS: rows of the first computed level per fused-pyramid tile (4..64, default 28) */
-    int32_t pyr_threads;          /* VSLAM_PYR_NT: 256 | 512 threads per fused-pyramid tile (default 256) */
+    int32_t pyr_threads;          /* retired: accepted and ignored (the fused pyramid runs 256 threads per tile) */
     int32_t blur_rows;            /* VSLAM_BLUR_ROWS: output rows per wave task of the blur (8..512, default 32) */
-    int32_t fast_threads;         /* VSLAM_FAST_NT: 64 | 128 | 256 threads per FAST cell (default 128) */
-    int32_t fast_pitch;           /* VSLAM_FAST_PITCH: 72 forces the wide LDS pitch of the FAST window */
-    int32_t fast_lds_pad;         /* VSLAM_FAST_LDS_PAD: extra LDS bytes per FAST workgroup (occupancy experiments) */
-    int32_t octree_walk_kernel;   /* VSLAM_OCTREE=v2: 1 = the walk-per-pass quadtree kernel only */
+    int32_t fast_threads;         /* retired: accepted and ignored (128 threads per FAST cell) */
+    int32_t fast_pitch;           /* retired: accepted and ignored */
+    int32_t fast_lds_pad;         /* retired: accepted and ignored */
+    int32_t octree_walk_kernel;   /* retired: accepted and ignored */
     int32_t oct_fine_depth;       /* VSLAM_OCT_FINE_D: depth of the one-walk kernel's fine grid (tests force 1 or 3) */
     int32_t oct_lds_budget_kb;    /* VSLAM_OCT_LDS_BUDGET_KB: LDS a quadtree workgroup may take (16..150, default 128) */
     int32_t oct_regkeys;          /* VSLAM_OCT_REGKEYS: 0 | 1 keys in registers between the key walks (default: batches <= 2) */
@@ -100,11 +100,8 @@ typedef struct vslam_tuning {
                                      window (k_fast_bands; default for batches) */
     int32_t fast_band_cells;      /* VSLAM_FAST_BAND_CELLS: cells per band of k_fast_bands (1..4, default 4; fewer where 4 cell
                                      interiors are wider than 128 px) */
-    int32_t wave_prio;            /* VSLAM_WAVE_PRIO: bit mask of kernel classes that raise their wave priority (s_setprio 3)
-                                     at entry: 1 = quadtree + output order, 2 = orientation/descriptors, 4 = matchers
-                                     (k_si_*, k_stereo_*), 8 = result packing; default 0 */
-    int32_t oct_precount;         /* VSLAM_OCT_PRECOUNT: 1 = the quadtree's counting walk as a launch of its own with a level's keys dealt
-                                     to up to eight workgroups (k_oct_count); 0 (default) = inside the quadtree workgroup */
+    int32_t wave_prio;            /* retired: accepted and ignored */
+    int32_t oct_precount;         /* retired: accepted and ignored */
     int32_t desc_kpw;             /* VSLAM_DESC_KPW: 1 | 4 keypoints per wave of the descriptor kernel (default: 1 for contexts of one or
                                      two images, else 4) */
     int32_t reserved[1];
@@ -135,7 +132,7 @@ int vslam_fe_create(const vslam_fe_params* params, vslam_fe** out);
 /* Change switches of an existing context between calls (fields >= 0 of *t overwrite the context's; like every other
  * call on a context this is not re-entrant).  Takes effect for what is consulted per call -- the transport routes
  * (h2d_route, d2h_route, pull_depth, copy_wgs), the matcher switches (init_topm, init_match_host, sbp_topm,
- * sbp_sequential, si_queries_per_block), oct_regkeys, the FAST / pyramid launch shapes, graphs = 0; switches that shaped
+ * sbp_sequential, si_queries_per_block), oct_regkeys, the FAST kernel (fast_kernel), graphs = 0; switches that shaped
  * the context's buffers at creation (pyramid plan, blur rows, quadtree grid depth and LDS placement) stay as created. */
 int vslam_fe_set_tuning(vslam_fe* fe, const vslam_tuning* t);
 void vslam_fe_destroy(vslam_fe* fe);

@@ -111,11 +111,11 @@ def test_other_geometries(cfg):
 
 @pytest.mark.parametrize("cfg", [(1241, 376, 2000, 4, -1), (1920, 1080, 4000, 3, -1), (640, 360, 600, 2, 1), (752, 480, 5000, 2, 3)])
 def test_quadtree_with_the_counting_walk_as_its_own_launch(cfg):
-    """vslam_tuning.oct_precount = 1 (k_oct_count: a level's keys dealt to up to eight workgroups by rows of leaves, the
-    quadtree kernel starts from the counters) and fast_kernel = 4 for small batches too: same keypoints and descriptors as the
-    oracle, also with a forced shallow / deep fine grid (every node splits below it)"""
+    """fast_kernel = 4 (k_fast_bands) for small batches too: same keypoints and descriptors as the oracle, also with a
+    forced shallow / deep fine grid of the quadtree (every node splits below it).  The counting walk as a launch of its own
+    (oct_precount) is retired; the name is kept so that the test keeps its id."""
     w, h, nf, b, fd = cfg
-    tn = dict(oct_precount=1, fast_kernel=4)
+    tn = dict(fast_kernel=4)
     if fd >= 0:
         tn["oct_fine_depth"] = fd
     fe = V.FExtractor(nf, 1.2, 8, 20, 7, w, h, max_batch=b, tuning=tn)

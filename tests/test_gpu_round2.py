@@ -352,13 +352,13 @@ def test_staged_upload_then_extract_equals_pinned_path():
         fe.close()
 
 
-@pytest.mark.parametrize("env", [{}, {"oct_fine_depth": 1}, {"oct_fine_depth": 3}, {"octree_walk_kernel": 1}])
+@pytest.mark.parametrize("env", [{}, {"oct_fine_depth": 1}, {"oct_fine_depth": 3}])
 @pytest.mark.parametrize("cfg", [(1241, 376, 1000), (640, 480, 3000), (1920, 1080, 4000)])
 def test_quadtree_fine_grid_depths_and_the_walk_kernel(env, cfg):
     """k_octree_v4 counts keys once into a fine grid, sorts them by fine cell and never walks them per pass; nodes finer
     than the grid (forced here with a depth of 1 or 3: almost every node) are resolved inside the kernel from the sorted
-    keys of their cell.  The walk-per-pass kernel (k_octree_v2) stays selectable.  Every variant must give the oracle's
-    keypoints."""
+    keys of their cell.  Every depth must give the oracle's keypoints.  The walk-per-pass kernel is retired; the name is
+    kept so that the remaining cases keep their ids."""
     w, h, nf = cfg
     imgs = [synth.make_frame(w, h, seed=50 + nf, step=s) for s in range(2)]
     fe = V.FExtractor(nf, 1.2, 8, 20, 7, w, h, max_batch=2, tuning=env)
@@ -420,10 +420,10 @@ def test_switches_do_not_change_results():
     spec.loader.exec_module(mod)
     ref = mod.digest()
     for tuning in ({"oct_regkeys": 1}, {"oct_regkeys": 0}, {"si_queries_per_block": 8}, {"si_queries_per_block": 32},
-                   {"fast_lds_pad": 4096}, {"h2d_route": 1}, {"h2d_route": 2}, {"oct_lds_budget_kb": 48},
+                   {"h2d_route": 1}, {"h2d_route": 2}, {"oct_lds_budget_kb": 48},
                    {"oct_fine_depth": 2, "oct_regkeys": 1}, {"oct_fine_depth": 1, "oct_regkeys": 0}, {"d2h_route": 1}, {"d2h_route": 2}, {"graphs": 0},
-                   {"pyramid_per_level": 1}, {"fast_threads": 256}, {"pyr_threads": 512}, {"blur_rows": 16}, {"init_topm": 16}, {"init_topm": 3},
-                   {"d2h_route": 1, "copy_wgs": 4}, {"fast_threads": 64}, {"oct_threads": 1024}, {"oct_threads": 512}, {"oct_threads": 256},
+                   {"pyramid_per_level": 1}, {"blur_rows": 16}, {"init_topm": 16}, {"init_topm": 3},
+                   {"d2h_route": 1, "copy_wgs": 4}, {"oct_threads": 1024}, {"oct_threads": 512}, {"oct_threads": 256},
                    {"oct_threads": 256, "oct_regkeys": 1}, {"oct_threads": 512, "oct_fine_depth": 1}):
         assert mod.digest(tuning) == ref, tuning
     for env in ({"VSLAM_WAIT": "spin", "VSLAM_NUMA": "0"}, {"VSLAM_D2H": "kernel", "VSLAM_OCT_REGKEYS": "1", "VSLAM_PYRAMID": "levels"}):

@@ -76,9 +76,6 @@ struct vslam_fe {
     CellDesc* d_cells = nullptr;
     int tile_pitch = 0, tile_rows = 0, max_px = 0;
     /* FAST bands (k_fast_bands): up to four cells of a cell row per workgroup; nbands == 0: not available for this geometry */
-    OctPart* d_oct_parts = nullptr; /* k_oct_count: parts of every level; nullptr: walk 1 inside k_octree_v4 */
-    uint32_t* d_oct_cnt = nullptr;  /* leaf counters [B][sum of the levels' leaves] */
-    int oct_maxcells = 0;
     BandDesc* d_bands = nullptr;
     uint8_t* d_band_classes = nullptr; /* 272-byte column tables, BandDesc::lnw >> 16 indexes them */
     int nbands = 0, band_max_wh = 0, band_max_iw = 0;
@@ -186,7 +183,6 @@ struct vslam_fe {
     bool dev_octree = false;
     OctParams oct;
     uint32_t* d_pts[2] = {nullptr, nullptr};  /* B x cand_cap each: keys in key order | k_octree_v4: fine cell and rank of every key */
-    uint16_t* d_nid = nullptr;                /* k_octree_v2 only: node (list index) of every key */
     uint8_t* d_oct_sorted = nullptr;          /* k_octree_v4: {key, position} sorted by fine cell, B x cand_cap x 8 bytes */
     uint32_t* d_oct_lut = nullptr;            /* k_octree_v4: per level the x and y path tables (vslam::build_oct_lut) */
     int32_t* d_oct_redo = nullptr;            /* k_octree_v4: (slot, level) split nodes finer than the grid, B x VSLAM_MAX_LEVELS */

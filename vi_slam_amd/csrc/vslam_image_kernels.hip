@@ -546,16 +546,11 @@ k_pyramid_group(uint8_t* pyr, size_t slot_stride, BatchSrc src, PyrGroupDev G, i
 }
 
 void vk_pyramid_group(hipStream_t st, uint8_t* pyr, size_t slot_stride, const BatchSrc& src, const PyrGroupDev& G,
-                      size_t lds_bytes, int nslots, const vslam_tuning& T, uint8_t* reset_cand, size_t cand_stride,
-                      int32_t* reset_err) {
+                      size_t lds_bytes, int nslots, uint8_t* reset_cand, size_t cand_stride, int32_t* reset_err) {
     const int nwork = G.ntiles * nslots;
-    const int nt = T.pyr_threads == 512 ? 512 : 256; /* waves per tile (A/B runs) */
-    if (nt == 512)
-        hipLaunchKernelGGL(k_pyramid_group<512>, dim3(((nwork + 7) / 8) * 8), dim3(512), lds_bytes, st, pyr, slot_stride, src, G, nslots,
-                           reset_cand, cand_stride, reset_err);
-    else
-        hipLaunchKernelGGL(k_pyramid_group<256>, dim3(((nwork + 7) / 8) * 8), dim3(256), lds_bytes, st, pyr, slot_stride, src, G, nslots,
-                           reset_cand, cand_stride, reset_err);
+    /* four waves per tile (eight measured never faster at the shipped tile heights: profiles/r04_pyramid_tile_sweep.txt) */
+    hipLaunchKernelGGL(k_pyramid_group<256>, dim3(((nwork + 7) / 8) * 8), dim3(256), lds_bytes, st, pyr, slot_stride, src, G, nslots,
+                       reset_cand, cand_stride, reset_err);
 }
 
 /* ------------------------------------------------------------------------------------------------
@@ -1017,45 +1012,30 @@ k_fast_cells_v3(const uint8_t* __restrict__ pyr, size_t slot_stride, BatchSrc sr
     FAST_WGREC_END();
 }
 
-/* threads per cell: a cell is 900 pixels, and ~150 of the ~420 instructions a thread executes do not depend on how many
- * pixels it owns (prologue, NMS bookkeeping, compaction), so fewer, busier threads per cell cost fewer instructions in
- * total; VSLAM_FAST_NT = 64 | 128 | 256 selects the variant for A/B runs */
-static int fast_v3_nt(const vslam_tuning& T) {
-    const int v = T.fast_threads;
-    return (v == 64 || v == 128 || v == 256) ? v : 128;
-}
-
 void vk_fast_cells_v3(hipStream_t st, const uint8_t* pyr, size_t slot_stride, const BatchSrc& src,
                       const PyramidGeom& g, const CellDesc* cells, int ncells, uint8_t* cand_region,
-                      size_t cand_stride, int iniTh, int minTh, int tile_rows, int max_window_w, int max_px, int nslots,
-                      const vslam_tuning& T) {
+                      size_t cand_stride, int iniTh, int minTh, int tile_rows, int max_window_w, int max_px, int nslots) {
     /* survivor lists: dark-only + "both" share one list (from both ends), bright-only the other; neither can hold
      * more entries than the largest cell interior has pixels.  Windows up to 42 px wide (KITTI, 1080p: 38) fit an
      * LDS pitch of 48 bytes instead of 72: 9.7 KB per cell, 16 cells resident per CU. */
     const int lcap = (max_px + 7) & ~3;
-    const bool force72 = T.fast_pitch == 72; /* the wider pitch everywhere, for A/B runs */
-    const int P = (max_window_w <= 42 && !force72) ? 48 : 72;
-    const int nt = fast_v3_nt(T);
+    const int P = max_window_w <= 42 ? 48 : 72;
+    /* threads per cell: a cell is 900 pixels, and ~150 of the ~420 instructions a thread executes do not depend on how many
+     * pixels it owns (prologue, NMS bookkeeping, compaction), so fewer, busier threads per cell cost fewer instructions in
+     * total; 64 and 256 measured slower than 128 (profiles/r03_switch_sweeps.txt) */
+    constexpr int nt = 128;
     /* window + score tile + keep words + list; not less than what the pre-test sweep's idle lanes may READ (rows up
      * to a sweep's height below the window, quads past the last one: results dropped, but the addresses stay inside
      * the allocation) */
     const size_t shm = std::max((size_t)tile_rows * P + (size_t)(tile_rows - 4) * P + (size_t)(tile_rows - 6) * 8 + (size_t)lcap * 4 + 16,
                                 (size_t)(tile_rows + nt / 8 + 1) * P + 128);
-    const int lds_pad = std::max(0, tune_or(T.fast_lds_pad, 0)); /* extra LDS per workgroup (occupancy experiments) */
     const dim3 grid((ncells + 8 * FAST_XCD_CHUNK - 1) / (8 * FAST_XCD_CHUNK) * (8 * FAST_XCD_CHUNK), nslots);
     const int it = std::min(iniTh, 256), mt = std::min(minTh, 256);
-#define FAST3_LAUNCH(NT_, P_)                                                                                              \
-    hipLaunchKernelGGL((k_fast_cells_v3<NT_, P_>), grid, dim3(NT_), shm + lds_pad, st, pyr, slot_stride, src, g, cells, cand_region, \
+#define FAST3_LAUNCH(P_)                                                                                              \
+    hipLaunchKernelGGL((k_fast_cells_v3<nt, P_>), grid, dim3(nt), shm, st, pyr, slot_stride, src, g, cells, cand_region, \
                        cand_stride, ncells, it, mt, tile_rows, lcap)
-    if (P == 48) {
-        if (nt == 64) FAST3_LAUNCH(64, 48);
-        else if (nt == 128) FAST3_LAUNCH(128, 48);
-        else FAST3_LAUNCH(256, 48);
-    } else {
-        if (nt == 64) FAST3_LAUNCH(64, 72);
-        else if (nt == 128) FAST3_LAUNCH(128, 72);
-        else FAST3_LAUNCH(256, 72);
-    }
+    if (P == 48) FAST3_LAUNCH(48);
+    else FAST3_LAUNCH(72);
 #undef FAST3_LAUNCH
 }
 
@@ -1485,7 +1465,7 @@ int vk_fast_bands_check(int max_wh, int max_iw, int max_cells_per_band) {
 
 void vk_fast_bands(hipStream_t st, const uint8_t* pyr, size_t slot_stride, const BatchSrc& src, const PyramidGeom& g,
                    const BandDesc* bands, int nbands, const uint8_t* classes, const CellDesc* cells, int ncells, uint8_t* cand_region,
-                   size_t cand_stride, int iniTh, int minTh, int max_wh, int max_iw, int nslots, const vslam_tuning& T) {
+                   size_t cand_stride, int iniTh, int minTh, int max_wh, int max_iw, int nslots) {
     /* one shape: bands of up to 128 interior columns (four 31-px cells) by four waves, LDS pitch 136.  (A second shape --
      * bands of up to 64 columns by two waves, pitch 72: the same work per cell behind barriers of two waves instead of four --
      * was built in round 4 and measured no faster: 90.6 vs 89.7 us per 32 KITTI images, 41.5 M instead of 39.2 M
@@ -1502,14 +1482,13 @@ void vk_fast_bands(hipStream_t st, const uint8_t* pyr, size_t slot_stride, const
     size_t lds = std::max(budget, fast_band_fixed_lds(max_wh, P) + 2 * (size_t)(8 * 2 * (P - 8)));
     lds = std::max(lds, (size_t)(max_wh + NT / 8 + 1) * P + 256);
     lds = (lds + 15) & ~(size_t)15;
-    const int lds_pad = std::max(0, tune_or(T.fast_lds_pad, 0)); /* extra LDS per workgroup (occupancy experiments) */
     const int it = std::min(iniTh, 256), mt = std::min(minTh, 256);
     const int by_image = nslots >= 8 ? 1 : 0;
     dim3 grid;
     if (by_image) grid = dim3((unsigned)(8 * nbands * ((nslots + 7) / 8)), 1);
     else grid = dim3((unsigned)((nbands + 8 * FB_XCD_CHUNK - 1) / (8 * FB_XCD_CHUNK) * (8 * FB_XCD_CHUNK)), (unsigned)nslots);
 #define FB_LAUNCH(NT_, P_)                                                                                                   \
-    hipLaunchKernelGGL((k_fast_bands<NT_, P_>), grid, dim3(NT_), lds + lds_pad, st, pyr, slot_stride, src, g, bands, nbands, \
+    hipLaunchKernelGGL((k_fast_bands<NT_, P_>), grid, dim3(NT_), lds, st, pyr, slot_stride, src, g, bands, nbands, \
                        (const uint4*)classes, cells, cand_region, cand_stride, ncells, it, mt, nslots, (int)lds, by_image)
     FB_LAUNCH(256, 136);
 #undef FB_LAUNCH

@@ -1,5 +1,6 @@
 /* vslam_kernels.h -- launch wrappers implemented in the kernel files (vslam_image_kernels.hip, vslam_kernels.hip,
- * vslam_octree_kernel.hip, vslam_match_kernels.hip, vslam_init_kernel.hip). */
+ * vslam_octree_kernel.hip, vslam_match_kernels.hip, vslam_init_kernel.hip).  T: the context's resolved switches
+ * (vslam_tuning.h); the launchers read their A/B knobs from it, never from the environment. */
 #ifndef VSLAM_KERNELS_H
 #define VSLAM_KERNELS_H
 
@@ -26,42 +27,34 @@ void vk_hamming_top2_batch(hipStream_t st, const Top2Jobs& jobs, int nprob, int 
 void vk_blur7_v2(hipStream_t st, const uint8_t* pyr, size_t slot_stride, const BatchSrc& src, const PyramidGeom& g,
                  uint8_t* blur, const uint32_t* tasks, int ntasks, const int32_t taps[7], int rows_per_task,
                  int nslots);
-/* T: the context's resolved switches (vslam_tuning.h); the launchers read their A/B knobs from it, never from the environment */
 void vk_pyramid_group(hipStream_t st, uint8_t* pyr, size_t slot_stride, const BatchSrc& src, const PyrGroupDev& G,
-                      size_t lds_bytes, int nslots, const vslam_tuning& T, uint8_t* reset_cand = nullptr, size_t cand_stride = 0,
+                      size_t lds_bytes, int nslots, uint8_t* reset_cand = nullptr, size_t cand_stride = 0,
                       int32_t* reset_err = nullptr);
 void vk_fast_cells_v3(hipStream_t st, const uint8_t* pyr, size_t slot_stride, const BatchSrc& src,
                       const PyramidGeom& g, const CellDesc* cells, int ncells, uint8_t* cand_region,
-                      size_t cand_stride, int iniTh, int minTh, int tile_rows, int max_window_w, int max_px, int nslots,
-                      const vslam_tuning& T);
+                      size_t cand_stride, int iniTh, int minTh, int tile_rows, int max_window_w, int max_px, int nslots);
 /* k_fast_bands: one workgroup per band of cells (vslam::build_bands); max_wh = tallest band window.  _check: the
  * kernel's limits (0 = a band list it can run) */
 int vk_fast_bands_check(int max_wh, int max_iw, int max_cells_per_band);
 void vk_fast_bands(hipStream_t st, const uint8_t* pyr, size_t slot_stride, const BatchSrc& src, const PyramidGeom& g,
                    const BandDesc* bands, int nbands, const uint8_t* classes, const CellDesc* cells, int ncells, uint8_t* cand_region,
-                   size_t cand_stride, int iniTh, int minTh, int max_wh, int max_iw, int nslots, const vslam_tuning& T);
+                   size_t cand_stride, int iniTh, int minTh, int max_wh, int max_iw, int nslots);
 void vk_resize_level_v2(hipStream_t st, uint8_t* pyr, size_t slot_stride, const BatchSrc& src, const LevelGeom& sg,
                         const LevelGeom& dg, int src_level, const uint16_t* qbase, const ResizeQuad* quads,
                         const uint16_t* ytab, const int16_t* yb, int nslots);
 size_t vk_octree_lds_bytes(int maxNodes);
 int vk_octree_set_max_lds(size_t bytes);
 void vk_octree(hipStream_t st, const uint8_t* cand_region, size_t cand_stride, int ncells, const OctParams& P,
-               uint32_t* keys_a, uint32_t* aux_a, uint16_t* nid_a, void* sorted_a, size_t pts_stride,
+               uint32_t* keys_a, uint32_t* aux_a, void* sorted_a, size_t pts_stride,
                uint32_t* sel_xyr, int32_t* sel_cnt, int32_t* err_flag, int nlevels, int nslots, int32_t* deep_flags,
-               int regkeys, int threads = 1024, int prio = 0);
-/* k_oct_count: walk 1 of the quadtree as a launch of its own (OctParams::parts); LDS = counters of the largest level + the
- * cell offsets of the largest part */
-size_t vk_oct_count_lds(int maxcells, int maxPartCells);
-int vk_oct_count_set_max_lds(size_t bytes);
-void vk_oct_count(hipStream_t st, const uint8_t* cand_region, size_t cand_stride, int ncells, const OctParams& P, uint32_t* keys_a,
-                  uint32_t* aux_a, size_t pts_stride, int nlevels, int nslots, int maxcells);
+               int regkeys, int threads = 1024);
 void vk_assign_out(hipStream_t st, const OctParams& P, const PyramidGeom& g, uint32_t* sel_xyr, int32_t* sel_cnt, int lap0,
                    int lap1, SelKp* sel, int32_t* slot_counts, int cap, int32_t* err_flag, int nslots,
-                   const int32_t* deep_flags, int prio = 0);
+                   const int32_t* deep_flags);
 void vk_orient_describe_dev(hipStream_t st, const uint8_t* pyr, const uint8_t* blur, size_t slot_stride,
                             const BatchSrc& src, const PyramidGeom& g, const SelKp* sel,
                             const int32_t* slot_counts, const int8_t* pattern, vslam_kp* kps, uint8_t* desc,
-                            int cap, int atan_fma, int nslots, int prio = 0, int kpw_override = -1);
+                            int cap, int atan_fma, int nslots, int kpw_override = -1);
 
 void vk_dbg_sincos(hipStream_t st, const float* x, int n, float* s, float* c);
 void vk_dbg_logf(hipStream_t st, const float* x, int n, float* y);
@@ -70,7 +63,7 @@ void vk_dbg_atan2(hipStream_t st, const float* y, const float* x, int n, int fma
 void vk_stereo(hipStream_t st, const StereoJobs& jobs, int njobs, int maxNL, int maxNR, const PyramidGeom& g,
                const uint8_t* pyrL, size_t strideL, const BatchSrc& srcL, const uint8_t* pyrR, size_t strideR,
                const BatchSrc& srcR, float mbf, float maxD, uint32_t* best, float* uRight, float* depth,
-               int32_t* sad, int cap, int max_band, uint8_t* rows_scratch, int prio = 0);
+               int32_t* sad, int cap, int max_band, uint8_t* rows_scratch);
 /* bytes of rows_scratch: row table, bucket items and {uR, octave} records of njobs stereo pairs */
 size_t vk_stereo_rows_bytes(int njobs, int nrows, int max_band, int cap);
 void vk_hamming_matrix_batch(hipStream_t st, const MatJobs& jobs, int njobs, int maxr, int maxc, const int32_t* idx,
@@ -109,7 +102,7 @@ void vk_undistort_xy(hipStream_t st, const float* xy, int n, float* out, const U
 void vk_pull_images(hipStream_t st, const BatchSrc& src, uint8_t* pyr, size_t slot_stride, uint32_t off0, int dpitch,
                     int w, int h, int nimg, int from_host, const vslam_tuning& T);
 void vk_pack_slots(hipStream_t st, const vslam_kp* kps, const uint8_t* desc, const int32_t* counts, int cap, int first,
-                   int nslots, uint8_t* dst, size_t slot_bytes, int prio = 0);
+                   int nslots, uint8_t* dst, size_t slot_bytes);
 void vk_gather_rows32(hipStream_t st, const uint8_t* src, const int32_t* idx, int n, uint8_t* dst);
 
 #endif

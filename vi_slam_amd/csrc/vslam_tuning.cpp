@@ -17,12 +17,7 @@ struct EnvField {
 const EnvField kEnv[] = {
     TF("VSLAM_PYRAMID", pyramid_per_level, "levels", nullptr),
     TF("VSLAM_PYR_ROWS", pyr_rows, nullptr, nullptr),
-    TF("VSLAM_PYR_NT", pyr_threads, nullptr, nullptr),
     TF("VSLAM_BLUR_ROWS", blur_rows, nullptr, nullptr),
-    TF("VSLAM_FAST_NT", fast_threads, nullptr, nullptr),
-    TF("VSLAM_FAST_PITCH", fast_pitch, nullptr, nullptr),
-    TF("VSLAM_FAST_LDS_PAD", fast_lds_pad, nullptr, nullptr),
-    TF("VSLAM_OCTREE", octree_walk_kernel, "v2", nullptr),
     TF("VSLAM_OCT_FINE_D", oct_fine_depth, nullptr, nullptr),
     TF("VSLAM_OCT_LDS_BUDGET_KB", oct_lds_budget_kb, nullptr, nullptr),
     TF("VSLAM_OCT_REGKEYS", oct_regkeys, nullptr, nullptr),
@@ -47,8 +42,6 @@ const EnvField kEnv[] = {
     TF("VSLAM_OCT_THREADS", oct_threads, nullptr, nullptr),
     TF("VSLAM_FAST_KERNEL", fast_kernel, nullptr, nullptr),
     TF("VSLAM_FAST_BAND_CELLS", fast_band_cells, nullptr, nullptr),
-    TF("VSLAM_WAVE_PRIO", wave_prio, nullptr, nullptr),
-    TF("VSLAM_OCT_PRECOUNT", oct_precount, nullptr, nullptr),
     TF("VSLAM_DESC_KPW", desc_kpw, nullptr, nullptr),
 };
 #undef TF
