@@ -42,8 +42,12 @@ extern "C" {
 
 /* flags for vslam_fe_params.flags: OpenCV build-dependent arithmetic the reference inherits */
 #define VSLAM_FLAG_ATAN_FMA 1u /* cv::fastAtan2 Horner polynomial FMA-contracted (AVX2/FMA3 dispatch, aarch64) */
-/* Run FExtractor::DistributeOctTree on the host worker pool instead of the GPU kernel (k_octree).  The
- * library picks this by itself only when a level's node list cannot fit LDS (nfeatures > ~11000). */
+/* Run FExtractor::DistributeOctTree on the host worker pool instead of the GPU kernel (k_octree).  Only the selection
+ * stage of a pass differs: the candidates are fetched to the host, distributed while the blur runs, and the selected
+ * keypoints and counts uploaded in the layout the kernel leaves; description, undistortion and every form of delivery
+ * (one transfer for a full batch, want_host = 2 included) are the device placement's.  Such a pass waits on the host
+ * inside the enqueue call and is never replayed from a captured graph.  The library picks this placement by itself only
+ * when a level's node list cannot fit LDS (nfeatures above about 12500 at scale factor 1.2 and 8 levels). */
 #define VSLAM_FLAG_HOST_OCTREE 2u
 
 /* Same 28-byte layout and field order as cv::KeyPoint (pt.x, pt.y, size, angle, response, octave,
@@ -272,7 +276,8 @@ void vslam_host_free(void* p);
 
 /* Stage timing with HIP events on the context's stream (the reference's REGISTER_TIMES spans,
  * frame.cpp:103-132, broken down per kernel stage): stage_ms[0..4] = pyramid (7 launches), FAST cells,
- * Gaussian blur, orientation+descriptor, quadtree distribution + output order (0 with the host quadtree),
+ * Gaussian blur, orientation+descriptor, quadtree distribution + output order (with the host quadtree a zero-length
+ * span behind the upload of the selected keypoints: that work is host time inside the enqueue call, not stream time),
  * accumulated over `batches` batched calls / `images` images since profiling was switched on. */
 int vslam_fe_set_profiling(vslam_fe* fe, int on);
 int vslam_fe_get_profile(vslam_fe* fe, double stage_ms[5], long* batches, long* images);

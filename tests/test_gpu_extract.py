@@ -439,3 +439,147 @@ def test_adversarial_patterns(nf):
             _assert_same(fe.compute(im), e.compute(im), name)
     finally:
         fe.close()
+
+
+# ---- the host quadtree as a selection stage: everything behind keypoint selection is the device placement's code, so the
+# ---- host placement is run through partial batches, an empty slot, deferred delivery, stereo and the automatic fallback
+def _dev_rows(imgs, pitch=1280):
+    import torch
+    dev = torch.zeros((len(imgs), imgs[0].shape[0], pitch), dtype=torch.uint8, device="cuda")
+    for s, im in enumerate(imgs):
+        dev[s, :, :im.shape[1]] = torch.from_numpy(im).cuda()
+    torch.cuda.synchronize()
+    return dev
+
+
+def test_host_quadtree_partial_and_full_batches_on_one_context():
+    """max_batch = 4 with 1, 3 and 4 images in turn on ONE host-quadtree context, device and host inputs, both lapping areas"""
+    imgs = [synth.make_frame(1241, 376, seed=31, step=s) for s in range(4)]
+    dev = _dev_rows(imgs)
+    e = orbo.Extractor(2000)
+    want = {lap: [e.compute(im, lap=lap) for im in imgs] for lap in ((0, 0), (0, 1000))}
+    assert all(len(w[0]) >= 2000 for w in want[(0, 0)])
+    fe = V.FExtractor(2000, 1.2, 8, 20, 7, 1241, 376, max_batch=4, flags=V.FLAG_HOST_OCTREE)
+    try:
+        for lap in ((0, 0), (0, 1000)):
+            for nimg in (1, 3, 4):
+                for route in ("device", "host"):
+                    if route == "device":
+                        res = fe.compute_batch(None, lap, device_ptrs=[dev[s].data_ptr() for s in range(nimg)], pitch=1280)
+                    else:
+                        res = fe.compute_batch(imgs[:nimg], lap)
+                    assert len(res) == nimg
+                    for s in range(nimg):
+                        _assert_same(res[s], want[lap][s], "host quadtree %s lap %s nimg %d slot %d" % (route, lap, nimg, s))
+        assert fe.octree_stats()[0] == 0  # nothing was distributed on the device
+    finally:
+        fe.close()
+
+
+def test_host_quadtree_slot_without_keypoints_between_two_normal_ones():
+    imgs = [synth.make_frame(1241, 376, seed=32), np.full((376, 1241), 100, np.uint8), synth.make_frame(1241, 376, seed=33)]
+    e = orbo.Extractor(2000)
+    want = [e.compute(im, lap=(0, 1000)) for im in imgs]
+    assert len(want[1][0]) == 0 and len(want[0][0]) >= 2000 and len(want[2][0]) >= 2000
+    dev = _dev_rows(imgs)
+    for B in (3, 4):  # a full batch and a partial one
+        fe = V.FExtractor(2000, 1.2, 8, 20, 7, 1241, 376, max_batch=B, flags=V.FLAG_HOST_OCTREE)
+        try:
+            for res in (fe.compute_batch(imgs, (0, 1000)),
+                        fe.compute_batch(None, (0, 1000), device_ptrs=[dev[s].data_ptr() for s in range(3)], pitch=1280)):
+                for s in range(3):
+                    _assert_same(res[s], want[s], "host quadtree, empty slot 1: B %d slot %d" % (B, s))
+        finally:
+            fe.close()
+
+
+def test_host_quadtree_deferred_delivery_equals_device_quadtree():
+    """a full batch with to_host="with_matcher", followed by the device SearchForInitialization and once by the wait alone:
+    the same calls on a host-quadtree and on a device-quadtree context give the same results, and the oracle's"""
+    B = 4
+    imgs = [synth.make_frame(1241, 376, seed=34, step=s) for s in range(B)]
+    dev = _dev_rows(imgs)
+    e = orbo.Extractor(2000)
+    want = [e.compute(im, lap=(0, 1000)) for im in imgs]
+    wantm = [orbo.search_for_initialization(want[s - 1][0], want[s - 1][1], want[s][0], want[s][1], 1241, 376, window=100,
+                                            nnratio=0.9) for s in range(1, B)]
+    assert all(w[0] > 50 for w in wantm)
+    got = {}
+    for name, flags in (("device", 0), ("host", V.FLAG_HOST_OCTREE)):
+        fe = V.FExtractor(2000, 1.2, 8, 20, 7, 1241, 376, max_batch=B, flags=flags)
+        try:
+            m = V.FMatcher(fe, 0.9, True)
+            runs = []
+            for with_matcher in (True, False):
+                fe.compute_batch_async([dev[s].data_ptr() for s in range(B)], 1280, (0, 1000), to_host="with_matcher")
+                if with_matcher:
+                    jobs = []
+                    for s in range(1, B):
+                        p, c = fe.slot_dev_ptrs(s - 1), fe.slot_dev_ptrs(s)
+                        jobs.append((p[0], p[1], p[2], c[0], c[1], c[2], 0))
+                    m.search_init_dev_async(jobs, 100)
+                res = fe.wait(copy=True)
+                out = None
+                if with_matcher:
+                    out = [(o[0], o[1].copy()) for o in m.search_init_dev_wait([len(want[s - 1][0]) for s in range(1, B)])]
+                runs.append((res, out))
+            got[name] = runs
+            assert fe.octree_stats()[0] == (0 if flags else 2 * B * 8)
+        finally:
+            fe.close()
+    for name in ("device", "host"):
+        for res, out in got[name]:
+            for s in range(B):
+                _assert_same(res[s], want[s], "%s quadtree, deferred delivery, slot %d" % (name, s))
+            if out is not None:
+                for j in range(B - 1):
+                    assert out[j][0] == wantm[j][0] and np.array_equal(out[j][1], wantm[j][1]), (name, j)
+    for (rh, oh), (rd, od) in zip(got["host"], got["device"]):
+        for s in range(B):
+            _assert_same(rh[s], rd[s], "host against device quadtree, slot %d" % s)
+        assert (oh is None) == (od is None)
+        if oh is not None:
+            assert all(a[0] == b[0] and np.array_equal(a[1], b[1]) for a, b in zip(oh, od))
+
+
+def test_host_quadtree_stereo_frame_equals_oracle():
+    """a stereo pair extracted and matched on a host-quadtree context: Frame::ComputeStereoMatches of the oracle"""
+    L, R = synth.make_stereo_pair(1241, 376, seed=35)
+    dev = _dev_rows([L, R])
+    eL, eR = orbo.Extractor(2000), orbo.Extractor(2000)
+    kL, dL, _ = eL.compute(L)
+    kR, dR, _ = eR.compute(R)
+    wu, wd, _, _ = orbo.stereo(eL, eR, kL, dL, kR, dR, 386.1448, 718.856)
+    assert (wu >= 0).sum() > 300
+    for B in (2, 4):  # the pair is the whole batch (one transfer for the step), and half of it
+        fe = V.FExtractor(2000, 1.2, 8, 20, 7, 1241, 376, max_batch=B, flags=V.FLAG_HOST_OCTREE)
+        try:
+            fe.frame_stereo_async([dev[0].data_ptr(), dev[1].data_ptr()], 1280, 386.1448, 718.856)
+            feats, st = fe.frame_stereo_wait()
+            for (k, d), (wk, wdsc) in zip(feats, ((kL, dL), (kR, dR))):
+                assert len(k) == len(wk) and all(np.array_equal(k[f], wk[f]) for f in wk.dtype.names), B
+                assert np.array_equal(d, wdsc), B
+            assert np.array_equal(st[0][0], wu) and np.array_equal(st[0][1], wd), B
+            assert fe.octree_stats()[0] == 0
+        finally:
+            fe.close()
+
+
+def test_node_list_beyond_lds_falls_back_to_the_host_quadtree():
+    """no flag: level 0's node list (quota + 4 entries of 56 bytes, rounded up to 16 entries) must exceed 150 KB of LDS, i.e.
+    a level-0 quota of 2733 or more; at scale 1.2 and 8 levels the quota is 0.2172 x nfeatures, so 13000 is the smallest
+    round thousand (12000: quota 2606, 144 KB)"""
+    NF = 13000
+    img = synth.make_frame(1241, 376, seed=36)
+    fe = V.FExtractor(NF, 1.2, 8, 20, 7, 1241, 376)
+    try:
+        q0 = int(fe.features_per_level()[0])
+        assert ((q0 + 4 + 15) & ~15) * 56 + 64 > 150 * 1024
+        q0_12k = int(orbo.Extractor(12000).tables()["quota"][0])
+        assert ((q0_12k + 4 + 15) & ~15) * 56 + 64 <= 150 * 1024
+        res = fe.compute(img, (0, 1000))
+        assert fe.octree_stats()[0] == 0  # vslam_fe_create chose the host placement by itself
+        _assert_same(res, orbo.Extractor(NF).compute(img, lap=(0, 1000)), "n13000")
+        assert len(res[0]) > 8000
+    finally:
+        fe.close()

@@ -316,3 +316,112 @@ def test_fused_pyramid_plan_emulation_equals_oracle_cascade(H, size, nlevels, sc
         hh, ww = sizes[l]
         assert np.array_equal(out[o:o + hh * ww].reshape(hh, ww), e.level(l)), l
         o += hh * ww
+
+
+# ---- what vslam_fe_create decides without a GPU call: keypoint capacity, the quadtree plan, the band tables
+BENCH_GEOMS = [(1241, 376), (752, 480), (1920, 1080)]
+OCT_NODE_BYTES = (56, 64)   # vk_octree_lds_bytes: 56 bytes a node + 64 (vslam_octree_kernel.hip)
+OCT_BUDGET = 128 * 1024     # vslam_tuning.oct_lds_budget_kb's default
+# fe->oct of the PARENT of the change that moved the plan to the host side (its create_impl arithmetic compiled on its own),
+# at the six bench workloads' (width, height, nfeatures): fine depth per level, maxNodes, selStride, keypoint capacity
+PARENT_OCT = {
+    (1241, 376, 1000): ([4, 4, 4, 4, 4, 4, 4, 3], 224, 1032, 1040),   # kitti00_mono n1000
+    (1241, 376, 2000): ([5, 5, 5, 4, 4, 4, 4, 4], 448, 2032, 2040),   # kitti00_mono n2000, kitti00_stereo, kitti00_stereo_track
+    (1920, 1080, 4000): ([6, 6, 6, 5, 5, 5, 5, 5], 880, 4032, 4040),  # synthetic_stereo
+    (752, 480, 1200): ([5, 5, 5, 5, 4, 4, 4, 4], 272, 1232, 1240),    # hut_stereo
+}
+# and its band list: (bands, column classes, tallest window, widest interior, most cells of a band)
+PARENT_BANDS = {(1241, 376): (323, 10, 46, 128, 4), (752, 480): (263, 12, 40, 128, 4), (1920, 1080): (1625, 10, 40, 128, 4)}
+
+
+def _context_geometry(H, w, h, nf, nlevels=8):
+    """what vslam_fe_create hands the planners: quotas, level sizes, the cell list of all levels and each level's first cell"""
+    sf, isf, s2, is2 = (np.zeros(nlevels, np.float32) for _ in range(4))
+    quota, um, dn = np.zeros(nlevels, np.int32), np.zeros(16, np.int32), C.c_int()
+    H.vslamh_tables(nf, C.c_float(1.2), nlevels, _p(sf), _p(isf), _p(s2), _p(is2), _p(quota), _p(um), C.byref(dn))
+    lw, lh, first, cells = np.zeros(nlevels, np.int32), np.zeros(nlevels, np.int32), np.zeros(nlevels + 1, np.int32), []
+    for l in range(nlevels):
+        a, b = C.c_int(), C.c_int()
+        H.vslamh_level_size(nf, C.c_float(1.2), nlevels, w, h, l, C.byref(a), C.byref(b))
+        lw[l], lh[l] = a.value, b.value
+        buf = np.zeros((8192, 5), np.uint16)
+        nc = H.vslamh_cells(l, a.value, b.value, _p(buf), 8192)
+        assert 0 < nc <= 8192
+        cells.append(buf[:nc])
+        first[l + 1] = first[l] + nc
+    return quota, lw, lh, first, np.ascontiguousarray(np.concatenate(cells))
+
+
+def _oct_plan(H, w, h, nf, forced=-1, budget=OCT_BUDGET):
+    quota, lw, lh, first, _ = _context_geometry(H, w, h, nf)
+    ctx, lvl = np.zeros(6, np.int32), np.zeros((8, 4), np.int32)
+    assert H.vslamh_oct_plan(_p(quota), _p(lw), _p(lh), _p(first), 8, forced, budget, OCT_NODE_BYTES[0], OCT_NODE_BYTES[1],
+                             _p(ctx), _p(lvl)) == 0
+    cap = H.vslamh_keypoint_capacity(_p(quota), _p(lw), _p(lh), 8, nf)
+    return [int(v) for v in ctx], lvl.astype(int), (quota.astype(int), lw.astype(int), lh.astype(int)), cap
+
+
+def test_quadtree_plan_invariants_and_parent_values(H):
+    for (w, h) in BENCH_GEOMS:
+        for nf in (500, 1000, 2000, 4000, 20000):
+            for forced in (-1, 1, 3):
+                (maxNodes, selStride, ldsOff, ldsBytes, fits, lut_bad), lvl, (quota, lws, lhs), cap = _oct_plan(H, w, h, nf, forced)
+                tag = (w, h, nf, forced)
+                assert lut_bad == 0, tag  # every (x, y) of every level: table path == oct_key_path at the level's depth
+                assert maxNodes % 16 == 0 and ldsOff % 16 == 0 and ldsOff >= OCT_NODE_BYTES[0] * maxNodes + OCT_NODE_BYTES[1], tag
+                assert not fits or ldsOff + ldsBytes <= OCT_BUDGET, tag
+                assert not fits or (ldsOff + ldsBytes <= 160 * 1024 and ldsOff <= 150 * 1024 + 16), tag
+                assert fits == (nf <= 4000), tag  # 20000 features: level 0's node list alone is 238 KB
+                off = 0
+                for l in range(8):
+                    nIni, selOff, D, lutW = lvl[l]
+                    assert nIni == int(np.float32(lws[l] - 32) / np.float32(lhs[l] - 32) + np.float32(0.5)) >= 1, tag
+                    cap_l = max(quota[l] + 3, 4 * nIni) + 1  # what DistributeOctTree can leave on the level, + 1
+                    assert selOff == off and cap_l <= maxNodes and lutW == lws[l] - 32 + 1, tag
+                    off += cap_l
+                    assert 1 <= D <= 11 and nIni << (2 * D) <= 16384, (tag, l)
+                    assert 2 * ((nIni << (2 * D)) + 1) * 4 + 16 <= ldsBytes, (tag, l)
+                    if forced >= 0 and fits:
+                        assert D == forced, (tag, l)  # admissible at these sizes
+                assert off == selStride and cap >= max(selStride - 8, nf + 40) and cap % 4 == 0, tag
+    for (w, h, nf), (D, maxNodes, selStride, cap) in PARENT_OCT.items():
+        ctx, lvl, _, got_cap = _oct_plan(H, w, h, nf)
+        assert list(lvl[:, 2]) == D and ctx[0] == maxNodes and ctx[1] == selStride and ctx[4] == 1, (w, h, nf)
+        assert got_cap == cap, (w, h, nf)
+    # tiny quota: the exact DistributeOctTree bound exceeds nfeatures + 4 * nlevels + 8
+    assert _oct_plan(H, 1241, 376, 10)[3] > (10 + 32 + 8 + 3) & ~3
+
+
+def test_band_tables_encode_the_bands(H):
+    for (w, h) in BENCH_GEOMS:
+        for per in (4, 2):
+            cells16 = _context_geometry(H, w, h, 1000)[4]
+            cells = cells16.astype(int)
+            words, classes, info = np.zeros((4096, 4), np.uint32), np.zeros(64 * 272, np.uint8), np.zeros(5, np.int32)
+            nb = H.vslamh_band_tables(_p(cells16), len(cells16), 8, per, 128, _p(words), 4096, _p(classes), len(classes), _p(info))
+            assert nb > 0 and info[4] == 1
+            if per == 4:
+                assert (nb,) + tuple(int(v) for v in info[:4]) == PARENT_BANDS[(w, h)]
+            words = words[:nb].astype(int)
+            ncls = int(info[0])
+            seen = np.zeros(len(cells), int)
+            assert np.all(np.diff(words[:, 0]) > 0)
+            for cell0, lnw, xy, wh in words:
+                lev, ncell, wcell, ci = lnw & 15, (lnw >> 4) & 15, (lnw >> 8) & 255, lnw >> 16
+                x0, y0, ww, bh = xy & 0xFFFF, xy >> 16, wh & 0xFFFF, wh >> 16
+                assert 1 <= ncell <= per and bh <= info[1]
+                assert ci < ncls
+                bit, fl = classes[ci * 272:ci * 272 + 136].astype(int), classes[ci * 272 + 136:ci * 272 + 272].astype(int)
+                iw = ww - 6
+                assert iw <= info[2] <= 128 and not bit[iw:].any() and not fl[iw:].any()
+                want_fl = np.zeros(iw, int)
+                for k in range(ncell):
+                    c = cells[cell0 + k]  # (level, x0, y0, x1, y1): interior columns x0 + 3 .. x1 - 4 of the level
+                    assert c[0] == lev and (c[1], c[2], c[4]) == (x0 + k * wcell, y0, y0 + bh)  # the cell build_bands put there
+                    a, b = c[1] - x0, c[3] - 6 - x0  # ... are the band's interior columns [a, b)
+                    assert 0 <= a < b <= iw and np.all(bit[a:b] == 1 << k), (w, h, cell0, k)
+                    want_fl[a] |= 1
+                    want_fl[b - 1] |= 2
+                    seen[cell0 + k] += 1
+                assert np.array_equal(fl[:iw], want_fl) and np.all(bit[:iw] != 0)
+            assert np.all(seen == 1)

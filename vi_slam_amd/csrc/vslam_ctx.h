@@ -236,4 +236,18 @@ static inline void vslam_count_delivery(vslam_fe* fe, int ops, const CopyRanges&
     for (int r = 0; r < R.n; r++) fe->n_delivery_bytes += R.bytes[r];
 }
 
+/* The result block -- counts | keypoints | descriptors -- and the `extra` bytes a matcher put behind them, from HBM to
+ * the pinned mirror in ONE transfer on the context's stream. */
+static inline int vslam_deliver_block(vslam_fe* fe, size_t extra) {
+    CopyRanges R;
+    memset(&R, 0, sizeof(R));
+    R.dst[0] = fe->h_res;
+    R.src[0] = fe->d_res;
+    R.bytes[0] = fe->res_feat_bytes + extra;
+    R.n = 1;
+    vslam_count_delivery(fe, vk_copy_ranges(fe->stream, R, fe->tune), R);
+    HIPCHK(hipGetLastError());
+    return VSLAM_OK;
+}
+
 #endif

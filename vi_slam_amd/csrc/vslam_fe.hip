@@ -1,11 +1,10 @@
 /* vslam_fe.hip -- the C ABI of include/vslam_fe.h: context, memory layout in HBM, launch sequence.
  *
  * Per batch of image slots the extractor issues, on ONE stream:
- *     [H2D level 0 | zero-copy]  ->  7 x k_resize_level  ->  k_fast_cells  ->  D2H candidates (event)
- *     ->  k_blur7 (overlaps the host quadtree)  ->  H2D selected keypoints  ->  k_orient_describe
- *     ->  D2H keypoints + descriptors
- * The quadtree distribution (FExtractor::DistributeOctTree) is sequential by construction and runs on
- * the host, one task per (slot, level), on a small worker pool.
+ *     front (upload, pyramid, FAST)  ->  blur, select  ->  describe + undistort  ->  deliver
+ * Only the selection stage (FExtractor::DistributeOctTree) knows where the quadtree runs: k_octree_v4 + k_assign_out on the
+ * device, or -- VSLAM_FLAG_HOST_OCTREE, or a node list too long for LDS -- candidates fetched to the host, one task per
+ * (slot, level) on a small worker pool while the blur runs, and the same per-slot lists and counts block uploaded.
  */
 #if defined(__SSE2__)
 #include <emmintrin.h>
@@ -117,40 +116,36 @@ extern "C" void vslam_fe_destroy(vslam_fe* fe) {
     free_ctx(fe);
 }
 
-template <typename T>
-static int upload(T** dst, const void* src, size_t bytes) {
-    HIPCHK(hipMalloc((void**)dst, bytes ? bytes : 4));
-    if (bytes) HIPCHK(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-    return VSLAM_OK;
-}
+/* a host table into an allocation of its own (at least 4 bytes, so that an empty table has an address too) */
+#define UPLOAD(dst, ptr, bytes)                                                                  \
+    do {                                                                                         \
+        const size_t n_ = (bytes);                                                               \
+        HIPCHK(hipMalloc((void**)&(dst), n_ ? n_ : 4));                                          \
+        if (n_) HIPCHK(hipMemcpy((dst), (ptr), n_, hipMemcpyHostToDevice));                      \
+    } while (0)
 
-static int create_impl(const vslam_fe_params* pp, vslam_fe* fe) {
+/* ---- vslam_fe_create in steps, called in this order by create_impl; what a failed step leaves behind, free_ctx frees */
+
+/* constructor tables, level sizes / pitches / offsets (level 0 staging included at offset 0), keypoint capacity, pyramids */
+static int create_geometry(vslam_fe* fe) {
     const vslam_fe_params& p = fe->p;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || p.device >= ndev) {
-        g_err = "no usable HIP device (this library has no CPU fallback)";
-        return VSLAM_ERR_NO_DEVICE;
-    }
-    HIPCHK(hipSetDevice(p.device));
-    (void)pp;
     vslam::build_tables(p.nfeatures, p.scale_factor, p.nlevels, fe->tab);
     fe->B = p.max_batch;
-    fe->cap = (p.nfeatures + 4 * p.nlevels + 8 + 3) & ~3; /* multiple of 4: packed descriptors stay 16-B aligned */
     static const int32_t def_taps[7] = {18, 34, 48, 56, 48, 34, 18};
     bool zero = true;
     for (int i = 0; i < 7; i++) zero = zero && p.gauss_taps[i] == 0;
     for (int i = 0; i < 7; i++) fe->taps[i] = zero ? def_taps[i] : p.gauss_taps[i];
 
-    /* geometry: level sizes, pitches, offsets (level 0 staging included at offset 0) */
     memset(&fe->geom, 0, sizeof(fe->geom));
     fe->geom.nlevels = p.nlevels;
+    int lws[VSLAM_MAX_LEVELS], lhs[VSLAM_MAX_LEVELS];
     size_t off = 0;
     for (int l = 0; l < p.nlevels; l++) {
         int lw, lh;
         vslam::level_size(fe->tab, p.width, p.height, l, &lw, &lh);
         LevelGeom& g = fe->geom.lv[l];
-        g.w = lw;
-        g.h = lh;
+        g.w = lws[l] = lw;
+        g.h = lhs[l] = lh;
         g.pitch = (lw + 127) & ~127;
         g.off = (uint32_t)off;
         g.scale = fe->tab.scale[l];
@@ -167,102 +162,93 @@ static int create_impl(const vslam_fe_params* pp, vslam_fe* fe) {
         }
     }
     fe->slot_stride = off;
-    {
-        /* exact bound of what DistributeOctTree can return: a level ends with at most N_l + 2 nodes, except that
-         * the first pass splits all nIni initial nodes unconditionally (up to 4*nIni).  Only matters for very
-         * small nfeatures; the documented formula stays the floor so common configurations keep their layout. */
-        int bound = 0;
-        for (int l = 0; l < p.nlevels; l++) {
-            const int W = fe->geom.lv[l].w - 2 * VSLAM_FAST_BORDER, H = fe->geom.lv[l].h - 2 * VSLAM_FAST_BORDER;
-            const int nIni = (int)std::round((float)W / (float)H);
-            bound += std::max(fe->tab.quota[l] + 3, 4 * nIni);
-        }
-        fe->cap = std::max(fe->cap, (bound + 3) & ~3);
-    }
+    fe->cap = vslam::keypoint_capacity(fe->tab.quota.data(), lws, lhs, p.nlevels, p.nfeatures);
     HIPCHK(hipMalloc((void**)&fe->d_pyr, fe->slot_stride * fe->B));
     HIPCHK(hipMalloc((void**)&fe->d_blur, fe->slot_stride * fe->B));
     HIPCHK(hipMemset(fe->d_pyr, 0, fe->slot_stride * fe->B));
     HIPCHK(hipMemset(fe->d_blur, 0, fe->slot_stride * fe->B));
+    return VSLAM_OK;
+}
 
+/* resize tables of every level, and the fused pyramid plan: levels 1-3 from level 0, then groups of four (8 levels = 2
+ * launches instead of 7).  Needs the quad table on every level; VSLAM_PYRAMID=levels keeps one launch per level (A/B runs). */
+static int create_pyramid(vslam_fe* fe) {
+    const vslam_fe_params& p = fe->p;
     std::vector<vslam::PyrLevelTables> pyr_tabs(p.nlevels);
     for (int l = 1; l < p.nlevels; l++) {
         vslam::ResizeTables& r = pyr_tabs[l].r;
         const LevelGeom &s = fe->geom.lv[l - 1], &d = fe->geom.lv[l];
         pyr_tabs[l].sw = s.w; pyr_tabs[l].sh = s.h; pyr_tabs[l].dw = d.w; pyr_tabs[l].dh = d.h;
         vslam::build_resize_tables(s.w, s.h, d.w, d.h, r);
-        int rc;
-        if ((rc = upload(&fe->d_xtab[l], r.xtab.data(), r.xtab.size() * 2))) return rc;
-        if ((rc = upload(&fe->d_xa[l], r.xa.data(), r.xa.size() * 2))) return rc;
-        if ((rc = upload(&fe->d_ytab[l], r.ytab.data(), r.ytab.size() * 2))) return rc;
-        if ((rc = upload(&fe->d_yb[l], r.yb.data(), r.yb.size() * 2))) return rc;
+        UPLOAD(fe->d_xtab[l], r.xtab.data(), r.xtab.size() * 2);
+        UPLOAD(fe->d_xa[l], r.xa.data(), r.xa.size() * 2);
+        UPLOAD(fe->d_ytab[l], r.ytab.data(), r.ytab.size() * 2);
+        UPLOAD(fe->d_yb[l], r.yb.data(), r.yb.size() * 2);
         std::vector<uint16_t>& qbase = pyr_tabs[l].qbase;
         std::vector<uint32_t>& quads = pyr_tabs[l].quads;
         /* four outputs whose eight taps do not fit one 8-byte source window (scale factors >~ 1.6): that level uses
          * the generic one-pixel-per-thread kernel */
         if (vslam::build_resize_quads(r, s.w, d.w, qbase, quads)) {
-            if ((rc = upload(&fe->d_qbase[l], qbase.data(), qbase.size() * 2))) return rc;
-            if ((rc = upload(&fe->d_quads[l], quads.data(), quads.size() * 4))) return rc;
+            UPLOAD(fe->d_qbase[l], qbase.data(), qbase.size() * 2);
+            UPLOAD(fe->d_quads[l], quads.data(), quads.size() * 4);
         } else {
             qbase.clear(); /* marks "no quad table" for the fused-pyramid planner */
             quads.clear();
         }
     }
-
-    /* fused pyramid plan: levels 1-3 from level 0, then groups of four (8 levels = 2 launches instead of 7).  Needs the
-     * quad table on every level; VSLAM_PYRAMID=levels keeps one launch per level (A/B runs). */
-    {
-        bool fused = fe->tune.pyramid_per_level != 1 && p.nlevels > 1;
-        for (int l = 1; l < p.nlevels && fused; l++) fused = fe->d_quads[l] != nullptr;
-        static_assert(sizeof(PyrTileDev) == sizeof(vslam::PyrTileLevel), "planner and kernel share the tile record");
-        for (int l0 = 0; fused && l0 + 1 < p.nlevels;) {
-            const int nl = std::min(l0 == 0 ? 3 : VSLAM_PYR_GROUP_LEVELS, p.nlevels - 1 - l0);
-            std::vector<const vslam::PyrLevelTables*> gt;
-            for (int j = 1; j <= nl; j++) gt.push_back(&pyr_tabs[l0 + j]);
-            vslam::PyrGroupPlan plan;
-            /* tile height: tall tiles (48 rows: less halo, fewer prologues) for batches, where the pyramid competes for
-             * issue slots; short ones (16) for contexts of one or two images, where a frame's latency counts and more
-             * workgroups per image finish sooner (batch-1 latency through the C ABI: 0.135 ms with 12-16 rows, 0.137 with
-             * 20-28, 0.142 with 36, 0.146 with 48) */
-            /* tile height: 16 rows for one or two images (latency), 48 for batches -- least halo, which is what counts in a
-             * VALU-bound pipeline -- and 40 above a megapixel, where the step is the sum of the wide kernels' single-context
-             * times and the pyramid alone is 7 % shorter with smaller tiles (profiles/r04_pyramid_tile_sweep.txt: 1080p +1.8 %) */
-            const int pyr_rows = fe->tune.pyr_rows >= 0 ? fe->tune.pyr_rows
-                                 : fe->B <= 2 ? 16 : (size_t)p.width * p.height > 1000000 ? 40 : 48;
+    bool fused = fe->tune.pyramid_per_level != 1 && p.nlevels > 1;
+    for (int l = 1; l < p.nlevels && fused; l++) fused = fe->d_quads[l] != nullptr;
+    static_assert(sizeof(PyrTileDev) == sizeof(vslam::PyrTileLevel), "planner and kernel share the tile record");
+    /* tile height: 16 rows for contexts of one or two images, where a frame's latency counts and more workgroups per image
+     * finish sooner (batch-1 latency through the C ABI: 0.135 ms with 12-16 rows, 0.137 with 20-28, 0.142 with 36, 0.146 with
+     * 48); 48 for batches, where the pyramid competes for issue slots -- least halo and fewest prologues, which is what
+     * counts in a VALU-bound pipeline -- and 40 above a megapixel, where the step is the sum of the wide kernels'
+     * single-context times and the pyramid alone is 7 % shorter with smaller tiles
+     * (profiles/r04_pyramid_tile_sweep.txt: 1080p +1.8 %) */
+    const int pyr_rows = fe->tune.pyr_rows >= 0 ? fe->tune.pyr_rows
+                         : fe->B <= 2 ? 16 : (size_t)p.width * p.height > 1000000 ? 40 : 48;
 #ifndef VSLAM_PYR_LDS_KB
 #define VSLAM_PYR_LDS_KB 64 /* LDS a pyramid tile's cascade may take (32 / 48 / 96 measured) */
 #endif
-            if (!vslam::build_pyramid_group(gt, l0, VSLAM_PYR_LDS_KB * 1024, plan, pyr_rows)) {
-                fused = false;
-                break;
-            }
-            vslam_fe::PyrGroupCtx g;
-            memset(&g.dev, 0, sizeof(g.dev));
-            g.dev.l0 = l0;
-            g.dev.nl = nl;
-            g.dev.ntiles = plan.ntx * plan.nty;
-            g.dev.readable_w0 = p.width;
-            g.lds_bytes = plan.lds_bytes;
-            g.d_tiles = nullptr;
-            int rc;
-            if ((rc = upload(&g.d_tiles, plan.tiles.data(), plan.tiles.size() * sizeof(PyrTileDev)))) return rc;
-            g.dev.tiles = g.d_tiles;
-            for (int j = 0; j <= nl; j++) g.dev.lg[j] = fe->geom.lv[l0 + j];
-            for (int j = 1; j <= nl; j++) {
-                g.dev.qbase[j - 1] = fe->d_qbase[l0 + j];
-                g.dev.quads[j - 1] = fe->d_quads[l0 + j];
-                g.dev.ytab[j - 1] = fe->d_ytab[l0 + j];
-                g.dev.yb[j - 1] = fe->d_yb[l0 + j];
-            }
-            fe->pyr_groups.push_back(g);
-            l0 += nl;
+    for (int l0 = 0; fused && l0 + 1 < p.nlevels;) {
+        const int nl = std::min(l0 == 0 ? 3 : VSLAM_PYR_GROUP_LEVELS, p.nlevels - 1 - l0);
+        std::vector<const vslam::PyrLevelTables*> gt;
+        for (int j = 1; j <= nl; j++) gt.push_back(&pyr_tabs[l0 + j]);
+        vslam::PyrGroupPlan plan;
+        if (!vslam::build_pyramid_group(gt, l0, VSLAM_PYR_LDS_KB * 1024, plan, pyr_rows)) {
+            fused = false;
+            break;
         }
-        if (!fused) {
-            for (auto& g : fe->pyr_groups) hipFree(g.d_tiles);
-            fe->pyr_groups.clear();
+        vslam_fe::PyrGroupCtx g;
+        memset(&g.dev, 0, sizeof(g.dev));
+        g.dev.l0 = l0;
+        g.dev.nl = nl;
+        g.dev.ntiles = plan.ntx * plan.nty;
+        g.dev.readable_w0 = p.width;
+        g.lds_bytes = plan.lds_bytes;
+        g.d_tiles = nullptr;
+        UPLOAD(g.d_tiles, plan.tiles.data(), plan.tiles.size() * sizeof(PyrTileDev));
+        g.dev.tiles = g.d_tiles;
+        for (int j = 0; j <= nl; j++) g.dev.lg[j] = fe->geom.lv[l0 + j];
+        for (int j = 1; j <= nl; j++) {
+            g.dev.qbase[j - 1] = fe->d_qbase[l0 + j];
+            g.dev.quads[j - 1] = fe->d_quads[l0 + j];
+            g.dev.ytab[j - 1] = fe->d_ytab[l0 + j];
+            g.dev.yb[j - 1] = fe->d_yb[l0 + j];
         }
+        fe->pyr_groups.push_back(g);
+        l0 += nl;
     }
+    if (!fused) {
+        for (auto& g : fe->pyr_groups) hipFree(g.d_tiles);
+        fe->pyr_groups.clear();
+    }
+    return VSLAM_OK;
+}
 
-    /* FAST cells */
+/* FAST cells, the bands of k_fast_bands and the candidate regions */
+static int create_fast(vslam_fe* fe) {
+    const vslam_fe_params& p = fe->p;
     for (int l = 0; l < p.nlevels; l++) {
         fe->level_cell_first[l] = (int)fe->cells.size();
         vslam::build_cells(l, fe->geom.lv[l].w, fe->geom.lv[l].h, fe->cells);
@@ -290,94 +276,58 @@ static int create_impl(const vslam_fe_params* pp, vslam_fe* fe) {
         g_err = "FAST cell larger than 8192 px";
         return VSLAM_ERR_UNSUPPORTED;
     }
-    {
-        int rc;
-        if ((rc = upload(&fe->d_cells, dc.data(), dc.size() * sizeof(CellDesc)))) return rc;
+    /* limits of k_fast_cells_v3 (LDS pitch 72, 2 keep words per interior row) and k_blur7_v2 (8-byte row windows); cell
+     * windows are at most 59 + 6 px on a side and levels at least 40 px wide, so these never trigger */
+    if (maxw > 66 || maxh > 134 || fe->geom.lv[p.nlevels - 1].w < 8) {
+        g_err = "FAST cell window larger than 66 x 134 px";
+        return VSLAM_ERR_UNSUPPORTED;
     }
-    {   /* bands of k_fast_bands: up to four cells of a cell row whose interiors are together at most 128 px wide */
-        std::vector<vslam::HostBand> hb;
-        const int per = std::min(4, std::max(1, tune_or(fe->tune.fast_band_cells, 4)));
-        vslam::build_bands(fe->cells, per, 128, hb);
-        int mwh = 0, miw = 0, mc = 0;
-        std::vector<BandDesc> db(hb.size());
-        /* column tables, one 272-byte record per (cell pitch, interior width) class: cellbit[136] = 1 << (cell of interior
-         * column x), 0 past the interior; cellfl[136] = bit 0 first / bit 1 last column of its cell */
-        std::vector<std::pair<int, int>> cls;
-        std::vector<uint8_t> tab;
-        for (size_t i = 0; i < hb.size(); i++) {
-            const vslam::HostBand& b = hb[i];
-            mwh = std::max(mwh, (int)b.wh);
-            miw = std::max(miw, (int)b.ww - 6);
-            mc = std::max(mc, (int)b.ncell);
-            const int iw = (int)b.ww - 6, wc = std::max(1, (int)b.wcell);
-            size_t ci = 0;
-            while (ci < cls.size() && cls[ci] != std::make_pair(wc, iw)) ci++;
-            if (ci == cls.size()) {
-                cls.push_back(std::make_pair(wc, iw));
-                tab.resize(tab.size() + 272, 0);
-                uint8_t* cb = tab.data() + ci * 272;
-                for (int x = 0; x < 136 && x < iw; x++) {
-                    const int c = x / wc, cend = std::min((c + 1) * wc, iw) - 1;
-                    cb[x] = (uint8_t)(1u << std::min(c, 7));
-                    cb[136 + x] = (uint8_t)((x == c * wc ? 1 : 0) | (x == cend ? 2 : 0));
-                }
-            }
-            db[i].cell0 = b.cell0;
-            db[i].lnw = (uint32_t)b.level | ((uint32_t)b.ncell << 4) | ((uint32_t)b.wcell << 8) | ((uint32_t)ci << 16);
-            db[i].xy = (uint32_t)b.x0 | ((uint32_t)b.y0 << 16);
-            db[i].wh = (uint32_t)b.ww | ((uint32_t)b.wh << 16);
-        }
-        bool ok = !hb.empty() && vk_fast_bands_check(mwh, miw, mc) == 0 && p.nlevels <= 16 && cls.size() < 65536;
-        for (const vslam::HostBand& b : hb) ok = ok && b.wcell < 256;
-        if (ok) {
-            int rc;
-            if ((rc = upload(&fe->d_band_classes, tab.data(), tab.size()))) return rc;
-            if ((rc = upload(&fe->d_bands, db.data(), db.size() * sizeof(BandDesc)))) return rc;
-            fe->nbands = (int)db.size();
-            fe->band_max_wh = mwh;
-            fe->band_max_iw = miw;
-        }
+    UPLOAD(fe->d_cells, dc.data(), dc.size() * sizeof(CellDesc));
+    /* bands of k_fast_bands: up to four cells of a cell row whose interiors are together at most 128 px wide */
+    std::vector<vslam::HostBand> hb;
+    vslam::build_bands(fe->cells, std::min(4, std::max(1, tune_or(fe->tune.fast_band_cells, 4))), 128, hb);
+    vslam::BandTables bt;
+    vslam::pack_bands(hb, p.nlevels, bt);
+    static_assert(sizeof(BandDesc) == sizeof(vslam::BandWords), "packer and kernel share the band record");
+    if (bt.ok && vk_fast_bands_check(bt.max_wh, bt.max_iw, bt.max_cells) == 0) {
+        UPLOAD(fe->d_band_classes, bt.classes.data(), bt.classes.size());
+        UPLOAD(fe->d_bands, bt.bands.data(), bt.bands.size() * sizeof(BandDesc));
+        fe->nbands = (int)bt.bands.size();
+        fe->band_max_wh = bt.max_wh;
+        fe->band_max_iw = bt.max_iw;
     }
-    const int ncells = (int)fe->cells.size();
     /* every cell owns a fixed segment sized by the exact upper bound of its NMS survivors */
     fe->cand_cap = (int)std::max<size_t>(cand_total, 16);
-    fe->cand_stride = (8 + (size_t)ncells * sizeof(CellOut) + (size_t)fe->cand_cap * 4 + 255) & ~(size_t)255;
+    fe->cand_stride = (8 + fe->cells.size() * sizeof(CellOut) + (size_t)fe->cand_cap * 4 + 255) & ~(size_t)255;
     HIPCHK(hipMalloc((void**)&fe->d_cand, fe->cand_stride * fe->B));
     HIPCHK((hipError_t)vslam_pinned_alloc((void**)&fe->h_cand, fe->cand_stride * fe->B));
+    return VSLAM_OK;
+}
 
-    {
-        int rc;
-        if ((rc = upload(&fe->d_pattern, VSLAM_ORB_PATTERN, 1024))) return rc;
-    }
+/* descriptor pattern and disc, and the marching-rows blur's task list: one wave task per (level, row chunk, 248-column strip) */
+static int create_blur(vslam_fe* fe) {
+    UPLOAD(fe->d_pattern, VSLAM_ORB_PATTERN, 1024);
     vk_upload_disc(fe->tab.umax);
-    {
-        /* marching-rows blur: one wave task per (level, row chunk, 248-column strip) */
-        if (fe->tune.blur_rows >= 0) fe->blur_rows = std::min(512, std::max(8, (int)fe->tune.blur_rows));
-        else if (fe->B <= 2) fe->blur_rows = 8; /* one or two images: more, shorter tasks finish sooner (batch-1 latency -5 us) */
-        std::vector<uint32_t> tasks;
-        for (int l = 0; l < p.nlevels; l++) {
-            const int br = fe->blur_rows;
-            const int ns = std::max(1, (fe->geom.lv[l].w + 247) / 248), nc = (fe->geom.lv[l].h + br - 1) / br;
-            for (int c = 0; c < nc; c++)
-                for (int s = 0; s < ns; s++) tasks.push_back(((uint32_t)l << 24) | ((uint32_t)c << 12) | (uint32_t)s);
-        }
-        fe->n_blur_tasks = (int)tasks.size();
-        int rc;
-        if ((rc = upload(&fe->d_blur_tasks, tasks.data(), tasks.size() * 4))) return rc;
-        /* limits of k_fast_cells_v3 (LDS pitch 72, 2 keep words per interior row) and
-         * k_blur7_v2 (8-byte row windows); cell windows are at most 59 + 6 px on a side and levels at least 40 px wide,
-         * so these never trigger */
-        if (maxw > 66 || maxh > 134 || fe->geom.lv[p.nlevels - 1].w < 8) {
-            g_err = "FAST cell window larger than 66 x 134 px";
-            return VSLAM_ERR_UNSUPPORTED;
-        }
+    if (fe->tune.blur_rows >= 0) fe->blur_rows = std::min(512, std::max(8, (int)fe->tune.blur_rows));
+    else if (fe->B <= 2) fe->blur_rows = 8; /* one or two images: more, shorter tasks finish sooner (batch-1 latency -5 us) */
+    std::vector<uint32_t> tasks;
+    for (int l = 0; l < fe->p.nlevels; l++) {
+        const int br = fe->blur_rows;
+        const int ns = std::max(1, (fe->geom.lv[l].w + 247) / 248), nc = (fe->geom.lv[l].h + br - 1) / br;
+        for (int c = 0; c < nc; c++)
+            for (int s = 0; s < ns; s++) tasks.push_back(((uint32_t)l << 24) | ((uint32_t)c << 12) | (uint32_t)s);
     }
+    fe->n_blur_tasks = (int)tasks.size();
+    UPLOAD(fe->d_blur_tasks, tasks.data(), tasks.size() * 4);
+    return VSLAM_OK;
+}
 
+/* the selected-keypoint lists, and ONE result block per context -- counts | keypoints | descriptors, back to back -- with
+ * one pinned mirror of it: a full batch leaves the device in a single transfer (vslam_deliver_block) */
+static int create_result_block(vslam_fe* fe) {
     const size_t nk = (size_t)fe->B * fe->cap;
     HIPCHK(hipMalloc((void**)&fe->d_sel, nk * sizeof(SelKp)));
     HIPCHK((hipError_t)vslam_pinned_alloc((void**)&fe->h_sel, nk * sizeof(SelKp)));
-    /* ONE result block per context -- counts | keypoints | descriptors, back to back -- and one pinned mirror of it: a
-     * full batch leaves the device in a single transfer (vslam_fe.hip: enqueue_extract_plain) */
     fe->res_counts_bytes = (((size_t)(fe->B * 4 + 4) * 4) + 255) & ~(size_t)255;
     fe->res_feat_bytes = fe->res_counts_bytes + nk * sizeof(vslam_kp) + nk * 32; /* multiple of 16: cap % 4 == 0 */
     /* ... followed by the outputs of the device SearchForInitialization for up to B pairs (vnMatches12 | vbPrevMatched |
@@ -398,131 +348,102 @@ static int create_impl(const vslam_fe_params* pp, vslam_fe* fe) {
     fe->h_init = fe->h_res + fe->res_feat_bytes;
     fe->init_bytes = fe->h_init_bytes = fe->res_init_bytes;
     fe->init_in_block = true;
+    return VSLAM_OK;
+}
 
-    /* GPU quadtree distribution (k_octree): per-level parameters, key ping-pong arrays, result lists */
-    {
-        OctParams& O = fe->oct;
-        memset(&O, 0, sizeof(O));
-        int maxNodes = 16, selOff = 0;
-        bool ok = !(p.flags & VSLAM_FLAG_HOST_OCTREE);
-        for (int l = 0; l < p.nlevels; l++) {
-            const int W = fe->geom.lv[l].w - 2 * VSLAM_FAST_BORDER, H = fe->geom.lv[l].h - 2 * VSLAM_FAST_BORDER;
-            const int nIni = (int)std::round((float)W / (float)H);
-            O.N[l] = fe->tab.quota[l];
-            O.H[l] = H;
-            O.nIni[l] = nIni;
-            O.hX[l] = (float)W / nIni;
-            O.cellFirst[l] = fe->level_cell_first[l];
-            O.selOff[l] = selOff;
-            const int cap_l = std::max(O.N[l] + 3, 4 * nIni) + 1;
-            selOff += cap_l;
-            maxNodes = std::max(maxNodes, cap_l);
-            /* at least one node per four cells of the level: k_octree_v4 borrows the node arrays behind the first one for the
-             * level's cell offsets and segment bases (2 u32 per cell + sentinel; 10 u32 per node there).  The bound is looser
-             * than v4 needs; it is kept as it is because v4's layout, fine depths and occupancy were measured with it */
-            maxNodes = std::max(maxNodes, (fe->level_cell_first[l + 1] - fe->level_cell_first[l] + 1 + 3) / 4); /* + sentinel */
-            if (nIni > 64) ok = false;
-        }
-        O.cellFirst[p.nlevels] = fe->level_cell_first[p.nlevels];
-        O.selStride = selOff;
-        O.maxNodes = (maxNodes + 15) & ~15;
-        std::vector<uint32_t> lut;
-        {
-            /* k_octree_v4's fine grid: one level deeper than the depth at which a full quadtree has N nodes (nIni * 4^d
-             * at depth d), so that the split passes, which stop at N nodes, mostly stay above it; keys that cluster
-             * below it are handled exactly by the kernel's in-cell path, so the depth only decides speed.  Both arrays
-             * of the largest level must fit LDS next to the node arrays (budget below), at most 16384 cells (the cell
-             * index travels in 16 bits), and no cell may be able to hold 65536 keys (the rank does too).
-             * vslam_tuning.oct_fine_depth forces a depth where it is admissible (tests: deep splits everywhere). */
-            const int fd = fe->tune.oct_fine_depth; /* -1: by the level's quota */
-            const size_t nb = (vk_octree_lds_bytes(O.maxNodes) + 15) & ~(size_t)15;
-            /* LDS a quadtree workgroup may take in all (default 128 KB of the CU's 160) */
-            const size_t budget = (size_t)std::min(150, std::max(16, tune_or(fe->tune.oct_lds_budget_kb, 128))) * 1024;
-            int maxcells = 0;
-            for (int l = 0; l < p.nlevels; l++) {
-                const int W = fe->geom.lv[l].w - 2 * VSLAM_FAST_BORDER, H = O.H[l];
-                int D = 1;
-                while ((O.nIni[l] << (2 * D)) < O.N[l]) D++;
-                D += 1;
-                if (fd >= 0) D = fd;
-                D = std::max(1, std::min(D, 11));
-                auto cell_keys = [&](int d) { /* strict 3x3 maxima a cell of depth d can hold: every other pixel of every other row */
-                    const long long cw = (W / O.nIni[l] >> d) + 2, ch = (H >> d) + 2;
-                    return ((cw + 1) / 2) * ((ch + 1) / 2);
-                };
-                while (D < 11 && cell_keys(D) >= 65535) D++;
-                while (D > 1 && (((long long)O.nIni[l] << (2 * D)) > 16384 ||
-                                 nb + 2 * (((size_t)O.nIni[l] << (2 * D)) + 1) * 4 + 16 > budget) && cell_keys(D - 1) < 65535)
-                    D--;
-                O.fineD[l] = D;
-                maxcells = std::max(maxcells, O.nIni[l] << (2 * D));
-                std::vector<uint32_t> xs, ys;
-                vslam::build_oct_lut(W, H, D, xs, ys);
-                O.lutOff[l] = (int32_t)lut.size();
-                O.lutW[l] = (int32_t)xs.size();
-                lut.insert(lut.end(), xs.begin(), xs.end());
-                lut.insert(lut.end(), ys.begin(), ys.end());
-            }
-            O.fineLdsOff = (int32_t)nb;
-            O.fineLdsBytes = (int32_t)(2 * ((size_t)maxcells + 1) * 4 + 16);
-            if (nb + (size_t)O.fineLdsBytes > 160 * 1024) ok = false; /* cannot happen with the limits above */
-        }
-        O.ptsCap = fe->cand_cap;
-        O.dbg = nullptr;
-        if (fe->tune.oct_debug == 1) {
-            HIPCHK(hipMalloc(&O.dbg, 64 * 8));
-            HIPCHK(hipMemset(O.dbg, 0, 64 * 8));
-        }
-        O.maxIter = tune_or(fe->tune.oct_max_iter, 64);
-        if (vk_octree_lds_bytes(O.maxNodes) > 150 * 1024) ok = false; /* list does not fit LDS: host quadtree */
-        fe->dev_octree = ok;
-        if (ok) {
-            if (vk_octree_set_max_lds((size_t)O.fineLdsOff + (size_t)O.fineLdsBytes + 16) != 0) {
-                g_err = "hipFuncSetAttribute(k_octree, max dynamic LDS) failed";
-                return VSLAM_ERR_HIP;
-            }
-            const size_t np = (size_t)fe->B * fe->cand_cap;
-            HIPCHK(hipMalloc((void**)&fe->d_pts[0], np * 4));
-            HIPCHK(hipMalloc((void**)&fe->d_pts[1], np * 4));
-            HIPCHK(hipMalloc((void**)&fe->d_sel_xyr, (size_t)fe->B * O.selStride * 4));
-            HIPCHK(hipMalloc((void**)&fe->d_sel_cnt, (size_t)fe->B * VSLAM_MAX_LEVELS * 4));
-            HIPCHK(hipMalloc((void**)&fe->d_oct_sorted, np * 8));
-            HIPCHK(hipMalloc((void**)&fe->d_oct_redo, (size_t)fe->B * VSLAM_MAX_LEVELS * 4));
-            HIPCHK(hipMemset(fe->d_oct_redo, 0, (size_t)fe->B * VSLAM_MAX_LEVELS * 4));
-            int rc;
-            if ((rc = upload(&fe->d_oct_lut, lut.data(), lut.size() * 4))) return rc;
-            O.lut = fe->d_oct_lut;
-        }
+/* quadtree distribution on the device (k_octree_v4): the plan (vslam::plan_octree) into OctParams, key ping-pong arrays,
+ * result lists; decides the placement */
+static int create_quadtree(vslam_fe* fe) {
+    const vslam_fe_params& p = fe->p;
+    int lws[VSLAM_MAX_LEVELS], lhs[VSLAM_MAX_LEVELS];
+    for (int l = 0; l < p.nlevels; l++) {
+        lws[l] = fe->geom.lv[l].w;
+        lhs[l] = fe->geom.lv[l].h;
     }
-
-    {
-        /* The runtime multiplexes HIP streams onto a fixed number of hardware queues (GPU_MAX_HW_QUEUES), one pool per
-         * stream priority, least-used queue first.  In a process that already holds dozens of streams (torch, four RCCL
-         * communicators) two contexts ended up on ONE hardware queue and their passes ran one behind the other (mono
-         * 157 k -> 97 k frames/s, the kernel trace shows the shared queue id).  Streams of a priority of their own draw
-         * from a pool nobody else uses: with stream_priority 2 (1 = low) the context's stream is created with a priority of
-         * its own.  The library default is 0 -- the default pool -- because a high-priority stream also pre-empts the
-         * host application's own default-priority work; a pipelined caller opts in (bench.py does).  Measured: collective path at world size 1 97 k -> 143 k (high) / 141 k (low),
-         * the plain path unchanged at 157 k. */
-        const int pr = tune_or(fe->tune.stream_priority, 0);
-        int lo = 0, hi = 0;
-        if (pr != 0 && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && lo != hi)
-            HIPCHK(hipStreamCreateWithPriority(&fe->stream, hipStreamNonBlocking, pr == 1 ? lo : hi));
-        else
-            HIPCHK(hipStreamCreateWithFlags(&fe->stream, hipStreamNonBlocking));
+    /* LDS a quadtree workgroup may take in all (default 128 KB of the CU's 160) */
+    const size_t budget = (size_t)std::min(150, std::max(16, tune_or(fe->tune.oct_lds_budget_kb, 128))) * 1024;
+    vslam::OctPlan plan;
+    vslam::plan_octree(fe->tab.quota.data(), lws, lhs, fe->level_cell_first, p.nlevels, fe->tune.oct_fine_depth, budget,
+                       vk_octree_lds_bytes, plan);
+    OctParams& O = fe->oct;
+    memset(&O, 0, sizeof(O));
+    for (int l = 0; l < p.nlevels; l++) {
+        O.N[l] = plan.N[l]; O.H[l] = plan.H[l]; O.nIni[l] = plan.nIni[l]; O.hX[l] = plan.hX[l];
+        O.selOff[l] = plan.selOff[l]; O.fineD[l] = plan.fineD[l]; O.lutOff[l] = plan.lutOff[l]; O.lutW[l] = plan.lutW[l];
     }
-    HIPCHK(hipEventCreateWithFlags(&fe->ev_cand, hipEventDisableTiming));
-    fe->use_graph = fe->tune.graphs != 0; /* 0: never replay captured graphs */
+    for (int l = 0; l <= p.nlevels; l++) O.cellFirst[l] = fe->level_cell_first[l];
+    O.selStride = plan.selStride;
+    O.maxNodes = plan.maxNodes;
+    O.fineLdsOff = plan.fineLdsOff;
+    O.fineLdsBytes = plan.fineLdsBytes;
+    O.ptsCap = fe->cand_cap;
+    if (fe->tune.oct_debug == 1) {
+        HIPCHK(hipMalloc(&O.dbg, 64 * 8));
+        HIPCHK(hipMemset(O.dbg, 0, 64 * 8));
+    }
+    O.maxIter = tune_or(fe->tune.oct_max_iter, 64);
+    const bool on_device = fe->dev_octree = plan.fits && !(p.flags & VSLAM_FLAG_HOST_OCTREE);
     /* threads per quadtree problem (vk_octree): 1024 for one or two images, else 256, 512 for frames above a megapixel */
     fe->oct_threads = fe->tune.oct_threads == 256 || fe->tune.oct_threads == 512 || fe->tune.oct_threads == 1024
                           ? fe->tune.oct_threads
                           : fe->B <= 2 ? 1024 : (size_t)p.width * p.height > 1000000 ? 512 : 256;
-    fe->sel_level.resize((size_t)fe->B * p.nlevels);
-    fe->cand_level.resize((size_t)fe->B * p.nlevels);
+    if (!on_device) return VSLAM_OK; /* none of the buffers below is needed */
+    if (vk_octree_set_max_lds((size_t)O.fineLdsOff + (size_t)O.fineLdsBytes + 16) != 0) {
+        g_err = "hipFuncSetAttribute(k_octree, max dynamic LDS) failed";
+        return VSLAM_ERR_HIP;
+    }
+    const size_t np = (size_t)fe->B * fe->cand_cap;
+    HIPCHK(hipMalloc((void**)&fe->d_pts[0], np * 4));
+    HIPCHK(hipMalloc((void**)&fe->d_pts[1], np * 4));
+    HIPCHK(hipMalloc((void**)&fe->d_sel_xyr, (size_t)fe->B * O.selStride * 4));
+    HIPCHK(hipMalloc((void**)&fe->d_sel_cnt, (size_t)fe->B * VSLAM_MAX_LEVELS * 4));
+    HIPCHK(hipMalloc((void**)&fe->d_oct_sorted, np * 8));
+    HIPCHK(hipMalloc((void**)&fe->d_oct_redo, (size_t)fe->B * VSLAM_MAX_LEVELS * 4));
+    HIPCHK(hipMemset(fe->d_oct_redo, 0, (size_t)fe->B * VSLAM_MAX_LEVELS * 4));
+    UPLOAD(fe->d_oct_lut, plan.lut.data(), plan.lut.size() * 4);
+    O.lut = fe->d_oct_lut;
+    return VSLAM_OK;
+}
+
+static int create_stream_and_pool(vslam_fe* fe) {
+    /* The runtime multiplexes HIP streams onto a fixed number of hardware queues (GPU_MAX_HW_QUEUES), one pool per
+     * stream priority, least-used queue first.  In a process that already holds dozens of streams (torch, four RCCL
+     * communicators) two contexts ended up on ONE hardware queue and their passes ran one behind the other (mono
+     * 157 k -> 97 k frames/s, the kernel trace shows the shared queue id).  Streams of a priority of their own draw
+     * from a pool nobody else uses: with stream_priority 2 (1 = low) the context's stream is created with a priority of
+     * its own.  The library default is 0 -- the default pool -- because a high-priority stream also pre-empts the
+     * host application's own default-priority work; a pipelined caller opts in (bench.py does).  Measured: collective path at world size 1 97 k -> 143 k (high) / 141 k (low),
+     * the plain path unchanged at 157 k. */
+    const int pr = tune_or(fe->tune.stream_priority, 0);
+    int lo = 0, hi = 0;
+    if (pr != 0 && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && lo != hi)
+        HIPCHK(hipStreamCreateWithPriority(&fe->stream, hipStreamNonBlocking, pr == 1 ? lo : hi));
+    else
+        HIPCHK(hipStreamCreateWithFlags(&fe->stream, hipStreamNonBlocking));
+    HIPCHK(hipEventCreateWithFlags(&fe->ev_cand, hipEventDisableTiming));
+    fe->use_graph = fe->tune.graphs != 0; /* 0: never replay captured graphs */
+    fe->sel_level.resize((size_t)fe->B * fe->p.nlevels);
+    fe->cand_level.resize((size_t)fe->B * fe->p.nlevels);
     unsigned hw = std::thread::hardware_concurrency();
     int nthreads = (int)std::min<unsigned>(hw ? hw : 4, 16) - 1;
-    nthreads = std::min(nthreads, fe->B * p.nlevels - 1);
+    nthreads = std::min(nthreads, fe->B * fe->p.nlevels - 1);
     fe->pool = new WorkerPool(std::max(nthreads, 0));
+    return VSLAM_OK;
+}
+
+static int create_impl(vslam_fe* fe) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || fe->p.device >= ndev) {
+        g_err = "no usable HIP device (this library has no CPU fallback)";
+        return VSLAM_ERR_NO_DEVICE;
+    }
+    HIPCHK(hipSetDevice(fe->p.device));
+    int (*const steps[])(vslam_fe*) = {create_geometry, create_pyramid, create_fast, create_blur, create_result_block,
+                                       create_quadtree, create_stream_and_pool};
+    for (auto step : steps) {
+        const int rc = step(fe);
+        if (rc != VSLAM_OK) return rc;
+    }
     HIPCHK(hipDeviceSynchronize());
     return VSLAM_OK;
 }
@@ -541,7 +462,7 @@ extern "C" int vslam_fe_create(const vslam_fe_params* p, vslam_fe** out) {
     fe->p = *p;
     fe->tune = vslam_resolve_tuning(p->tuning);
     fe->p.tuning = nullptr; /* the caller's struct need not outlive the call */
-    int rc = create_impl(p, fe);
+    int rc = create_impl(fe);
     if (rc != VSLAM_OK) {
         std::string keep = g_err;
         free_ctx(fe);
@@ -676,18 +597,6 @@ extern "C" int vslam_fe_get_profile(vslam_fe* fe, double stage_ms[5], long* batc
     return VSLAM_OK;
 }
 
-static int pack_range(vslam_fe* fe, int first, int nslots, void* dev_dst, size_t slot_bytes, bool sync);
-
-extern "C" int vslam_fe_pack_slot_range(vslam_fe* fe, int first, int nslots, void* dev_dst, size_t slot_bytes) {
-    return pack_range(fe, first, nslots, dev_dst, slot_bytes, true);
-}
-
-/* same, but only enqueued on the context's stream (ordered after the extraction that produced the slots) */
-extern "C" int vslam_fe_pack_slot_range_async(vslam_fe* fe, int first, int nslots, void* dev_dst,
-                                              size_t slot_bytes) {
-    return pack_range(fe, first, nslots, dev_dst, slot_bytes, false);
-}
-
 static int pack_range(vslam_fe* fe, int first, int nslots, void* dev_dst, size_t slot_bytes, bool sync) {
     if (!fe || first < 0 || nslots < 0 || first + nslots > fe->B || !dev_dst ||
         slot_bytes < 16 + (size_t)fe->cap * 60 || (slot_bytes & 15) || ((uintptr_t)dev_dst & 15)) {
@@ -700,6 +609,16 @@ static int pack_range(vslam_fe* fe, int first, int nslots, void* dev_dst, size_t
     HIPCHK(hipGetLastError());
     if (sync) HIPCHK(vslam_stream_wait(fe->stream));
     return VSLAM_OK;
+}
+
+extern "C" int vslam_fe_pack_slot_range(vslam_fe* fe, int first, int nslots, void* dev_dst, size_t slot_bytes) {
+    return pack_range(fe, first, nslots, dev_dst, slot_bytes, true);
+}
+
+/* same, but only enqueued on the context's stream (ordered after the extraction that produced the slots) */
+extern "C" int vslam_fe_pack_slot_range_async(vslam_fe* fe, int first, int nslots, void* dev_dst,
+                                              size_t slot_bytes) {
+    return pack_range(fe, first, nslots, dev_dst, slot_bytes, false);
 }
 
 extern "C" int vslam_fe_pack_slots(vslam_fe* fe, int nslots, void* dev_dst, size_t slot_bytes) {
@@ -890,6 +809,14 @@ static int upload_host_rows(vslam_fe* fe, int nimg, const uint8_t* const* imgs, 
     return VSLAM_OK;
 }
 
+/* level 0 of slots 0..nimg-1 is read from the context's own pyramid */
+static void src_at_slots(vslam_fe* fe, int nimg) {
+    for (int s = 0; s < nimg; s++) {
+        fe->src.l0[s] = fe->d_pyr + (size_t)s * fe->slot_stride + fe->geom.lv[0].off;
+        fe->src.pitch0[s] = (uint32_t)fe->geom.lv[0].pitch;
+    }
+}
+
 static int enqueue_front(vslam_fe* fe, int nimg, const uint8_t* const* imgs, size_t pitch, int on_device) {
     const vslam_fe_params& p = fe->p;
     const int L = p.nlevels;
@@ -903,18 +830,12 @@ static int enqueue_front(vslam_fe* fe, int nimg, const uint8_t* const* imgs, siz
             fe->src.l0[s] = imgs[s];
             fe->src.pitch0[s] = (uint32_t)pitch;
         }
-    } else if (on_device == VSLAM_IMGS_STAGED) {
-        for (int s = 0; s < nimg; s++) { /* vslam_fe_stage_images_async put them there */
-            fe->src.l0[s] = fe->d_pyr + (size_t)s * fe->slot_stride + fe->geom.lv[0].off;
-            fe->src.pitch0[s] = (uint32_t)fe->geom.lv[0].pitch;
-        }
     } else {
-        int rc = upload_host_rows(fe, nimg, imgs, pitch, on_device);
-        if (rc) return rc;
-        for (int s = 0; s < nimg; s++) {
-            fe->src.l0[s] = fe->d_pyr + (size_t)s * fe->slot_stride + fe->geom.lv[0].off;
-            fe->src.pitch0[s] = (uint32_t)fe->geom.lv[0].pitch;
+        if (on_device != VSLAM_IMGS_STAGED) { /* staged: vslam_fe_stage_images_async put them there */
+            int rc = upload_host_rows(fe, nimg, imgs, pitch, on_device);
+            if (rc) return rc;
         }
+        src_at_slots(fe, nimg);
     }
     fe->last_nimg = nimg;
     fe->cand_on_host = false;
@@ -954,20 +875,17 @@ static int enqueue_front(vslam_fe* fe, int nimg, const uint8_t* const* imgs, siz
     return VSLAM_OK;
 }
 
-static int fetch_candidates(vslam_fe* fe, int nimg, bool everything) {
-    /* header + cell table + a first chunk speculatively; the rest only if a slot needs it */
-    hipStream_t st = fe->stream;
+static int fetch_candidates(vslam_fe* fe, int nimg) {
+    /* header + cell table + candidates of every slot: the cells own fixed segments, so the used entries are scattered and
+     * the whole region travels */
     const size_t hdr_bytes = 8 + fe->cells.size() * sizeof(CellOut);
-    (void)everything; /* fixed per-cell segments: the used entries are scattered, copy the whole region */
-    const size_t first_cands = (size_t)fe->cand_cap;
-    HIPCHK(hipMemcpy2DAsync(fe->h_cand, fe->cand_stride, fe->d_cand, fe->cand_stride, hdr_bytes + first_cands * 4,
-                            nimg, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipEventRecord(fe->ev_cand, st));
+    HIPCHK(hipMemcpy2DAsync(fe->h_cand, fe->cand_stride, fe->d_cand, fe->cand_stride, hdr_bytes + (size_t)fe->cand_cap * 4,
+                            nimg, hipMemcpyDeviceToHost, fe->stream));
+    HIPCHK(hipEventRecord(fe->ev_cand, fe->stream));
     return VSLAM_OK;
 }
 
 static int wait_candidates(vslam_fe* fe, int nimg) {
-    hipStream_t st = fe->stream;
     HIPCHK(hipEventSynchronize(fe->ev_cand));
     for (int s = 0; s < nimg; s++) {
         const uint32_t* hdr = (const uint32_t*)(fe->h_cand + (size_t)s * fe->cand_stride);
@@ -976,27 +894,27 @@ static int wait_candidates(vslam_fe* fe, int nimg) {
             return VSLAM_ERR_CAPACITY;
         }
     }
-    (void)st;
     fe->cand_on_host = true;
     return VSLAM_OK;
 }
 
-static void enqueue_blur(vslam_fe* fe, int nimg) {
+static int enqueue_blur(vslam_fe* fe, int nimg) {
+    if (fe->profiling) HIPCHK(hipEventRecord(fe->ev_prof[3], fe->stream));
     vk_blur7_v2(fe->stream, fe->d_pyr, fe->slot_stride, fe->src, fe->geom, fe->d_blur, fe->d_blur_tasks,
                 fe->n_blur_tasks, fe->taps, fe->blur_rows, nimg);
+    if (fe->profiling) HIPCHK(hipEventRecord(fe->ev_prof[4], fe->stream));
+    return VSLAM_OK;
 }
 
-/* quadtree on the host (fallback when the node list does not fit LDS, or VSLAM_FLAG_HOST_OCTREE) */
-static int enqueue_back_host(vslam_fe* fe, int nimg, int lap0, int lap1) {
-    const vslam_fe_params& p = fe->p;
-    const int L = p.nlevels;
+/* Selection on the host (VSLAM_FLAG_HOST_OCTREE, or a node list that does not fit LDS): fetch the candidates, distribute
+ * them on the worker pool while the blur runs, and upload exactly what k_assign_out leaves behind -- the SelKp list of
+ * slot s at d_sel + s * cap and the counts block.  What it finds wrong is returned here, at enqueue time. */
+static int select_host(vslam_fe* fe, int nimg, int lap0, int lap1) {
+    const int L = fe->p.nlevels;
     hipStream_t st = fe->stream;
-    const bool prof = fe->profiling;
-    int rc = fetch_candidates(fe, nimg, false);
+    int rc = fetch_candidates(fe, nimg);
+    if (rc == VSLAM_OK) rc = enqueue_blur(fe, nimg); /* runs while the host distributes */
     if (rc) return rc;
-    if (prof) HIPCHK(hipEventRecord(fe->ev_prof[3], st));
-    enqueue_blur(fe, nimg); /* runs while the host distributes */
-    if (prof) HIPCHK(hipEventRecord(fe->ev_prof[4], st));
     HIPCHK(hipGetLastError());
     if ((rc = wait_candidates(fe, nimg))) return rc;
     std::atomic<int> bad(0);
@@ -1015,7 +933,6 @@ static int enqueue_back_host(vslam_fe* fe, int nimg, int lap0, int lap1) {
         return VSLAM_ERR_UNSUPPORTED;
     }
     /* output order (fextractor.cpp:1071-1129): level-major, lapping-area keypoints from the tail */
-    int nsel = 0;
     for (int s = 0; s < nimg; s++) {
         int nk = 0;
         for (int l = 0; l < L; l++) nk += (int)fe->sel_level[(size_t)s * L + l].size();
@@ -1023,6 +940,7 @@ static int enqueue_back_host(vslam_fe* fe, int nimg, int lap0, int lap1) {
             g_err = "internal keypoint capacity exceeded";
             return VSLAM_ERR_CAPACITY;
         }
+        SelKp* sel = fe->h_sel + (size_t)s * fe->cap;
         int monoIndex = 0, stereoIndex = nk - 1;
         for (int l = 0; l < L; l++) {
             const float scale = fe->tab.scale[l];
@@ -1038,60 +956,54 @@ static int enqueue_back_host(vslam_fe* fe, int nimg, int lap0, int lap1) {
                 k.response = c.response;
                 k.pad = 0;
                 k.out = (px >= (float)lap0 && px <= (float)lap1) ? (uint32_t)stereoIndex-- : (uint32_t)monoIndex++;
-                fe->h_sel[nsel++] = k;
+                *sel++ = k;
             }
         }
-        fe->n_out[s] = nk;
-        fe->mono_out[s] = monoIndex;
         fe->h_counts[s * 4] = nk;
         fe->h_counts[s * 4 + 1] = monoIndex;
+        fe->h_counts[s * 4 + 2] = 0; /* the device quadtree's deep-level mask */
     }
-    /* device-side consumers (stereo matcher) read the counts from HBM */
-    HIPCHK(hipMemcpyAsync(fe->d_counts, fe->h_counts, (size_t)nimg * 16, hipMemcpyHostToDevice, st));
-    if (nsel) {
-        HIPCHK(hipMemcpyAsync(fe->d_sel, fe->h_sel, (size_t)nsel * sizeof(SelKp), hipMemcpyHostToDevice, st));
-        if (prof) HIPCHK(hipEventRecord(fe->ev_prof[5], st));
-        vk_orient_describe(st, fe->d_pyr, fe->d_blur, fe->slot_stride, fe->src, fe->geom, fe->d_sel, nsel,
-                           fe->d_pattern, fe->d_kps, fe->d_desc, fe->cap, (p.flags & VSLAM_FLAG_ATAN_FMA) ? 1 : 0);
-        if ((rc = vslam_enqueue_undistort(fe, nimg))) return rc;
-        if (prof) HIPCHK(hipEventRecord(fe->ev_prof[6], st));
-    } else if (prof) {
-        HIPCHK(hipEventRecord(fe->ev_prof[5], st));
-        HIPCHK(hipEventRecord(fe->ev_prof[6], st));
-    }
-    if (prof) {
+    fe->h_counts[fe->B * 4] = 0; /* error word */
+    HIPCHK(hipMemcpyAsync(fe->d_counts, fe->h_counts, (size_t)(fe->B * 4 + 4) * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(fe->d_sel, fe->h_sel, (size_t)nimg * fe->cap * sizeof(SelKp), hipMemcpyHostToDevice, st));
+    if (fe->profiling) { /* nothing of this stage runs on the device: a zero-length span */
         HIPCHK(hipEventRecord(fe->ev_prof[7], st));
         HIPCHK(hipEventRecord(fe->ev_prof[8], st));
     }
-    HIPCHK(hipGetLastError());
     return VSLAM_OK;
 }
 
-/* quadtree on the device: nothing returns to the host until the results do */
-static int enqueue_back_dev(vslam_fe* fe, int nimg, int lap0, int lap1) {
-    const vslam_fe_params& p = fe->p;
+/* selection on the device: nothing returns to the host until the results do */
+static int select_dev(vslam_fe* fe, int nimg, int lap0, int lap1) {
     hipStream_t st = fe->stream;
-    const bool prof = fe->profiling;
     int32_t* d_err = fe->d_counts + (size_t)fe->B * 4;
-    if (prof) HIPCHK(hipEventRecord(fe->ev_prof[3], st));
-    enqueue_blur(fe, nimg);
-    if (prof) HIPCHK(hipEventRecord(fe->ev_prof[4], st));
-    if (prof) HIPCHK(hipEventRecord(fe->ev_prof[7], st));
+    const int rc = enqueue_blur(fe, nimg);
+    if (rc) return rc;
+    if (fe->profiling) HIPCHK(hipEventRecord(fe->ev_prof[7], st));
     vk_octree(st, fe->d_cand, fe->cand_stride, (int)fe->cells.size(), fe->oct, fe->d_pts[0], fe->d_pts[1],
-              fe->d_oct_sorted, (size_t)fe->cand_cap, fe->d_sel_xyr, fe->d_sel_cnt, d_err, p.nlevels, nimg,
+              fe->d_oct_sorted, (size_t)fe->cand_cap, fe->d_sel_xyr, fe->d_sel_cnt, d_err, fe->p.nlevels, nimg,
               fe->d_oct_redo, fe->tune.oct_regkeys, fe->oct_threads);
     vk_assign_out(st, fe->oct, fe->geom, fe->d_sel_xyr, fe->d_sel_cnt, lap0, lap1, fe->d_sel, fe->d_counts, fe->cap,
                   d_err, nimg, fe->d_oct_redo);
-    if (prof) HIPCHK(hipEventRecord(fe->ev_prof[8], st));
+    if (fe->profiling) HIPCHK(hipEventRecord(fe->ev_prof[8], st));
+    return VSLAM_OK;
+}
+
+/* blur and selection, then what both placements share: orientation + descriptors of the per-slot lists, undistortion */
+static int enqueue_back(vslam_fe* fe, int nimg, int lap0, int lap1) {
+    hipStream_t st = fe->stream;
+    const bool prof = fe->profiling;
+    int rc = fe->dev_octree ? select_dev(fe, nimg, lap0, lap1) : select_host(fe, nimg, lap0, lap1);
+    if (rc) return rc;
     if (prof) HIPCHK(hipEventRecord(fe->ev_prof[5], st));
     vk_orient_describe_dev(st, fe->d_pyr, fe->d_blur, fe->slot_stride, fe->src, fe->geom, fe->d_sel, fe->d_counts,
-                           fe->d_pattern, fe->d_kps, fe->d_desc, fe->cap, (p.flags & VSLAM_FLAG_ATAN_FMA) ? 1 : 0,
+                           fe->d_pattern, fe->d_kps, fe->d_desc, fe->cap, (fe->p.flags & VSLAM_FLAG_ATAN_FMA) ? 1 : 0,
                            nimg, fe->tune.desc_kpw >= 0 ? fe->tune.desc_kpw : fe->desc_kpw_hint);
-    const int rc = vslam_enqueue_undistort(fe, nimg); /* Frame::UndistortKeyPoints, if a camera asks for it */
+    rc = vslam_enqueue_undistort(fe, nimg); /* Frame::UndistortKeyPoints, if a camera asks for it */
     if (rc) return rc;
     if (prof) HIPCHK(hipEventRecord(fe->ev_prof[6], st));
     HIPCHK(hipGetLastError());
-    return VSLAM_OK; /* counts travel to the host with the results (vslam_enqueue_extract) */
+    return VSLAM_OK; /* counts travel to the host with the results (deliver) */
 }
 
 /* VSLAM_HOST_PROF=1: host-side wall time per API phase, printed by vslam_fe_destroy (diagnostics only) */
@@ -1112,21 +1024,46 @@ void vslam_host_prof_report() {
 }
 
 static int enqueue_extract_plain(vslam_fe* fe, int nimg, const uint8_t* const* imgs, size_t pitch, int on_device,
-                                 int lap0, int lap1, int want_host);
+                                 int lap0, int lap1, int want_host) {
+    const double t0 = hp_now();
+    int rc = enqueue_front(fe, nimg, imgs, pitch, on_device);
+    if (rc) return rc;
+    const double t1 = hp_now();
+    rc = enqueue_back(fe, nimg, lap0, lap1);
+    if (rc) return rc;
+    const double t2 = hp_now();
+    g_hp[0] += t1 - t0;
+    g_hp[1] += t2 - t1;
+    g_hp_n++;
+    struct D2hTimer {
+        double t;
+        ~D2hTimer() { g_hp[2] += hp_now() - t; }
+    } d2h_timer{t2};
+    /* results go to pinned host memory by a kernel (whole blocks: the host does not know the counts yet) */
+    if (nimg == fe->B && want_host == 2 && fe->res_init_bytes != 0)
+        return VSLAM_OK; /* deferred: vslam_search_init_dev_async (or the wait) sends the block; vslam_enqueue_extract sets the flag */
+    if (nimg == fe->B && want_host) /* a full batch: counts, keypoints and descriptors are one contiguous block -> ONE transfer */
+        return vslam_deliver_block(fe, 0);
+    CopyRanges R;
+    memset(&R, 0, sizeof(R));
+    R.dst[R.n] = fe->h_counts;
+    R.src[R.n] = fe->d_counts;
+    R.bytes[R.n++] = (size_t)(fe->B * 4 + 4) * 4;
+    if (want_host) {
+        R.dst[R.n] = fe->h_kps;
+        R.src[R.n] = fe->d_kps;
+        R.bytes[R.n++] = (size_t)nimg * fe->cap * sizeof(vslam_kp);
+        R.dst[R.n] = fe->h_desc;
+        R.src[R.n] = fe->d_desc;
+        R.bytes[R.n++] = (size_t)nimg * fe->cap * 32;
+    }
+    vslam_count_delivery(fe, vk_copy_ranges(fe->stream, R, fe->tune), R);
+    HIPCHK(hipGetLastError());
+    return VSLAM_OK;
+}
 
 /* want_host: 0 results stay in HBM (counts still reach the host), 1 delivered by this pass, 2 delivery DEFERRED to the
  * device SearchForInitialization that follows on this context (one transfer for both); if none follows, the wait delivers */
-static int enqueue_extract_impl(vslam_fe* fe, int nimg, const uint8_t* const* imgs, size_t pitch, int on_device, int lap0,
-                                int lap1, int want_host);
-
-int vslam_enqueue_extract(vslam_fe* fe, int nimg, const uint8_t* const* imgs, size_t pitch, int on_device,
-                          int lap0, int lap1, int want_host) {
-    const int rc = enqueue_extract_impl(fe, nimg, imgs, pitch, on_device, lap0, lap1, want_host);
-    /* set on every path, a replayed graph included (the captured pass of want_host = 2 holds no copy) */
-    fe->deliver_deferred = rc == VSLAM_OK && want_host == 2 && fe->dev_octree && nimg == fe->B && fe->res_init_bytes != 0;
-    return rc;
-}
-
 static int enqueue_extract_impl(vslam_fe* fe, int nimg, const uint8_t* const* imgs, size_t pitch, int on_device, int lap0,
                                 int lap1, int want_host) {
     HIPCHK(hipSetDevice(fe->p.device));
@@ -1161,10 +1098,7 @@ static int enqueue_extract_impl(vslam_fe* fe, int nimg, const uint8_t* const* im
         /* what enqueue_front records on a plain pass: later NON-captured consumers (stereo refinement,
          * vslam_fe_level_copy level 0) read fe->src, which a device-image pass in between may have pointed at the
          * caller's (by now possibly freed) images */
-        for (int s = 0; s < nimg; s++) {
-            fe->src.l0[s] = fe->d_pyr + (size_t)s * fe->slot_stride + fe->geom.lv[0].off;
-            fe->src.pitch0[s] = (uint32_t)fe->geom.lv[0].pitch;
-        }
+        src_at_slots(fe, nimg);
         HIPCHK(hipGraphLaunch(fe->graph_exec, fe->stream));
         fe->n_deliveries += fe->graph_deliveries;
         fe->n_delivery_bytes += fe->graph_delivery_bytes;
@@ -1208,90 +1142,40 @@ static int enqueue_extract_impl(vslam_fe* fe, int nimg, const uint8_t* const* im
     return VSLAM_OK;
 }
 
-static int enqueue_extract_plain(vslam_fe* fe, int nimg, const uint8_t* const* imgs, size_t pitch, int on_device,
-                                 int lap0, int lap1, int want_host) {
-    const double t0 = hp_now();
-    int rc = enqueue_front(fe, nimg, imgs, pitch, on_device);
-    if (rc) return rc;
-    const double t1 = hp_now();
-    rc = fe->dev_octree ? enqueue_back_dev(fe, nimg, lap0, lap1) : enqueue_back_host(fe, nimg, lap0, lap1);
-    if (rc) return rc;
-    const double t2 = hp_now();
-    g_hp[0] += t1 - t0;
-    g_hp[1] += t2 - t1;
-    g_hp_n++;
-    struct D2hTimer {
-        double t;
-        ~D2hTimer() { g_hp[2] += hp_now() - t; }
-    } d2h_timer{t2};
-    hipStream_t st = fe->stream;
-    /* results go to pinned host memory by a kernel (whole blocks: the host does not know the counts yet) */
-    CopyRanges R;
-    memset(&R, 0, sizeof(R));
-    if (want_host == 2 && fe->dev_octree && nimg == fe->B && fe->res_init_bytes != 0)
-        return VSLAM_OK; /* deferred: vslam_search_init_dev_async (or the wait) sends the block; vslam_enqueue_extract sets the flag */
-    if (want_host && fe->dev_octree && nimg == fe->B) {
-        /* a full batch: counts, keypoints and descriptors are one contiguous block -> ONE transfer */
-        R.dst[0] = fe->h_res;
-        R.src[0] = fe->d_res;
-        R.bytes[0] = fe->res_feat_bytes;
-        R.n = 1;
-        vslam_count_delivery(fe, vk_copy_ranges(st, R, fe->tune), R);
-        HIPCHK(hipGetLastError());
-        return VSLAM_OK;
-    }
-    if (fe->dev_octree) {
-        R.dst[R.n] = fe->h_counts;
-        R.src[R.n] = fe->d_counts;
-        R.bytes[R.n++] = (size_t)(fe->B * 4 + 4) * 4;
-    }
-    if (want_host) {
-        R.dst[R.n] = fe->h_kps;
-        R.src[R.n] = fe->d_kps;
-        R.bytes[R.n++] = (size_t)nimg * fe->cap * sizeof(vslam_kp);
-        R.dst[R.n] = fe->h_desc;
-        R.src[R.n] = fe->d_desc;
-        R.bytes[R.n++] = (size_t)nimg * fe->cap * 32;
-    }
-    vslam_count_delivery(fe, vk_copy_ranges(st, R, fe->tune), R);
-    HIPCHK(hipGetLastError());
-    return VSLAM_OK;
+int vslam_enqueue_extract(vslam_fe* fe, int nimg, const uint8_t* const* imgs, size_t pitch, int on_device,
+                          int lap0, int lap1, int want_host) {
+    const int rc = enqueue_extract_impl(fe, nimg, imgs, pitch, on_device, lap0, lap1, want_host);
+    /* set on every path, a replayed graph included (the captured pass of want_host = 2 holds no copy) */
+    fe->deliver_deferred = rc == VSLAM_OK && want_host == 2 && nimg == fe->B && fe->res_init_bytes != 0;
+    return rc;
 }
 
 int vslam_finish_extract(vslam_fe* fe, int nimg) {
     hipStream_t st = fe->stream;
     if (fe->deliver_deferred) { /* a deferred delivery that no matcher call picked up */
         fe->deliver_deferred = false;
-        CopyRanges R;
-        memset(&R, 0, sizeof(R));
-        R.dst[0] = fe->h_res;
-        R.src[0] = fe->d_res;
-        R.bytes[0] = fe->res_feat_bytes;
-        R.n = 1;
-        vslam_count_delivery(fe, vk_copy_ranges(st, R, fe->tune), R);
-        HIPCHK(hipGetLastError());
+        const int rc = vslam_deliver_block(fe, 0);
+        if (rc) return rc;
     }
     const double t_sync = hp_now();
     HIPCHK(vslam_stream_wait(st));
     g_hp[3] += hp_now() - t_sync;
-    if (fe->dev_octree) {
-        const int32_t* err = fe->h_counts + (size_t)fe->B * 4;
-        if (err[0] & 1) {
-            g_err = "FAST candidate buffer overflow (or > 65535 candidates on one level)";
-            return VSLAM_ERR_CAPACITY;
-        }
-        if (err[0] & 2) {
-            g_err = "internal keypoint capacity exceeded";
-            return VSLAM_ERR_CAPACITY;
-        }
-        for (int s = 0; s < nimg; s++) {
-            fe->n_out[s] = fe->h_counts[s * 4];
-            fe->mono_out[s] = fe->h_counts[s * 4 + 1];
-            fe->oct_last_mask[s] = (uint32_t)fe->h_counts[s * 4 + 2];
-            fe->oct_deep += (unsigned)__builtin_popcount(fe->oct_last_mask[s]);
-        }
-        fe->oct_problems += (unsigned long long)nimg * fe->p.nlevels;
+    const int32_t err = fe->h_counts[(size_t)fe->B * 4];
+    if (err & 1) {
+        g_err = "FAST candidate buffer overflow (or > 65535 candidates on one level)";
+        return VSLAM_ERR_CAPACITY;
     }
+    if (err & 2) {
+        g_err = "internal keypoint capacity exceeded";
+        return VSLAM_ERR_CAPACITY;
+    }
+    for (int s = 0; s < nimg; s++) {
+        fe->n_out[s] = fe->h_counts[s * 4];
+        fe->mono_out[s] = fe->h_counts[s * 4 + 1];
+        fe->oct_last_mask[s] = (uint32_t)fe->h_counts[s * 4 + 2];
+        fe->oct_deep += (unsigned)__builtin_popcount(fe->oct_last_mask[s]);
+    }
+    if (fe->dev_octree) fe->oct_problems += (unsigned long long)nimg * fe->p.nlevels; /* problems distributed on the device */
     if (fe->profiling) {
         float ms;
         static const int span[5][2] = {{0, 1}, {1, 2}, {3, 4}, {5, 6}, {7, 8}};
@@ -1411,13 +1295,13 @@ extern "C" int vslam_fe_stage_images_async(vslam_fe* fe, int nimg, const uint8_t
 extern "C" int vslam_fe_candidates(vslam_fe* fe, int slot, int level, vslam_kp* out, int cap) {
     if (!fe || slot < 0 || slot >= fe->B || level < 0 || level >= fe->p.nlevels || slot >= fe->last_nimg)
         return VSLAM_ERR_INVALID;
-    if (!fe->cand_on_host) { /* device-quadtree path: the candidates never left HBM; fetch them now */
+    if (!fe->cand_on_host) { /* device quadtree: the candidates never left HBM; fetch them now */
         HIPCHK(hipSetDevice(fe->p.device));
-        int rc = fetch_candidates(fe, fe->last_nimg, true);
+        int rc = fetch_candidates(fe, fe->last_nimg);
         if (rc == VSLAM_OK) rc = wait_candidates(fe, fe->last_nimg);
         if (rc) return rc;
     }
-    if (fe->dev_octree || true) decode_candidates(fe, slot, level);
+    decode_candidates(fe, slot, level);
     const std::vector<vslam::Cand>& cl = fe->cand_level[(size_t)slot * fe->p.nlevels + level];
     for (int i = 0; i < (int)cl.size() && i < cap && out; i++) {
         out[i].x = (float)cl[i].x;

@@ -552,6 +552,112 @@ uint32_t oct_key_path(int x, int y, int W, int H, int depth) {
     return ((uint32_t)b << (2 * depth)) | code;
 }
 
+void pack_bands(const std::vector<HostBand>& hb, int nlevels, BandTables& out) {
+    out = BandTables();
+    out.bands.resize(hb.size());
+    std::vector<std::pair<int, int>> cls;
+    bool ok = !hb.empty() && nlevels <= 16;
+    for (size_t i = 0; i < hb.size(); i++) {
+        const HostBand& b = hb[i];
+        out.max_wh = std::max(out.max_wh, (int)b.wh);
+        out.max_iw = std::max(out.max_iw, (int)b.ww - 6);
+        out.max_cells = std::max(out.max_cells, (int)b.ncell);
+        ok = ok && b.wcell < 256;
+        const int iw = (int)b.ww - 6, wc = std::max(1, (int)b.wcell);
+        size_t ci = 0;
+        while (ci < cls.size() && cls[ci] != std::make_pair(wc, iw)) ci++;
+        if (ci == cls.size()) {
+            cls.push_back(std::make_pair(wc, iw));
+            out.classes.resize(out.classes.size() + 272, 0);
+            uint8_t* cb = out.classes.data() + ci * 272;
+            for (int x = 0; x < 136 && x < iw; x++) {
+                const int c = x / wc, cend = std::min((c + 1) * wc, iw) - 1;
+                cb[x] = (uint8_t)(1u << std::min(c, 7));
+                cb[136 + x] = (uint8_t)((x == c * wc ? 1 : 0) | (x == cend ? 2 : 0));
+            }
+        }
+        out.bands[i].cell0 = b.cell0;
+        out.bands[i].lnw = (uint32_t)b.level | ((uint32_t)b.ncell << 4) | ((uint32_t)b.wcell << 8) | ((uint32_t)ci << 16);
+        out.bands[i].xy = (uint32_t)b.x0 | ((uint32_t)b.y0 << 16);
+        out.bands[i].wh = (uint32_t)b.ww | ((uint32_t)b.wh << 16);
+    }
+    out.ok = ok && cls.size() < 65536;
+}
+
+int keypoint_capacity(const int* quota, const int* lw, const int* lh, int nlevels, int nfeatures) {
+    /* a level ends with at most N_l + 2 nodes, except that the first pass splits all nIni initial nodes unconditionally (up
+     * to 4 * nIni); the documented formula stays the floor so common configurations keep their layout */
+    int bound = 0;
+    for (int l = 0; l < nlevels; l++) {
+        const int W = lw[l] - 2 * VSLAM_FAST_BORDER, H = lh[l] - 2 * VSLAM_FAST_BORDER;
+        bound += std::max(quota[l] + 3, 4 * (int)std::round((float)W / (float)H));
+    }
+    return std::max((nfeatures + 4 * nlevels + 8 + 3) & ~3, (bound + 3) & ~3);
+}
+
+void plan_octree(const int* quota, const int* lw, const int* lh, const int* cell_first, int L, int forced_depth,
+                 size_t budget, const std::function<size_t(int)>& node_bytes, OctPlan& P) {
+    P = OctPlan();
+    int maxNodes = 16, selOff = 0;
+    bool fits = true;
+    for (int l = 0; l < L; l++) {
+        const int W = lw[l] - 2 * VSLAM_FAST_BORDER, H = lh[l] - 2 * VSLAM_FAST_BORDER;
+        const int nIni = (int)std::round((float)W / (float)H);
+        P.N[l] = quota[l];
+        P.H[l] = H;
+        P.nIni[l] = nIni;
+        P.hX[l] = (float)W / nIni;
+        P.selOff[l] = selOff;
+        const int cap_l = std::max(P.N[l] + 3, 4 * nIni) + 1;
+        selOff += cap_l;
+        maxNodes = std::max(maxNodes, cap_l);
+        /* at least one node per four cells of the level: k_octree_v4 borrows the node arrays behind the first one for the
+         * level's cell offsets and segment bases (2 u32 per cell + sentinel; 10 u32 per node there).  The bound is looser
+         * than v4 needs; it is kept as it is because v4's layout, fine depths and occupancy were measured with it */
+        maxNodes = std::max(maxNodes, (cell_first[l + 1] - cell_first[l] + 1 + 3) / 4); /* + sentinel */
+        if (nIni > 64) fits = false;
+    }
+    P.selStride = selOff;
+    P.maxNodes = (maxNodes + 15) & ~15;
+    /* k_octree_v4's fine grid: one level deeper than the depth at which a full quadtree has N nodes (nIni * 4^d
+     * at depth d), so that the split passes, which stop at N nodes, mostly stay above it; keys that cluster
+     * below it are handled exactly by the kernel's in-cell path, so the depth only decides speed.  Both arrays
+     * of the largest level must fit LDS next to the node arrays (budget), at most 16384 cells (the cell
+     * index travels in 16 bits), and no cell may be able to hold 65536 keys (the rank does too).
+     * forced_depth forces a depth where it is admissible (tests: deep splits everywhere). */
+    const size_t nb = (node_bytes(P.maxNodes) + 15) & ~(size_t)15;
+    int maxcells = 0;
+    for (int l = 0; l < L; l++) {
+        const int W = lw[l] - 2 * VSLAM_FAST_BORDER, H = P.H[l], nIni = P.nIni[l];
+        int D = 1;
+        while ((nIni << (2 * D)) < P.N[l]) D++;
+        D += 1;
+        if (forced_depth >= 0) D = forced_depth;
+        D = std::max(1, std::min(D, 11));
+        auto cell_keys = [&](int d) { /* strict 3x3 maxima a cell of depth d can hold: every other pixel of every other row */
+            const long long cw = (W / nIni >> d) + 2, ch = (H >> d) + 2;
+            return ((cw + 1) / 2) * ((ch + 1) / 2);
+        };
+        while (D < 11 && cell_keys(D) >= 65535) D++;
+        while (D > 1 && (((long long)nIni << (2 * D)) > 16384 || nb + 2 * (((size_t)nIni << (2 * D)) + 1) * 4 + 16 > budget) &&
+               cell_keys(D - 1) < 65535)
+            D--;
+        P.fineD[l] = D;
+        maxcells = std::max(maxcells, nIni << (2 * D));
+        std::vector<uint32_t> xs, ys;
+        build_oct_lut(W, H, D, xs, ys);
+        P.lutOff[l] = (int32_t)P.lut.size();
+        P.lutW[l] = (int32_t)xs.size();
+        P.lut.insert(P.lut.end(), xs.begin(), xs.end());
+        P.lut.insert(P.lut.end(), ys.begin(), ys.end());
+    }
+    P.fineLdsOff = (int32_t)nb;
+    P.fineLdsBytes = (int32_t)(2 * ((size_t)maxcells + 1) * 4 + 16);
+    /* depth 1 is the floor even over the budget, so the verdict is checked, not assumed: the whole allocation within a CU's
+     * 160 KB and the node arrays within 150 KB of them (a list that does not fit LDS: host quadtree) */
+    P.fits = fits && nb + (size_t)P.fineLdsBytes <= 160 * 1024 && node_bytes(P.maxNodes) <= 150 * 1024;
+}
+
 void build_oct_lut(int W, int H, int D, std::vector<uint32_t>& xs, std::vector<uint32_t>& ys) {
     const int nIni = (int)std::round((float)W / (float)H);
     const float hX = (float)W / (float)nIni;
@@ -926,6 +1032,50 @@ int vslamh_oct_lut_check(int W, int H, int D) {
     return bad;
 }
 unsigned vslamh_oct_key_path(int x, int y, int W, int H, int depth) { return vslam::oct_key_path(x, y, W, H, depth); }
+
+int vslamh_keypoint_capacity(const int* quota, const int* lw, const int* lh, int nlevels, int nfeatures) {
+    return vslam::keypoint_capacity(quota, lw, lh, nlevels, nfeatures);
+}
+
+/* plan_octree with node arrays of node_per * maxNodes + node_fixed bytes.  ctx6 = maxNodes, selStride, fineLdsOff,
+ * fineLdsBytes, fits, number of (x, y) of all levels whose table path differs from oct_key_path at the level's depth;
+ * lvl4 rows = nIni, selOff, fineD, lutW */
+int vslamh_oct_plan(const int* quota, const int* lw, const int* lh, const int* cell_first, int nlevels, int forced_depth,
+                    int budget, int node_per, int node_fixed, int32_t* ctx6, int32_t* lvl4) {
+    vslam::OctPlan P;
+    vslam::plan_octree(quota, lw, lh, cell_first, nlevels, forced_depth, (size_t)budget,
+                       [=](int n) { return (size_t)n * node_per + node_fixed; }, P);
+    int bad = 0;
+    for (int l = 0; l < nlevels; l++) {
+        const int W = P.lutW[l] - 1, H = P.H[l];
+        const uint32_t *xs = P.lut.data() + P.lutOff[l], *ys = xs + P.lutW[l];
+        for (int y = 0; y <= H; y++)
+            for (int x = 0; x <= W; x++) bad += (xs[x] | ys[y]) != vslam::oct_key_path(x, y, W, H, P.fineD[l]);
+        const int32_t o[4] = {P.nIni[l], P.selOff[l], P.fineD[l], P.lutW[l]};
+        memcpy(lvl4 + 4 * l, o, sizeof(o));
+    }
+    const int32_t c[6] = {P.maxNodes, P.selStride, P.fineLdsOff, P.fineLdsBytes, P.fits, bad};
+    memcpy(ctx6, c, sizeof(c));
+    return 0;
+}
+
+/* pack_bands over the bands of a cell list (rows as vslamh_cells writes them, all levels): words4 rows = BandWords, classes =
+ * 272 bytes per class; info5 = classes, max_wh, max_iw, max_cells, ok.  Returns the bands, -1 if a buffer is too small. */
+int vslamh_band_tables(const uint16_t* cells5, int ncells, int nlevels, int max_cells, int max_width, uint32_t* words4,
+                       int cap_bands, uint8_t* classes, int cap_class_bytes, int32_t* info5) {
+    static_assert(sizeof(vslam::HostCell) == 10 && sizeof(vslam::BandWords) == 16, "rows of five u16 / four u32");
+    const vslam::HostCell* c = (const vslam::HostCell*)cells5;
+    std::vector<vslam::HostBand> b;
+    vslam::build_bands(std::vector<vslam::HostCell>(c, c + ncells), max_cells, max_width, b);
+    vslam::BandTables T;
+    vslam::pack_bands(b, nlevels, T);
+    if ((int)b.size() > cap_bands || (int)T.classes.size() > cap_class_bytes) return -1;
+    memcpy(words4, T.bands.data(), T.bands.size() * sizeof(vslam::BandWords));
+    memcpy(classes, T.classes.data(), T.classes.size());
+    const int32_t o[5] = {(int32_t)(T.classes.size() / 272), T.max_wh, T.max_iw, T.max_cells, T.ok};
+    memcpy(info5, o, sizeof(o));
+    return (int)b.size();
+}
 
 } /* extern "C" */
 

@@ -7,6 +7,7 @@
 #define VSLAM_HOST_H
 
 #include <cstdint>
+#include <functional>
 #include <vector>
 
 #include "../../include/vslam_fe.h"
@@ -99,6 +100,46 @@ struct HostBand {
     uint16_t x0, y0, ww, wh;         /* shared window: [x0, x0 + ww) x [y0, y0 + wh) in level coordinates */
 };
 void build_bands(const std::vector<HostCell>& cells, int max_cells, int max_width, std::vector<HostBand>& out);
+
+/* The band list in the words k_fast_bands reads (BandDesc in vslam_device.h has the same 16 bytes) and its column tables,
+ * one 272-byte record per (cell pitch, interior width) class: cellbit[136] = 1 << (cell of interior column x), 0 past the
+ * interior; cellfl[136] = bit 0 first / bit 1 last column of its cell. */
+struct BandWords {
+    uint32_t cell0; /* first cell of the band in the cell list */
+    uint32_t lnw;   /* level | ncell << 4 | wcell << 8 | column-table class << 16 */
+    uint32_t xy;    /* x0 | y0 << 16 */
+    uint32_t wh;    /* window width | height << 16 */
+};
+struct BandTables {
+    std::vector<BandWords> bands;
+    std::vector<uint8_t> classes;
+    int max_wh = 0, max_iw = 0, max_cells = 0; /* tallest window, widest interior, most cells of a band */
+    bool ok = false; /* the words can hold the list: a band exists, level < 16, wcell < 256, class < 65536 */
+};
+void pack_bands(const std::vector<HostBand>& hb, int nlevels, BandTables& out);
+
+/* Slots of a context's keypoint arrays: nfeatures + 4 * nlevels + 8, or the exact bound of what DistributeOctTree can
+ * return if that is more (only for very small nfeatures); a multiple of 4, so packed descriptors stay 16-byte aligned.
+ * quota: mnFeaturesPerLevel; lw / lh: level sizes. */
+int keypoint_capacity(const int* quota, const int* lw, const int* lh, int nlevels, int nfeatures);
+
+/* Plan of the device quadtree (k_octree_v4): the per-level fields of OctParams (vslam_device.h), the list capacities and the
+ * fine grid.  selOff: the level's result list (max(N + 3, 4 * nIni) + 1 entries) in a slot's lists; lut: build_oct_lut of
+ * every level at its fineD, x table (lutW entries) then y table, from lutOff. */
+struct OctPlan {
+    int32_t N[VSLAM_MAX_LEVELS], H[VSLAM_MAX_LEVELS], nIni[VSLAM_MAX_LEVELS], selOff[VSLAM_MAX_LEVELS];
+    int32_t fineD[VSLAM_MAX_LEVELS], lutOff[VSLAM_MAX_LEVELS], lutW[VSLAM_MAX_LEVELS];
+    float hX[VSLAM_MAX_LEVELS];
+    int32_t selStride = 0, maxNodes = 0, fineLdsOff = 0, fineLdsBytes = 0;
+    std::vector<uint32_t> lut;
+    bool fits = false; /* the device kernel can run this plan; otherwise the quadtree stays on the host */
+};
+/* cell_first[l]: index of the level's first FAST cell (nlevels + 1 entries); forced_depth: vslam_tuning.oct_fine_depth (-1:
+ * by the level's quota); budget: LDS bytes a workgroup should take in all -- it steers the depths, whose floor is 1, while
+ * `fits` is judged against the CU's 160 KB and the 150 KB the node arrays may have of it; node_bytes(maxNodes): size of
+ * the kernel's node arrays (vk_octree_lds_bytes, which belongs to the kernel file). */
+void plan_octree(const int* quota, const int* lw, const int* lh, const int* cell_first, int nlevels, int forced_depth,
+                 size_t budget, const std::function<size_t(int)>& node_bytes, OctPlan& P);
 
 /* A FAST candidate / selected keypoint in level coordinates relative to the 16-px border. */
 struct Cand {

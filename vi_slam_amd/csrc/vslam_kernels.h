@@ -13,10 +13,6 @@ void vk_resize_level(hipStream_t st, uint8_t* pyr, size_t slot_stride, const Bat
                      const LevelGeom& sg, const LevelGeom& dg, int src_level, const uint16_t* xtab,
                      const int16_t* xa, const uint16_t* ytab, const int16_t* yb, int nslots);
 
-void vk_orient_describe(hipStream_t st, const uint8_t* pyr, const uint8_t* blur, size_t slot_stride,
-                        const BatchSrc& src, const PyramidGeom& g, const SelKp* sel, int nsel,
-                        const int8_t* pattern, vslam_kp* kps, uint8_t* desc, int cap, int atan_fma);
-
 void vk_hamming_matrix(hipStream_t st, const uint8_t* q, int nq, const uint8_t* t, int nt, uint8_t* out);
 /* nprob problems in one launch: part holds nrows * nsplit * 2 words (nrows = queries of all problems back to back,
  * Top2Job::row0), idx2 / dist2 nrows * 2; nsplit from vk_hamming_top2_batch_split */

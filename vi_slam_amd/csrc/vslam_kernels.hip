@@ -314,19 +314,7 @@ __device__ __forceinline__ void describe_run(const uint8_t* __restrict__ pyr, co
         }
 }
 
-/* host-selected keypoints (quadtree on the host): one flat list for the batch */
-__global__ void __launch_bounds__(256)
-k_orient_describe(const uint8_t* __restrict__ pyr, const uint8_t* __restrict__ blur, size_t slot_stride,
-                  BatchSrc src, PyramidGeom g, const SelKp* __restrict__ sel, int nsel,
-                  const int8_t* __restrict__ pattern, vslam_kp* kps, uint8_t* desc, int cap, int atan_fma) {
-    __shared__ __align__(16) uint8_t s_tile[4][DESC_TILE_BYTES];
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); /* scalar keypoint records, as in the _dev form */
-    const int k0 = (blockIdx.x * 4 + wave) * DESC_KPW;
-    describe_run<DESC_KPW>(pyr, blur, slot_stride, src, g, sel, k0, min(k0 + DESC_KPW, nsel), pattern, kps, desc, cap, atan_fma,
-                           s_tile[wave]);
-}
-
-/* device-selected keypoints (k_octree + k_assign_out): per-slot lists, counts read from HBM.  KPW keypoints per wave:
+/* the selected keypoints (k_assign_out, or the host quadtree's upload): per-slot lists, counts read from HBM.  KPW keypoints per wave:
  * DESC_KPW for batches (2 and 8 measured: -6 % / -10 % in the pipeline), ONE for one or two images, where the launch is a
  * frame's latency and four times the waves finish sooner (batch-1 latency -4 us) */
 #ifndef DESC_WPB
@@ -426,15 +414,6 @@ void vk_resize_level(hipStream_t st, uint8_t* pyr, size_t slot_stride, const Bat
     dim3 grid((dg.w + 63) / 64, (dg.h + 3) / 4, nslots);
     hipLaunchKernelGGL(k_resize_level, grid, dim3(256), 0, st, pyr, slot_stride, src, sg, dg, src_level, xtab,
                        xa, ytab, yb);
-}
-
-void vk_orient_describe(hipStream_t st, const uint8_t* pyr, const uint8_t* blur, size_t slot_stride,
-                        const BatchSrc& src, const PyramidGeom& g, const SelKp* sel, int nsel,
-                        const int8_t* pattern, vslam_kp* kps, uint8_t* desc, int cap, int atan_fma) {
-    if (nsel <= 0) return;
-    const int per_wg = 4 * DESC_KPW;
-    hipLaunchKernelGGL(k_orient_describe, dim3((nsel + per_wg - 1) / per_wg), dim3(256), 0, st, pyr, blur, slot_stride, src, g,
-                       sel, nsel, pattern, kps, desc, cap, atan_fma);
 }
 
 void vk_orient_describe_dev(hipStream_t st, const uint8_t* pyr, const uint8_t* blur, size_t slot_stride,

@@ -80,25 +80,22 @@ static int enqueue_stereo(vslam_fe* feL, vslam_fe* feR, int npairs, const int* s
               feR->slot_stride, feR->src, bf, maxD, sc.best, sc.uRight, sc.depth, sc.sad, feL->cap, sc.max_band, sc.rows);
     HIPCHK(hipGetLastError());
     const size_t n = (size_t)npairs * feL->cap;
-    CopyRanges R;
-    memset(&R, 0, sizeof(R));
+    feL->h_stereo_cur = in_block ? (float*)(feL->h_res + feL->res_feat_bytes) : feL->h_stereo;
     if (in_block && feL->deliver_deferred) {
         /* the extraction of this call left its delivery to us (want_host = 2): counts | keypoints | descriptors | mvuRight |
          * mvDepth are contiguous -> ONE transfer for the whole stereo step */
         feL->deliver_deferred = false;
-        R.dst[0] = feL->h_res;
-        R.src[0] = feL->d_res;
-        R.bytes[0] = feL->res_feat_bytes + n * 8;
-        feL->h_stereo_cur = (float*)(feL->h_res + feL->res_feat_bytes);
+        if ((rc = vslam_deliver_block(feL, n * 8))) return rc;
     } else {
-        R.dst[0] = in_block ? (void*)(feL->h_res + feL->res_feat_bytes) : (void*)feL->h_stereo;
+        CopyRanges R;
+        memset(&R, 0, sizeof(R));
+        R.dst[0] = feL->h_stereo_cur;
         R.src[0] = sc.uRight; /* uRight | depth */
         R.bytes[0] = n * 8;
-        feL->h_stereo_cur = in_block ? (float*)(feL->h_res + feL->res_feat_bytes) : feL->h_stereo;
+        R.n = 1;
+        vslam_count_delivery(feL, vk_copy_ranges(st, R, feL->tune), R);
+        HIPCHK(hipGetLastError());
     }
-    R.n = 1;
-    vslam_count_delivery(feL, vk_copy_ranges(st, R, feL->tune), R);
-    HIPCHK(hipGetLastError());
     feL->stereo_pairs = npairs;
     for (int j = 0; j < npairs; j++) feL->stereo_slotL[j] = slotsL[j];
     return VSLAM_OK;
@@ -149,7 +146,7 @@ extern "C" int vslam_frame_stereo_batch_async(vslam_fe* fe, int npairs, const ui
     /* a full batch whose results go to the host: mvuRight / mvDepth live behind the extraction's results in the result
      * block (the region SearchForInitialization's outputs use in a context that runs that matcher: whoever comes first
      * in a context's life owns it) and the whole step leaves in one transfer */
-    const bool blk = want_host && fe->dev_octree && 2 * npairs == fe->B && fe->res_init_bytes >= (size_t)npairs * fe->cap * 8 &&
+    const bool blk = want_host && 2 * npairs == fe->B && fe->res_init_bytes >= (size_t)npairs * fe->cap * 8 &&
                      fe->block_region_owner != VSLAM_REGION_INIT && fe->d_res;
     if (blk) fe->block_region_owner = VSLAM_REGION_STEREO;
     /* stereo frames: the contexts of a pipelined caller are independent of each other and the step is the sum of the wide
@@ -285,23 +282,22 @@ static int search_init_dev_async_b(vslam_fe* fe, int npairs, const vslam_init_jo
     vk_search_init(fe->stream, J, npairs, fe->cap, bnd, window, nnratio, check_orientation, d_m, d_p, d_n,
                    max_c2, M, fe->d_init_scratch, fe->d_init_fb, fe->tune);
     HIPCHK(hipGetLastError());
-    CopyRanges R;
-    memset(&R, 0, sizeof(R));
     if (fe->deliver_deferred && fe->init_in_block) {
         /* the extraction of this step asked for its delivery to be deferred (want_host = 2): counts, keypoints, descriptors
          * and the matcher's outputs are contiguous in the result block -> ONE transfer for the whole step */
         fe->deliver_deferred = false;
-        R.dst[0] = fe->h_res;
-        R.src[0] = fe->d_res;
-        R.bytes[0] = fe->res_feat_bytes + ((nm * 12 + (size_t)npairs * 4 + 15) & ~(size_t)15);
+        const int rc = vslam_deliver_block(fe, (nm * 12 + (size_t)npairs * 4 + 15) & ~(size_t)15);
+        if (rc) return rc;
     } else {
+        CopyRanges R;
+        memset(&R, 0, sizeof(R));
         R.dst[0] = fe->h_init;
         R.src[0] = fe->d_init;
         R.bytes[0] = nm * 12 + (size_t)npairs * 4;
+        R.n = 1;
+        vslam_count_delivery(fe, vk_copy_ranges(fe->stream, R, fe->tune), R);
+        HIPCHK(hipGetLastError());
     }
-    R.n = 1;
-    vslam_count_delivery(fe, vk_copy_ranges(fe->stream, R, fe->tune), R);
-    HIPCHK(hipGetLastError());
     fe->init_pairs = npairs;
     return VSLAM_OK;
 }
