@@ -432,6 +432,31 @@ int vslam_search_for_initialization_batch_ex(vslam_fe* fe, int npairs, const vsl
 int vslam_search_init_dev_async_ex(vslam_fe* fe, int npairs, const vslam_init_job* jobs, const vslam_bounds* b,
                                    int window, float nnratio, int check_orientation);
 
+/* The grid bounds of every matcher that runs after initialisation.  In the reference mnMinX / mnMaxX / mnMinY / mnMaxY
+ * are static members of Frame (frame.cpp:28), computed once on the first frame and copied into every KeyFrame
+ * (keyframe.cpp:44): a property of the camera, so here a property of the context, next to its camera.  While bounds are
+ * set,
+ *   vslam_search_by_projection_frame / _keyframe / _sim3 (both proj_variants) / _mappoints,
+ *   vslam_search_by_projection_dev_async / _wait and vslam_fuse_search (sim3 = 0, 1, 2)
+ * take them from the context -- the 64 x 48 grid (mfGridElementWidthInv = (float)64 / (maxX - minX), PosInGrid =
+ * round((x - minX) * inv), frame.cpp:322-323, 746-756), the window cells of GetFeaturesInArea (frame.cpp:678-744,
+ * keyframe.cpp:655-699) and the in-image test of the projection (u < mnMinX || u > mnMaxX in the Frame / KeyFrame-into-
+ * Frame forms, fmatcher.cpp:2514-2517, 2719-2722; KeyFrame::IsInImage, x >= mnMinX && x < mnMaxX, in the Sim3 forms, Fuse
+ * and SearchBySim3) -- and read the img_w / img_h of their own parameters only to validate them as before.  Keypoints are
+ * then ukeypoints_ (vslam_fe_slot_ukps / vslam_fe_ukps_copy) and the bounds those of vslam_fe_image_bounds.
+ * The KeyFrame-side forms (_sim3, vslam_fuse_search) reproduce what a KeyFrame does with them: it stores the four bounds as
+ * `const int` (keyframe.h:255-258), truncated toward zero, keeps the Frame's cells and float grid inverses, and reads the
+ * integers for the window origin of KeyFrame::GetFeaturesInArea and in KeyFrame::IsInImage -- a projection between mnMinX and
+ * ceil(mnMinX), or between floor(mnMaxX) and mnMaxX, is outside for them.  The caller always passes the Frame's floats.
+ * b == NULL = none (the default): every matcher uses {0, img_w, 0, img_h} of its own parameters, as before.  Bounds must
+ * be finite with max > min; VSLAM_ERR_INVALID otherwise, and the previous setting stays in force.  Like every call on a
+ * context the setter is not re-entrant: do not call it while another thread runs a matcher on fe.
+ * The SearchForInitialization entry points above keep their explicit bounds argument (img_w / img_h or the _ex forms'
+ * vslam_bounds) and do not consult the context's bounds. */
+int vslam_fe_set_grid_bounds(vslam_fe* fe, const vslam_bounds* b);
+/* The bounds in force; *is_set = 0 and {0, width, 0, height} of the context when none are set. */
+int vslam_fe_get_grid_bounds(const vslam_fe* fe, vslam_bounds* b, int* is_set);
+
 /* ---------------------------------------------------------------- diagnostics */
 
 /* FMatcher::SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, th, bMono)
@@ -439,7 +464,8 @@ int vslam_search_init_dev_async_ex(vslam_fe* fe, int npairs, const vslam_init_jo
  * TrackWithMotionModel (tracking.cpp:2728).  What the function reads of the two frames is passed explicitly:
  *   p            pose of CurrentFrame as rows [Rcw | tcw] (the reference's T_w_c_ member is used that way),
  *                pinhole intrinsics, mbf, th, bForward/bBackward (vslam_projection_direction), image bounds of
- *                CurrentFrame's grid (mnMinX = mnMinY = 0, mnMaxX = img_w, mnMaxY = img_h)
+ *                CurrentFrame's grid (mnMinX = mnMinY = 0, mnMaxX = img_w, mnMaxY = img_h; the context's bounds
+ *                instead while vslam_fe_set_grid_bounds has set some)
  *   last frame   host arrays of n_last entries: keypoints (octave from keypoints_, angle from ukeypoints_),
  *                flags (bit0: mvpMapPoints[i] != NULL && !mvbOutlier[i]; bit1: that MapPoint has
  *                Observations() > 0), world positions (3 floats), MapPoint descriptors (32 bytes)
@@ -466,7 +492,8 @@ int vslam_search_by_projection_frame(vslam_fe* fe, const vslam_proj_params* p, c
 
 /* FMatcher::SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF, const set<MapPoint*>& sAlreadyFound, th, ORBdist)
  * (fmatcher.cpp:2689-2811) -- the matcher of Tracking::Relocalization.  p carries T_w_c_'s Rcw | tcw in Tcw, the camera,
- * th, check_orientation, the image bounds and gemm_float (forward / backward / mbf are not used); Ow = -Rcw^T tcw as the
+ * th, check_orientation, the image bounds (img_w / img_h; CurrentFrame's float bounds of vslam_fe_set_grid_bounds while
+ * some are set) and gemm_float (forward / backward / mbf are not used); Ow = -Rcw^T tcw as the
  * function computes it (:2695); log_scale_factor = CurrentFrame.mfLogScaleFactor; orb_dist 1..255.  Per KeyFrame
  * keypoint i: kf_kps_host = pKF->mvKeysUn, mp_flags[i] & 1 iff vpMPs[i] && !isBad() && !sAlreadyFound.count(it),
  * world position, Get{Min,Max}DistanceInvariance(), descriptor.  cur_occupied_host marks CurrentFrame.mvpMapPoints
@@ -481,7 +508,8 @@ int vslam_search_by_projection_keyframe(vslam_fe* fe, const vslam_proj_params* p
 /* FMatcher::SearchByProjection(KeyFrame* pKF, cv::Mat Scw, const vector<MapPoint*>& vpPoints, vector<MapPoint*>& vpMatched,
  * int th, float ratioHamming) (fmatcher.cpp:750-863; proj_variant 0) and the overload that also fills vpMatchedKF from
  * vpPointsKFs (:865-981; it projects as fx*(x*(1/z))+cx, proj_variant 1) -- the loop-closing matchers.  p carries
- * Rcw | tcw (= sRcw/scw, Scw's translation/scw, :760-763) in Tcw, the camera, th, the image bounds and gemm_float;
+ * Rcw | tcw (= sRcw/scw, Scw's translation/scw, :760-763) in Tcw, the camera, th, the image bounds (img_w / img_h; while
+ * vslam_fe_set_grid_bounds has set some, pKF's integer copies of them, see there) and gemm_float;
  * Ow = -Rcw^T tcw; log_scale_factor = pKF->mfLogScaleFactor.  Per candidate MapPoint: flag (!isBad() &&
  * !spAlreadyFound.count(pMP)), world position, normal, Get{Min,Max}DistanceInvariance(), descriptor.
  * kf_matched_host[idx] != 0 iff vpMatched[idx] != NULL on entry.  match_kf[idx] = iMP (vpMatched[idx] = vpPoints[iMP],
@@ -499,7 +527,8 @@ int vslam_search_by_projection_sim3(vslam_fe* fe, const vslam_proj_params* p, co
  *   flags bit0 = mbTrackInView && !isBad() && !(bFarPoints && mTrackDepth > thFarPoints), bit1 = Observations() > 0.
  * cur_occupied_host marks keypoints whose mvpMapPoints entry already holds a MapPoint with observations (the
  * matches of TrackWithMotionModel).  match_cur[idx] = index of the MapPoint written to F.mvpMapPoints[idx], or -1.
- * nnratio is FMatcher::mfNNratio (>= 0.4 on the device). */
+ * nnratio is FMatcher::mfNNratio (>= 0.4 on the device).  img_w / img_h are F's grid bounds {0, img_w, 0, img_h}; while
+ * vslam_fe_set_grid_bounds has set some, the grid takes those and img_w / img_h are only validated. */
 typedef struct vslam_mp_track {
     float proj_x, proj_y, proj_xr, view_cos; /* mTrackProjX, mTrackProjY, mTrackProjXR, mTrackViewCos */
     int32_t level;                           /* mnTrackScaleLevel */
@@ -664,7 +693,8 @@ typedef struct vslam_fuse_params {
     float Rcw[9], tcw[3], Ow[3];
     float fx, fy, cx, cy, bf, th;
     float log_scale_factor; /* pKF->mfLogScaleFactor */
-    int32_t img_w, img_h;   /* mnMaxX, mnMaxY (mnMinX = mnMinY = 0: undistorted pinhole images) */
+    int32_t img_w, img_h;   /* mnMaxX, mnMaxY (mnMinX = mnMinY = 0: undistorted pinhole images); while the context holds grid
+                             * bounds (vslam_fe_set_grid_bounds) those are used -- as pKF holds them, truncated to int */
     int32_t sim3;           /* 0 / 1: the two Fuse overloads; 2: one direction of SearchBySim3, see below */
     int32_t gemm_float;     /* as in vslam_proj_params */
     float Rb[9], tb[3];     /* sim3 == 2 only */

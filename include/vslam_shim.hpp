@@ -267,6 +267,21 @@ inline void ComputeImageBounds(const FExtractor& extractor, float& mnMinX, float
     mnMaxY = b[3];
 }
 
+/* Frame::mnMinX, mnMaxX, mnMinY, mnMaxY for the matchers that run on the extractor's context after initialisation (every
+ * SearchByProjection form, Fuse, SearchBySim3): call it once ComputeImageBounds has run, and again after the extractor
+ * re-created its context for another image size.  ClearGridBounds returns to {0, cols, 0, rows}.  While bounds are set
+ * FMatcher's two SearchByProjection wrappers below hand the device the slot's ukeypoints_ instead of keypoints_.  Always
+ * pass the Frame's floats: the KeyFrame-side matchers truncate them to int themselves, as KeyFrame does. */
+inline void SetGridBounds(const FExtractor& extractor, float mnMinX, float mnMaxX, float mnMinY, float mnMaxY) {
+    if (!extractor.context()) throw std::runtime_error("SetGridBounds: no image has been processed yet");
+    const vslam_bounds b = {mnMinX, mnMaxX, mnMinY, mnMaxY};
+    if (vslam_fe_set_grid_bounds(extractor.context(), &b) != VSLAM_OK) throw std::runtime_error(vslam_last_error());
+}
+inline void ClearGridBounds(const FExtractor& extractor) {
+    if (extractor.context() && vslam_fe_set_grid_bounds(extractor.context(), nullptr) != VSLAM_OK)
+        throw std::runtime_error(vslam_last_error());
+}
+
 /* What the matchers read of a Frame (frame.h:71-91): undistorted keypoints, the image bounds of its grid,
  * and where its descriptors are in HBM (the extractor that produced them still holds them). */
 struct FrameView {
@@ -274,7 +289,7 @@ struct FrameView {
     const FExtractor* extractor = nullptr;             /* descriptors_ live in its slot 0 */
     int mnMaxX = 0, mnMaxY = 0;                        /* image bounds (no distortion: cols, rows) */
     /* float grid bounds of a distorted camera (ComputeImageBounds); unset = {0, mnMaxX, 0, mnMaxY}.  Used by
-     * SearchForInitialization only (the other matchers take integer bounds). */
+     * SearchForInitialization only (the matchers after initialisation read the context's: SetGridBounds above). */
     bool has_bounds = false;
     vslam_bounds bounds = {0.0f, 0.0f, 0.0f, 0.0f};
 };
@@ -362,7 +377,7 @@ public:
         const vslam_kp* dk = nullptr;
         const uint8_t* dd = nullptr;
         int n2 = 0, nm = 0;
-        check(vslam_fe_slot_buffers(cur.frame.extractor->context(), 0, &dk, &dd, &n2));
+        slot_keypoints(*cur.frame.extractor, &dk, &dd, &n2);
         mvpMapPointIndex.assign(n2, -1);
         const int n = (int)last.ukeypoints->size();
         check(vslam_search_by_projection_frame(cur.frame.extractor->context(), &p,
@@ -382,7 +397,7 @@ public:
         const vslam_kp* dk = nullptr;
         const uint8_t* dd = nullptr;
         int n2 = 0, nm = 0;
-        check(vslam_fe_slot_buffers(F.extractor->context(), 0, &dk, &dd, &n2));
+        slot_keypoints(*F.extractor, &dk, &dd, &n2);
         mvpMapPointIndex.assign(n2, -1);
         check(vslam_search_by_projection_mappoints(F.extractor->context(), vpMapPoints.data(), mapPointDescriptors.data(),
                                                    (int)vpMapPoints.size(), dk, dd, n2,
@@ -393,6 +408,16 @@ public:
     }
 
 protected:
+    /* the current frame's keypoints for the projection matchers: keypoints_ of slot 0 as before, ukeypoints_ once the
+     * context holds grid bounds (SetGridBounds) -- the undistorted grid bins undistorted keypoints */
+    static void slot_keypoints(const FExtractor& e, const vslam_kp** dk, const uint8_t** dd, int* n) {
+        check(vslam_fe_slot_buffers(e.context(), 0, dk, dd, n));
+        vslam_bounds b;
+        int is_set = 0;
+        check(vslam_fe_get_grid_bounds(e.context(), &b, &is_set));
+        if (is_set && e.HasCamera()) check(vslam_fe_slot_ukps(e.context(), 0, dk));
+    }
+
     float mfNNratio;
     bool mbCheckOrientation;
 };

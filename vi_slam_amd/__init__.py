@@ -52,6 +52,7 @@ ABI_SYMBOLS = [
     "vslam_voc_load", "vslam_voc_file_open", "vslam_voc_file_close", "vslam_voc_file_info", "vslam_voc_file_arrays",
     "vslam_voc_file_last_error", "vslam_dbg_qlz_decode",
     "vslam_fe_set_camera", "vslam_fe_slot_ukps", "vslam_fe_ukps_copy", "vslam_undistort_points", "vslam_fe_image_bounds",
+    "vslam_fe_set_grid_bounds", "vslam_fe_get_grid_bounds",
     "vslam_search_for_initialization_ex", "vslam_search_for_initialization_batch_ex", "vslam_search_init_dev_async_ex",
 ]
 
@@ -284,6 +285,8 @@ def lib():
         L.vslam_search_for_initialization_batch_ex.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, C.POINTER(_Bounds), vp, vp, i,
                                                                f, i, vp]
         L.vslam_search_init_dev_async_ex.argtypes = [vp, i, vp, C.POINTER(_Bounds), i, f, i]
+        L.vslam_fe_set_grid_bounds.argtypes = [vp, C.POINTER(_Bounds)]
+        L.vslam_fe_get_grid_bounds.argtypes = [vp, C.POINTER(_Bounds), C.POINTER(i)]
         _lib = L
     return _lib
 
@@ -611,6 +614,22 @@ class FExtractor:
         b = np.zeros(4, np.float32)
         _check(lib().vslam_fe_image_bounds(self._h, _p(b)))
         return b
+
+    def set_grid_bounds(self, bounds):
+        """Frame::mnMinX, mnMaxX, mnMinY, mnMaxY (image_bounds() order) for every SearchByProjection form, FuseSearch and
+        SearchBySim3 run on this context, in place of their img_size; set_grid_bounds(None) returns to img_size (the
+        default).  SearchForInitialization keeps its own bounds argument."""
+        if bounds is None:
+            _check(lib().vslam_fe_set_grid_bounds(self._h, None))
+            return
+        b = _bounds(bounds)
+        _check(lib().vslam_fe_set_grid_bounds(self._h, C.byref(b)))
+
+    def grid_bounds(self):
+        """-> (bounds as float32[4] in image_bounds() order, is_set); (0, width, 0, height) while none are set"""
+        b, s = _Bounds(), C.c_int()
+        _check(lib().vslam_fe_get_grid_bounds(self._h, C.byref(b), C.byref(s)))
+        return np.array([b.min_x, b.max_x, b.min_y, b.max_y], np.float32), bool(s.value)
 
     def wait_for(self, other):
         """GPU-side: work enqueued on this context from now on runs after everything enqueued on `other`."""

@@ -137,6 +137,9 @@ struct vslam_fe {
     bool has_cam = false;
     UdCam ud;
     vslam_kp* d_ukps = nullptr; /* B x cap, allocated by the first camera with k1 != 0 */
+    /* vslam_fe_set_grid_bounds: Frame::mnMinX.. for the SearchByProjection / Fuse / SearchBySim3 matchers */
+    bool has_grid_bounds = false;
+    SiBounds grid_bounds = {0.0f, 0.0f, 0.0f, 0.0f};
     uint8_t* d_init_scratch = nullptr; /* k_si_topm -> k_si_replay: compacted octave-0 lists + sorted prefixes */
     size_t init_scratch_bytes = 0;
     int* d_init_fb = nullptr; /* number of full re-scans in k_si_replay / k_sbp_replay (diagnostics) */

@@ -157,6 +157,11 @@ struct PyrGroupDev { /* by-value kernel argument */
     LevelGeom lg[VSLAM_PYR_GROUP_LEVELS + 1]; /* lg[0] = source level */
 };
 
+/* A frame's grid bounds mnMinX, mnMaxX, mnMinY, mnMaxY (frame.cpp:793-821): {0, cols, 0, rows} without distortion */
+struct SiBounds {
+    float minX, maxX, minY, maxY;
+};
+
 /* vslam_mp_track: per MapPoint, what Frame::isInFrustum left in it */
 struct MpTrack {
     float projX, projY, projXR, viewCos;
@@ -174,7 +179,8 @@ struct FuseArgsDev {
     float Rcw[9], tcw[3], Ow[3];
     float Rb[9], tb[3]; /* sim3 == 2 (SearchBySim3): second transform, p2 = Rb * (Rcw * p + tcw) + tb */
     float fx, fy, cx, cy, bf, th, logScaleFactor;
-    int32_t imgW, imgH, sim3, gemmFloat, nlevels, nPoints, nKF;
+    SiBounds bnd; /* the KeyFrame's mnMinX.. : grid and KeyFrame::IsInImage */
+    int32_t sim3, gemmFloat, nlevels, nPoints, nKF;
     float scale[VSLAM_MAX_LEVELS], invSigma2[VSLAM_MAX_LEVELS];
     const FusePoint* pts;
     const uint8_t* mpDesc;
@@ -190,7 +196,8 @@ struct SbpProj;
 struct SbpJobDev {
     float Tcw[12];
     float fx, fy, cx, cy, mbf, th;
-    int32_t forward, backward, checkOri, imgW, imgH, gemmFloat;
+    uint8_t forward, backward, checkOri, gemmFloat; /* 0 / 1; bytes, so that the job keeps its 240 bytes with the bounds below */
+    SiBounds bnd; /* the current frame's (mode 3: the KeyFrame's) mnMinX..: grid, window and in-image test */
     int32_t nLast, nCur;
     const vslam_kp* lastKps;
     const int32_t* nLastPtr;
@@ -227,6 +234,7 @@ struct SbpKfDev {
     const float* normals;
 };
 #define VSLAM_MAX_SBP_JOBS 16
+static_assert(sizeof(SbpJobDev) == 240, "16 of these travel as one kernel argument");
 struct SbpJobs { /* by-value kernel argument (< 4 KB) */
     SbpJobDev job[VSLAM_MAX_SBP_JOBS];
     float scale[VSLAM_MAX_LEVELS];
@@ -269,10 +277,6 @@ struct InitJob {
 };
 struct InitJobs {
     InitJob job[VSLAM_MAX_MAT_JOBS];
-};
-/* Frame 2's grid bounds mnMinX, mnMaxX, mnMinY, mnMaxY (frame.cpp:793-821): {0, cols, 0, rows} without distortion */
-struct SiBounds {
-    float minX, maxX, minY, maxY;
 };
 /* the camera of vslam_fe_set_camera as k_undistort_kps takes it: fx, fy, cx, cy | k1, k2, p1, p2, k3 */
 struct UdCam {

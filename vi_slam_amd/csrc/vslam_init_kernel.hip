@@ -59,19 +59,19 @@ struct SiWindow {
     int minX, maxX, minY, maxY;
     bool empty;
 };
-/* GetFeaturesInArea(x, y, r, 0, 0): cell range (frame.cpp:686-708) */
-__device__ __forceinline__ SiWindow si_window(float px, float py, float r, float invW, float invH) {
-    SiWindow w;
-    w.minX = max(0, (int)floorf(__fmul_rn(__fsub_rn(px, r), invW)));
-    w.maxX = min(SI_GRID_COLS - 1, (int)ceilf(__fmul_rn(__fadd_rn(px, r), invW)));
-    w.minY = max(0, (int)floorf(__fmul_rn(__fsub_rn(py, r), invH)));
-    w.maxY = min(SI_GRID_ROWS - 1, (int)ceilf(__fmul_rn(__fadd_rn(py, r), invH)));
-    w.empty = w.minX >= SI_GRID_COLS || w.maxX < 0 || w.minY >= SI_GRID_ROWS || w.maxY < 0;
-    return w;
+/* GetFeaturesInArea(x, y, r, ..): cell range over the grid bounds (frame.cpp:686-708 with mnMinX / mnMinY; KeyFrame's
+ * copy, keyframe.cpp:655-699, is the same expression over its integer bounds: pass si_kf_bounds): floor((x - minX - r) *
+ * inv), left to right.  With
+ * minX = minY = 0 (the integer image, int_bounds() on the host) x - 0.0f == x, so every value equals the plain
+ * floor((x - r) * inv) bit for bit. */
+/* A KeyFrame keeps the bounds as `const int mnMinX, mnMinY, mnMaxX, mnMaxY` (keyframe.h:255-258), initialised from the
+ * Frame's floats (keyframe.cpp:44): truncated toward zero.  Its grid cells are the Frame's (binned with the float bounds,
+ * keyframe.cpp:58-67) and its mfGridElement*Inv the Frame's floats (:36), but the window origin of
+ * KeyFrame::GetFeaturesInArea (:663-675) and KeyFrame::IsInImage (:701-703) read the integers, converted back to float by
+ * the comparison / subtraction.  {0, w, 0, h} is its own truncation. */
+__device__ __forceinline__ SiBounds si_kf_bounds(const SiBounds& b) {
+    return SiBounds{(float)(int)b.minX, (float)(int)b.maxX, (float)(int)b.minY, (float)(int)b.maxY};
 }
-/* the same with float grid bounds (frame.cpp:686-708 with mnMinX / mnMinY): floor((x - minX - r) * inv), left to right.
- * With minX = minY = 0 every value equals si_window's bit for bit (x - 0.0f == x), which the SearchByProjection / Fuse /
- * Sim3 kernels keep using. */
 __device__ __forceinline__ SiWindow si_window_b(float px, float py, float r, const SiBounds& b, float invW, float invH) {
     SiWindow w;
     const float dx = __fsub_rn(px, b.minX), dy = __fsub_rn(py, b.minY);
@@ -732,12 +732,14 @@ __device__ __forceinline__ bool sbp_candidate_ok(const SbpCand& cd, const SiWind
     return true;
 }
 
-__device__ __forceinline__ SbpCand sbp_make_cand(const vslam_kp& k, float uRight, float invW, float invH, bool* in_grid) {
+__device__ __forceinline__ SbpCand sbp_make_cand(const vslam_kp& k, float uRight, const SiBounds& b, float invW, float invH,
+                                                 bool* in_grid) {
     SbpCand c;
     c.x = k.x;
     c.y = k.y;
     c.uRight = uRight;
-    const int gx = (int)roundf(__fmul_rn(k.x, invW)), gy = (int)roundf(__fmul_rn(k.y, invH));
+    const int gx = (int)roundf(__fmul_rn(__fsub_rn(k.x, b.minX), invW));
+    const int gy = (int)roundf(__fmul_rn(__fsub_rn(k.y, b.minY), invH));
     *in_grid = !(gx < 0 || gx >= SI_GRID_COLS || gy < 0 || gy >= SI_GRID_ROWS); /* PosInGrid, frame.cpp:746-756 */
     c.cell = (uint16_t)(*in_grid ? gx * 64 + gy : 0xFFFF);
     c.octave = (uint16_t)k.octave;
@@ -759,11 +761,13 @@ k_sbp_rank(SbpJobs JS) {
     const uint8_t* __restrict__ mpDesc = J.mpDesc;
     const float* __restrict__ uRight = J.uRight;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float invW = __fdiv_rn((float)SI_GRID_COLS, (float)J.imgW);
-    const float invH = __fdiv_rn((float)SI_GRID_ROWS, (float)J.imgH);
+    const SiBounds bnd = J.bnd; /* the frame's grid bounds mnMinX.. (frame.cpp:793-821) */
+    const SiBounds wbnd = J.mode == 3 ? si_kf_bounds(bnd) : bnd; /* window origin / in-image test: a KeyFrame's are integers */
+    const float invW = __fdiv_rn((float)SI_GRID_COLS, __fsub_rn(bnd.maxX, bnd.minX)); /* frame.cpp:322-323 */
+    const float invH = __fdiv_rn((float)SI_GRID_ROWS, __fsub_rn(bnd.maxY, bnd.minY));
     for (int i = tid; i < nCur; i += 256) {
         bool ing;
-        cand[i] = sbp_make_cand(curKps[i], uRight ? uRight[i] : -1.f, invW, invH, &ing);
+        cand[i] = sbp_make_cand(curKps[i], uRight ? uRight[i] : -1.f, bnd, invW, invH, &ing);
     }
     __syncthreads();
     for (int q = blockIdx.x * SBP_QPB + wave; q < min(nLast, (int)(blockIdx.x + 1) * SBP_QPB); q += 4) {
@@ -793,7 +797,7 @@ k_sbp_rank(SbpJobs JS) {
                 const float zc = sbp_gemm_row(J.Tcw + 8, X, Y, Z, J.Tcw[11], J.gemmFloat);
                 const float u = __fadd_rn(__fdiv_rn(__fmul_rn(J.fx, xc), zc), J.cx); /* no depth test here */
                 const float v = __fadd_rn(__fdiv_rn(__fmul_rn(J.fy, yc), zc), J.cy);
-                if (!(u < 0.f || u > (float)J.imgW) && !(v < 0.f || v > (float)J.imgH)) {
+                if (!(u < bnd.minX || u > bnd.maxX) && !(v < bnd.minY || v > bnd.maxY)) {
                     /* Ow = -Rcw^T tcw is cv::Mat algebra on the caller's side: it arrives in JS.kf.ow */
                     const float p0 = __fsub_rn(X, JS.kf.ow[0]), p1 = __fsub_rn(Y, JS.kf.ow[1]), p2 = __fsub_rn(Z, JS.kf.ow[2]);
                     double n2 = __dmul_rn((double)p0, (double)p0); /* cv::norm: double accumulation */
@@ -829,7 +833,7 @@ k_sbp_rank(SbpJobs JS) {
                         u = __fadd_rn(__fmul_rn(J.fx, __fmul_rn(xc, invz)), J.cx);
                         v = __fadd_rn(__fmul_rn(J.fy, __fmul_rn(yc, invz)), J.cy);
                     }
-                    if (u >= 0.f && u < (float)J.imgW && v >= 0.f && v < (float)J.imgH) { /* KeyFrame::IsInImage */
+                    if (u >= wbnd.minX && u < wbnd.maxX && v >= wbnd.minY && v < wbnd.maxY) { /* KeyFrame::IsInImage, keyframe.cpp:701-703 */
                         const float p0 = __fsub_rn(X, JS.kf.ow[0]), p1 = __fsub_rn(Y, JS.kf.ow[1]), p2 = __fsub_rn(Z, JS.kf.ow[2]);
                         double n2 = __dmul_rn((double)p0, (double)p0);
                         n2 = __dadd_rn(n2, __dmul_rn((double)p1, (double)p1));
@@ -866,7 +870,7 @@ k_sbp_rank(SbpJobs JS) {
             if (!(invzc < 0.f)) {
                 const float u = __fadd_rn(__fdiv_rn(__fmul_rn(J.fx, xc), zc), J.cx); /* pinhole.cpp:13-16 */
                 const float v = __fadd_rn(__fdiv_rn(__fmul_rn(J.fy, yc), zc), J.cy);
-                if (!(u < 0.f || u > (float)J.imgW) && !(v < 0.f || v > (float)J.imgH)) {
+                if (!(u < bnd.minX || u > bnd.maxX) && !(v < bnd.minY || v > bnd.maxY)) {
                     const int oct = lastKps[q].octave;
                     pr.u = u;
                     pr.v = v;
@@ -884,7 +888,7 @@ k_sbp_rank(SbpJobs JS) {
 #pragma unroll
         for (int j = 0; j < SI_MAX_M; j++) best[j] = 0xFFFFFFFFu;
         if (pr.valid) { /* wave-uniform */
-            const SiWindow win = si_window(pr.u, pr.v, pr.radius, invW, invH);
+            const SiWindow win = si_window_b(pr.u, pr.v, pr.radius, wbnd, invW, invH);
             if (!win.empty) {
                 const uint4 da = ((const uint4*)mpDesc)[(size_t)q * 2], db = ((const uint4*)mpDesc)[(size_t)q * 2 + 1];
                 for (int c = lane; c < nCur; c += 64) {
@@ -919,15 +923,15 @@ k_sbp_rank(SbpJobs JS) {
 
 /* full re-scan of one query's window in candidate order (the reference loop body) -> best key or ~0 */
 __device__ uint32_t sbp_full_scan(const SbpProj& pr, const vslam_kp* curKps, const float* uRight, int nCur,
-                                  const uint8_t* mpDescQ, const uint8_t* curDesc, const uint32_t* occupied, float invW,
-                                  float invH, int lane) {
+                                  const uint8_t* mpDescQ, const uint8_t* curDesc, const uint32_t* occupied,
+                                  const SiBounds& bnd, const SiBounds& wbnd, float invW, float invH, int lane) {
     uint32_t bestKey = 0xFFFFFFFFu;
-    const SiWindow win = si_window(pr.u, pr.v, pr.radius, invW, invH);
+    const SiWindow win = si_window_b(pr.u, pr.v, pr.radius, wbnd, invW, invH);
     if (!win.empty) {
         const uint4 da = ((const uint4*)mpDescQ)[0], db = ((const uint4*)mpDescQ)[1];
         for (int c = lane; c < nCur; c += 64) {
             bool ing;
-            const SbpCand cd = sbp_make_cand(curKps[c], uRight ? uRight[c] : -1.f, invW, invH, &ing);
+            const SbpCand cd = sbp_make_cand(curKps[c], uRight ? uRight[c] : -1.f, bnd, invW, invH, &ing);
             if (!ing || occupied[c] || !sbp_candidate_ok(cd, win, pr)) continue;
             const uint4 ta = ((const uint4*)curDesc)[(size_t)c * 2], tb = ((const uint4*)curDesc)[(size_t)c * 2 + 1];
             bestKey = min(bestKey, (min(si_hamming(da, db, ta, tb), 255u) << 24) | ((uint32_t)cd.cell << 12) | (uint32_t)c);
@@ -1084,7 +1088,7 @@ k_sbp_replay(SbpJobs JS, int* fallbacks) {
     const uint32_t* __restrict__ topm = J.topm;
     int32_t* __restrict__ matchCur = J.matchCur;
     int32_t* __restrict__ nmatches_out = J.nmatches;
-    struct { int checkOri, imgW, imgH; } A = {J.checkOri, J.imgW, J.imgH};
+    struct { int checkOri; SiBounds bnd; } A = {J.checkOri, J.bnd};
     uint32_t* occupied = (uint32_t*)sbsm;              /* nCur: mvpMapPoints[i2] with Observations() > 0 */
     int32_t* ownerEntry = (int32_t*)(occupied + nCur); /* nCur: last log entry that wrote mvpMapPoints[i2] */
     uint32_t* alog = (uint32_t*)(ownerEntry + nCur);   /* nLast: (query << 12 | i2), in order */
@@ -1093,8 +1097,9 @@ k_sbp_replay(SbpJobs JS, int* fallbacks) {
     __shared__ int s_hist[SI_HISTO];
     const int lane = threadIdx.x;
     if (*J.needSeq == 0) return; /* k_sbp_resolve finished this job */
-    const float invW = __fdiv_rn((float)SI_GRID_COLS, (float)A.imgW);
-    const float invH = __fdiv_rn((float)SI_GRID_ROWS, (float)A.imgH);
+    const float invW = __fdiv_rn((float)SI_GRID_COLS, __fsub_rn(A.bnd.maxX, A.bnd.minX));
+    const float invH = __fdiv_rn((float)SI_GRID_ROWS, __fsub_rn(A.bnd.maxY, A.bnd.minY));
+    const SiBounds wbnd = J.mode == 3 ? si_kf_bounds(A.bnd) : A.bnd;
     for (int c = lane; c < nCur; c += 64) {
         occupied[c] = occupied0 ? occupied0[c] : 0u;
         ownerEntry[c] = -1;
@@ -1130,7 +1135,7 @@ k_sbp_replay(SbpJobs JS, int* fallbacks) {
             } else {
                 nfb++;
                 gBest = sbp_full_scan(proj[qb + tq], curKps, uRight, nCur, mpDesc + (size_t)(qb + tq) * 32, curDesc,
-                                      occupied, invW, invH, lane);
+                                      occupied, A.bnd, wbnd, invW, invH, lane);
                 if (gBest == 0xFFFFFFFFu) continue;
             }
             if ((gBest >> 24) > thHigh) continue; /* bestDist <= TH_HIGH (ORBdist in the KeyFrame overload) */
@@ -1346,8 +1351,9 @@ k_sbpm_replay(SbpJobs JS, int* fallbacks) {
     const int nCur = J.nCurPtr ? min(*J.nCurPtr, J.nCur) : J.nCur;
     uint32_t* occupied = (uint32_t*)sbsm;
     const int lane = threadIdx.x;
-    const float invW = __fdiv_rn((float)SI_GRID_COLS, (float)J.imgW);
-    const float invH = __fdiv_rn((float)SI_GRID_ROWS, (float)J.imgH);
+    const SiBounds bnd = J.bnd;
+    const float invW = __fdiv_rn((float)SI_GRID_COLS, __fsub_rn(bnd.maxX, bnd.minX));
+    const float invH = __fdiv_rn((float)SI_GRID_ROWS, __fsub_rn(bnd.maxY, bnd.minY));
     for (int c = lane; c < nCur; c += 64) {
         occupied[c] = J.occupied0 ? J.occupied0[c] : 0u;
         J.matchCur[c] = -1;
@@ -1358,13 +1364,13 @@ k_sbpm_replay(SbpJobs JS, int* fallbacks) {
         const SbpProj pr = J.proj[q];
         if (!pr.valid) continue;
         nscan++;
-        const SiWindow win = si_window(pr.u, pr.v, pr.radius, invW, invH);
+        const SiWindow win = si_window_b(pr.u, pr.v, pr.radius, bnd, invW, invH);
         if (win.empty) continue;
         const uint4 da = ((const uint4*)J.mpDesc)[(size_t)q * 2], db = ((const uint4*)J.mpDesc)[(size_t)q * 2 + 1];
         uint32_t k1 = 0xFFFFFFFFu, k2 = 0xFFFFFFFFu; /* this lane's two smallest free keys */
         for (int c = lane; c < nCur; c += 64) {
             bool ing;
-            const SbpCand cd = sbp_make_cand(J.curKps[c], J.uRight ? J.uRight[c] : -1.f, invW, invH, &ing);
+            const SbpCand cd = sbp_make_cand(J.curKps[c], J.uRight ? J.uRight[c] : -1.f, bnd, invW, invH, &ing);
             if (!ing || occupied[c] || !sbp_candidate_ok(cd, win, pr)) continue;
             const uint4 ta = ((const uint4*)J.curDesc)[(size_t)c * 2], tb = ((const uint4*)J.curDesc)[(size_t)c * 2 + 1];
             const uint32_t key = (min(si_hamming(da, db, ta, tb), 255u) << 24) | ((uint32_t)cd.cell << 12) | (uint32_t)c;
@@ -1470,11 +1476,13 @@ k_fuse_rank(FuseArgsDev A) {
     extern __shared__ __align__(16) uint8_t sbsm[];
     SbpCand* cand = (SbpCand*)sbsm;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float invW = __fdiv_rn((float)SI_GRID_COLS, (float)A.imgW);
-    const float invH = __fdiv_rn((float)SI_GRID_ROWS, (float)A.imgH);
+    const SiBounds bnd = A.bnd;               /* Frame::mnMinX..: the cells of the grid the KeyFrame copied */
+    const SiBounds kbnd = si_kf_bounds(bnd);  /* the KeyFrame's integer copy (keyframe.cpp:44): window origin, IsInImage */
+    const float invW = __fdiv_rn((float)SI_GRID_COLS, __fsub_rn(bnd.maxX, bnd.minX));
+    const float invH = __fdiv_rn((float)SI_GRID_ROWS, __fsub_rn(bnd.maxY, bnd.minY));
     for (int i = tid; i < A.nKF; i += 256) {
         bool ing;
-        cand[i] = sbp_make_cand(A.kfKps[i], A.kfURight[i], invW, invH, &ing);
+        cand[i] = sbp_make_cand(A.kfKps[i], A.kfURight[i], bnd, invW, invH, &ing);
     }
     __syncthreads();
     for (int q = blockIdx.x * FUSE_QPB + wave; q < min(A.nPoints, (int)(blockIdx.x + 1) * FUSE_QPB); q += 4) {
@@ -1495,7 +1503,7 @@ k_fuse_rank(FuseArgsDev A) {
                 const float invz = (float)__ddiv_rn(1.0, (double)zc); /* const float invz = 1.0/z */
                 u = __fadd_rn(__fmul_rn(A.fx, __fmul_rn(xc, invz)), A.cx);
                 v = __fadd_rn(__fmul_rn(A.fy, __fmul_rn(yc, invz)), A.cy);
-                go = u >= 0.0f && u < (float)A.imgW && v >= 0.0f && v < (float)A.imgH;
+                go = u >= kbnd.minX && u < kbnd.maxX && v >= kbnd.minY && v < kbnd.maxY; /* KeyFrame::IsInImage */
             }
             if (go) {
                 double n2 = __dmul_rn((double)xc, (double)xc); /* cv::norm(p3Dc2) */
@@ -1518,7 +1526,7 @@ k_fuse_rank(FuseArgsDev A) {
                 const float invz = __fdiv_rn(1.0f, zc);
                 u = __fadd_rn(__fdiv_rn(__fmul_rn(A.fx, xc), zc), A.cx);
                 v = __fadd_rn(__fdiv_rn(__fmul_rn(A.fy, yc), zc), A.cy);
-                go = u >= 0.0f && u < (float)A.imgW && v >= 0.0f && v < (float)A.imgH;
+                go = u >= kbnd.minX && u < kbnd.maxX && v >= kbnd.minY && v < kbnd.maxY; /* KeyFrame::IsInImage */
                 ur = __fsub_rn(u, __fmul_rn(A.bf, invz));
             }
             if (go) {
@@ -1546,7 +1554,7 @@ k_fuse_rank(FuseArgsDev A) {
             }
         }
         if (go) {
-            const SiWindow win = si_window(u, v, radius, invW, invH);
+            const SiWindow win = si_window_b(u, v, radius, kbnd, invW, invH);
             if (!win.empty) {
                 const uint4 da = ((const uint4*)A.mpDesc)[(size_t)q * 2], db = ((const uint4*)A.mpDesc)[(size_t)q * 2 + 1];
                 for (int c = lane; c < A.nKF; c += 64) {

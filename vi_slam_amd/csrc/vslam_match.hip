@@ -217,6 +217,40 @@ static bool bounds_ok(const vslam_bounds* b) {
  * the float-bounds matcher -- x - 0.0f, (float)W - 0.0f, the window and PosInGrid -- equals the integer-bounds one bit for
  * bit, so their results do not change. */
 static SiBounds int_bounds(int img_w, int img_h) { return SiBounds{0.0f, (float)img_w, 0.0f, (float)img_h}; }
+/* SearchByProjection / Fuse / SearchBySim3: the context's grid bounds (vslam_fe_set_grid_bounds) while they are set, else
+ * the call's own img_w / img_h.  SearchForInitialization does not come here: its bounds are an argument. */
+static SiBounds matcher_bounds(const vslam_fe* fe, int img_w, int img_h) {
+    return fe->has_grid_bounds ? fe->grid_bounds : int_bounds(img_w, img_h);
+}
+
+extern "C" int vslam_fe_set_grid_bounds(vslam_fe* fe, const vslam_bounds* b) {
+    if (!fe) {
+        g_err = "invalid arguments";
+        return VSLAM_ERR_INVALID;
+    }
+    if (!b) {
+        fe->has_grid_bounds = false;
+        return VSLAM_OK;
+    }
+    if (!bounds_ok(b)) {
+        g_err = "invalid image bounds";
+        return VSLAM_ERR_INVALID;
+    }
+    fe->grid_bounds = SiBounds{b->min_x, b->max_x, b->min_y, b->max_y};
+    fe->has_grid_bounds = true;
+    return VSLAM_OK;
+}
+
+extern "C" int vslam_fe_get_grid_bounds(const vslam_fe* fe, vslam_bounds* b, int* is_set) {
+    if (!fe || !b || !is_set) {
+        g_err = "invalid arguments";
+        return VSLAM_ERR_INVALID;
+    }
+    const SiBounds s = matcher_bounds(fe, fe->p.width, fe->p.height);
+    *b = vslam_bounds{s.minX, s.maxX, s.minY, s.maxY};
+    *is_set = fe->has_grid_bounds ? 1 : 0;
+    return VSLAM_OK;
+}
 
 static int search_init_dev_async_b(vslam_fe* fe, int npairs, const vslam_init_job* jobs, const SiBounds& bnd, int window,
                                    float nnratio, int check_orientation) {
@@ -730,8 +764,8 @@ static int sbp_frame_impl(vslam_fe* fe, const vslam_proj_params* p, const vslam_
     SbpJobDev& J = JS.job[0];
     memcpy(J.Tcw, p->Tcw, sizeof(J.Tcw));
     J.fx = p->fx; J.fy = p->fy; J.cx = p->cx; J.cy = p->cy; J.mbf = p->mbf; J.th = p->th;
-    J.forward = p->forward; J.backward = p->backward; J.checkOri = p->check_orientation;
-    J.imgW = p->img_w; J.imgH = p->img_h; J.gemmFloat = p->gemm_float;
+    J.forward = p->forward != 0; J.backward = p->backward != 0; J.checkOri = p->check_orientation != 0;
+    J.bnd = matcher_bounds(fe, p->img_w, p->img_h); J.gemmFloat = p->gemm_float != 0;
     J.nLast = n_last; J.nCur = n_cur;
     J.lastKps = (const vslam_kp*)(d + o_kps);
     J.flags = d + o_f;
@@ -913,8 +947,8 @@ extern "C" int vslam_search_by_projection_dev_async(vslam_fe* fe, int njobs, con
         SbpJobDev& J = JS.job[j];
         memcpy(J.Tcw, s.p.Tcw, sizeof(J.Tcw));
         J.fx = s.p.fx; J.fy = s.p.fy; J.cx = s.p.cx; J.cy = s.p.cy; J.mbf = s.p.mbf; J.th = s.p.th;
-        J.forward = s.p.forward; J.backward = s.p.backward; J.checkOri = s.p.check_orientation;
-        J.imgW = s.p.img_w; J.imgH = s.p.img_h; J.gemmFloat = s.p.gemm_float;
+        J.forward = s.p.forward != 0; J.backward = s.p.backward != 0; J.checkOri = s.p.check_orientation != 0;
+        J.bnd = matcher_bounds(fe, s.p.img_w, s.p.img_h); J.gemmFloat = s.p.gemm_float != 0;
         J.nLast = cap; J.nCur = cap;
         J.lastKps = s.dev_last_kps; J.nLastPtr = s.dev_n_last; J.flags = s.dev_last_flags; J.x3Dw = s.dev_last_x3dw;
         J.mpDesc = s.dev_mp_desc; J.curKps = s.dev_cur_kps; J.curDesc = s.dev_cur_desc; J.nCurPtr = s.dev_n_cur;
@@ -1080,8 +1114,7 @@ extern "C" int vslam_search_by_projection_mappoints(vslam_fe* fe, const vslam_mp
     J.mode = 1;
     J.th = th;
     J.nnratio = nnratio;
-    J.imgW = img_w;
-    J.imgH = img_h;
+    J.bnd = matcher_bounds(fe, img_w, img_h);
     J.nLast = n_mp;
     J.nCur = n_cur;
     J.mps = (const MpTrack*)(d + o_mp);
@@ -1233,7 +1266,7 @@ extern "C" int vslam_fuse_search(vslam_fe* fe, const vslam_fuse_params* p, const
     for (int i = 0; i < 3; i++) A.tb[i] = p->tb[i];
     A.fx = p->fx; A.fy = p->fy; A.cx = p->cx; A.cy = p->cy; A.bf = p->bf; A.th = p->th;
     A.logScaleFactor = p->log_scale_factor;
-    A.imgW = p->img_w; A.imgH = p->img_h; A.sim3 = p->sim3; A.gemmFloat = p->gemm_float;
+    A.bnd = matcher_bounds(fe, p->img_w, p->img_h); A.sim3 = p->sim3; A.gemmFloat = p->gemm_float;
     A.nlevels = fe->p.nlevels; A.nPoints = n_points; A.nKF = n_kf;
     for (int l = 0; l < fe->p.nlevels; l++) {
         A.scale[l] = fe->tab.scale[l];
