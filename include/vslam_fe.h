@@ -148,7 +148,7 @@ int vslam_fe_tables(const vslam_fe* fe, float* scale, float* inv_scale, float* s
                     int32_t* features_per_level);
 
 /* FExtractor::compute (fextractor.h:38-40, fextractor.cpp:1034-1133) for one host image, synchronous.
- *   img/pitch : CV_8UC1 rows.   lap0/lap1 : vLappingArea (frame.cpp:107-108 passes {0,0}, :289 {0,1000}).
+ *   img/pitch : CV_8UC1 rows (or the context's pixel format, vslam_fe_set_pixel_format).   lap0/lap1 : vLappingArea (frame.cpp:107-108 passes {0,0}, :289 {0,1000}).
  *   kps/desc  : caller storage for cap keypoints / cap*32 descriptor bytes; cap >= vslam_fe_capacity(fe).
  *   *n        : keypoints written;  *mono_index : the reference's return value.
  * Uses image slot 0. */
@@ -340,6 +340,43 @@ int vslam_frame_stereo_batch_async(vslam_fe* fe, int npairs, const uint8_t* cons
 int vslam_frame_stereo_wait(vslam_fe* fe, vslam_kp* const* kps, uint8_t* const* desc, int cap, int* n,
                             float* const* u_right, float* const* depth);
 
+/* The extraction + depth section of Frame::Frame(imGray, imDepth, ...) (frame.cpp:185-257) for nframes (<= max_batch) RGB-D
+ * frames in ONE enqueue on fe's stream: slot j <- imgs[j] (the context's pixel format; vLappingArea {0,0},
+ * ExtractORB(0, imGray, 0, 0)), Frame::UndistortKeyPoints if the context has a camera, then Frame::ComputeStereoFromRGBD
+ * (:1000-1021) on the device, one lane per keypoint:
+ *     d = imDepth.at<float>((int)kp.y, (int)kp.x)       kp = keypoints_[i]: truncation toward zero
+ *     d > 0:  mvDepth[i] = d,  mvuRight[i] = ukeypoints_[i].pt.x - bf / d          else both -1 (NaN, zero, negative)
+ * imDepth is the caller's depth image after Tracking::GrabImageRGBD's conversion (tracking.cpp:1305-1306): a sample is
+ * multiplied by depth_map_factor in float if depth_type != VSLAM_DEPTH_F32 or fabsf(depth_map_factor - 1.0f) > 1e-5, and
+ * taken raw otherwise.  depth_map_factor is the reference's mDepthMapFactor, i.e. the MULTIPLIER 1 / DepthMapFactor
+ * (tracking.cpp:1108-1113).  A sample position outside the depth image gives -1; keypoints of this extractor never lie
+ * there and the reference does not test for it.
+ * depth[j]: width x height samples of the context's size, rows depth_pitch bytes apart.  depth_where = VSLAM_IMGS_DEVICE or
+ * VSLAM_IMGS_PINNED: read IN PLACE by the kernel (only the samples under keypoints are touched); VSLAM_IMGS_HOST (pageable):
+ * copied into pinned staging of the context first -- the context has ONE such staging, so with pageable depth images the
+ * call first waits on the host for everything enqueued on fe's stream before (it is synchronous with the previous pass;
+ * pin the depth images to keep several passes in flight).  Pinned and pageable depth images must stay untouched until _wait
+ * returns.  The depth gather is a plain launch behind the (possibly replayed) extraction: no captured graph holds a depth
+ * pointer.
+ * mvuRight / mvDepth lie where vslam_frame_stereo_batch_async puts them (full batches with want_host != 0: behind the
+ * extraction's results, the step leaves in one transfer), "pair j" = frame j = slot j: vslam_stereo_points_dev_async and
+ * vslam_stereo_points_buffers work after an RGB-D pass as after a stereo pass, with their own limit: at most 16 pairs per call
+ * and pair indices below 16, so only frames 0..15 of a larger RGB-D batch can be unprojected (mvuRight / mvDepth of all frames
+ * are delivered by _wait).  want_host: 0 keypoints and descriptors
+ * stay in HBM (counts, mvuRight and mvDepth still travel), 1 or 2 delivered.  _wait delivers like vslam_frame_stereo_wait:
+ * arrays of nframes entries, any may be NULL. */
+#define VSLAM_DEPTH_U16 0 /* CV_16UC1 */
+#define VSLAM_DEPTH_F32 1 /* CV_32FC1 */
+int vslam_frame_rgbd_batch_async(vslam_fe* fe, int nframes, const uint8_t* const* imgs, size_t pitch, int imgs_where,
+                                 const void* const* depth, size_t depth_pitch, int depth_type, int depth_where,
+                                 float depth_map_factor, float bf, int want_host);
+/* VSLAM_ERR_INVALID unless the last pass enqueued on fe was an RGB-D pass. */
+int vslam_frame_rgbd_wait(vslam_fe* fe, vslam_kp* const* kps, uint8_t* const* desc, int cap, int* n,
+                          float* const* u_right, float* const* depth);
+/* With vslam_fe_set_profiling on: HIP-event time of the depth gather (k_rgbd_depth) alone, summed over the RGB-D passes
+ * waited for since profiling was switched on.  Either pointer may be NULL. */
+int vslam_fe_get_rgbd_profile(vslam_fe* fe, double* depth_ms, long* passes);
+
 /* FMatcher::SearchForInitialization (fmatcher.h:106, fmatcher.cpp:983-1098).  Frame 1 / frame 2
  * keypoints+descriptors are device arrays (e.g. from vslam_fe_slot_buffers, or a slot of an RCCL
  * exchange buffer); kps1_host/kps2_host are the same keypoints on the host.  prev_matched: 2*n1 floats
@@ -456,6 +493,33 @@ int vslam_search_init_dev_async_ex(vslam_fe* fe, int npairs, const vslam_init_jo
 int vslam_fe_set_grid_bounds(vslam_fe* fe, const vslam_bounds* b);
 /* The bounds in force; *is_set = 0 and {0, width, 0, height} of the context when none are set. */
 int vslam_fe_get_grid_bounds(const vslam_fe* fe, vslam_bounds* b, int* is_set);
+
+/* ---------------------------------------------------------------- colour input images
+ *
+ * Tracking::GrabImageStereo / GrabImageRGBD / GrabImageMonocular (tracking.cpp:1235-1258, 1285-1303, 1324-1336) turn a 3- or
+ * 4-channel image into gray with cv::cvtColor(im, im, COLOR_{RGB,BGR,RGBA,BGRA}2GRAY) before anything else.  The pixel
+ * format is a property of the context, like its camera and its grid bounds.  With a format other than VSLAM_PIX_GRAY8
+ * every entry that takes images -- vslam_fe_extract, _extract_batch, _extract_batch_async, vslam_fe_stage_images_async,
+ * vslam_frame_stereo_batch_async, vslam_frame_rgbd_batch_async -- reads imgs[i] as interleaved pixels of 3 or 4 bytes,
+ * rows `pitch` >= width * bytes-per-pixel bytes apart (any such pitch, odd ones included), and one kernel
+ * (k_gray_images) writes the gray image into level 0 of the slot:
+ *     gray = (R * cr + G * cg + B * cb + (1 << (shift - 1))) >> shift          alpha ignored
+ *     shift 15: (cr, cg, cb) = (9798, 19235, 3735)   OpenCV 4.x 8-bit RGB2Gray (the default)
+ *     shift 14: (cr, cg, cb) = (4899,  9617, 1868)   OpenCV 3.x
+ * The coefficients are restated from OpenCV, not checked against a build of it here (tools/dump_opencv_cvtcolor.cpp is the
+ * route to settle them), which is why the shift is a knob.  VSLAM_IMGS_DEVICE images of a colour format are NOT used in
+ * place: level 0 lives in the context's pyramid and the caller's buffer is free once the pass has run.
+ * Setting a format waits for the context's stream, drops its captured graph and sizes its pinned and device staging for
+ * the wider rows.  VSLAM_PIX_GRAY8 restores the gray path exactly, zero copy for device images included.  The grid
+ * detector (vslam_fastgrid.h) keeps gray input. */
+#define VSLAM_PIX_GRAY8 0 /* default */
+#define VSLAM_PIX_RGB8 1
+#define VSLAM_PIX_BGR8 2
+#define VSLAM_PIX_RGBA8 3
+#define VSLAM_PIX_BGRA8 4
+/* gray_shift: 0 = default (15), 14 or 15; VSLAM_ERR_INVALID for anything else or an unknown fmt (the setting in force stays) */
+int vslam_fe_set_pixel_format(vslam_fe* fe, int fmt, int gray_shift);
+int vslam_fe_get_pixel_format(const vslam_fe* fe, int* fmt, int* gray_shift);
 
 /* ---------------------------------------------------------------- diagnostics */
 

@@ -51,21 +51,24 @@ struct KeyPoint { /* field order of cv::KeyPoint */
     float size, angle, response;
     int octave, class_id;
 };
-/* CV_8UC1 matrix stand-in: non-owning view or owning buffer */
+/* CV_8UC1 (or, for colour input, CV_8UC3 / CV_8UC4) matrix stand-in: non-owning view or owning buffer */
 struct Mat8u {
     int rows = 0, cols = 0;
     size_t step = 0;
     uint8_t* data = nullptr;
     std::vector<uint8_t> own;
+    int nchannels = 1;
     Mat8u() {}
-    Mat8u(int r, int c, uint8_t* d, size_t s) : rows(r), cols(c), step(s), data(d) {}
-    void create(int r, int c) {
+    Mat8u(int r, int c, uint8_t* d, size_t s, int ch = 1) : rows(r), cols(c), step(s), data(d), nchannels(ch) {}
+    void create(int r, int c, int ch = 1) {
         rows = r;
         cols = c;
-        step = (size_t)c;
-        own.assign((size_t)r * c, 0);
+        nchannels = ch;
+        step = (size_t)c * ch;
+        own.assign((size_t)r * c * ch, 0);
         data = own.data();
     }
+    int channels() const { return nchannels; }
     void release() {
         rows = cols = 0;
         step = 0;
@@ -125,10 +128,10 @@ public:
                 cv::OutputArray descriptors, std::vector<int>& vLappingArea) {
         if (image.empty()) return -1;
         cv::Mat im = image.getMat();
-        CV_Assert(im.type() == CV_8UC1);
+        CV_Assert(im.depth() == CV_8U);
         std::vector<uint8_t> d;
         int n = 0;
-        const int mono = run(im.data, im.cols, im.rows, im.step, keypoints, d, vLappingArea, &n);
+        const int mono = run(im.data, im.cols, im.rows, im.step, im.channels(), keypoints, d, vLappingArea, &n);
         if (n == 0) descriptors.release();
         else cv::Mat(n, 32, CV_8U, d.data()).copyTo(descriptors);
         return mono;
@@ -140,7 +143,7 @@ public:
         if (image.empty()) return -1; /* fextractor.cpp:1037-1038 */
         std::vector<uint8_t> d;
         int n = 0;
-        const int mono = run(image.data, image.cols, image.rows, image.step, keypoints, d, vLappingArea, &n);
+        const int mono = run(image.data, image.cols, image.rows, image.step, image.channels(), keypoints, d, vLappingArea, &n);
         if (n == 0) descriptors.release();
         else {
             descriptors.create(n, 32);
@@ -189,9 +192,54 @@ public:
     bool HasCamera() const { return has_cam_; }
     float DistortionK1() const { return has_cam_ ? cam_.dist[0] : 0.0f; }
 
+    /* The cvtColor calls of Tracking::GrabImageMonocular / GrabImageStereo / GrabImageRGBD (tracking.cpp:1235-1336):
+     * channels = mImGray.channels() (1, 3 or 4), mbRGB = Tracking::mbRGB (Camera.RGB).  Later compute() calls take images of
+     * that many channels and the device converts them (COLOR_RGB2GRAY / BGR2GRAY / RGBA2GRAY / BGRA2GRAY).  gray_shift: 0 =
+     * OpenCV 4.x coefficients, 14 = OpenCV 3.x.  Kept across the re-creation of the context. */
+    void SetPixelFormat(int channels, bool mbRGB, int gray_shift = 0) {
+        if (channels != 1 && channels != 3 && channels != 4) throw std::invalid_argument("images have 1, 3 or 4 channels");
+        const int fmt = channels == 1 ? VSLAM_PIX_GRAY8
+                        : channels == 3 ? (mbRGB ? VSLAM_PIX_RGB8 : VSLAM_PIX_BGR8) : (mbRGB ? VSLAM_PIX_RGBA8 : VSLAM_PIX_BGRA8);
+        if (fe_) check(vslam_fe_set_pixel_format(fe_, fmt, gray_shift));
+        pix_fmt_ = fmt;
+        gray_shift_ = gray_shift;
+    }
+    int Channels() const { return pix_fmt_ == VSLAM_PIX_GRAY8 ? 1 : pix_fmt_ <= VSLAM_PIX_BGR8 ? 3 : 4; }
+
+    /* The extraction + depth section of Frame::Frame(imGray, imDepth, ...) (frame.cpp:185-257): ExtractORB(0, imGray, 0, 0),
+     * UndistortKeyPoints, ComputeStereoFromRGBD in one pass of the device.  imRGB: the image as GrabImageRGBD receives it (the
+     * extractor's pixel format); imDepth / depth_step / depth_type: the caller's CV_16UC1 (VSLAM_DEPTH_U16) or CV_32FC1
+     * (VSLAM_DEPTH_F32) depth image BEFORE convertTo; mDepthMapFactor as Tracking holds it (1 / DepthMapFactor). */
+    void computeRGBD(const uint8_t* imRGB, int cols, int rows, size_t step, const void* imDepth, size_t depth_step,
+                     int depth_type, float mDepthMapFactor, float mbf, std::vector<KeyPoint>& keypoints,
+                     std::vector<KeyPoint>& ukeypoints, std::vector<uint8_t>& descriptors, std::vector<float>& mvuRight,
+                     std::vector<float>& mvDepth) {
+        ensure(cols, rows);
+        const int cap = vslam_fe_capacity(fe_);
+        keypoints.resize(cap);
+        descriptors.resize((size_t)cap * 32);
+        mvuRight.assign(cap, -1.0f);
+        mvDepth.assign(cap, -1.0f);
+        vslam_kp* kp = reinterpret_cast<vslam_kp*>(keypoints.data());
+        uint8_t* dp = descriptors.data();
+        float *up = mvuRight.data(), *zp = mvDepth.data();
+        int n = 0;
+        check(vslam_frame_rgbd_batch_async(fe_, 1, &imRGB, step, VSLAM_IMGS_HOST, &imDepth, depth_step, depth_type,
+                                           VSLAM_IMGS_HOST, mDepthMapFactor, mbf, 1));
+        check(vslam_frame_rgbd_wait(fe_, &kp, &dp, cap, &n, &up, &zp));
+        keypoints.resize(n);
+        descriptors.resize((size_t)n * 32);
+        mvuRight.resize(n);
+        mvDepth.resize(n);
+        ukeypoints = keypoints;
+        if (has_cam_ && cam_.dist[0] != 0.0f && n) {
+            int nu = 0;
+            check(vslam_fe_ukps_copy(fe_, 0, reinterpret_cast<vslam_kp*>(ukeypoints.data()), n, &nu));
+        }
+    }
+
 protected:
-    int run(const uint8_t* data, int cols, int rows, size_t step, std::vector<KeyPoint>& keypoints,
-            std::vector<uint8_t>& desc, std::vector<int>& vLappingArea, int* n_out) {
+    void ensure(int cols, int rows) {
         if (!fe_ || cols != w_ || rows != h_) {
             if (fe_) vslam_fe_destroy(fe_);
             fe_ = nullptr;
@@ -210,7 +258,14 @@ protected:
             w_ = cols;
             h_ = rows;
             if (has_cam_) check(vslam_fe_set_camera(fe_, &cam_));
+            if (pix_fmt_ != VSLAM_PIX_GRAY8) check(vslam_fe_set_pixel_format(fe_, pix_fmt_, gray_shift_));
         }
+    }
+
+    int run(const uint8_t* data, int cols, int rows, size_t step, int channels, std::vector<KeyPoint>& keypoints,
+            std::vector<uint8_t>& desc, std::vector<int>& vLappingArea, int* n_out) {
+        if (channels != Channels()) throw std::invalid_argument("FExtractor: image channels differ from SetPixelFormat");
+        ensure(cols, rows);
         const int cap = vslam_fe_capacity(fe_); /* quota + the quadtree's overshoot, see vslam_fe.h */
         keypoints.resize(cap);
         desc.resize((size_t)cap * 32);
@@ -234,6 +289,7 @@ protected:
     int w_ = 0, h_ = 0;
     bool has_cam_ = false;
     vslam_camera cam_;
+    int pix_fmt_ = VSLAM_PIX_GRAY8, gray_shift_ = 0;
 };
 
 /* Frame::UndistortKeyPoints (frame.cpp:758-790) for the keypoints the extractor's last compute() returned: with
@@ -292,6 +348,44 @@ struct FrameView {
      * SearchForInitialization only (the matchers after initialisation read the context's: SetGridBounds above). */
     bool has_bounds = false;
     vslam_bounds bounds = {0.0f, 0.0f, 0.0f, 0.0f};
+};
+
+/* Frame::Frame(imGray, imDepth, timeStamp, extractor, voc, K, distCoef, bf, thDepth, pCamera) (frame.cpp:185-257), the part
+ * that runs on the device: the members a Frame keeps of it, over a FrameView for the matchers.  imGray is the image as
+ * Tracking::GrabImageRGBD receives it (the extractor converts colour input: FExtractor::SetPixelFormat), imDepth the depth
+ * image before GrabImageRGBD's convertTo, which the device applies with mDepthMapFactor.  K and distCoef go to the
+ * extractor once (FExtractor::SetCamera), as they are the same for every Frame.  The vocabulary, the time stamp and thDepth
+ * are not read by anything computed here. */
+struct DepthImage {
+    const void* data = nullptr;
+    size_t step = 0;
+    int type = VSLAM_DEPTH_U16; /* VSLAM_DEPTH_U16 (CV_16UC1) or VSLAM_DEPTH_F32 (CV_32FC1) */
+};
+struct FrameRGBD : FrameView {
+    std::vector<KeyPoint> keypoints_, ukeypoints_;
+    std::vector<uint8_t> descriptors_; /* N x 32 */
+    std::vector<float> mvuRight, mvDepth;
+    int N = 0;
+    float mbf = 0.0f, mThDepth = 0.0f;
+    double mTimeStamp = 0.0;
+
+    FrameRGBD(const uint8_t* imGray, int cols, int rows, size_t step, const DepthImage& imDepth, float mDepthMapFactor,
+              double timeStamp, FExtractor* pExtractor, float bf, float thDepth)
+        : mbf(bf), mThDepth(thDepth), mTimeStamp(timeStamp) {
+        pExtractor->computeRGBD(imGray, cols, rows, step, imDepth.data, imDepth.step, imDepth.type, mDepthMapFactor, bf,
+                                keypoints_, ukeypoints_, descriptors_, mvuRight, mvDepth);
+        N = (int)keypoints_.size();
+        ukeypoints = &ukeypoints_;
+        extractor = pExtractor;
+        mnMaxX = cols;
+        mnMaxY = rows;
+        if (pExtractor->HasCamera()) {
+            ComputeImageBounds(*pExtractor, bounds.min_x, bounds.max_x, bounds.min_y, bounds.max_y);
+            has_bounds = true;
+        }
+    }
+    FrameRGBD(const FrameRGBD&) = delete; /* FrameView::ukeypoints points into this object */
+    FrameRGBD& operator=(const FrameRGBD&) = delete;
 };
 
 /* ---------------------------------------------------------------------------------------------------

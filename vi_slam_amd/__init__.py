@@ -19,6 +19,8 @@ HOST_LIB_PATH = os.path.join(_HERE, "libvslam_host.so")
 VSLAM_OK = 0
 ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_CAPACITY, ERR_UNSUPPORTED, ERR_COMM = -1, -2, -3, -4, -5, -6
 IMGS_HOST, IMGS_DEVICE, IMGS_PINNED, IMGS_STAGED = 0, 1, 2, 3  # where the input images live (vslam_fe.h VSLAM_IMGS_*)
+PIX_GRAY8, PIX_RGB8, PIX_BGR8, PIX_RGBA8, PIX_BGRA8 = 0, 1, 2, 3, 4  # vslam_fe_set_pixel_format (VSLAM_PIX_*)
+DEPTH_U16, DEPTH_F32 = 0, 1  # depth image types of the RGB-D frame entry (VSLAM_DEPTH_*)
 COMM_ID_BYTES = 128
 FLAG_ATAN_FMA = 1
 FLAG_HOST_OCTREE = 2
@@ -54,6 +56,8 @@ ABI_SYMBOLS = [
     "vslam_fe_set_camera", "vslam_fe_slot_ukps", "vslam_fe_ukps_copy", "vslam_undistort_points", "vslam_fe_image_bounds",
     "vslam_fe_set_grid_bounds", "vslam_fe_get_grid_bounds",
     "vslam_search_for_initialization_ex", "vslam_search_for_initialization_batch_ex", "vslam_search_init_dev_async_ex",
+    "vslam_fe_set_pixel_format", "vslam_fe_get_pixel_format", "vslam_frame_rgbd_batch_async", "vslam_frame_rgbd_wait",
+    "vslam_fe_get_rgbd_profile",
 ]
 
 
@@ -147,6 +151,31 @@ class _Bounds(C.Structure):  # vslam_bounds
 def _bounds(b):
     """(min_x, max_x, min_y, max_y) -> vslam_bounds (FExtractor.image_bounds() order)"""
     return _Bounds(*[float(v) for v in b])
+
+
+def pixel_bytes(fmt):
+    """bytes per pixel of a PIX_* format"""
+    if fmt not in (PIX_GRAY8, PIX_RGB8, PIX_BGR8, PIX_RGBA8, PIX_BGRA8):
+        raise VslamError(ERR_INVALID, "unknown pixel format %r" % (fmt,))
+    return 1 if fmt == PIX_GRAY8 else 3 if fmt in (PIX_RGB8, PIX_BGR8) else 4
+
+
+def check_pixel_format(fmt, gray_shift=0):
+    """the argument check of vslam_fe_set_pixel_format -> (fmt, the shift in force: 14 or 15)"""
+    pixel_bytes(fmt)
+    if gray_shift not in (0, 14, 15):
+        raise VslamError(ERR_INVALID, "gray_shift must be 0 (default 15), 14 or 15")
+    return int(fmt), int(gray_shift) or 15
+
+
+def check_depth_args(depth_type, depth_map_factor, bf=1.0):
+    """the scalar argument checks of vslam_frame_rgbd_batch_async -> (numpy dtype of a depth sample, factor as float32)"""
+    if depth_type not in (DEPTH_U16, DEPTH_F32):
+        raise VslamError(ERR_INVALID, "depth_type must be DEPTH_U16 or DEPTH_F32")
+    f, b = np.float32(depth_map_factor), np.float32(bf)
+    if not (np.isfinite(f) and np.isfinite(b)):
+        raise VslamError(ERR_INVALID, "depth_map_factor and bf must be finite")
+    return np.dtype(np.float32 if depth_type == DEPTH_F32 else np.uint16), f
 
 
 def bind_voc_file(L):
@@ -287,6 +316,11 @@ def lib():
         L.vslam_search_init_dev_async_ex.argtypes = [vp, i, vp, C.POINTER(_Bounds), i, f, i]
         L.vslam_fe_set_grid_bounds.argtypes = [vp, C.POINTER(_Bounds)]
         L.vslam_fe_get_grid_bounds.argtypes = [vp, C.POINTER(_Bounds), C.POINTER(i)]
+        L.vslam_fe_set_pixel_format.argtypes = [vp, i, i]
+        L.vslam_fe_get_pixel_format.argtypes = [vp, C.POINTER(i), C.POINTER(i)]
+        L.vslam_frame_rgbd_batch_async.argtypes = [vp, i, vp, C.c_size_t, i, vp, C.c_size_t, i, i, f, f, i]
+        L.vslam_frame_rgbd_wait.argtypes = [vp, vp, vp, i, vp, vp, vp]
+        L.vslam_fe_get_rgbd_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long)]
         _lib = L
     return _lib
 
@@ -421,12 +455,17 @@ class FExtractor:
     def features_per_level(self):
         return self._tables()[4]
 
+    def _image_shape(self):
+        """shape of one host image array under the context's pixel format"""
+        bpp = pixel_bytes(self.pixel_format[0])
+        return (self.height, self.width) if bpp == 1 else (self.height, self.width, bpp)
+
     # ---- compute (fextractor.h:38-40)
     def compute(self, image, vLappingArea=(0, 0)):
         """FExtractor::compute.  Returns (keypoints[KP_DTYPE], descriptors[N,32] u8, monoIndex)."""
         image = np.ascontiguousarray(image, dtype=np.uint8)
-        if image.ndim != 2 or image.shape != (self.height, self.width):
-            raise VslamError(ERR_INVALID, "image must be %dx%d CV_8UC1" % (self.width, self.height))
+        if image.shape != self._image_shape():
+            raise VslamError(ERR_INVALID, "image must be %dx%d CV_8UC1 (or the context's pixel format)" % (self.width, self.height))
         kps = np.zeros(self.cap, KP_DTYPE)
         desc = np.zeros((self.cap, 32), np.uint8)
         n, mono = C.c_int(0), C.c_int(0)
@@ -445,12 +484,13 @@ class FExtractor:
             keep = None
         else:
             keep = [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
+            shape = self._image_shape()
             for im in keep:
-                if im.shape != (self.height, self.width):
-                    raise VslamError(ERR_INVALID, "image must be %dx%d CV_8UC1" % (self.width, self.height))
+                if im.shape != shape:
+                    raise VslamError(ERR_INVALID, "image must be %dx%d CV_8UC1 (or the context's pixel format)" % (self.width, self.height))
             nimg = len(keep)
             ptrs = (C.c_void_p * nimg)(*[im.ctypes.data for im in keep])
-            pitch = self.width
+            pitch = self.width * (shape[2] if len(shape) == 3 else 1)
             on_dev = 0
         n = (C.c_int * nimg)()
         mono = (C.c_int * nimg)()
@@ -542,6 +582,73 @@ class FExtractor:
             [(n[i], None) for i in range(nimg)]
         stereo = [(self._out_u[j, :n[2 * j]], self._out_dep[j, :n[2 * j]]) for j in range(npairs)]
         return feats, stereo
+
+    # ---- colour input (the cvtColor calls of Tracking::GrabImage*, tracking.cpp:1235-1336)
+    def set_pixel_format(self, fmt, gray_shift=0):
+        """Every later image of this context is interleaved PIX_RGB8 / BGR8 / RGBA8 / BGRA8 (PIX_GRAY8 restores the
+        default) and is converted as cv::cvtColor's 8-bit RGB2Gray does; gray_shift 15 (0 = default, OpenCV 4.x) or 14."""
+        fmt, gray_shift = check_pixel_format(fmt, gray_shift)
+        _check(lib().vslam_fe_set_pixel_format(self._h, fmt, gray_shift))
+
+    @property
+    def pixel_format(self):
+        """(fmt, gray_shift) in force"""
+        f, s = C.c_int(), C.c_int()
+        _check(lib().vslam_fe_get_pixel_format(self._h, C.byref(f), C.byref(s)))
+        return f.value, s.value
+
+    # ---- Frame::Frame(imGray, imDepth, ...) hot section (frame.cpp:185-257), several frames per enqueue
+    def frame_rgbd_async(self, ptrs, pitch, depth_ptrs, depth_pitch, depth_type, depth_map_factor, bf, to_host=True,
+                         where=IMGS_DEVICE, depth_where=IMGS_DEVICE):
+        """ptrs / depth_ptrs: one image and one depth image (DEPTH_U16 / DEPTH_F32, the context's width x height) per
+        frame, each HBM-resident, pinned or pageable host memory (where / depth_where); depth_map_factor is the reference's
+        mDepthMapFactor = 1 / DepthMapFactor.  Enqueues extraction, undistortion and ComputeStereoFromRGBD of every frame
+        and returns; collect with frame_rgbd_wait().  to_host: False (want_host 0), True (1) or "deferred" (2)."""
+        check_depth_args(depth_type, depth_map_factor, bf)
+        n = len(depth_ptrs)
+        p = ptrs if isinstance(ptrs, C.Array) or ptrs is None else (C.c_void_p * n)(*ptrs)
+        d = depth_ptrs if isinstance(depth_ptrs, C.Array) else (C.c_void_p * n)(*depth_ptrs)
+        want = 2 if to_host == "deferred" else int(bool(to_host))
+        _check(lib().vslam_frame_rgbd_batch_async(self._h, n, p, pitch, where, d, depth_pitch, depth_type, depth_where,
+                                                  depth_map_factor, bf, want))
+        self._pending = (n, bool(to_host))
+
+    def frame_rgbd_wait(self):
+        """-> (list of (keypoints, descriptors) per frame, list of (mvuRight, mvDepth) per frame); copies."""
+        nimg, to_host = self._pending
+        n = (C.c_int * nimg)()
+        self._host_views()
+        u = np.zeros((nimg, self.cap), np.float32)
+        dep = np.zeros((nimg, self.cap), np.float32)
+        u_ptrs = (C.c_void_p * nimg)(*[u[j].ctypes.data for j in range(nimg)])
+        d_ptrs = (C.c_void_p * nimg)(*[dep[j].ctypes.data for j in range(nimg)])
+        _check(lib().vslam_frame_rgbd_wait(self._h, None, None, self.cap, n, u_ptrs, d_ptrs))
+        feats = [(self._out_kps[j, :n[j]].copy(), self._out_desc[j, :n[j]].copy()) for j in range(nimg)] if to_host else \
+            [(n[j], None) for j in range(nimg)]
+        return feats, [(u[j, :n[j]], dep[j, :n[j]]) for j in range(nimg)]
+
+    def rgbd_profile(self):
+        """(ms spent in the depth gather alone, RGB-D passes) since set_profiling(True)"""
+        ms, n = C.c_double(), C.c_long()
+        _check(lib().vslam_fe_get_rgbd_profile(self._h, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
+    def frame_rgbd(self, images, depths, depth_map_factor, bf):
+        """Synchronous form over host arrays: images H x W (PIX_GRAY8) or H x W x 3 | 4 uint8 of the context's pixel
+        format, depths H x W uint16 or float32."""
+        bpp = pixel_bytes(self.pixel_format[0])
+        keep = [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
+        shape = (self.height, self.width) if bpp == 1 else (self.height, self.width, bpp)
+        dk = [np.ascontiguousarray(d) for d in depths]
+        if len(keep) != len(dk) or any(im.shape != shape for im in keep) or \
+                any(d.shape != (self.height, self.width) or d.dtype != dk[0].dtype for d in dk) or \
+                dk[0].dtype not in (np.dtype(np.uint16), np.dtype(np.float32)):
+            raise VslamError(ERR_INVALID, "images must be %s uint8, depths %dx%d uint16 or float32, one per image"
+                             % ("x".join(map(str, shape)), self.height, self.width))
+        dtype = DEPTH_F32 if dk[0].dtype == np.float32 else DEPTH_U16
+        self.frame_rgbd_async([im.ctypes.data for im in keep], self.width * bpp, [d.ctypes.data for d in dk],
+                              self.width * dk[0].itemsize, dtype, depth_map_factor, bf, True, IMGS_HOST, IMGS_HOST)
+        return self.frame_rgbd_wait()
 
     # ---- mvImagePyramid (fextractor.h:64)
     def level_size(self, level):

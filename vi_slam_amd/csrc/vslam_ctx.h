@@ -180,7 +180,17 @@ struct vslam_fe {
     size_t h_stereo_bytes = 0;
     int stereo_pairs = 0;
     int stereo_capR = 0; /* slot capacity of the right context of the last stereo enqueue (scratch carving) */
-    int stereo_slotL[VSLAM_MAX_STEREO_JOBS] = {};
+    int stereo_slotL[VSLAM_MAX_BATCH] = {}; /* an RGB-D pass has one "pair" per image slot */
+    /* vslam_fe_set_pixel_format: interleaved colour input, converted to gray into level 0 by k_gray_images */
+    int pix_fmt = VSLAM_PIX_GRAY8, gray_shift = 15;
+    size_t h_img_bytes = 0;     /* bytes of h_img (sized for the pixel format in force) */
+    uint8_t* h_depth = nullptr; /* pinned staging of pageable depth images (vslam_frame_rgbd_batch_async, VSLAM_IMGS_HOST) */
+    size_t h_depth_bytes = 0;
+    bool last_rgbd = false;     /* the last pass enqueued was an RGB-D pass: vslam_frame_rgbd_wait may deliver it */
+    hipEvent_t ev_rgbd[2] = {}; /* profiling: around k_rgbd_depth */
+    bool rgbd_timed = false;
+    double rgbd_ms = 0;
+    long rgbd_passes = 0;
 
     /* GPU quadtree distribution */
     bool dev_octree = false;
@@ -206,6 +216,10 @@ struct vslam_fe {
     WorkerPool* pool = nullptr;
 };
 
+
+/* bytes per pixel of the context's input format, and bytes of one input row */
+static inline int vslam_pix_bpp(int fmt) { return fmt == VSLAM_PIX_GRAY8 ? 1 : fmt <= VSLAM_PIX_BGR8 ? 3 : 4; }
+static inline size_t vslam_row_bytes(const vslam_fe* fe) { return (size_t)fe->p.width * vslam_pix_bpp(fe->pix_fmt); }
 
 int vslam_ensure(void** p, size_t* have, size_t want);
 int vslam_ensure_pinned(uint8_t** p, size_t* have, size_t want); /* grow-only pinned host buffer */

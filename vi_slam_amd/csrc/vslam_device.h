@@ -284,4 +284,14 @@ struct UdCam {
     float dist[5];
 };
 
+/* the depth images of an RGB-D pass as k_rgbd_depth takes them (by value): slot s reads img[s] */
+struct RgbdDepthSrc {
+    const void* img[VSLAM_MAX_BATCH]; /* HBM or pinned host memory */
+    uint32_t pitch;                   /* bytes per row */
+    int32_t type;                     /* VSLAM_DEPTH_* */
+    int32_t w, h;
+    int32_t scale;                    /* 1: multiply every sample by factor (tracking.cpp:1305) */
+    float factor, bf;
+};
+
 #endif

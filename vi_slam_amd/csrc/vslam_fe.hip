@@ -87,6 +87,7 @@ static void free_ctx(vslam_fe* fe) {
     hipFree(fe->d_mpflags);
     if (fe->h_proj) hipHostFree(fe->h_proj);
     if (fe->h_img) hipHostFree(fe->h_img);
+    if (fe->h_depth) hipHostFree(fe->h_depth);
     hipFree(fe->d_stage);
     if (fe->graph_exec) hipGraphExecDestroy(fe->graph_exec);
     hipFree(fe->d_bow);
@@ -104,6 +105,8 @@ static void free_ctx(vslam_fe* fe) {
         fe->gate_waiters.clear();
     }
     if (fe->ev_fast) hipEventDestroy(fe->ev_fast);
+    for (int i = 0; i < 2; i++)
+        if (fe->ev_rgbd[i]) hipEventDestroy(fe->ev_rgbd[i]);
     for (int i = 0; i < 10; i++)
         if (fe->ev_prof[i]) hipEventDestroy(fe->ev_prof[i]);
     if (fe->stream) hipStreamDestroy(fe->stream);
@@ -586,6 +589,8 @@ extern "C" int vslam_fe_set_profiling(vslam_fe* fe, int on) {
     fe->profiling = on != 0;
     for (int i = 0; i < 5; i++) fe->prof_ms[i] = 0;
     fe->prof_batches = fe->prof_images = 0;
+    fe->rgbd_ms = 0;
+    fe->rgbd_passes = 0;
     return VSLAM_OK;
 }
 
@@ -697,15 +702,35 @@ static void copy_streaming(uint8_t* dst, const uint8_t* src, size_t n) {
 #endif
 }
 
+/* bytes of one image in the pinned staging h_img: level-0 pitch x height for gray, dense colour rows (256-byte aligned) else */
+static size_t host_stage_stride(const vslam_fe* fe) {
+    if (fe->pix_fmt == VSLAM_PIX_GRAY8) return (size_t)fe->geom.lv[0].pitch * (size_t)fe->p.height;
+    return (vslam_row_bytes(fe) * (size_t)fe->p.height + 255) & ~(size_t)255;
+}
+
 static int stage_host_images(vslam_fe* fe, int nimg, const uint8_t* const* imgs, size_t pitch) {
     const vslam_fe_params& p = fe->p;
-    const size_t lp = fe->geom.lv[0].pitch, img_bytes = lp * (size_t)p.height;
-    if (!fe->h_img) HIPCHK((hipError_t)vslam_pinned_alloc((void**)&fe->h_img, img_bytes * fe->B));
+    const size_t lp = fe->geom.lv[0].pitch, img_bytes = host_stage_stride(fe);
+    if (!fe->h_img) { /* colour formats: vslam_fe_set_pixel_format allocated it */
+        HIPCHK((hipError_t)vslam_pinned_alloc((void**)&fe->h_img, img_bytes * fe->B));
+        fe->h_img_bytes = img_bytes * fe->B;
+    }
     for (int s = 0; s < nimg; s++)
         if (!imgs[s]) {
             g_err = "null image";
             return VSLAM_ERR_INVALID;
         }
+    if (fe->pix_fmt != VSLAM_PIX_GRAY8) { /* colour rows are staged dense, whatever the caller's pitch */
+        const size_t rowb = vslam_row_bytes(fe);
+        fe->h_img_pitch = rowb;
+        fe->pool->parallel_for(nimg, [&](int s) {
+            uint8_t* hs = fe->h_img + img_bytes * s;
+            if (pitch == rowb) copy_streaming(hs, imgs[s], rowb * p.height);
+            else
+                for (int y = 0; y < p.height; y++) memcpy(hs + (size_t)y * rowb, imgs[s] + (size_t)y * pitch, rowb);
+        });
+        return VSLAM_OK;
+    }
     /* one task per image on the context's worker pool: a single thread copies ~18 GB/s, which bounded the
      * host-image batch path at 0.85 ms per 32 KITTI frames */
     /* dense rows (pitch == width, what cv::Mat::isContinuous() images are) stay dense in the staging: ONE memcpy per
@@ -722,6 +747,11 @@ static int stage_host_images(vslam_fe* fe, int nimg, const uint8_t* const* imgs,
     return VSLAM_OK;
 }
 
+/* the widest row pitch stage_host_images leaves in h_img */
+static size_t host_stage_pitch(const vslam_fe* fe) {
+    return fe->pix_fmt == VSLAM_PIX_GRAY8 ? (size_t)fe->geom.lv[0].pitch : vslam_row_bytes(fe);
+}
+
 /* VSLAM_H2D = sdma | pull forces one transport; default: the DMA engines for batches (they run beside the other
  * contexts' kernels without disturbing them), the pull kernel for one or two images (a synchronous single-frame call
  * has nothing to overlap with, and the hand-over between the DMA engine and the compute queue costs ~30 us) */
@@ -733,7 +763,7 @@ static bool h2d_uses_sdma(const vslam_fe* fe, int nimg) {
 /* the device staging buffer of the sdma transport, allocated OUTSIDE stream capture (hipMalloc is not capturable) */
 static int ensure_stage(vslam_fe* fe, size_t spitch, int nimg) {
     if (!h2d_uses_sdma(fe, nimg)) return VSLAM_OK;
-    const size_t one = (size_t)(fe->p.height - 1) * spitch + fe->p.width;
+    const size_t one = (size_t)(fe->p.height - 1) * spitch + vslam_row_bytes(fe);
     const size_t stride = (one + 255) & ~(size_t)255;
     if (fe->d_stage_bytes >= stride * fe->B + 256) return VSLAM_OK;
     HIPCHK(vslam_stream_wait(fe->stream)); /* an earlier pass may still read the old buffer */
@@ -757,7 +787,8 @@ static bool hip_stream_capturing(hipStream_t s) {
 static int upload_host_rows(vslam_fe* fe, int nimg, const uint8_t* const* imgs, size_t pitch, int where) {
     const vslam_fe_params& p = fe->p;
     hipStream_t st = fe->stream;
-    const size_t lp = fe->geom.lv[0].pitch, img_bytes = lp * (size_t)p.height;
+    const size_t lp = fe->geom.lv[0].pitch, img_bytes = host_stage_stride(fe);
+    const size_t rowb = vslam_row_bytes(fe); /* bytes of a source row: the width, or width x 3 | 4 of a colour format */
     const bool use_sdma = h2d_uses_sdma(fe, nimg);
     BatchSrc hs;
     for (int s = 0; s < nimg; s++) {
@@ -771,7 +802,7 @@ static int upload_host_rows(vslam_fe* fe, int nimg, const uint8_t* const* imgs, 
     int from_host = 1;
     if (use_sdma) {
         const size_t spitch = hs.pitch0[0];
-        const size_t one = (size_t)(p.height - 1) * spitch + p.width; /* bytes of one image, first to last pixel */
+        const size_t one = (size_t)(p.height - 1) * spitch + rowb; /* bytes of one image, first to last pixel */
         const size_t stride = (one + 255) & ~(size_t)255;
         if (fe->d_stage_bytes < stride * fe->B + 256) { /* ensure_stage() runs before any capture; cannot happen */
             g_err = "internal: device staging buffer not allocated";
@@ -805,7 +836,11 @@ static int upload_host_rows(vslam_fe* fe, int nimg, const uint8_t* const* imgs, 
         }
         from_host = 0;
     }
-    vk_pull_images(st, hs, fe->d_pyr, fe->slot_stride, fe->geom.lv[0].off, (int)lp, p.width, p.height, nimg, from_host, fe->tune);
+    if (fe->pix_fmt != VSLAM_PIX_GRAY8) /* cv::cvtColor on the way into level 0 */
+        vk_gray_images(st, hs, fe->d_pyr, fe->slot_stride, fe->geom.lv[0].off, (int)lp, p.width, p.height, nimg, from_host,
+                       fe->pix_fmt, fe->gray_shift, fe->tune);
+    else
+        vk_pull_images(st, hs, fe->d_pyr, fe->slot_stride, fe->geom.lv[0].off, (int)lp, p.width, p.height, nimg, from_host, fe->tune);
     return VSLAM_OK;
 }
 
@@ -822,13 +857,19 @@ static int enqueue_front(vslam_fe* fe, int nimg, const uint8_t* const* imgs, siz
     const int L = p.nlevels;
     hipStream_t st = fe->stream;
     if (on_device == VSLAM_IMGS_DEVICE) {
+        BatchSrc ds;
         for (int s = 0; s < nimg; s++) {
             if (!imgs[s]) {
                 g_err = "null image";
                 return VSLAM_ERR_INVALID;
             }
-            fe->src.l0[s] = imgs[s];
-            fe->src.pitch0[s] = (uint32_t)pitch;
+            ds.l0[s] = fe->src.l0[s] = imgs[s];
+            ds.pitch0[s] = fe->src.pitch0[s] = (uint32_t)pitch;
+        }
+        if (fe->pix_fmt != VSLAM_PIX_GRAY8) { /* colour: not zero copy, the gray image lives in the context's level 0 */
+            vk_gray_images(st, ds, fe->d_pyr, fe->slot_stride, fe->geom.lv[0].off, fe->geom.lv[0].pitch, p.width, p.height, nimg,
+                           0, fe->pix_fmt, fe->gray_shift, fe->tune);
+            src_at_slots(fe, nimg);
         }
     } else {
         if (on_device != VSLAM_IMGS_STAGED) { /* staged: vslam_fe_stage_images_async put them there */
@@ -1072,7 +1113,7 @@ static int enqueue_extract_impl(vslam_fe* fe, int nimg, const uint8_t* const* im
         if (rc) return rc;
     }
     if (on_device == VSLAM_IMGS_HOST || on_device == VSLAM_IMGS_PINNED) {
-        int rc = ensure_stage(fe, on_device == VSLAM_IMGS_PINNED ? pitch : (size_t)fe->geom.lv[0].pitch, nimg);
+        int rc = ensure_stage(fe, on_device == VSLAM_IMGS_PINNED ? pitch : host_stage_pitch(fe), nimg);
         if (rc) return rc;
     }
     /* Host-image passes of one shape replay a captured HIP graph: every kernel argument of such a pass is fixed
@@ -1144,6 +1185,7 @@ static int enqueue_extract_impl(vslam_fe* fe, int nimg, const uint8_t* const* im
 
 int vslam_enqueue_extract(vslam_fe* fe, int nimg, const uint8_t* const* imgs, size_t pitch, int on_device,
                           int lap0, int lap1, int want_host) {
+    fe->last_rgbd = false; /* vslam_frame_rgbd_batch_async sets it behind its depth gather */
     const int rc = enqueue_extract_impl(fe, nimg, imgs, pitch, on_device, lap0, lap1, want_host);
     /* set on every path, a replayed graph included (the captured pass of want_host = 2 holds no copy) */
     fe->deliver_deferred = rc == VSLAM_OK && want_host == 2 && nimg == fe->B && fe->res_init_bytes != 0;
@@ -1216,7 +1258,7 @@ extern "C" int vslam_fe_extract_batch(vslam_fe* fe, int nimg, const uint8_t* con
                                       int imgs_on_device, int lap0, int lap1, vslam_kp* const* kps,
                                       uint8_t* const* desc, int cap, int* n, int* mono_index) {
     if (!fe || (!imgs && imgs_on_device != VSLAM_IMGS_STAGED) || nimg < 1 || nimg > fe->B ||
-        (pitch < (size_t)fe->p.width && imgs_on_device != VSLAM_IMGS_STAGED) || imgs_on_device < 0 ||
+        (pitch < vslam_row_bytes(fe) && imgs_on_device != VSLAM_IMGS_STAGED) || imgs_on_device < 0 ||
         imgs_on_device > VSLAM_IMGS_STAGED) {
         g_err = "invalid arguments";
         return VSLAM_ERR_INVALID;
@@ -1234,7 +1276,7 @@ extern "C" int vslam_fe_extract_batch(vslam_fe* fe, int nimg, const uint8_t* con
 extern "C" int vslam_fe_extract_batch_async(vslam_fe* fe, int nimg, const uint8_t* const* imgs, size_t pitch,
                                             int imgs_on_device, int lap0, int lap1, int want_host) {
     if (!fe || (!imgs && imgs_on_device != VSLAM_IMGS_STAGED) || nimg < 1 || nimg > fe->B ||
-        (pitch < (size_t)fe->p.width && imgs_on_device != VSLAM_IMGS_STAGED) || imgs_on_device < 0 ||
+        (pitch < vslam_row_bytes(fe) && imgs_on_device != VSLAM_IMGS_STAGED) || imgs_on_device < 0 ||
         imgs_on_device > VSLAM_IMGS_STAGED) {
         g_err = "invalid arguments";
         return VSLAM_ERR_INVALID;
@@ -1270,7 +1312,7 @@ extern "C" int vslam_fe_extract(vslam_fe* fe, const uint8_t* img, size_t pitch, 
 
 extern "C" int vslam_fe_stage_images_async(vslam_fe* fe, int nimg, const uint8_t* const* imgs, size_t pitch,
                                            int where) {
-    if (!fe || !imgs || nimg < 1 || nimg > fe->B || pitch < (size_t)fe->p.width ||
+    if (!fe || !imgs || nimg < 1 || nimg > fe->B || pitch < vslam_row_bytes(fe) ||
         (where != VSLAM_IMGS_PINNED && where != VSLAM_IMGS_HOST)) {
         g_err = "invalid arguments";
         return VSLAM_ERR_INVALID;
@@ -1281,7 +1323,7 @@ extern "C" int vslam_fe_stage_images_async(vslam_fe* fe, int nimg, const uint8_t
         int rc = stage_host_images(fe, nimg, imgs, pitch);
         if (rc) return rc;
     }
-    int rc2 = ensure_stage(fe, where == VSLAM_IMGS_PINNED ? pitch : (size_t)fe->geom.lv[0].pitch, nimg);
+    int rc2 = ensure_stage(fe, where == VSLAM_IMGS_PINNED ? pitch : host_stage_pitch(fe), nimg);
     if (rc2) return rc2;
     /* (Tried in round 2 and removed: the DMA copy on an upload stream of its own, issued passes ahead of its use.  One
      * upload stream serialises copies that otherwise overlap on several DMA engines -- 77-86 k against 85-103 k mono
@@ -1289,6 +1331,47 @@ extern "C" int vslam_fe_stage_images_async(vslam_fe* fe, int nimg, const uint8_t
     rc2 = upload_host_rows(fe, nimg, imgs, pitch, where);
     if (rc2) return rc2;
     HIPCHK(hipGetLastError());
+    return VSLAM_OK;
+}
+
+/* The pixel format of every image entry (cv::cvtColor in front of the three GrabImage* callers).  The captured graph holds
+ * the upload kernel of the format it was captured with: dropped.  Staging for the wider rows is allocated here, outside
+ * any capture: the pinned rows of pageable images, and the DMA route's device buffer for dense rows (ensure_stage grows it
+ * for a wider pitch before a pass is captured, as it does for gray). */
+extern "C" int vslam_fe_set_pixel_format(vslam_fe* fe, int fmt, int gray_shift) {
+    if (!fe || fmt < VSLAM_PIX_GRAY8 || fmt > VSLAM_PIX_BGRA8 || (gray_shift != 0 && gray_shift != 14 && gray_shift != 15)) {
+        g_err = "invalid pixel format or gray shift (0, 14 or 15)";
+        return VSLAM_ERR_INVALID;
+    }
+    HIPCHK(hipSetDevice(fe->p.device));
+    if (fe->stream) HIPCHK(hipStreamSynchronize(fe->stream)); /* a pass in flight may still read the staging */
+    if (fe->graph_exec) {
+        (void)hipGraphExecDestroy(fe->graph_exec);
+        fe->graph_exec = nullptr;
+        fe->graph_key = 0;
+    }
+    fe->pix_fmt = fmt;
+    fe->gray_shift = gray_shift ? gray_shift : 15;
+    const size_t want = host_stage_stride(fe) * fe->B;
+    if (fe->h_img && (fmt == VSLAM_PIX_GRAY8 || fe->h_img_bytes < want)) { /* gray allocates its own on first use, as ever */
+        HIPCHK(hipHostFree(fe->h_img));
+        fe->h_img = nullptr;
+        fe->h_img_bytes = 0;
+    }
+    if (fmt != VSLAM_PIX_GRAY8) {
+        if (!fe->h_img) {
+            HIPCHK((hipError_t)vslam_pinned_alloc((void**)&fe->h_img, want));
+            fe->h_img_bytes = want;
+        }
+        return ensure_stage(fe, vslam_row_bytes(fe), fe->B);
+    }
+    return VSLAM_OK;
+}
+
+extern "C" int vslam_fe_get_pixel_format(const vslam_fe* fe, int* fmt, int* gray_shift) {
+    if (!fe) return VSLAM_ERR_INVALID;
+    if (fmt) *fmt = fe->pix_fmt;
+    if (gray_shift) *gray_shift = fe->gray_shift;
     return VSLAM_OK;
 }
 

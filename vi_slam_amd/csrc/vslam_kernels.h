@@ -97,6 +97,12 @@ void vk_undistort_xy(hipStream_t st, const float* xy, int n, float* out, const U
 /* host (pinned) images -> level 0 of the slots, one launch; src.l0 / src.pitch0 describe the host rows */
 void vk_pull_images(hipStream_t st, const BatchSrc& src, uint8_t* pyr, size_t slot_stride, uint32_t off0, int dpitch,
                     int w, int h, int nimg, int from_host, const vslam_tuning& T);
+/* interleaved colour rows (fmt = VSLAM_PIX_*, not GRAY8; shift 14 | 15) -> gray level 0 of the slots, in vk_pull_images' place */
+void vk_gray_images(hipStream_t st, const BatchSrc& src, uint8_t* pyr, size_t slot_stride, uint32_t off0, int dpitch, int w,
+                    int h, int nimg, int from_host, int fmt, int shift, const vslam_tuning& T);
+/* Frame::ComputeStereoFromRGBD for every keypoint of slots 0..nimg-1: u_right / depth are nimg x cap floats */
+void vk_rgbd_depth(hipStream_t st, const vslam_kp* kps, const vslam_kp* ukps, const int32_t* counts, int cap, int nimg,
+                   const RgbdDepthSrc& D, float* u_right, float* depth);
 void vk_pack_slots(hipStream_t st, const vslam_kp* kps, const uint8_t* desc, const int32_t* counts, int cap, int first,
                    int nslots, uint8_t* dst, size_t slot_bytes);
 void vk_gather_rows32(hipStream_t st, const uint8_t* src, const int32_t* idx, int n, uint8_t* dst);

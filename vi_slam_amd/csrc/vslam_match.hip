@@ -34,6 +34,30 @@ static int stereo_scratch(vslam_fe* fe, int njobs, int capR, StereoScratch* s) {
     return VSLAM_OK;
 }
 
+/* mvuRight | mvDepth of npairs pairs (uRight, then depth, npairs x cap floats each) to the host, enqueued on fe's stream */
+static int send_stereo_outputs(vslam_fe* fe, int npairs, const float* uRight, bool in_block) {
+    const size_t n = (size_t)npairs * fe->cap;
+    fe->h_stereo_cur = in_block ? (float*)(fe->h_res + fe->res_feat_bytes) : fe->h_stereo;
+    if (in_block && fe->deliver_deferred) {
+        /* the extraction of this call left its delivery to us (want_host = 2): counts | keypoints | descriptors | mvuRight |
+         * mvDepth are contiguous -> ONE transfer for the whole stereo step */
+        fe->deliver_deferred = false;
+        const int rc = vslam_deliver_block(fe, n * 8);
+        if (rc) return rc;
+    } else {
+        CopyRanges R;
+        memset(&R, 0, sizeof(R));
+        R.dst[0] = fe->h_stereo_cur;
+        R.src[0] = uRight; /* uRight | depth */
+        R.bytes[0] = n * 8;
+        R.n = 1;
+        vslam_count_delivery(fe, vk_copy_ranges(fe->stream, R, fe->tune), R);
+        HIPCHK(hipGetLastError());
+    }
+    fe->stereo_pairs = npairs;
+    return VSLAM_OK;
+}
+
 /* enqueue the matcher kernels and the D2H of mvuRight/mvDepth (whole capacity: the keypoint counts may
  * not be known on the host yet); nothing waits */
 static int enqueue_stereo(vslam_fe* feL, vslam_fe* feR, int npairs, const int* slotsL, const int* slotsR,
@@ -62,6 +86,7 @@ static int enqueue_stereo(vslam_fe* feL, vslam_fe* feR, int npairs, const int* s
         jb.slotR = sR;
     }
     if (feL != feR) HIPCHK(vslam_stream_wait(feR->stream)); /* right results must be complete */
+    feL->last_rgbd = false; /* the stereo outputs of feL are the matcher's from here on */
     StereoScratch sc;
     int rc = stereo_scratch(feL, npairs, feR->cap, &sc);
     feL->stereo_capR = feR->cap;
@@ -79,24 +104,7 @@ static int enqueue_stereo(vslam_fe* feL, vslam_fe* feR, int npairs, const int* s
     vk_stereo(st, jobs, npairs, feL->cap, feR->cap, feL->geom, feL->d_pyr, feL->slot_stride, feL->src, feR->d_pyr,
               feR->slot_stride, feR->src, bf, maxD, sc.best, sc.uRight, sc.depth, sc.sad, feL->cap, sc.max_band, sc.rows);
     HIPCHK(hipGetLastError());
-    const size_t n = (size_t)npairs * feL->cap;
-    feL->h_stereo_cur = in_block ? (float*)(feL->h_res + feL->res_feat_bytes) : feL->h_stereo;
-    if (in_block && feL->deliver_deferred) {
-        /* the extraction of this call left its delivery to us (want_host = 2): counts | keypoints | descriptors | mvuRight |
-         * mvDepth are contiguous -> ONE transfer for the whole stereo step */
-        feL->deliver_deferred = false;
-        if ((rc = vslam_deliver_block(feL, n * 8))) return rc;
-    } else {
-        CopyRanges R;
-        memset(&R, 0, sizeof(R));
-        R.dst[0] = feL->h_stereo_cur;
-        R.src[0] = sc.uRight; /* uRight | depth */
-        R.bytes[0] = n * 8;
-        R.n = 1;
-        vslam_count_delivery(feL, vk_copy_ranges(st, R, feL->tune), R);
-        HIPCHK(hipGetLastError());
-    }
-    feL->stereo_pairs = npairs;
+    if ((rc = send_stereo_outputs(feL, npairs, sc.uRight, in_block))) return rc;
     for (int j = 0; j < npairs; j++) feL->stereo_slotL[j] = slotsL[j];
     return VSLAM_OK;
 }
@@ -138,7 +146,7 @@ extern "C" int vslam_stereo_match(vslam_fe* feL, int sL, vslam_fe* feR, int sR, 
 extern "C" int vslam_frame_stereo_batch_async(vslam_fe* fe, int npairs, const uint8_t* const* imgs, size_t pitch,
                                               int imgs_on_device, float bf, float fx, int want_host) {
     if (!fe || npairs < 1 || npairs > VSLAM_MAX_STEREO_JOBS || 2 * npairs > fe->B ||
-        (imgs_on_device != VSLAM_IMGS_STAGED && (!imgs || pitch < (size_t)fe->p.width)) || imgs_on_device < 0 ||
+        (imgs_on_device != VSLAM_IMGS_STAGED && (!imgs || pitch < vslam_row_bytes(fe))) || imgs_on_device < 0 ||
         imgs_on_device > VSLAM_IMGS_STAGED) {
         g_err = "invalid arguments";
         return VSLAM_ERR_INVALID;
@@ -179,6 +187,126 @@ extern "C" int vslam_frame_stereo_wait(vslam_fe* fe, vslam_kp* const* kps, uint8
     rc = vslam_deliver(fe, fe->last_nimg, kps, desc, cap, n, nullptr);
     if (rc != VSLAM_OK) return rc;
     deliver_stereo(fe, u_right, depth);
+    return VSLAM_OK;
+}
+
+/* The extraction + depth section of Frame::Frame(imGray, imDepth, ...) (frame.cpp:185-257) for nframes frames in one enqueue:
+ * slot j = frame j.  The extraction may replay the context's captured graph; Frame::ComputeStereoFromRGBD (k_rgbd_depth) is
+ * always a plain launch behind it, with this call's depth pointers and parameters as its arguments, so a replay can never
+ * read the depth images of an earlier call.  mvuRight / mvDepth take the stereo matcher's place: "pair j" = slot j. */
+extern "C" int vslam_frame_rgbd_batch_async(vslam_fe* fe, int nframes, const uint8_t* const* imgs, size_t pitch, int imgs_where,
+                                            const void* const* depth, size_t depth_pitch, int depth_type, int depth_where,
+                                            float depth_map_factor, float bf, int want_host) {
+    if (!fe || nframes < 1 || nframes > fe->B || imgs_where < 0 || imgs_where > VSLAM_IMGS_STAGED ||
+        (imgs_where != VSLAM_IMGS_STAGED && (!imgs || pitch < vslam_row_bytes(fe))) || !depth ||
+        (depth_type != VSLAM_DEPTH_U16 && depth_type != VSLAM_DEPTH_F32) ||
+        (depth_where != VSLAM_IMGS_HOST && depth_where != VSLAM_IMGS_DEVICE && depth_where != VSLAM_IMGS_PINNED) ||
+        depth_pitch < (size_t)fe->p.width * (depth_type == VSLAM_DEPTH_F32 ? 4 : 2) || depth_pitch > 0xFFFFFFFFu ||
+        (depth_pitch & (depth_type == VSLAM_DEPTH_F32 ? 3 : 1)) || !std::isfinite(depth_map_factor) || !std::isfinite(bf)) {
+        g_err = "invalid arguments";
+        return VSLAM_ERR_INVALID;
+    }
+    const size_t esize = depth_type == VSLAM_DEPTH_F32 ? 4 : 2;
+    for (int j = 0; j < nframes; j++)
+        if (!depth[j] || ((uintptr_t)depth[j] & (esize - 1)) || (imgs_where != VSLAM_IMGS_STAGED && !imgs[j])) {
+            g_err = "null or misaligned image";
+            return VSLAM_ERR_INVALID;
+        }
+    HIPCHK(hipSetDevice(fe->p.device));
+    RgbdDepthSrc D;
+    memset(&D, 0, sizeof(D));
+    D.pitch = (uint32_t)depth_pitch;
+    D.type = depth_type;
+    D.w = fe->p.width;
+    D.h = fe->p.height;
+    /* the conversion rule of tracking.cpp:1305-1306: every image that is not float is converted, a float image only when the
+     * factor is further than 1e-5 from 1 (a float difference, compared as a double) */
+    D.scale = (std::fabs((double)(depth_map_factor - 1.0f)) > 1e-5 || depth_type != VSLAM_DEPTH_F32) ? 1 : 0;
+    D.factor = depth_map_factor;
+    D.bf = bf;
+    if (depth_where == VSLAM_IMGS_HOST) { /* pageable: dense rows into pinned staging, which the kernel reads in place */
+        const size_t rowb = (size_t)fe->p.width * esize, one = (rowb * fe->p.height + 255) & ~(size_t)255;
+        HIPCHK(vslam_stream_wait(fe->stream)); /* the previous pass's gather may still read the staging */
+        int rc = vslam_ensure_pinned(&fe->h_depth, &fe->h_depth_bytes, one * fe->B);
+        if (rc) return rc;
+        fe->pool->parallel_for(nframes, [&](int j) {
+            uint8_t* hd = fe->h_depth + one * j;
+            if (depth_pitch == rowb) memcpy(hd, depth[j], rowb * fe->p.height);
+            else
+                for (int y = 0; y < fe->p.height; y++) memcpy(hd + (size_t)y * rowb, (const uint8_t*)depth[j] + (size_t)y * depth_pitch, rowb);
+        });
+        for (int j = 0; j < nframes; j++) D.img[j] = fe->h_depth + one * j;
+        D.pitch = (uint32_t)rowb;
+    } else
+        for (int j = 0; j < nframes; j++) D.img[j] = depth[j];
+    /* full batches whose results go to the host: mvuRight | mvDepth behind the extraction's results, one transfer (as the
+     * stereo frame entry does it) */
+    const bool blk = want_host && nframes == fe->B && fe->res_init_bytes >= (size_t)nframes * fe->cap * 8 &&
+                     fe->block_region_owner != VSLAM_REGION_INIT && fe->d_res;
+    if (blk) fe->block_region_owner = VSLAM_REGION_STEREO;
+    /* the stereo matcher's scratch, row table included although no RGB-D pass reads it: vslam_stereo_points_* carve the
+     * buffer again with (stereo_pairs, stereo_capR) and must find it large enough, or they would move it.  Outside any capture. */
+    StereoScratch sc;
+    int rc = stereo_scratch(fe, nframes, fe->cap, &sc);
+    if (rc) return rc;
+    fe->stereo_capR = fe->cap;
+    rc = vslam_enqueue_extract(fe, nframes, imgs, pitch, imgs_where, 0, 0, blk ? 2 : (want_host != 0));
+    const bool prof = rc == VSLAM_OK && fe->profiling;
+    if (prof && !fe->ev_rgbd[0])
+        for (int i = 0; i < 2 && rc == VSLAM_OK; i++)
+            if (hipEventCreate(&fe->ev_rgbd[i]) != hipSuccess) rc = VSLAM_ERR_HIP;
+    if (rc == VSLAM_OK) {
+        if (blk) {
+            sc.uRight = (float*)(fe->d_res + fe->res_feat_bytes);
+            sc.depth = sc.uRight + (size_t)nframes * fe->cap;
+        }
+        fe->d_stereo_u = sc.uRight;
+        fe->d_stereo_depth = sc.depth;
+        const vslam_kp* ukps = fe->d_kps; /* ukeypoints_ = keypoints_ without a camera or with k1 == 0 */
+        if (fe->has_cam && vslam_fe_slot_ukps(fe, 0, &ukps) != VSLAM_OK) ukps = fe->d_kps;
+        if (prof) (void)hipEventRecord(fe->ev_rgbd[0], fe->stream);
+        vk_rgbd_depth(fe->stream, fe->d_kps, ukps, fe->d_counts, fe->cap, nframes, D, sc.uRight, sc.depth);
+        if (prof) (void)hipEventRecord(fe->ev_rgbd[1], fe->stream);
+        fe->rgbd_timed = prof;
+        if (hipGetLastError() != hipSuccess) {
+            g_err = "k_rgbd_depth launch failed";
+            rc = VSLAM_ERR_HIP;
+        }
+    }
+    if (rc == VSLAM_OK) rc = send_stereo_outputs(fe, nframes, sc.uRight, blk);
+    if (rc == VSLAM_OK)
+        for (int j = 0; j < nframes; j++) fe->stereo_slotL[j] = j;
+    fe->last_rgbd = rc == VSLAM_OK; /* vslam_enqueue_extract cleared it */
+    if (rc != VSLAM_OK) hipStreamSynchronize(fe->stream);
+    return rc;
+}
+
+extern "C" int vslam_frame_rgbd_wait(vslam_fe* fe, vslam_kp* const* kps, uint8_t* const* desc, int cap, int* n,
+                                     float* const* u_right, float* const* depth) {
+    if (!fe || !fe->last_rgbd || fe->last_nimg < 1) {
+        g_err = "no RGB-D pass enqueued";
+        return VSLAM_ERR_INVALID;
+    }
+    int rc = vslam_finish_extract(fe, fe->last_nimg);
+    if (rc != VSLAM_OK) return rc;
+    if (fe->rgbd_timed) { /* vslam_fe_set_profiling: the depth gather's own span */
+        float ms = 0.0f;
+        HIPCHK(hipEventElapsedTime(&ms, fe->ev_rgbd[0], fe->ev_rgbd[1]));
+        fe->rgbd_ms += ms;
+        fe->rgbd_passes++;
+        fe->rgbd_timed = false;
+    }
+    rc = vslam_deliver(fe, fe->last_nimg, kps, desc, cap, n, nullptr);
+    if (rc != VSLAM_OK) return rc;
+    deliver_stereo(fe, u_right, depth);
+    return VSLAM_OK;
+}
+
+/* with vslam_fe_set_profiling on: HIP-event time of k_rgbd_depth alone, summed over the RGB-D passes waited for since */
+extern "C" int vslam_fe_get_rgbd_profile(vslam_fe* fe, double* depth_ms, long* passes) {
+    if (!fe) return VSLAM_ERR_INVALID;
+    if (depth_ms) *depth_ms = fe->rgbd_ms;
+    if (passes) *passes = fe->rgbd_passes;
     return VSLAM_OK;
 }
 

@@ -622,6 +622,144 @@ void vk_pull_images(hipStream_t st, const BatchSrc& src, uint8_t* pyr, size_t sl
     else hipLaunchKernelGGL(k_pull_images<1>, grid, dim3(256), 0, st, src, pyr, slot_stride, off0, dpitch, w, h);
 }
 
+/* Interleaved colour rows -> gray level 0 of the slots (vslam_fe_set_pixel_format): k_pull_images' shape -- the same small
+ * fixed grid, a lane owns one 16-byte chunk of a destination row -- with cv::cvtColor's 8-bit RGB2Gray between the loads and
+ * the store:  gray = (R * cr + G * cg + B * cb + (1 << (shift - 1))) >> shift, alpha ignored.  A lane issues the 16 * BPP
+ * source bytes of its 16 pixels as BPP unaligned 16-byte loads (rows may start at any address) and writes one aligned
+ * 16-byte store.  A pixel's bytes are brought into one dword (4-byte formats: they are one; 3-byte formats: one
+ * v_alignbyte_b32 over two neighbouring dwords) and multiplied by two v_dot4_u32_u8, against the low and the high bytes of
+ * the 16-bit coefficients (the fourth byte's coefficient is 0: alpha, or the next pixel's first channel): 2 dot + 1
+ * shift-add + 1 shift per pixel against 3 byte extracts + 3 v_mad_u32_u24 + 1 shift.  The sum is below 2^24
+ * (255 * 32768 + 16384).  ITEMS chunks per lane are in flight, so ITEMS * BPP loads: the launcher divides pull_depth by 4.
+ * Only the last partial chunk of the image's LAST row is read bytewise: nothing past row h-1's w * BPP bytes is touched
+ * (other rows' last chunks may run into the next row, which pitch >= w * BPP and w >= 40 make part of the image). */
+struct GrayCoef {
+    uint32_t lo, hi; /* byte k = low / high byte of the coefficient of a pixel's byte k */
+    uint32_t round, shift;
+};
+
+template <int BPP>
+__device__ __forceinline__ uint32_t gray_px(const uint32_t* q, int k, const GrayCoef c) {
+    uint32_t px;
+    if (BPP == 4) px = q[k];
+    else {
+        const int b = 3 * k; /* byte offset of pixel k in the lane's 48 bytes; k < 16 is a compile-time constant */
+        px = (b & 3) == 0 ? q[b >> 2] : __builtin_amdgcn_alignbyte(q[(b >> 2) + 1], q[b >> 2], (uint32_t)(b & 3));
+    }
+    const uint32_t lo = __builtin_amdgcn_udot4(px, c.lo, c.round, false);
+    const uint32_t hi = __builtin_amdgcn_udot4(px, c.hi, 0u, false);
+    return ((hi << 8) + lo) >> c.shift;
+}
+
+template <int ITEMS, int BPP>
+__global__ void __launch_bounds__(256)
+k_gray_images(BatchSrc src, uint8_t* pyr, size_t slot_stride, uint32_t off0, int dpitch, int w, int h, GrayCoef coef) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int slot = blockIdx.y;
+    const uint8_t* simg = src.l0[slot];
+    const size_t spitch = src.pitch0[slot];
+    uint8_t* dimg = pyr + (size_t)slot * slot_stride + off0;
+    const int nch = (w + 15) >> 4; /* 16-pixel chunks per row */
+    const int nitems = h * nch;
+    const int total_waves = (int)gridDim.x * 4, wid = blockIdx.x * 4 + wave;
+    for (int i0 = wid * 64 * ITEMS; i0 < nitems; i0 += total_waves * 64 * ITEMS) {
+        uint32_t v[ITEMS][4 * BPP + 1]; /* + 1: the dword the last 3-byte pixel's alignbyte may name (never selected) */
+#pragma unroll
+        for (int u = 0; u < ITEMS; u++) {
+            const int i = i0 + u * 64 + lane;
+#pragma unroll
+            for (int k = 0; k <= 4 * BPP; k++) v[u][k] = 0;
+            if (i < nitems) {
+                const int y = i / nch, ch = i - y * nch;
+                const uint8_t* p = simg + (size_t)y * spitch + (size_t)(16 * BPP) * ch;
+                if (16 * ch + 16 <= w || y < h - 1) {
+#pragma unroll
+                    for (int k = 0; k < BPP; k++) {
+                        const uint4 t = *(const uint4*)(p + 16 * k);
+                        v[u][4 * k] = t.x; v[u][4 * k + 1] = t.y; v[u][4 * k + 2] = t.z; v[u][4 * k + 3] = t.w;
+                    }
+                } else {
+                    const int nb = (w - 16 * ch) * BPP; /* bytes of the row's last pixels */
+#pragma unroll
+                    for (int k = 0; k < 4 * BPP; k++) /* constant indices: v stays in registers */
+#pragma unroll
+                        for (int b = 0; b < 4; b++)
+                            if (4 * k + b < nb) v[u][k] |= (uint32_t)p[4 * k + b] << (8 * b);
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < ITEMS; u++) {
+            const int i = i0 + u * 64 + lane;
+            if (i < nitems) {
+                const int y = i / nch, ch = i - y * nch;
+                uint32_t o[4];
+#pragma unroll
+                for (int d = 0; d < 4; d++)
+                    o[d] = gray_px<BPP>(v[u], 4 * d, coef) | (gray_px<BPP>(v[u], 4 * d + 1, coef) << 8) |
+                           (gray_px<BPP>(v[u], 4 * d + 2, coef) << 16) | (gray_px<BPP>(v[u], 4 * d + 3, coef) << 24);
+                *(uint4*)(dimg + (size_t)y * dpitch + 16 * ch) = make_uint4(o[0], o[1], o[2], o[3]); /* padding may be written */
+            }
+        }
+    }
+}
+
+template <int BPP>
+static void launch_gray(hipStream_t st, dim3 grid, int items, const BatchSrc& src, uint8_t* pyr, size_t slot_stride,
+                        uint32_t off0, int dpitch, int w, int h, const GrayCoef& c) {
+    if (items >= 2) hipLaunchKernelGGL((k_gray_images<2, BPP>), grid, dim3(256), 0, st, src, pyr, slot_stride, off0, dpitch, w, h, c);
+    else hipLaunchKernelGGL((k_gray_images<1, BPP>), grid, dim3(256), 0, st, src, pyr, slot_stride, off0, dpitch, w, h, c);
+}
+
+void vk_gray_images(hipStream_t st, const BatchSrc& src, uint8_t* pyr, size_t slot_stride, uint32_t off0, int dpitch, int w,
+                    int h, int nimg, int from_host, int fmt, int shift, const vslam_tuning& T) {
+    /* grid and loads in flight as vk_pull_images chooses them; a chunk is 3 or 4 loads, so a quarter as many chunks */
+    const int depth_host = tune_or(T.pull_depth, 0);
+    const dim3 grid(nimg <= 2 ? 32 : PULL_WG_PER_IMG, nimg);
+    const int depth = !from_host ? 8 : depth_host ? depth_host : nimg <= 2 ? 8 : 1;
+    const uint32_t cr = shift == 14 ? 4899u : 9798u, cg = shift == 14 ? 9617u : 19235u, cb = shift == 14 ? 1868u : 3735u;
+    const bool rgb = fmt == VSLAM_PIX_RGB8 || fmt == VSLAM_PIX_RGBA8;
+    const uint32_t c0 = rgb ? cr : cb, c2 = rgb ? cb : cr; /* coefficients of a pixel's bytes 0, 1, 2 */
+    GrayCoef c;
+    c.lo = (c0 & 255u) | ((cg & 255u) << 8) | ((c2 & 255u) << 16);
+    c.hi = (c0 >> 8) | ((cg >> 8) << 8) | ((c2 >> 8) << 16);
+    c.round = 1u << (shift - 1);
+    c.shift = (uint32_t)shift;
+    if (fmt == VSLAM_PIX_RGB8 || fmt == VSLAM_PIX_BGR8) launch_gray<3>(st, grid, depth / 4, src, pyr, slot_stride, off0, dpitch, w, h, c);
+    else launch_gray<4>(st, grid, depth / 4, src, pyr, slot_stride, off0, dpitch, w, h, c);
+}
+
+/* Frame::ComputeStereoFromRGBD (frame.cpp:1000-1021) behind the extraction of an RGB-D pass: one lane per keypoint slot
+ * position over all slots, counts read from HBM (k_undistort_kps' shape).  The depth images are read in place -- HBM or
+ * pinned host memory, one sample per keypoint -- after Tracking::GrabImageRGBD's conversion rule (tracking.cpp:1305-1306;
+ * cv::Mat::convertTo to CV_32F with a zero offset is one float multiplication, as fma(x, a, 0) rounds).  kps are keypoints_
+ * (they index the depth image, truncated toward zero as cv::Mat::at<float>(float, float) does), ukps ukeypoints_. */
+__global__ void __launch_bounds__(256)
+k_rgbd_depth(const vslam_kp* __restrict__ kps, const vslam_kp* __restrict__ ukps, const int32_t* __restrict__ counts, int cap,
+             RgbdDepthSrc D, float* __restrict__ u_right, float* __restrict__ depth) {
+    const int s = blockIdx.y;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int n = min(counts[s * 4], cap);
+    if (i >= n) return;
+    const size_t at = (size_t)s * cap + i;
+    const int u = (int)kps[at].x, v = (int)kps[at].y;
+    float d = -1.0f;
+    if (u >= 0 && u < D.w && v >= 0 && v < D.h) {
+        const uint8_t* row = (const uint8_t*)D.img[s] + (size_t)v * D.pitch;
+        d = D.type == VSLAM_DEPTH_F32 ? ((const float*)row)[u] : (float)((const uint16_t*)row)[u];
+        if (D.scale) d = __fmul_rn(d, D.factor);
+    }
+    const bool ok = d > 0.0f; /* false for NaN */
+    depth[at] = ok ? d : -1.0f;
+    u_right[at] = ok ? __fsub_rn(ukps[at].x, __fdiv_rn(D.bf, d)) : -1.0f;
+}
+
+void vk_rgbd_depth(hipStream_t st, const vslam_kp* kps, const vslam_kp* ukps, const int32_t* counts, int cap, int nimg,
+                   const RgbdDepthSrc& D, float* u_right, float* depth) {
+    if (nimg <= 0 || cap <= 0) return;
+    hipLaunchKernelGGL(k_rgbd_depth, dim3((cap + 255) / 256, nimg), dim3(256), 0, st, kps, ukps, counts, cap, D, u_right, depth);
+}
+
 /* zero the (total, overflow) header of every slot's candidate buffer and the quadtree's 16-byte error word */
 __global__ void k_reset_headers(uint8_t* d_cand, size_t stride, int nimg, int32_t* d_err) {
     const int t = threadIdx.x;
