@@ -692,6 +692,83 @@ int vslam_bow_assemble(int weighting, int norm, const int32_t* word_id, const do
                        int n, int32_t* bow_ids, double* bow_vals, int* n_bow, int32_t* fv_nodes, int32_t* fv_off,
                        int32_t* fv_feat, int* n_fv);
 
+/* ---------------------------------------------------------------- KeyFrameDatabase (relocalisation / loop candidates)
+ *
+ * KeyFrameDatabase (src/datastructures/keyframedatabase.cpp) between Frame::ComputeBoW and SearchByBoW: the keyframes'
+ * BowVectors live in HBM, and one kernel computes for every (query, keyframe) pair what the reference's walk over its
+ * inverted file and DBoW3's L1Scoring::score (thirdparty/DBoW3/DBoW3/src/ScoringObject.cpp:23-68) compute: the number
+ * of common words, the smallest common word and the score, whose terms are added in ascending word order into one
+ * double exactly as the reference adds them.  Keyframes and maps are named by ids (KeyFrame::mnId, Map::GetId()).
+ *
+ * scoring is DBoW3's ScoringType as vslam_voc_file_info reports it; only 0 (L1_NORM) is implemented, anything else
+ * returns VSLAM_ERR_UNSUPPORTED.  The pool holds 4096 (id, value) entries at first (vslam_kfdb_create_ex: the number
+ * given, 0 = that default), doubles when an add does not fit, and is compacted -- the erased keyframes' entries and
+ * slots dropped, the order of the rest kept -- whenever the erased entries exceed half of those handed out.
+ *
+ * add (keyframedatabase.cpp:21-27): bow_ids / bow_vals are a BowVector as vslam_bow_assemble produces it: n strictly
+ * ascending word ids in [0, n_words) and their values.  n = 0 is legal; such a keyframe is never found.  A kf_id that
+ * is in the database, ids out of order or out of range return VSLAM_ERR_INVALID and change nothing.  A keyframe's
+ * place in `add` order is its place in every inverted list of the reference (push_back); an id erased and added again
+ * goes last.  erase (:29-48; an unknown id is not an error, as there), clear (:50-54), clear_map (:56-80).
+ * size: live keyframes and their entries.  stats: pool capacity and entries handed out, slots (live and erased, not
+ * compacted away yet), and how often the pool grew / was compacted.  All of these wait for a query still in flight.
+ * A database is not re-entrant across queries: one query (of up to 32 BowVectors) is in flight or delivered at a time.
+ *
+ * query_async: nq (1..32) host BowVectors, staged through pinned memory of `fe` and enqueued on its stream.  query_wait
+ * delivers query q of the last query_async on (db, fe) -- any number of times, in any order, until the next
+ * query_async -- as the hit list: every live keyframe sharing at least one word, in the order in which the reference's
+ * walk over the query's words first meets it (smallest common word, then add order), i.e. lKFsSharingWords before any
+ * exclusion; per hit the keyframe's id and map, words = mnRelocWords / mnPlaceRecognitionWords, score =
+ * L1Scoring::score(query, keyframe) and si = (float)score.  Any output array may be NULL; *n_hits is always set, and
+ * VSLAM_ERR_CAPACITY returned when it exceeds cap (nothing is written then).  `fe` must outlive the wait.  The hit
+ * list is ordered and compacted on the host from a dense per-slot result. */
+typedef struct vslam_kfdb vslam_kfdb;
+int vslam_kfdb_create(int device, int n_words, int scoring, vslam_kfdb** out);
+int vslam_kfdb_create_ex(int device, int n_words, int scoring, int initial_entries, vslam_kfdb** out);
+void vslam_kfdb_destroy(vslam_kfdb* db);
+int vslam_kfdb_add(vslam_kfdb* db, int64_t kf_id, int32_t map_id, const int32_t* bow_ids, const double* bow_vals, int n);
+int vslam_kfdb_erase(vslam_kfdb* db, int64_t kf_id);
+int vslam_kfdb_clear(vslam_kfdb* db);
+int vslam_kfdb_clear_map(vslam_kfdb* db, int32_t map_id);
+int vslam_kfdb_size(vslam_kfdb* db, int* n_keyframes, long long* n_entries);
+int vslam_kfdb_stats(vslam_kfdb* db, long long* capacity, long long* used, int* n_slots, int* n_growths,
+                     int* n_compactions);
+int vslam_kfdb_query_async(vslam_kfdb* db, vslam_fe* fe, int nq, const int32_t* const* bow_ids,
+                           const double* const* bow_vals, const int* n);
+int vslam_kfdb_query_wait(vslam_kfdb* db, vslam_fe* fe, int q, int cap, int64_t* hit_kf, int32_t* hit_map,
+                          int32_t* hit_words, float* hit_si, double* hit_score, int* n_hits);
+
+/* The selection stage: KeyFrameDatabase::DetectRelocalizationCandidates (keyframedatabase.cpp:707-811) and
+ * DetectNBestCandidates (:579-705) from the hit list on.  Pure host code without a database handle (libvslam_host.so
+ * has them too); they return 0, -1 for invalid arguments or -4 when `cap` is too small (*n_out = the number needed).
+ *   hits          hit_kf / hit_map / hit_words / hit_si of vslam_kfdb_query_wait, in its order
+ *   score_io      n_hits floats: what the reference keeps in the KeyFrames (mRelocScore / mPlaceRecognitionScore).  In:
+ *                 the caller's last value for each hit; out: replaced by si for the hits this query scored (words >
+ *                 minCommonWords = (int)(maxCommonWords * 0.8f)).  The covisibility step reads it for neighbours that
+ *                 were not scored, as the reference reads the stale member.
+ *   neighbours_fn pKFi->GetBestCovisibilityKeyFrames(10): writes at most 10 ids, returns how many.  A neighbour that
+ *                 is not a (non-excluded) hit is skipped, as the query stamp does in the reference.  NULL: no neighbours.
+ *   relocalization: out_kf = vpRelocCandidates -- accScore > 0.75f * bestAccScore, pBestKF in map_id, first occurrence.
+ *   nbest         connected_ids = pKF->GetConnectedKeyFrames(): such hits are neither listed nor seen by the
+ *                 neighbour step (:597-606).  n_candidates = nNumCandidates (3 at loopclosing.cpp:415); loop_kf and
+ *                 merge_kf hold n_candidates ids each; bad_maps = ids of maps with IsBad().  The fill loop is :684-704:
+ *                 a keyframe enters spAlreadyAddedKF even when neither vector took it.
+ * Deviations from the reference: mRelocScore is uninitialised in its constructors (keyframe.cpp:20-38) -- callers start
+ * score_io at 0.0f, as mPlaceRecognitionScore starts; every query counts as carrying a fresh query id (the reference's
+ * callers guarantee it; the mn*Query(0) collision of a query with id 0 is not modelled); DetectNBestCandidates never
+ * ends on a bad keyframe (:687-688 `continue` without advancing) -- SetBadFlag erases bad keyframes from the database
+ * (keyframe.cpp:634), so PRECONDITION: no hit is a bad keyframe, and there is no bad flag to pass. */
+typedef int (*vslam_kfdb_neighbours_fn)(void* user, int64_t kf_id, int64_t* out_ids /* [10] */);
+int vslam_kfdb_select_relocalization(const int64_t* hit_kf, const int32_t* hit_map, const int32_t* hit_words,
+                                     const float* hit_si, int n_hits, float* score_io, int32_t map_id,
+                                     vslam_kfdb_neighbours_fn neighbours_fn, void* user, int64_t* out_kf, int cap,
+                                     int* n_out);
+int vslam_kfdb_select_nbest(const int64_t* hit_kf, const int32_t* hit_map, const int32_t* hit_words, const float* hit_si,
+                            int n_hits, float* score_io, int32_t query_map_id, const int64_t* connected_ids,
+                            int n_connected, int n_candidates, const int32_t* bad_maps, int n_bad_maps,
+                            vslam_kfdb_neighbours_fn neighbours_fn, void* user, int64_t* loop_kf, int* n_loop,
+                            int64_t* merge_kf, int* n_merge);
+
 /* FMatcher::SearchByBoW(KeyFrame* pKF, Frame& F, vector<MapPoint*>& vpMapPointMatches) (fmatcher.cpp:546-748,
  * pinhole frames).  FeatureVectors as produced by vslam_bow_assemble (ascending node ids, offsets, feature
  * indices); kf_flags[i] != 0 iff pKF's i-th keypoint has a MapPoint that is not bad; keypoints only contribute

@@ -20,6 +20,8 @@
 
 #include <cstdint>
 #include <cstring>
+#include <functional>
+#include <map>
 #include <stdexcept>
 #include <string>
 #include <memory>
@@ -639,6 +641,140 @@ public:
 private:
     std::unique_ptr<FASTGPU> det_;
     int w_ = 0, h_ = 0;
+};
+
+/* ---------------------------------------------------------------------------------------------------
+ * KeyFrameDatabase (src/datastructures/keyframedatabase.cpp) with the reference's method names over ids: a keyframe
+ * is KeyFrame::mnId, a map Map::GetId(), a BowVector two parallel vectors (ascending word ids, values) as
+ * vslam_bow_assemble produces them.  The class keeps what the reference keeps in the KeyFrame objects between
+ * queries (mRelocScore, mPlaceRecognitionScore; 0 until first scored).  Neighbours = GetBestCovisibilityKeyFrames(10)
+ * of a keyframe.  PRECONDITION of DetectNBestCandidates: bad keyframes have been erased (SetBadFlag does).
+ * ------------------------------------------------------------------------------------------------- */
+struct BowVector {
+    std::vector<int32_t> ids;
+    std::vector<double> values;
+};
+class KeyFrameDatabase {
+public:
+    typedef std::function<std::vector<long long>(long long)> Neighbours;
+
+    explicit KeyFrameDatabase(int n_words, int scoring = 0, int device = 0) { check(vslam_kfdb_create(device, n_words, scoring, &db_)); }
+    ~KeyFrameDatabase() { vslam_kfdb_destroy(db_); }
+    KeyFrameDatabase(const KeyFrameDatabase&) = delete;
+    KeyFrameDatabase& operator=(const KeyFrameDatabase&) = delete;
+
+    void add(long long kf_id, int map_id, const BowVector& v) {
+        check(vslam_kfdb_add(db_, kf_id, map_id, v.ids.data(), v.values.data(), (int)v.ids.size()));
+        maps_[kf_id] = map_id;
+    }
+    void erase(long long kf_id) {
+        check(vslam_kfdb_erase(db_, kf_id));
+        forget(kf_id);
+    }
+    void clear() {
+        check(vslam_kfdb_clear(db_));
+        maps_.clear();
+        reloc_.clear();
+        place_.clear();
+    }
+    void clearMap(int map_id) {
+        check(vslam_kfdb_clear_map(db_, map_id));
+        std::vector<long long> gone;
+        for (const auto& kv : maps_)
+            if (kv.second == map_id) gone.push_back(kv.first);
+        for (long long k : gone) forget(k);
+    }
+    int size() const {
+        int n = 0;
+        check(vslam_kfdb_size(db_, &n, nullptr));
+        return n;
+    }
+
+    /* tracking.cpp:3464 */
+    std::vector<long long> DetectRelocalizationCandidates(const FExtractor& extractor, const BowVector& F_mBowVec, int map_id,
+                                                          const Neighbours& neighbours) {
+        Hits h = query(extractor, F_mBowVec, reloc_);
+        std::vector<int64_t> out(h.kf.size() + 1);
+        int n = 0;
+        check_select(vslam_kfdb_select_relocalization(h.kf.data(), h.map.data(), h.words.data(), h.si.data(), (int)h.kf.size(),
+                                                      h.io.data(), map_id, &KeyFrameDatabase::neighbours_cb, (void*)&neighbours,
+                                                      out.data(), (int)out.size(), &n));
+        keep(h, reloc_);
+        return std::vector<long long>(out.begin(), out.begin() + n);
+    }
+    /* loopclosing.cpp:415 */
+    void DetectNBestCandidates(const FExtractor& extractor, const BowVector& pKF_mBowVec, int map_id,
+                               const std::vector<long long>& connected, std::vector<long long>& vpLoopCand,
+                               std::vector<long long>& vpMergeCand, int nNumCandidates, const Neighbours& neighbours,
+                               const std::vector<int32_t>& bad_maps = std::vector<int32_t>()) {
+        Hits h = query(extractor, pKF_mBowVec, place_);
+        const std::vector<int64_t> conn(connected.begin(), connected.end());
+        std::vector<int64_t> lo((size_t)nNumCandidates + 1), me((size_t)nNumCandidates + 1);
+        int nl = 0, nm = 0;
+        check_select(vslam_kfdb_select_nbest(h.kf.data(), h.map.data(), h.words.data(), h.si.data(), (int)h.kf.size(), h.io.data(),
+                                             map_id, conn.data(), (int)conn.size(), nNumCandidates, bad_maps.data(),
+                                             (int)bad_maps.size(), &KeyFrameDatabase::neighbours_cb, (void*)&neighbours, lo.data(),
+                                             &nl, me.data(), &nm));
+        keep(h, place_);
+        vpLoopCand.assign(lo.begin(), lo.begin() + nl);
+        vpMergeCand.assign(me.begin(), me.begin() + nm);
+    }
+
+private:
+    struct Hits {
+        std::vector<int64_t> kf;
+        std::vector<int32_t> map, words;
+        std::vector<float> si, io;
+    };
+    static vslam_fe* context_of(const FExtractor& extractor) {
+        if (!extractor.context()) throw std::runtime_error("KeyFrameDatabase: the extractor has not processed an image yet");
+        return extractor.context();
+    }
+    static void check_select(int rc) {
+        if (rc != 0) throw std::runtime_error("libvslam_fe: KeyFrameDatabase selection failed");
+    }
+    static int neighbours_cb(void* user, int64_t kf_id, int64_t* out) {
+        const std::vector<long long> v = (*(const Neighbours*)user)(kf_id);
+        const int n = v.size() < 10 ? (int)v.size() : 10;
+        for (int i = 0; i < n; i++) out[i] = v[i];
+        return n;
+    }
+    Hits query(const FExtractor& extractor, const BowVector& v, const std::map<long long, float>& stale) {
+        const int32_t* ids = v.ids.data();
+        const double* vals = v.values.data();
+        const int n = (int)v.ids.size();
+        check(vslam_kfdb_query_async(db_, context_of(extractor), 1, &ids, &vals, &n));
+        Hits h;
+        const size_t cap = maps_.size() + 1;
+        h.kf.resize(cap);
+        h.map.resize(cap);
+        h.words.resize(cap);
+        h.si.resize(cap);
+        int nh = 0;
+        check(vslam_kfdb_query_wait(db_, context_of(extractor), 0, (int)cap, h.kf.data(), h.map.data(), h.words.data(), h.si.data(),
+                                    nullptr, &nh));
+        h.kf.resize(nh);
+        h.map.resize(nh);
+        h.words.resize(nh);
+        h.si.resize(nh);
+        for (int i = 0; i < nh; i++) {
+            auto it = stale.find(h.kf[i]);
+            h.io.push_back(it == stale.end() ? 0.0f : it->second);
+        }
+        h.io.resize((size_t)nh + 1); /* never an empty array */
+        return h;
+    }
+    static void keep(const Hits& h, std::map<long long, float>& stale) {
+        for (size_t i = 0; i < h.kf.size(); i++) stale[h.kf[i]] = h.io[i];
+    }
+    void forget(long long k) {
+        maps_.erase(k);
+        reloc_.erase(k);
+        place_.erase(k);
+    }
+    vslam_kfdb* db_ = nullptr;
+    std::map<long long, int> maps_;
+    std::map<long long, float> reloc_, place_;
 };
 
 } /* namespace geometry */

@@ -58,6 +58,9 @@ ABI_SYMBOLS = [
     "vslam_search_for_initialization_ex", "vslam_search_for_initialization_batch_ex", "vslam_search_init_dev_async_ex",
     "vslam_fe_set_pixel_format", "vslam_fe_get_pixel_format", "vslam_frame_rgbd_batch_async", "vslam_frame_rgbd_wait",
     "vslam_fe_get_rgbd_profile",
+    "vslam_kfdb_create", "vslam_kfdb_create_ex", "vslam_kfdb_destroy", "vslam_kfdb_add", "vslam_kfdb_erase",
+    "vslam_kfdb_clear", "vslam_kfdb_clear_map", "vslam_kfdb_size", "vslam_kfdb_stats", "vslam_kfdb_query_async",
+    "vslam_kfdb_query_wait", "vslam_kfdb_select_relocalization", "vslam_kfdb_select_nbest",
 ]
 
 
@@ -192,6 +195,77 @@ def bind_voc_file(L):
     return L
 
 
+#: vslam_kfdb_neighbours_fn: int (*)(void* user, int64_t kf_id, int64_t out_ids[10])
+KFDB_NEIGHBOURS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64))
+
+
+def bind_kfdb_select(L):
+    """ctypes signatures of the KeyFrameDatabase selection stage (in libvslam_fe.so and in the GPU-free libvslam_host.so)"""
+    vp, i = C.c_void_p, C.c_int
+    L.vslam_kfdb_select_relocalization.argtypes = [vp, vp, vp, vp, i, vp, C.c_int32, KFDB_NEIGHBOURS_FN, vp, vp, i, vp]
+    L.vslam_kfdb_select_nbest.argtypes = [vp, vp, vp, vp, i, vp, C.c_int32, vp, i, i, vp, i, KFDB_NEIGHBOURS_FN, vp, vp,
+                                          vp, vp, vp]
+    return L
+
+
+_host_lib = None
+
+
+def host_lib():
+    """libvslam_host.so: the GPU-free host logic (selection stages, file readers)."""
+    global _host_lib
+    if _host_lib is None:
+        _host_lib = bind_kfdb_select(C.CDLL(HOST_LIB_PATH))
+    return _host_lib
+
+
+def _neighbours_cb(neighbours):
+    """dict {kf_id: [ids]} or callable kf_id -> ids  ->  vslam_kfdb_neighbours_fn (GetBestCovisibilityKeyFrames(10))"""
+    get = neighbours if callable(neighbours) else (lambda k: (neighbours or {}).get(k, ()))
+
+    def cb(_user, kf_id, out):
+        ids = list(get(int(kf_id)))[:10]
+        for k, v in enumerate(ids):
+            out[k] = int(v)
+        return len(ids)
+    return KFDB_NEIGHBOURS_FN(cb)
+
+
+def _hit_arrays(hits):
+    return (np.ascontiguousarray(hits["kf"], np.int64), np.ascontiguousarray(hits["map"], np.int32),
+            np.ascontiguousarray(hits["words"], np.int32), np.ascontiguousarray(hits["si"], np.float32))
+
+
+def kfdb_select_relocalization(hits, score_io, map_id, neighbours, library=None, cap=None):
+    """vslam_kfdb_select_relocalization (pure host): hits = dict(kf, map, words, si) in query order, score_io = float32
+    array of len(hits) updated in place -> list of candidate keyframe ids."""
+    L = library if library is not None else host_lib()
+    kf, mp, words, si = _hit_arrays(hits)
+    n = len(kf)
+    cap = n if cap is None else cap
+    out, n_out, cb = np.zeros(max(cap, 1), np.int64), C.c_int(), _neighbours_cb(neighbours)
+    rc = L.vslam_kfdb_select_relocalization(_p(kf), _p(mp), _p(words), _p(si), n, _p(score_io), map_id, cb, None,
+                                            _p(out), cap, C.byref(n_out))
+    if rc:
+        raise VslamError(rc, "vslam_kfdb_select_relocalization")
+    return [int(v) for v in out[:n_out.value]]
+
+
+def kfdb_select_nbest(hits, score_io, query_map_id, connected, neighbours, n=3, bad_maps=(), library=None):
+    """vslam_kfdb_select_nbest (pure host) -> (loop candidate ids, merge candidate ids)."""
+    L = library if library is not None else host_lib()
+    kf, mp, words, si = _hit_arrays(hits)
+    conn = np.ascontiguousarray(sorted(connected), np.int64)
+    bad = np.ascontiguousarray(list(bad_maps), np.int32)
+    lo, me = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64)
+    nl, nm, cb = C.c_int(), C.c_int(), _neighbours_cb(neighbours)
+    rc = L.vslam_kfdb_select_nbest(_p(kf), _p(mp), _p(words), _p(si), len(kf), _p(score_io), query_map_id, _p(conn),
+                                   len(conn), n, _p(bad), len(bad), cb, None, _p(lo), C.byref(nl), _p(me), C.byref(nm))
+    if rc:
+        raise VslamError(rc, "vslam_kfdb_select_nbest")
+    return [int(v) for v in lo[:nl.value]], [int(v) for v in me[:nm.value]]
+
+
 def qlz_decode(packet, library=None, cap=None):
     """vslam_dbg_qlz_decode: one QuickLZ level-1 packet -> (bytes, packet size); raises ValueError on a damaged packet."""
     L = library if library is not None else lib()
@@ -321,6 +395,20 @@ def lib():
         L.vslam_frame_rgbd_batch_async.argtypes = [vp, i, vp, C.c_size_t, i, vp, C.c_size_t, i, i, f, f, i]
         L.vslam_frame_rgbd_wait.argtypes = [vp, vp, vp, i, vp, vp, vp]
         L.vslam_fe_get_rgbd_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long)]
+        L.vslam_kfdb_create.argtypes = [i, i, i, C.POINTER(vp)]
+        L.vslam_kfdb_create_ex.argtypes = [i, i, i, i, C.POINTER(vp)]
+        L.vslam_kfdb_destroy.argtypes = [vp]
+        L.vslam_kfdb_destroy.restype = None
+        L.vslam_kfdb_add.argtypes = [vp, C.c_int64, C.c_int32, vp, vp, i]
+        L.vslam_kfdb_erase.argtypes = [vp, C.c_int64]
+        L.vslam_kfdb_clear.argtypes = [vp]
+        L.vslam_kfdb_clear_map.argtypes = [vp, C.c_int32]
+        L.vslam_kfdb_size.argtypes = [vp, C.POINTER(i), C.POINTER(C.c_longlong)]
+        L.vslam_kfdb_stats.argtypes = [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(i), C.POINTER(i),
+                                       C.POINTER(i)]
+        L.vslam_kfdb_query_async.argtypes = [vp, vp, i, vp, vp, vp]
+        L.vslam_kfdb_query_wait.argtypes = [vp, vp, i, i, vp, vp, vp, vp, vp, C.POINTER(i)]
+        bind_kfdb_select(L)
         _lib = L
     return _lib
 
@@ -1367,6 +1455,123 @@ class Vocabulary:
             out.update(word=w, weight=wt, nid=nd)
             res.append(out)
         return res
+
+
+def _bow_arrays(bow):
+    """a BowVector as dict(bow_ids, bow_vals) (Vocabulary.transform*) or an (ids, vals) pair -> contiguous arrays"""
+    ids, vals = (bow["bow_ids"], bow["bow_vals"]) if isinstance(bow, dict) else bow
+    ids, vals = np.ascontiguousarray(ids, np.int32), np.ascontiguousarray(vals, np.float64)
+    if ids.shape != vals.shape or ids.ndim != 1:
+        raise ValueError("a BowVector is two 1-D arrays of one length")
+    return ids, vals
+
+
+class KeyFrameDatabase:
+    """KeyFrameDatabase (src/datastructures/keyframedatabase.cpp) on the device; keyframes and maps are ids.  The
+    wrapper owns what the reference keeps in the KeyFrame objects between queries: mRelocScore and
+    mPlaceRecognitionScore, 0.0 for a keyframe that was never scored; erase / clear / clear_map forget them (a
+    keyframe added again is a new KeyFrame)."""
+
+    def __init__(self, n_words, scoring=0, device=0, initial_entries=0):
+        h = C.c_void_p()
+        _check(lib().vslam_kfdb_create_ex(device, n_words, scoring, initial_entries, C.byref(h)))
+        self._h = h
+        self._map = {}  # kf_id -> map_id of the live keyframes
+        self.reloc_score, self.place_score = {}, {}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().vslam_kfdb_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, kf_id, map_id, bow):
+        ids, vals = _bow_arrays(bow)
+        _check(lib().vslam_kfdb_add(self._h, kf_id, map_id, _p(ids), _p(vals), len(ids)))
+        self._map[kf_id] = map_id
+
+    def _forget(self, ids):
+        for k in ids:
+            self._map.pop(k, None)
+            self.reloc_score.pop(k, None)
+            self.place_score.pop(k, None)
+
+    def erase(self, kf_id):
+        _check(lib().vslam_kfdb_erase(self._h, kf_id))
+        self._forget([kf_id])
+
+    def clear(self):
+        _check(lib().vslam_kfdb_clear(self._h))
+        self._forget(list(self._map))
+
+    def clear_map(self, map_id):
+        _check(lib().vslam_kfdb_clear_map(self._h, map_id))
+        self._forget([k for k, m in self._map.items() if m == map_id])
+
+    def size(self):
+        """(live keyframes, their BowVector entries)"""
+        n, e = C.c_int(), C.c_longlong()
+        _check(lib().vslam_kfdb_size(self._h, C.byref(n), C.byref(e)))
+        return n.value, e.value
+
+    def stats(self):
+        cap, used, ns, ng, nc = C.c_longlong(), C.c_longlong(), C.c_int(), C.c_int(), C.c_int()
+        _check(lib().vslam_kfdb_stats(self._h, C.byref(cap), C.byref(used), C.byref(ns), C.byref(ng), C.byref(nc)))
+        return dict(capacity=cap.value, used=used.value, slots=ns.value, growths=ng.value, compactions=nc.value)
+
+    def query_async(self, fe, bows):
+        arrs = [_bow_arrays(b) for b in bows]
+        nq = len(arrs)
+        ids = (C.c_void_p * max(nq, 1))(*[a[0].ctypes.data for a in arrs])
+        vals = (C.c_void_p * max(nq, 1))(*[a[1].ctypes.data for a in arrs])
+        n = (C.c_int * max(nq, 1))(*[len(a[0]) for a in arrs])
+        _check(lib().vslam_kfdb_query_async(self._h, fe._h, nq, ids, vals, n))
+        self._pending = (fe, nq)
+
+    def query_wait(self):
+        fe, nq = self._pending
+        cap = max(len(self._map), 1)
+        kf, mp, words = np.zeros(cap, np.int64), np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+        si, score, nh, out = np.zeros(cap, np.float32), np.zeros(cap, np.float64), C.c_int(), []
+        for q in range(nq):
+            _check(lib().vslam_kfdb_query_wait(self._h, fe._h, q, cap, _p(kf), _p(mp), _p(words), _p(si), _p(score),
+                                               C.byref(nh)))
+            m = nh.value
+            out.append(dict(kf=kf[:m].copy(), map=mp[:m].copy(), words=words[:m].copy(), si=si[:m].copy(),
+                            score=score[:m].copy()))
+        return out
+
+    def query(self, fe, bows):
+        """Hit lists of up to 32 BowVectors: per query dict(kf, map, words, si, score), every live keyframe sharing a
+        word, in the order of the reference's lKFsSharingWords."""
+        self.query_async(fe, bows)
+        return self.query_wait()
+
+    def _select(self, hits, stale, run):
+        io = np.array([stale.get(int(k), 0.0) for k in hits["kf"]], np.float32)
+        res = run(io)
+        for k, v in zip(hits["kf"], io):
+            stale[int(k)] = float(v)
+        return res
+
+    def DetectRelocalizationCandidates(self, fe, bow, map_id, neighbours):
+        """keyframedatabase.cpp:707-811 (tracking.cpp:3464) -> candidate keyframe ids"""
+        hits = self.query(fe, [bow])[0]
+        return self._select(hits, self.reloc_score,
+                            lambda io: kfdb_select_relocalization(hits, io, map_id, neighbours, library=lib()))
+
+    def DetectNBestCandidates(self, fe, bow, kf_id, map_id, connected, neighbours, n=3, bad_maps=()):
+        """keyframedatabase.cpp:579-705 (loopclosing.cpp:415) -> (vpLoopCand ids, vpMergeCand ids).  kf_id names the
+        query keyframe (every call counts as a fresh query id); connected = its GetConnectedKeyFrames()."""
+        hits = self.query(fe, [bow])[0]
+        return self._select(hits, self.place_score,
+                            lambda io: kfdb_select_nbest(hits, io, map_id, connected, neighbours, n, bad_maps,
+                                                         library=lib()))
 
 
 def ComputeDistinctiveDescriptors(fe, desc, offsets):

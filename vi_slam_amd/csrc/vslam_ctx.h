@@ -153,6 +153,10 @@ struct vslam_fe {
     uint8_t* h_bow = nullptr;   /* pinned mirror */
     size_t h_bow_bytes = 0;
     int bow_jobs = 0;
+    uint8_t* d_kfdb = nullptr;  /* KeyFrameDatabase query: uploaded BowVectors | dense per-slot results (vslam_kfdb.hip) */
+    size_t kfdb_bytes = 0;
+    uint8_t* h_kfdb = nullptr;  /* pinned mirror (inputs, then results) */
+    size_t h_kfdb_bytes = 0;
     bool use_graph = true;          /* host-image passes replay a captured HIP graph (VSLAM_GRAPH=0 disables) */
     hipGraphExec_t graph_exec = nullptr;
     long long graph_key = 0;

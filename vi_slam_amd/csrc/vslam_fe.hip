@@ -92,6 +92,8 @@ static void free_ctx(vslam_fe* fe) {
     if (fe->graph_exec) hipGraphExecDestroy(fe->graph_exec);
     hipFree(fe->d_bow);
     if (fe->h_bow) hipHostFree(fe->h_bow);
+    hipFree(fe->d_kfdb);
+    if (fe->h_kfdb) hipHostFree(fe->h_kfdb);
     hipFree(fe->d_init_fb);
     if (fe->h_init && !fe->init_in_block) hipHostFree(fe->h_init);
     if (fe->ev_cand) hipEventDestroy(fe->ev_cand);
