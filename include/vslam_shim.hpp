@@ -503,6 +503,53 @@ public:
         return nm;
     }
 
+    /* Tracking::SearchLocalPoints from its second loop on (tracking.cpp:3214-3263): Frame::isInFrustum(pMP, 0.5) over
+     * mvpLocalMapPoints and matcher.SearchByProjection(mCurrentFrame, mvpLocalMapPoints, th, mbFarPoints, mThFarPoints) in
+     * one enqueue.  What the two functions read of the Frame and of the MapPoints:
+     *   cur               pose rows [mRcwx | mtcwx], mOwx, intrinsics, mbf, mfLogScaleFactor, mvuRight, and the extractor slot
+     *   mvpLocalMapPoints vslam_map_point per MapPoint (GetWorldPos2, GetNormal2, Get{Min,Max}DistanceInvariance, flags bit0 =
+     *                     mnLastFrameSeen != mCurrentFrame.id_ && !isBad(), bit1 = Observations() > 0) + descriptors
+     * mvpMapPointIndex[i2] = index into mvpLocalMapPoints of the point written to mCurrentFrame.mvpMapPoints[i2], or -1;
+     * nToMatch as the reference counts it; mTrack (may be NULL) receives what isInFrustum left in every MapPoint
+     * (mbTrackInView = flags & 1, mTrackProjX / Y for mmProjectPoints).  The loop over mCurrentFrame.mvpMapPoints
+     * (:3195-3212), IncreaseVisible and the choice of th stay with the caller.  Returns the matches. */
+    struct LocalFrameView {
+        FrameView frame;
+        float Tcw[12], Ow[3];
+        float fx, fy, cx, cy, mbf, mfLogScaleFactor;
+        const std::vector<float>* mvuRight = nullptr; /* NULL: monocular */
+    };
+    int SearchLocalPoints(const LocalFrameView& cur, const std::vector<vslam_map_point>& mvpLocalMapPoints,
+                          const std::vector<uint8_t>& mapPointDescriptors, const std::vector<uint8_t>* occupied,
+                          const float th, const bool bFarPoints, const float thFarPoints,
+                          std::vector<int>& mvpMapPointIndex, int& nToMatch, std::vector<vslam_mp_track>* mTrack = nullptr,
+                          const float viewingCosLimit = 0.5f) {
+        vslam_frustum_params p;
+        std::memset(&p, 0, sizeof(p));
+        std::memcpy(p.Tcw, cur.Tcw, sizeof(p.Tcw));
+        std::memcpy(p.Ow, cur.Ow, sizeof(p.Ow));
+        p.fx = cur.fx; p.fy = cur.fy; p.cx = cur.cx; p.cy = cur.cy; p.mbf = cur.mbf;
+        p.viewing_cos_limit = viewingCosLimit;
+        p.log_scale_factor = cur.mfLogScaleFactor;
+        p.img_w = cur.frame.mnMaxX;
+        p.img_h = cur.frame.mnMaxY;
+        p.far_points = bFarPoints ? 1 : 0;
+        p.th_far_points = thFarPoints;
+        const vslam_kp* dk = nullptr;
+        const uint8_t* dd = nullptr;
+        int n2 = 0, nm = 0, against = 0;
+        slot_keypoints(*cur.frame.extractor, &dk, &dd, &n2);
+        mvpMapPointIndex.assign(n2, -1);
+        nToMatch = 0;
+        if (mTrack) mTrack->resize(mvpLocalMapPoints.size());
+        check(vslam_search_local_points(cur.frame.extractor->context(), &p, mvpLocalMapPoints.data(),
+                                        mapPointDescriptors.data(), (int)mvpLocalMapPoints.size(), VSLAM_IMGS_HOST, dk, dd, n2,
+                                        cur.mvuRight ? cur.mvuRight->data() : nullptr,
+                                        occupied ? occupied->data() : nullptr, th, mfNNratio, mvpMapPointIndex.data(), &nm,
+                                        &nToMatch, &against, (mTrack && n2 > 0 && !mTrack->empty()) ? mTrack->data() : nullptr));
+        return nm;
+    }
+
 protected:
     /* the current frame's keypoints for the projection matchers: keypoints_ of slot 0 as before, ukeypoints_ once the
      * context holds grid bounds (SetGridBounds) -- the undistorted grid bins undistorted keypoints */

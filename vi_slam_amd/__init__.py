@@ -58,6 +58,8 @@ ABI_SYMBOLS = [
     "vslam_search_for_initialization_ex", "vslam_search_for_initialization_batch_ex", "vslam_search_init_dev_async_ex",
     "vslam_fe_set_pixel_format", "vslam_fe_get_pixel_format", "vslam_frame_rgbd_batch_async", "vslam_frame_rgbd_wait",
     "vslam_fe_get_rgbd_profile",
+    "vslam_frame_in_frustum", "vslam_search_local_points_async", "vslam_search_local_points_wait",
+    "vslam_search_local_points", "vslam_fe_get_local_points_profile",
     "vslam_kfdb_create", "vslam_kfdb_create_ex", "vslam_kfdb_destroy", "vslam_kfdb_add", "vslam_kfdb_erase",
     "vslam_kfdb_clear", "vslam_kfdb_clear_map", "vslam_kfdb_size", "vslam_kfdb_stats", "vslam_kfdb_query_async",
     "vslam_kfdb_query_wait", "vslam_kfdb_select_relocalization", "vslam_kfdb_select_nbest",
@@ -67,6 +69,15 @@ ABI_SYMBOLS = [
 #: vslam_mp_track: per-MapPoint tracking record (mappoint.h:73-81 after Frame::isInFrustum)
 MP_TRACK_DTYPE = np.dtype([("proj_x", "<f4"), ("proj_y", "<f4"), ("proj_xr", "<f4"), ("view_cos", "<f4"),
                            ("level", "<i4"), ("flags", "<u4")])
+
+
+#: vslam_map_point: one MapPoint of the local map as Frame::isInFrustum reads it (36 bytes); flags bit0: candidate
+#: (mnLastFrameSeen != frame id && !isBad()), bit1: Observations() > 0
+MAP_POINT_DTYPE = np.dtype([("pos", "<f4", 3), ("normal", "<f4", 3), ("min_dist", "<f4"), ("max_dist", "<f4"),
+                            ("flags", "<u4")])
+#: MapPoints per frame_in_frustum / search_local_points call, and points the matcher behind it takes
+LOCAL_POINTS_MAX = 65536
+LOCAL_POINTS_MATCHER_CAP = 4096
 
 
 #: vslam_fuse_point: one candidate MapPoint of FMatcher::Fuse
@@ -91,6 +102,29 @@ class _ProjParams(C.Structure):  # vslam_proj_params
                 ("mbf", C.c_float), ("th", C.c_float), ("forward", C.c_int32), ("backward", C.c_int32),
                 ("check_orientation", C.c_int32), ("img_w", C.c_int32), ("img_h", C.c_int32),
                 ("gemm_float", C.c_int32)]
+
+
+class _FrustumParams(C.Structure):  # vslam_frustum_params
+    _fields_ = [("Tcw", C.c_float * 12), ("Ow", C.c_float * 3), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float),
+                ("cy", C.c_float), ("mbf", C.c_float), ("viewing_cos_limit", C.c_float), ("log_scale_factor", C.c_float),
+                ("img_w", C.c_int32), ("img_h", C.c_int32), ("far_points", C.c_int32), ("th_far_points", C.c_float)]
+
+
+def frustum_params(Tcw, Ow, cam, log_scale_factor, img_size, viewing_cos_limit=0.5, far_points=False, th_far_points=0.0):
+    """vslam_frustum_params: Tcw = rows [mRcwx | mtcwx] (3 x 4), Ow = mOwx, cam = (fx, fy, cx, cy, mbf)"""
+    P = _FrustumParams()
+    T = np.asarray(Tcw, np.float32).reshape(-1)
+    for k in range(12):
+        P.Tcw[k] = float(T[k])
+    for k in range(3):
+        P.Ow[k] = float(np.float32(Ow[k]))
+    P.fx, P.fy, P.cx, P.cy, P.mbf = [float(np.float32(v)) for v in cam[:5]]
+    P.viewing_cos_limit = float(np.float32(viewing_cos_limit))
+    P.log_scale_factor = float(np.float32(log_scale_factor))
+    P.img_w, P.img_h = int(img_size[0]), int(img_size[1])
+    P.far_points = int(bool(far_points))
+    P.th_far_points = float(np.float32(th_far_points))
+    return P
 
 
 class _SbpJob(C.Structure):  # vslam_sbp_job
@@ -395,6 +429,13 @@ def lib():
         L.vslam_frame_rgbd_batch_async.argtypes = [vp, i, vp, C.c_size_t, i, vp, C.c_size_t, i, i, f, f, i]
         L.vslam_frame_rgbd_wait.argtypes = [vp, vp, vp, i, vp, vp, vp]
         L.vslam_fe_get_rgbd_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long)]
+        fp = C.POINTER(_FrustumParams)
+        L.vslam_frame_in_frustum.argtypes = [vp, fp, vp, i, vp, vp, C.POINTER(i)]
+        L.vslam_search_local_points_async.argtypes = [vp, fp, vp, vp, i, i, vp, vp, i, vp, vp, f, f]
+        L.vslam_search_local_points_wait.argtypes = [vp, vp, C.POINTER(i), C.POINTER(i), C.POINTER(i), vp]
+        L.vslam_fe_get_local_points_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_long)]
+        L.vslam_search_local_points.argtypes = [vp, fp, vp, vp, i, i, vp, vp, i, vp, vp, f, f, vp, C.POINTER(i),
+                                                C.POINTER(i), C.POINTER(i), vp]
         L.vslam_kfdb_create.argtypes = [i, i, i, C.POINTER(vp)]
         L.vslam_kfdb_create_ex.argtypes = [i, i, i, i, C.POINTER(vp)]
         L.vslam_kfdb_destroy.argtypes = [vp]
@@ -819,6 +860,71 @@ class FExtractor:
             return
         b = _bounds(bounds)
         _check(lib().vslam_fe_set_grid_bounds(self._h, C.byref(b)))
+
+    def get_local_points_profile(self):
+        """with set_profiling(True): (k_frustum ms, k_frustum_compact ms, searches) by HIP events, summed since"""
+        a, b, n = C.c_double(), C.c_double(), C.c_long()
+        _check(lib().vslam_fe_get_local_points_profile(self._h, C.byref(a), C.byref(b), C.byref(n)))
+        return a.value, b.value, n.value
+
+    def frame_in_frustum(self, params, points):
+        """Frame::isInFrustum (frame.cpp:529-595, pinhole) over `points` (MAP_POINT_DTYPE) on the device; params from
+        frustum_params().  -> (records as MP_TRACK_DTYPE, mTrackDepth as float32, nToMatch).  Grid bounds set on the
+        context replace params' image size."""
+        pts = np.ascontiguousarray(points, MAP_POINT_DTYPE)
+        track = np.zeros(len(pts), MP_TRACK_DTYPE)
+        depth = np.zeros(len(pts), np.float32)
+        nv = C.c_int(0)
+        _check(lib().vslam_frame_in_frustum(self._h, C.byref(params), _p(pts), len(pts), _p(track), _p(depth),
+                                            C.byref(nv)))
+        return track, depth, nv.value
+
+    def search_local_points_async(self, params, points, mp_desc, dev_cur_kps, dev_cur_desc, n_cur, cur_u_right=None,
+                                  occupied=None, th=1.0, nnratio=0.8, n_mp=None):
+        """Enqueue isInFrustum + ordered compaction + FMatcher::SearchByProjection(F, vpMapPoints, th, bFarPoints,
+        thFarPoints) (tracking.cpp:3214-3263) and return.  points / mp_desc: numpy arrays (MAP_POINT_DTYPE, n x 32
+        uint8), or two device addresses (ints) with n_mp given -- a map that lives in HBM is not uploaded."""
+        on_dev = isinstance(points, int)
+        if on_dev:
+            if n_mp is None:
+                raise ValueError("n_mp is required with device addresses")
+            pp, dp = C.c_void_p(points), C.c_void_p(int(mp_desc))
+        else:
+            self._lp_keep = (np.ascontiguousarray(points, MAP_POINT_DTYPE), np.ascontiguousarray(mp_desc, np.uint8))
+            n_mp = len(self._lp_keep[0])
+            pp, dp = _p(self._lp_keep[0]), _p(self._lp_keep[1])
+        ur = None if cur_u_right is None else np.ascontiguousarray(cur_u_right, np.float32)
+        oc = None if occupied is None else np.ascontiguousarray(occupied, np.uint8)
+        _check(lib().vslam_search_local_points_async(
+            self._h, C.byref(params), pp, dp, n_mp, IMGS_DEVICE if on_dev else IMGS_HOST, C.c_void_p(dev_cur_kps),
+            C.c_void_p(dev_cur_desc), n_cur, _p(ur) if ur is not None else None, _p(oc) if oc is not None else None,
+            C.c_float(th), C.c_float(nnratio)))
+        self._lp_shape = (n_mp, n_cur)
+
+    def search_local_points_wait(self, want_track=False):
+        """-> (nmatches, match_cur[n_cur] = index into `points` or -1, nToMatch, points handed to the matcher[, records]).
+        Raises VslamError(ERR_UNSUPPORTED) when more than 4096 points went on to the matcher; the error carries
+        .n_to_match and .n_matched_against."""
+        n_mp, n_cur = self._lp_shape
+        m = np.full(max(n_cur, 1), -1, np.int32)
+        track = np.zeros(max(n_mp, 1), MP_TRACK_DTYPE) if want_track else None
+        nm, nt, na = C.c_int(0), C.c_int(0), C.c_int(0)
+        rc = lib().vslam_search_local_points_wait(self._h, _p(m), C.byref(nm), C.byref(nt), C.byref(na),
+                                                  _p(track) if want_track else None)
+        self._lp_keep = None
+        if rc != VSLAM_OK:
+            e = VslamError(rc, lib().vslam_last_error().decode())
+            e.n_to_match, e.n_matched_against, e.match_cur = nt.value, na.value, m[:n_cur]
+            raise e
+        out = (nm.value, m[:n_cur], nt.value, na.value)
+        return out + (track[:n_mp],) if want_track else out
+
+    def search_local_points(self, params, points, mp_desc, dev_cur_kps, dev_cur_desc, n_cur, cur_u_right=None,
+                            occupied=None, th=1.0, nnratio=0.8, n_mp=None, want_track=False):
+        """search_local_points_async + search_local_points_wait"""
+        self.search_local_points_async(params, points, mp_desc, dev_cur_kps, dev_cur_desc, n_cur, cur_u_right, occupied, th,
+                                       nnratio, n_mp)
+        return self.search_local_points_wait(want_track)
 
     def grid_bounds(self):
         """-> (bounds as float32[4] in image_bounds() order, is_set); (0, width, 0, height) while none are set"""

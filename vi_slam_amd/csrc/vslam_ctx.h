@@ -157,6 +157,13 @@ struct vslam_fe {
     size_t kfdb_bytes = 0;
     uint8_t* h_kfdb = nullptr;  /* pinned mirror (inputs, then results) */
     size_t h_kfdb_bytes = 0;
+    uint8_t* d_lp = nullptr;    /* SearchLocalPoints: inputs | frustum records | compacted arrays | matcher scratch | results (vslam_match.hip) */
+    size_t lp_bytes = 0;
+    uint8_t* h_lp = nullptr;    /* pinned mirror (inputs, then results) */
+    size_t h_lp_bytes = 0;
+    int lp_state = 0;           /* 0: nothing enqueued, 1: a search is in flight, 2: an empty search (nothing launched) */
+    int lp_n_mp = 0, lp_n_cur = 0, lp_cap = 0;
+    size_t lp_o_track = 0, lp_o_res = 0; /* where the records and the result block (matches | counts | indices) start */
     bool use_graph = true;          /* host-image passes replay a captured HIP graph (VSLAM_GRAPH=0 disables) */
     hipGraphExec_t graph_exec = nullptr;
     long long graph_key = 0;
@@ -195,6 +202,10 @@ struct vslam_fe {
     bool rgbd_timed = false;
     double rgbd_ms = 0;
     long rgbd_passes = 0;
+    hipEvent_t ev_lp[3] = {};   /* profiling: before k_frustum | between | behind k_frustum_compact */
+    bool lp_timed = false;
+    double lp_ms[2] = {0, 0};
+    long lp_passes = 0;
 
     /* GPU quadtree distribution */
     bool dev_octree = false;

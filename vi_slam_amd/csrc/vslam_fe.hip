@@ -94,6 +94,8 @@ static void free_ctx(vslam_fe* fe) {
     if (fe->h_bow) hipHostFree(fe->h_bow);
     hipFree(fe->d_kfdb);
     if (fe->h_kfdb) hipHostFree(fe->h_kfdb);
+    hipFree(fe->d_lp);
+    if (fe->h_lp) hipHostFree(fe->h_lp);
     hipFree(fe->d_init_fb);
     if (fe->h_init && !fe->init_in_block) hipHostFree(fe->h_init);
     if (fe->ev_cand) hipEventDestroy(fe->ev_cand);
@@ -109,6 +111,8 @@ static void free_ctx(vslam_fe* fe) {
     if (fe->ev_fast) hipEventDestroy(fe->ev_fast);
     for (int i = 0; i < 2; i++)
         if (fe->ev_rgbd[i]) hipEventDestroy(fe->ev_rgbd[i]);
+    for (int i = 0; i < 3; i++)
+        if (fe->ev_lp[i]) hipEventDestroy(fe->ev_lp[i]);
     for (int i = 0; i < 10; i++)
         if (fe->ev_prof[i]) hipEventDestroy(fe->ev_prof[i]);
     if (fe->stream) hipStreamDestroy(fe->stream);
@@ -593,6 +597,8 @@ extern "C" int vslam_fe_set_profiling(vslam_fe* fe, int on) {
     fe->prof_batches = fe->prof_images = 0;
     fe->rgbd_ms = 0;
     fe->rgbd_passes = 0;
+    fe->lp_ms[0] = fe->lp_ms[1] = 0;
+    fe->lp_passes = 0;
     return VSLAM_OK;
 }
 

@@ -1,6 +1,7 @@
 /* vslam_host.cpp -- see vslam_host.h.  Reference lines are cited per function. */
 #include "vslam_host.h"
 #include "vslam_undistort.h"
+#include "vslam_frustum.h"
 
 #include <algorithm>
 #include <climits>
@@ -1020,6 +1021,44 @@ int vslamh_image_bounds(const float* cam, const float* dist, int ndist, int cols
     for (int i = 0; i < ndist; i++) d[i] = dist[i];
     vslam_ud::image_bounds(cam, d, cols, rows, b);
     return 0;
+}
+
+/* Frame::isInFrustum over n MapPoints, the shared vslam_frustum.h code (CPU tests, the stand-alone demo; the product runs
+ * k_frustum).  Beside the parameters and the points it takes what the product reads from its context: the grid bounds in
+ * force (bounds = minX, maxX, minY, maxY or NULL for {0, img_w, 0, img_h}) and the extractor's level count (the clamp of
+ * PredictScale); depth_out may be NULL.  Returns nToMatch,
+ * -1 for bad arguments. */
+int vslamh_in_frustum(const vslam_frustum_params* p, const float* bounds, int nlevels, const vslam_map_point* points, int n,
+                      vslam_mp_track* track_out, float* depth_out) {
+    if (!p || n < 0 || nlevels < 1 || (n && (!points || !track_out))) return -1;
+    const float whole[4] = {0.0f, (float)p->img_w, 0.0f, (float)p->img_h};
+    const vslam_fr::Frame F = vslam_fr::make_frame(*p, bounds ? bounds : whole, nlevels);
+    int in_view = 0;
+    for (int i = 0; i < n; i++) {
+        float depth;
+        vslam_fr::in_frustum(F, points[i], &track_out[i], &depth);
+        if (depth_out) depth_out[i] = depth;
+        in_view += (int)(track_out[i].flags & 1u);
+    }
+    return in_view;
+}
+
+/* The host end of vslam_search_local_points_wait: the matcher ran on the compacted list, so match_compact[idx] counts kept
+ * points; orig_index[k] is the k-th kept point's index in the caller's array.  More kept points than the matcher's capacity:
+ * nothing can be said about any keypoint -- all -1 and VSLAM_ERR_UNSUPPORTED. */
+int vslamh_local_points_finish(const int32_t* match_compact, int n_cur, const int32_t* orig_index, int n_kept, int capacity,
+                               int32_t* match_cur) {
+    if (n_cur < 0 || n_kept < 0 || capacity < 0 || (n_cur && (!match_compact || !match_cur)) || (n_kept && !orig_index))
+        return VSLAM_ERR_INVALID;
+    if (n_kept > capacity) {
+        for (int i = 0; i < n_cur; i++) match_cur[i] = -1;
+        return VSLAM_ERR_UNSUPPORTED;
+    }
+    for (int i = 0; i < n_cur; i++) {
+        const int32_t k = match_compact[i];
+        match_cur[i] = (k >= 0 && k < n_kept) ? orig_index[k] : -1;
+    }
+    return VSLAM_OK;
 }
 
 /* quadtree path tables of k_octree_v4 against the literal halvings: returns the number of (x, y) whose table path differs */

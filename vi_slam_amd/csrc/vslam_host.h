@@ -190,4 +190,8 @@ int search_for_initialization_replay(const vslam_kp* kps1, int n1, const vslam_k
                                      int windowSize, float nnratio, bool checkOri);
 
 } // namespace vslam
+
+/* vslam_host.cpp: index map-back and over-capacity decision of vslam_search_local_points_wait */
+extern "C" int vslamh_local_points_finish(const int32_t* match_compact, int n_cur, const int32_t* orig_index, int n_kept,
+                                          int capacity, int32_t* match_cur);
 #endif

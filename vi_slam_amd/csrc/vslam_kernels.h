@@ -103,6 +103,11 @@ void vk_gray_images(hipStream_t st, const BatchSrc& src, uint8_t* pyr, size_t sl
 /* Frame::ComputeStereoFromRGBD for every keypoint of slots 0..nimg-1: u_right / depth are nimg x cap floats */
 void vk_rgbd_depth(hipStream_t st, const vslam_kp* kps, const vslam_kp* ukps, const int32_t* counts, int cap, int nimg,
                    const RgbdDepthSrc& D, float* u_right, float* depth);
+/* Frame::isInFrustum over a local map, and the ordered compaction of the points that go on to the matcher (vslam_frustum.hip) */
+struct FrustumArgsDev;
+struct FrustumCompactDev;
+void vk_frustum(hipStream_t st, const FrustumArgsDev& A);
+void vk_frustum_compact(hipStream_t st, const FrustumCompactDev& A);
 void vk_pack_slots(hipStream_t st, const vslam_kp* kps, const uint8_t* desc, const int32_t* counts, int cap, int first,
                    int nslots, uint8_t* dst, size_t slot_bytes);
 void vk_gather_rows32(hipStream_t st, const uint8_t* src, const int32_t* idx, int n, uint8_t* dst);

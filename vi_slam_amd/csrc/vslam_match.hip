@@ -1,6 +1,7 @@
 /* vslam_match.hip -- matcher half of the C ABI: Frame::ComputeStereoMatches on the device and the
  * host-replayed FMatcher::SearchForInitialization (distances from the device). */
 #include "vslam_ctx.h"
+#include "vslam_frustum.h"
 
 /* ------------------------------------------------------------------ stereo */
 struct StereoScratch { /* carved out of fe->d_stereo */
@@ -1416,5 +1417,315 @@ extern "C" int vslam_fuse_search(vslam_fe* fe, const vslam_fuse_params* p, const
     HIPCHK(vslam_stream_wait(st));
     memcpy(best_idx, h + o_bi, (size_t)n_points * 4);
     memcpy(best_dist, h + o_bd, (size_t)n_points * 4);
+    return VSLAM_OK;
+}
+
+/* ------------------------------------------------------------------ Frame::isInFrustum + SearchLocalPoints
+ * The frustum stage (vslam_frustum.hip) in front of the matcher of vslam_search_by_projection_mappoints.  k_sbp_rank,
+ * k_sbpm_resolve and k_sbpm_replay read their MapPoint count as min(*nLastPtr, nLast) in mode 1 exactly as in mode 0, so the
+ * matcher is enqueued behind the compaction with nLast = the capacity and nLastPtr = the clamped count in HBM: no host
+ * wait between the stages. */
+static bool frustum_params_ok(const vslam_frustum_params* p) {
+    if (!p || p->img_w < 1 || p->img_h < 1) return false;
+    for (int i = 0; i < 12; i++)
+        if (!std::isfinite(p->Tcw[i])) return false;
+    for (int i = 0; i < 3; i++)
+        if (!std::isfinite(p->Ow[i])) return false;
+    return std::isfinite(p->fx) && std::isfinite(p->fy) && std::isfinite(p->cx) && std::isfinite(p->cy) &&
+           std::isfinite(p->mbf) && std::isfinite(p->viewing_cos_limit) && std::isfinite(p->log_scale_factor) &&
+           std::isfinite(p->th_far_points);
+}
+
+static vslam_fr::Frame frustum_frame(const vslam_fe* fe, const vslam_frustum_params* p) {
+    const SiBounds b = matcher_bounds(fe, p->img_w, p->img_h);
+    const float bb[4] = {b.minX, b.maxX, b.minY, b.maxY};
+    return vslam_fr::make_frame(*p, bb, fe->p.nlevels);
+}
+
+static size_t lp_al(size_t v) { return (v + 255) & ~(size_t)255; }
+
+extern "C" int vslam_frame_in_frustum(vslam_fe* fe, const vslam_frustum_params* p, const vslam_map_point* points_host, int n,
+                                      vslam_mp_track* track_out, float* depth_out, int* n_in_view) {
+    if (!fe || !n_in_view || n < 0 || (n && (!points_host || !track_out)) || !frustum_params_ok(p)) {
+        g_err = "invalid arguments";
+        return VSLAM_ERR_INVALID;
+    }
+    *n_in_view = 0;
+    if (n == 0) return VSLAM_OK;
+    if (n > VSLAM_LOCAL_POINTS_MAX) {
+        g_err = "Frame::isInFrustum on the device supports at most 65536 MapPoints per call";
+        return VSLAM_ERR_UNSUPPORTED;
+    }
+    if (fe->lp_state == 1) {
+        g_err = "a local-points search is in flight (vslam_search_local_points_wait)";
+        return VSLAM_ERR_INVALID;
+    }
+    HIPCHK(hipSetDevice(fe->p.device));
+    const int nchunks = (n + VSLAM_FRUSTUM_CHUNK - 1) / VSLAM_FRUSTUM_CHUNK;
+    const size_t o_pts = 0, o_track = lp_al((size_t)n * sizeof(vslam_map_point)),
+                 o_depth = o_track + lp_al((size_t)n * sizeof(vslam_mp_track)), o_cv = o_depth + lp_al((size_t)n * 4),
+                 o_ck = o_cv + lp_al((size_t)nchunks * 4), total = o_ck + lp_al((size_t)nchunks * 4);
+    int rc = vslam_ensure((void**)&fe->d_lp, &fe->lp_bytes, total);
+    if (rc) return rc;
+    if ((rc = vslam_ensure_pinned(&fe->h_lp, &fe->h_lp_bytes, total))) return rc;
+    uint8_t *h = fe->h_lp, *d = fe->d_lp;
+    memcpy(h + o_pts, points_host, (size_t)n * sizeof(vslam_map_point));
+    hipStream_t st = fe->stream;
+    CopyRanges R;
+    memset(&R, 0, sizeof(R));
+    R.dst[0] = d + o_pts;
+    R.src[0] = h + o_pts;
+    R.bytes[0] = o_track;
+    R.n = 1;
+    vk_copy_ranges(st, R);
+    FrustumArgsDev A;
+    A.F = frustum_frame(fe, p);
+    A.n = n;
+    A.farPoints = p->far_points != 0;
+    A.thFarPoints = p->th_far_points;
+    A.pts = (const vslam_map_point*)(d + o_pts);
+    A.track = (vslam_mp_track*)(d + o_track);
+    A.depth = (float*)(d + o_depth);
+    A.chunkInView = (int32_t*)(d + o_cv);
+    A.chunkKeep = (int32_t*)(d + o_ck);
+    vk_frustum(st, A);
+    HIPCHK(hipGetLastError());
+    R.dst[0] = h + o_track;
+    R.src[0] = d + o_track;
+    R.bytes[0] = o_ck - o_track; /* records | depths | in-view counts */
+    vk_copy_ranges(st, R);
+    HIPCHK(hipGetLastError());
+    HIPCHK(vslam_stream_wait(st));
+    memcpy(track_out, h + o_track, (size_t)n * sizeof(vslam_mp_track));
+    if (depth_out) memcpy(depth_out, h + o_depth, (size_t)n * 4);
+    int nv = 0;
+    for (int c = 0; c < nchunks; c++) nv += ((const int32_t*)(h + o_cv))[c];
+    *n_in_view = nv;
+    return VSLAM_OK;
+}
+
+extern "C" int vslam_search_local_points_async(vslam_fe* fe, const vslam_frustum_params* p, const vslam_map_point* points,
+                                               const uint8_t* mp_desc, int n_mp, int points_where,
+                                               const vslam_kp* dev_cur_kps, const uint8_t* dev_cur_desc, int n_cur,
+                                               const float* cur_u_right_host, const uint8_t* cur_occupied_host, float th,
+                                               float nnratio) {
+    if (!fe || n_mp < 0 || n_cur < 0 || (n_cur && (!dev_cur_kps || !dev_cur_desc)) || (n_mp && (!points || !mp_desc)) ||
+        (points_where != VSLAM_IMGS_HOST && points_where != VSLAM_IMGS_DEVICE) || !frustum_params_ok(p) ||
+        !std::isfinite(th)) {
+        g_err = "invalid arguments";
+        return VSLAM_ERR_INVALID;
+    }
+    if (points_where == VSLAM_IMGS_DEVICE && n_mp && ((((uintptr_t)mp_desc) & 15) || (((uintptr_t)points) & 3))) {
+        g_err = "device MapPoint descriptors must be 16-byte aligned, device MapPoints 4-byte aligned";
+        return VSLAM_ERR_INVALID;
+    }
+    if (fe->lp_state == 1) {
+        g_err = "a local-points search is already in flight (vslam_search_local_points_wait)";
+        return VSLAM_ERR_INVALID;
+    }
+    if (n_mp > VSLAM_LOCAL_POINTS_MAX) {
+        g_err = "SearchLocalPoints on the device supports at most 65536 MapPoints per call";
+        return VSLAM_ERR_UNSUPPORTED;
+    }
+    if (n_cur > 4096) {
+        g_err = "SearchByProjection on the device supports at most 4096 keypoints per call";
+        return VSLAM_ERR_UNSUPPORTED;
+    }
+    if (!(nnratio >= 0.4f)) { /* see vslam_search_by_projection_mappoints */
+        g_err = "SearchByProjection on the device needs nnratio >= 0.4";
+        return VSLAM_ERR_UNSUPPORTED;
+    }
+    fe->lp_n_mp = n_mp;
+    fe->lp_n_cur = n_cur;
+    if (n_mp == 0 || n_cur == 0) {
+        fe->lp_state = 2;
+        return VSLAM_OK;
+    }
+    HIPCHK(hipSetDevice(fe->p.device));
+    int M;
+    int rc = sbp_prepare(fe, &M);
+    if (rc) return rc;
+    const bool from_host = points_where == VSLAM_IMGS_HOST;
+    const int cap = std::min(n_mp, VSLAM_FRUSTUM_MAX_KEPT);
+    const int nchunks = (n_mp + VSLAM_FRUSTUM_CHUNK - 1) / VSLAM_FRUSTUM_CHUNK;
+    /* uploaded inputs | records of all points | compacted arrays | matcher scratch | results (one copy) */
+    const size_t o_u = 0, o_o = o_u + lp_al((size_t)n_cur * 4), o_pts = o_o + lp_al((size_t)n_cur),
+                 o_desc = o_pts + (from_host ? lp_al((size_t)n_mp * sizeof(vslam_map_point)) : 0),
+                 in_bytes = o_desc + (from_host ? lp_al((size_t)n_mp * 32) : 0);
+    const size_t o_track = in_bytes, o_depth = o_track + lp_al((size_t)n_mp * sizeof(vslam_mp_track)),
+                 o_cv = o_depth + lp_al((size_t)n_mp * 4), o_ck = o_cv + lp_al((size_t)nchunks * 4),
+                 o_tc = o_ck + lp_al((size_t)nchunks * 4), o_dc = o_tc + lp_al((size_t)cap * sizeof(vslam_mp_track)),
+                 o_fc = o_dc + lp_al((size_t)cap * 32), o_scr = o_fc + lp_al((size_t)cap),
+                 o_m = o_scr + lp_al(vk_sbp_scratch_bytes(cap, M)), o_cnt = o_m + lp_al((size_t)n_cur * 4),
+                 o_idx = o_cnt + 256, total = o_idx + lp_al((size_t)cap * 4);
+    rc = vslam_ensure((void**)&fe->d_lp, &fe->lp_bytes, total);
+    if (rc) return rc;
+    if ((rc = vslam_ensure_pinned(&fe->h_lp, &fe->h_lp_bytes, total))) return rc;
+    uint8_t *h = fe->h_lp, *d = fe->d_lp;
+    if (cur_u_right_host) memcpy(h + o_u, cur_u_right_host, (size_t)n_cur * 4);
+    if (cur_occupied_host) memcpy(h + o_o, cur_occupied_host, (size_t)n_cur);
+    if (from_host) {
+        memcpy(h + o_pts, points, (size_t)n_mp * sizeof(vslam_map_point));
+        memcpy(h + o_desc, mp_desc, (size_t)n_mp * 32);
+    }
+    hipStream_t st = fe->stream;
+    CopyRanges R;
+    memset(&R, 0, sizeof(R));
+    /* without right coordinates and occupancy a device-resident map uploads nothing */
+    const size_t up0 = cur_u_right_host ? o_u : cur_occupied_host ? o_o : o_pts;
+    R.dst[0] = d + up0;
+    R.src[0] = h + up0;
+    R.bytes[0] = in_bytes - up0;
+    R.n = 1;
+    vk_copy_ranges(st, R);
+    const bool prof = fe->profiling; /* vslam_fe_set_profiling: the two kernels' own spans (vslam_fe_get_local_points_profile) */
+    if (prof && !fe->ev_lp[0])
+        for (int i = 0; i < 3; i++) HIPCHK(hipEventCreate(&fe->ev_lp[i]));
+    FrustumArgsDev A;
+    A.F = frustum_frame(fe, p);
+    A.n = n_mp;
+    A.farPoints = p->far_points != 0;
+    A.thFarPoints = p->th_far_points;
+    A.pts = from_host ? (const vslam_map_point*)(d + o_pts) : points;
+    A.track = (vslam_mp_track*)(d + o_track);
+    A.depth = (float*)(d + o_depth);
+    A.chunkInView = (int32_t*)(d + o_cv);
+    A.chunkKeep = (int32_t*)(d + o_ck);
+    if (prof) (void)hipEventRecord(fe->ev_lp[0], st);
+    vk_frustum(st, A);
+    if (prof) (void)hipEventRecord(fe->ev_lp[1], st);
+    FrustumCompactDev K;
+    K.n = n_mp;
+    K.nchunks = nchunks;
+    K.farPoints = A.farPoints;
+    K.cap = cap;
+    K.thFarPoints = A.thFarPoints;
+    K.track = A.track;
+    K.depth = A.depth;
+    K.desc = from_host ? d + o_desc : mp_desc;
+    K.chunkKeep = A.chunkKeep;
+    K.chunkInView = A.chunkInView;
+    K.trackC = (vslam_mp_track*)(d + o_tc);
+    K.descC = d + o_dc;
+    K.flagsC = d + o_fc;
+    K.indexC = (int32_t*)(d + o_idx);
+    int32_t* cnt = (int32_t*)(d + o_cnt); /* nmatches, needSeq | kept, min(kept, cap), nToMatch */
+    K.counts = cnt + 2;
+    vk_frustum_compact(st, K);
+    if (prof) (void)hipEventRecord(fe->ev_lp[2], st);
+    fe->lp_timed = prof;
+    HIPCHK(hipGetLastError());
+    SbpJobs JS;
+    memset(&JS, 0, sizeof(JS));
+    for (int l = 0; l < fe->p.nlevels; l++) JS.scale[l] = fe->tab.scale[l];
+    JS.nlevels = fe->p.nlevels;
+    JS.M = M;
+    SbpJobDev& J = JS.job[0];
+    J.mode = 1;
+    J.th = th;
+    J.nnratio = nnratio;
+    J.bnd = matcher_bounds(fe, p->img_w, p->img_h);
+    J.nLast = cap;
+    J.nLastPtr = cnt + 3;
+    J.nCur = n_cur;
+    J.mps = (const MpTrack*)(d + o_tc);
+    J.mpDesc = d + o_dc;
+    J.flags = d + o_fc;
+    J.curKps = dev_cur_kps;
+    J.curDesc = dev_cur_desc;
+    J.uRight = cur_u_right_host ? (const float*)(d + o_u) : nullptr;
+    J.occupied0 = cur_occupied_host ? d + o_o : nullptr;
+    J.proj = (SbpProj*)(d + o_scr);
+    J.topm = (uint32_t*)(d + o_scr + vk_sbp_proj_bytes(cap));
+    J.matchCur = (int32_t*)(d + o_m);
+    J.nmatches = cnt;
+    J.needSeq = cnt + 1;
+    const bool seq_mode = fe->tune.sbp_sequential == 1;
+    vk_search_by_projection(st, JS, 1, cap, n_cur, fe->d_init_fb, seq_mode);
+    HIPCHK(hipGetLastError());
+    R.dst[0] = h + o_m;
+    R.src[0] = d + o_m;
+    R.bytes[0] = total - o_m; /* match table | counts | original indices */
+    vk_copy_ranges(st, R);
+    HIPCHK(hipGetLastError());
+    fe->lp_state = 1;
+    fe->lp_cap = cap;
+    fe->lp_o_track = o_track;
+    fe->lp_o_res = o_m;
+    return VSLAM_OK;
+}
+
+extern "C" int vslam_search_local_points_wait(vslam_fe* fe, int32_t* match_cur, int* nmatches, int* n_to_match,
+                                              int* n_matched_against, vslam_mp_track* track_out) {
+    if (!fe || fe->lp_state == 0) {
+        g_err = "nothing enqueued";
+        return VSLAM_ERR_INVALID;
+    }
+    const int n_mp = fe->lp_n_mp, n_cur = fe->lp_n_cur;
+    if (!nmatches || !n_to_match || !n_matched_against || (n_cur && !match_cur)) {
+        g_err = "invalid arguments";
+        return VSLAM_ERR_INVALID;
+    }
+    *nmatches = *n_to_match = *n_matched_against = 0;
+    if (fe->lp_state == 2) { /* n_mp == 0 or n_cur == 0: nothing was launched */
+        fe->lp_state = 0;
+        for (int i = 0; i < n_cur; i++) match_cur[i] = -1;
+        if (track_out && n_mp) { /* async launched nothing and kept no inputs: there are no records to hand out */
+            g_err = "no records: a search without keypoints launches nothing; call vslam_frame_in_frustum for the records";
+            return VSLAM_ERR_INVALID;
+        }
+        return VSLAM_OK;
+    }
+    HIPCHK(hipSetDevice(fe->p.device));
+    fe->lp_state = 0;
+    HIPCHK(vslam_stream_wait(fe->stream));
+    if (fe->lp_timed) {
+        float a = 0.0f, b = 0.0f;
+        fe->lp_timed = false;
+        HIPCHK(hipEventElapsedTime(&a, fe->ev_lp[0], fe->ev_lp[1]));
+        HIPCHK(hipEventElapsedTime(&b, fe->ev_lp[1], fe->ev_lp[2]));
+        fe->lp_ms[0] += a;
+        fe->lp_ms[1] += b;
+        fe->lp_passes++;
+    }
+    const uint8_t* h = fe->h_lp + fe->lp_o_res;
+    const int32_t* cnt = (const int32_t*)(h + lp_al((size_t)n_cur * 4));
+    const int32_t* idx = (const int32_t*)((const uint8_t*)cnt + 256);
+    *n_matched_against = cnt[2];
+    *n_to_match = cnt[4];
+    if (track_out)
+        HIPCHK(hipMemcpy(track_out, fe->d_lp + fe->lp_o_track, (size_t)n_mp * sizeof(vslam_mp_track), hipMemcpyDeviceToHost));
+    const int rc = vslamh_local_points_finish((const int32_t*)h, n_cur, idx, cnt[2], fe->lp_cap, match_cur);
+    if (rc == VSLAM_ERR_UNSUPPORTED)
+        g_err = "SearchLocalPoints: more than 4096 MapPoints in view; SearchByProjection on the device takes at most 4096";
+    else if (rc)
+        g_err = "invalid arguments";
+    else
+        *nmatches = cnt[0];
+    return rc;
+}
+
+extern "C" int vslam_search_local_points(vslam_fe* fe, const vslam_frustum_params* p, const vslam_map_point* points,
+                                         const uint8_t* mp_desc, int n_mp, int points_where, const vslam_kp* dev_cur_kps,
+                                         const uint8_t* dev_cur_desc, int n_cur, const float* cur_u_right_host,
+                                         const uint8_t* cur_occupied_host, float th, float nnratio, int32_t* match_cur,
+                                         int* nmatches, int* n_to_match, int* n_matched_against, vslam_mp_track* track_out) {
+    if (!nmatches || !n_to_match || !n_matched_against || (n_cur > 0 && !match_cur)) {
+        g_err = "invalid arguments";
+        return VSLAM_ERR_INVALID;
+    }
+    int rc = vslam_search_local_points_async(fe, p, points, mp_desc, n_mp, points_where, dev_cur_kps, dev_cur_desc, n_cur,
+                                             cur_u_right_host, cur_occupied_host, th, nnratio);
+    if (rc) return rc;
+    return vslam_search_local_points_wait(fe, match_cur, nmatches, n_to_match, n_matched_against, track_out);
+}
+
+/* with vslam_fe_set_profiling on: HIP-event time of k_frustum and of k_frustum_compact alone, summed over the searches
+ * waited for since */
+extern "C" int vslam_fe_get_local_points_profile(vslam_fe* fe, double* frustum_ms, double* compact_ms, long* passes) {
+    if (!fe) return VSLAM_ERR_INVALID;
+    if (frustum_ms) *frustum_ms = fe->lp_ms[0];
+    if (compact_ms) *compact_ms = fe->lp_ms[1];
+    if (passes) *passes = fe->lp_passes;
     return VSLAM_OK;
 }
