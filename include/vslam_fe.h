@@ -73,7 +73,7 @@ typedef struct vslam_tuning {
     int32_t octree_walk_kernel;   /* retired: accepted and ignored */
     int32_t oct_fine_depth;       /* VSLAM_OCT_FINE_D: depth of the one-walk kernel's fine grid (tests force 1 or 3) */
     int32_t oct_lds_budget_kb;    /* VSLAM_OCT_LDS_BUDGET_KB: LDS a quadtree workgroup may take (16..150, default 128) */
-    int32_t oct_regkeys;          /* VSLAM_OCT_REGKEYS: 0 | 1 keys in registers between the key walks (default: batches <= 2) */
+    int32_t oct_regkeys;          /* VSLAM_OCT_REGKEYS: deprecated alias, 1 = oct_threads 1024 */
     int32_t oct_max_iter;         /* VSLAM_OCT_MAXITER: split-pass limit (default 64) */
     int32_t oct_debug;            /* VSLAM_OCT_DBG: 1 = allocate the stamp buffer of diagnostic builds */
     int32_t graphs;               /* VSLAM_GRAPH: 0 = never capture / replay HIP graphs */

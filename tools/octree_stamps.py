@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""In-kernel stamps of k_octree_v3 (diagnostic build only:  make -C vi_slam_amd/csrc EXTRA_HIPFLAGS=-DVSLAM_OCT_STAMPS after
+"""In-kernel stamps of k_octree_v4 (diagnostic build only:  make -C vi_slam_amd/csrc EXTRA_HIPFLAGS=-DVSLAM_OCT_STAMPS after
 touching vslam_octree_kernel.hip, library copied aside and loaded with VSLAM_FE_LIB=..., and VSLAM_OCT_DBG=1 in the
-environment): where the level-0 workgroup of slot 0 spends its time.  Seven stamps: start, keys gathered, fine cells
-counted, prefix sums, split passes, owners filled, keys selected.
+environment): where one workgroup of slot 0 spends its time -- level 0, or the level given with -DVSLAM_OCT_STAMP_LEVEL=n.
+Stamps: start, key walk done, prefix sums, initial nodes, one per split pass, passes left, keys selected.  B > 2 gives the
+256-thread batch kernel (profiles/octree_batch_phase_budget.txt).
     octree_stamps.py [W H NF B]   -> microseconds since the kernel's first stamp"""
 import ctypes as C
 import os

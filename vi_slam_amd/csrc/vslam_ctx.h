@@ -210,8 +210,8 @@ struct vslam_fe {
     /* GPU quadtree distribution */
     bool dev_octree = false;
     OctParams oct;
-    uint32_t* d_pts[2] = {nullptr, nullptr};  /* B x cand_cap each: keys in key order | k_octree_v4: fine cell and rank of every key */
-    uint8_t* d_oct_sorted = nullptr;          /* k_octree_v4: {key, position} sorted by fine cell, B x cand_cap x 8 bytes */
+    uint32_t* d_pts = nullptr;                /* k_octree_v4: every level's keys in key order, B x cand_cap */
+    uint8_t* d_oct_sorted = nullptr;          /* k_octree_v4: {key, position} sorted by fine cell, B x cand_cap x 8 bytes (written only by problems that split below the grid) */
     uint32_t* d_oct_lut = nullptr;            /* k_octree_v4: per level the x and y path tables (vslam::build_oct_lut) */
     int32_t* d_oct_redo = nullptr;            /* k_octree_v4: (slot, level) split nodes finer than the grid, B x VSLAM_MAX_LEVELS */
     uint32_t* d_sel_xyr = nullptr;            /* per slot / level result lists */

@@ -78,7 +78,7 @@ struct OctParams {
     int32_t maxIter;                  /* split passes allowed (64; lower only for timing experiments) */
     void* dbg;                        /* timing stamps (diagnostic builds only) */
     /* k_octree_v4: keys are counted ONCE into the leaves of an implicit quadtree of depth fineD below the initial nodes
-     * (nIni << 2*fineD fine cells, <= 16384, counters and prefix sums in LDS) and sorted by leaf; a node of depth
+     * (nIni << 2*fineD fine cells, <= 16384, best keys and prefix sums in LDS; sorted by leaf only below the grid); a node of depth
      * d <= fineD is a run of 4^(fineD-d) fine cells, so the child counts of every split pass are differences of one
      * prefix-sum array; a key's leaf is lut[lutOff + x] | lut[lutOff + lutW + y] (vslam::build_oct_lut) */
     int32_t fineD[VSLAM_MAX_LEVELS];

@@ -69,8 +69,7 @@ static void free_ctx(vslam_fe* fe) {
     hipFree(fe->d_tmp_desc[0]);
     hipFree(fe->d_tmp_desc[1]);
     hipFree(fe->d_stereo);
-    hipFree(fe->d_pts[0]);
-    hipFree(fe->d_pts[1]);
+    hipFree(fe->d_pts);
     hipFree(fe->d_oct_sorted);
     hipFree(fe->d_oct_lut);
     hipFree(fe->d_sel_xyr);
@@ -360,7 +359,7 @@ static int create_result_block(vslam_fe* fe) {
     return VSLAM_OK;
 }
 
-/* quadtree distribution on the device (k_octree_v4): the plan (vslam::plan_octree) into OctParams, key ping-pong arrays,
+/* quadtree distribution on the device (k_octree_v4): the plan (vslam::plan_octree) into OctParams, key arrays,
  * result lists; decides the placement */
 static int create_quadtree(vslam_fe* fe) {
     const vslam_fe_params& p = fe->p;
@@ -392,18 +391,17 @@ static int create_quadtree(vslam_fe* fe) {
     }
     O.maxIter = tune_or(fe->tune.oct_max_iter, 64);
     const bool on_device = fe->dev_octree = plan.fits && !(p.flags & VSLAM_FLAG_HOST_OCTREE);
-    /* threads per quadtree problem (vk_octree): 1024 for one or two images, else 256, 512 for frames above a megapixel */
+    /* threads per quadtree problem (vk_octree): 1024 for one or two images, else 256 at every frame size */
     fe->oct_threads = fe->tune.oct_threads == 256 || fe->tune.oct_threads == 512 || fe->tune.oct_threads == 1024
                           ? fe->tune.oct_threads
-                          : fe->B <= 2 ? 1024 : (size_t)p.width * p.height > 1000000 ? 512 : 256;
+                          : fe->B <= 2 ? 1024 : 256;
     if (!on_device) return VSLAM_OK; /* none of the buffers below is needed */
     if (vk_octree_set_max_lds((size_t)O.fineLdsOff + (size_t)O.fineLdsBytes + 16) != 0) {
         g_err = "hipFuncSetAttribute(k_octree, max dynamic LDS) failed";
         return VSLAM_ERR_HIP;
     }
     const size_t np = (size_t)fe->B * fe->cand_cap;
-    HIPCHK(hipMalloc((void**)&fe->d_pts[0], np * 4));
-    HIPCHK(hipMalloc((void**)&fe->d_pts[1], np * 4));
+    HIPCHK(hipMalloc((void**)&fe->d_pts, np * 4));
     HIPCHK(hipMalloc((void**)&fe->d_sel_xyr, (size_t)fe->B * O.selStride * 4));
     HIPCHK(hipMalloc((void**)&fe->d_sel_cnt, (size_t)fe->B * VSLAM_MAX_LEVELS * 4));
     HIPCHK(hipMalloc((void**)&fe->d_oct_sorted, np * 8));
@@ -1029,7 +1027,7 @@ static int select_dev(vslam_fe* fe, int nimg, int lap0, int lap1) {
     const int rc = enqueue_blur(fe, nimg);
     if (rc) return rc;
     if (fe->profiling) HIPCHK(hipEventRecord(fe->ev_prof[7], st));
-    vk_octree(st, fe->d_cand, fe->cand_stride, (int)fe->cells.size(), fe->oct, fe->d_pts[0], fe->d_pts[1],
+    vk_octree(st, fe->d_cand, fe->cand_stride, (int)fe->cells.size(), fe->oct, fe->d_pts,
               fe->d_oct_sorted, (size_t)fe->cand_cap, fe->d_sel_xyr, fe->d_sel_cnt, d_err, fe->p.nlevels, nimg,
               fe->d_oct_redo, fe->tune.oct_regkeys, fe->oct_threads);
     vk_assign_out(st, fe->oct, fe->geom, fe->d_sel_xyr, fe->d_sel_cnt, lap0, lap1, fe->d_sel, fe->d_counts, fe->cap,

@@ -623,8 +623,9 @@ void plan_octree(const int* quota, const int* lw, const int* lh, const int* cell
     /* k_octree_v4's fine grid: one level deeper than the depth at which a full quadtree has N nodes (nIni * 4^d
      * at depth d), so that the split passes, which stop at N nodes, mostly stay above it; keys that cluster
      * below it are handled exactly by the kernel's in-cell path, so the depth only decides speed.  Both arrays
-     * of the largest level must fit LDS next to the node arrays (budget), at most 16384 cells (the cell
-     * index travels in 16 bits), and no cell may be able to hold 65536 keys (the rank does too).
+     * of the largest level must fit LDS next to the node arrays (budget), and there are at most 16384 cells:
+     * the kernel zeroes and scans both arrays once per problem, and that many cells are already 128 KB of LDS.
+     * (The two-walk kernel also bounded the keys a cell can hold, for a 16-bit rank; nothing packs a rank now.)
      * forced_depth forces a depth where it is admissible (tests: deep splits everywhere). */
     const size_t nb = (node_bytes(P.maxNodes) + 15) & ~(size_t)15;
     int maxcells = 0;
@@ -635,13 +636,7 @@ void plan_octree(const int* quota, const int* lw, const int* lh, const int* cell
         D += 1;
         if (forced_depth >= 0) D = forced_depth;
         D = std::max(1, std::min(D, 11));
-        auto cell_keys = [&](int d) { /* strict 3x3 maxima a cell of depth d can hold: every other pixel of every other row */
-            const long long cw = (W / nIni >> d) + 2, ch = (H >> d) + 2;
-            return ((cw + 1) / 2) * ((ch + 1) / 2);
-        };
-        while (D < 11 && cell_keys(D) >= 65535) D++;
-        while (D > 1 && (((long long)nIni << (2 * D)) > 16384 || nb + 2 * (((size_t)nIni << (2 * D)) + 1) * 4 + 16 > budget) &&
-               cell_keys(D - 1) < 65535)
+        while (D > 1 && (((long long)nIni << (2 * D)) > 16384 || nb + 2 * (((size_t)nIni << (2 * D)) + 1) * 4 + 16 > budget))
             D--;
         P.fineD[l] = D;
         maxcells = std::max(maxcells, nIni << (2 * D));

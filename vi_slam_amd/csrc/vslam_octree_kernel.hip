@@ -22,9 +22,8 @@
 
 #include <mutex>
 
-#define OKPT 16 /* k_octree_v4<true, ...>: keys per thread kept in registers (problems up to 16384 keys) */
 #ifndef O4BATCH
-#define O4BATCH 8 /* k_octree_v4: keys per thread and batch of the streaming walks (loads in flight per lane) */
+#define O4BATCH 8 /* k_octree_v4: keys per thread and batch of the key walk (loads in flight per lane) */
 #endif
 typedef unsigned long long u64;
 
@@ -71,24 +70,26 @@ __device__ __forceinline__ T block_excl_scan(T v, T* s_wave, T* total) {
 }
 
 /* ------------------------------------------------------------------------------------------------
- * k_octree_v4: the distribution with TWO key walks in all, no walk per pass, and no limit on how finely keys cluster.
+ * k_octree_v4: the distribution with ONE key walk, no walk per pass, and no limit on how finely keys cluster.
  *
  * DivideNode's boundaries depend on the node alone (midpoints, fextractor.cpp:474-475), never on the keys, so the
  * quadtree below an initial node is a fixed implicit tree; and because x and y are halved separately, a key's path to
  * depth D (one 2-bit quadrant per depth) is two table look-ups, path = xs[x] | ys[y] (vslam::build_oct_lut).
- *   walk 1  every key is read ONCE from the FAST cells' segments (position in cell order = the reference's key order),
- *           its leaf of depth D ("fine cell", nIni * 4^D of them, counters in LDS) is counted with a returning LDS
- *           atomic: the old count is the key's rank inside its fine cell;
- *           -> one prefix sum over the fine cells;
- *   walk 2  every key is stored at sorted[PS[cell] + rank]: the keys are now sorted by fine cell, so a node of depth
- *           d <= D IS the contiguous run of the 4^(D-d) fine cells under its path, in the prefix array and in the keys.
+ *   walk    every key is read ONCE from the FAST cells' segments (position in cell order = the reference's key order);
+ *           its leaf of depth D ("fine cell", nIni * 4^D of them) gets two LDS atomics: the cell's key count, and the
+ *           cell's best key, a max on response << 20 | ~position (28 bits).  The key is also stored in key order.
+ *           -> one prefix sum over the fine counts, in place.  A node of depth d <= D IS the contiguous run of the
+ *           4^(D-d) fine cells under its path, in the prefix array and in the best keys.
  *   passes  the reference's list logic (list order, "largest first until N", creation ranks); the child counts a pass
  *           needs are four differences of the prefix array, per NODE, not per key.  A node DEEPER than the grid (keys
  *           closer together than a fine cell: real images do that on the sparse top levels, where every node is split
- *           down to single keys) lies inside one fine cell: its few keys are enumerated from the sorted array and
- *           tested against the node's path by walking the halvings -- exact at any depth, no fallback kernel.
- *   select  "best response, first key wins" (fextractor.cpp:732-751): four lanes per final node reduce its run of
- *           the sorted array (response, then original position); no atomics, no owner table.
+ *           down to single keys) lies inside one fine cell.  The first pass that meets one sorts the keys by fine cell
+ *           (a second walk, over the stored keys: rank from a returning atomic, sorted[PS[cell] + rank]); the node's
+ *           few keys are then enumerated from its cell's run and tested against the node's path by walking the
+ *           halvings -- exact at any depth, no fallback kernel.  Most problems never sort.
+ *   select  "best response, first key wins" (fextractor.cpp:732-751): four lanes per final node reduce the best keys of
+ *           its cells to the winner's position, and the winners are gathered from the keys in key order; a problem
+ *           that sorted reduces the node's run of the sorted keys instead (response, then original position).
  * One workgroup per (slot, level): the quadtree stays a narrow kernel that hides behind the grid-filling ones.
  * History (git): v3 kept an owner table instead of sorted keys (gather + count + owner fill + select walks, fine cell by D
  * dependent halvings per key: 52 / 89 / 251 us for the level-0 problem at KITTI N=1000 / 2000 / 1080p N=4000) and
@@ -124,13 +125,26 @@ __device__ __forceinline__ uint32_t wave_incl_add(uint32_t v) {
     return v;
 }
 
-/* REGKEYS: keys (and their cell | rank words) of problems up to OKPT * 1024 keys stay in registers between the two walks
- * (1-2 images: latency); otherwise both are written to the slot's scratch by walk 1 and re-read, coalesced, by walk 2
- * (batches: fewer VGPRs, so that foreign waves fit next to a 1024-thread workgroup). */
-template <bool REGKEYS, int OTV> /* OTV: threads of the workgroup (256 / 512 / 1024, vk_octree) */
+/* packed child counts of a node at or below the grid depth D: its keys are among the few of ONE fine cell's sorted run */
+__device__ __forceinline__ u64 deep_child_counts(const uint2* sorted, const uint32_t* PS, uint32_t path, int depth, int D,
+                                                 float hX, int nIni, int Hh) {
+    u64 c = 0ull;
+    const uint32_t f = path >> (2 * (depth - D));
+    for (uint32_t j = PS[f]; j < PS[f + 1]; j++) {
+        const uint32_t kp = oct_key_path(sorted[j].x, hX, nIni, Hh, depth + 1);
+        if ((kp >> 2) == path) c += onehot((int)(kp & 3u));
+    }
+    return c;
+}
+
+/* the key that wins a fine cell, as one 32-bit LDS atomicMax: response, then the EARLIEST position in key order (n < 2^20) */
+#define OCT_BEST(key, pos) ((((key) >> 24) << 20) | (0xFFFFFu - (uint32_t)(pos)))
+#define OCT_BEST_POS(b) (0xFFFFFu - ((b) & 0xFFFFFu))
+
+template <int OTV> /* OTV: threads of the workgroup (256 / 512 / 1024, vk_octree) */
 __global__ void __launch_bounds__(OTV)
 k_octree_v4(const uint8_t* __restrict__ cand_region, size_t cand_stride, int ncells, OctParams P, uint32_t* keys_a,
-            uint32_t* aux_a, uint2* sorted_a, size_t pts_stride, uint32_t* sel_xyr, int32_t* sel_cnt, int32_t* err_flag,
+            uint2* sorted_a, size_t pts_stride, uint32_t* sel_xyr, int32_t* sel_cnt, int32_t* err_flag,
             int32_t* deep_flags) {
     extern __shared__ __align__(16) uint8_t osm[];
     const int MAXN = P.maxNodes;
@@ -151,9 +165,8 @@ k_octree_v4(const uint8_t* __restrict__ cand_region, size_t cand_stride, int nce
     const uint32_t* hdr = (const uint32_t*)(cand_region + (size_t)slot * cand_stride);
     const CellOut* cout = (const CellOut*)(hdr + 2);
     const uint32_t* cand = (const uint32_t*)(cout + ncells);
-    uint32_t* pa = keys_a + (size_t)slot * pts_stride;
-    uint32_t* aux = aux_a + (size_t)slot * pts_stride;   /* fine cell | rank in the cell << 16 of every key */
-    uint2* sorted = sorted_a + (size_t)slot * pts_stride; /* {key, position in key order}, sorted by fine cell */
+    uint32_t* pa = keys_a + (size_t)slot * pts_stride;    /* the level's keys in key order */
+    uint2* sorted = sorted_a + (size_t)slot * pts_stride; /* {key, position in key order}, sorted by fine cell: built on demand */
     uint32_t* out = sel_xyr + (size_t)slot * P.selStride + P.selOff[level];
     int32_t* ocnt = sel_cnt + slot * VSLAM_MAX_LEVELS + level;
     if (tid == 0) {
@@ -163,7 +176,10 @@ k_octree_v4(const uint8_t* __restrict__ cand_region, size_t cand_stride, int nce
 #ifdef VSLAM_OCT_STAMPS
     int dbgn3 = 0;
     unsigned long long* DBG3 = (unsigned long long*)P.dbg;
-#define STAMP3() do { if (DBG3 && tid == 0 && level == 0 && slot == 0 && dbgn3 < 60) DBG3[dbgn3++] = __builtin_amdgcn_s_memrealtime(); } while (0)
+#ifndef VSLAM_OCT_STAMP_LEVEL
+#define VSLAM_OCT_STAMP_LEVEL 0 /* the level of slot 0 whose workgroup is stamped */
+#endif
+#define STAMP3() do { if (DBG3 && tid == 0 && level == VSLAM_OCT_STAMP_LEVEL && slot == 0 && dbgn3 < 60) DBG3[dbgn3++] = __builtin_amdgcn_s_memrealtime(); } while (0)
 #else
 #define STAMP3() do { } while (0)
 #endif
@@ -198,7 +214,6 @@ k_octree_v4(const uint8_t* __restrict__ cand_region, size_t cand_stride, int nce
         return;
     }
     pa += off0;
-    aux += off0;
     sorted += off0;
     /* cell offsets (+ sentinel) and the cells' segment bases, borrowed from the node arrays (2 * ncl + 1 words; the host
      * sizes MAXN >= ncl / 4, i.e. 14 * MAXN words of node arrays): the walk needs ONE global round trip (the keys) */
@@ -223,31 +238,25 @@ k_octree_v4(const uint8_t* __restrict__ cand_region, size_t cand_stride, int nce
     const int Hh = P.H[level];
     const int D = P.fineD[level];
     const int cells = nIni << (2 * D);
-    uint32_t* Hc = (uint32_t*)(osm + P.fineLdsOff); /* key counts of the fine cells */
-    uint32_t* PS = Hc + cells + 1;                  /* their exclusive prefix sums */
+    uint32_t* PS = (uint32_t*)(osm + P.fineLdsOff); /* key counts of the fine cells, then (in place) their exclusive prefix sums */
+    uint32_t* Bst = PS + cells + 1;                 /* OCT_BEST of every fine cell; counters of the sort where it is built */
     const uint32_t* __restrict__ xs = P.lut + P.lutOff[level];
     const uint32_t* __restrict__ ys = xs + P.lutW[level];
-    for (int i = tid; i <= cells; i += OTV) Hc[i] = 0u;
+    for (int i = tid; i <= cells; i += OTV) PS[i] = Bst[i] = 0u;
     /* the path tables are cold (another XCD's L2 or HBM) the first time a workgroup touches them: start pulling their
      * lines now, the key loads below hide the round trip */
     uint32_t warm = 0u;
-    if (tid * 16 < P.lutW[level] + Hh + 1) warm = xs[tid * 16]; /* consumed (by nothing) behind walk 1 */
+    if (tid * 16 < P.lutW[level] + Hh + 1) warm = xs[tid * 16]; /* consumed (by nothing) behind the walk */
     __syncthreads();
 
-    /* positions are dealt to WAVES in contiguous chunks of EW (a multiple of 64) and to the lanes of a wave interleaved:
-     * lane l holds positions wbeg + 64 k + l, so that a wave's loads (mostly one FAST cell segment after the other) and
-     * its stores are coalesced */
-    const bool inReg = REGKEYS && n <= OKPT * OTV;
-    const int KW = (n + OTV - 1) / OTV, EW = KW * 64; /* keys per lane, positions per wave */
-    const int wbeg = wv * EW;
-    uint32_t keyR[OKPT];
-    uint32_t auxR[OKPT];
-#pragma unroll
-    for (int k = 0; k < OKPT; k++) keyR[k] = auxR[k] = 0u;
-
-    /* ---- 1. walk 1: read every key, count it into its fine cell; the counter's old value is its rank in the cell */
+    /* ---- 1. the ONE walk over the keys: every key is read once, counted into its fine cell, offered as the cell's best
+     * key, and kept in key order (pa) for the gather of the winners and for the sort of a problem that splits below the
+     * grid.  Positions are dealt to WAVES in contiguous chunks of EW (a multiple of 64) and to the lanes of a wave
+     * interleaved: lane l holds positions wbeg + 64 k + l, so that a wave's loads (mostly one FAST cell segment after the
+     * other) and its stores are coalesced */
     {
-        const int p0 = wbeg + lane;
+        const int KW = (n + OTV - 1) / OTV, EW = KW * 64; /* keys per lane, positions per wave */
+        const int p0 = wv * EW + lane;
         int c = 0;
         if (p0 < n) {
             int lo = 0, hi = ncl - 1; /* last cell with coff <= p0 (empty cells share an offset: the last one holds it) */
@@ -259,72 +268,46 @@ k_octree_v4(const uint8_t* __restrict__ cand_region, size_t cand_stride, int nce
             c = lo;
         }
         uint32_t cbase = p0 < n ? cbas[c] : 0u, cfirst = p0 < n ? coff[c] : 0u, cnext = p0 < n ? coff[c + 1] : 0u;
-        if (inReg) {
+        for (int kb = 0; kb < KW; kb += O4BATCH) { /* O4BATCH loads in flight, then the table look-ups, then the atomics */
+            uint32_t kk[O4BATCH], ff[O4BATCH];
 #pragma unroll
-            for (int k = 0; k < OKPT; k++) {
-                const int i = p0 + 64 * k;
-                if (k < KW && i < n) {
+            for (int j = 0; j < O4BATCH; j++) {
+                const int i = p0 + 64 * (kb + j);
+                kk[j] = 0u;
+                if (kb + j < KW && i < n) {
                     while ((uint32_t)i >= cnext) { /* on to the cell that holds position i */
                         c++;
                         cfirst = cnext;
                         cnext = coff[c + 1];
                         cbase = cbas[c];
                     }
-                    keyR[k] = cand[cbase + ((uint32_t)i - cfirst)];
+                    kk[j] = cand[cbase + ((uint32_t)i - cfirst)];
                 }
             }
 #pragma unroll
-            for (int k = 0; k < OKPT; k++)
-                if (k < KW && p0 + 64 * k < n) auxR[k] = xs[keyR[k] & 0xFFF] | ys[(keyR[k] >> 12) & 0xFFF];
+            for (int j = 0; j < O4BATCH; j++)
+                ff[j] = (kb + j < KW && p0 + 64 * (kb + j) < n) ? xs[kk[j] & 0xFFF] | ys[(kk[j] >> 12) & 0xFFF] : 0u;
 #pragma unroll
-            for (int k = 0; k < OKPT; k++)
-                if (k < KW && p0 + 64 * k < n) auxR[k] |= atomicAdd(&Hc[auxR[k]], 1u) << 16;
-        } else {
-            for (int kb = 0; kb < KW; kb += O4BATCH) { /* O4BATCH loads in flight, then the table look-ups, then the atomics */
-                uint32_t kk[O4BATCH], ff[O4BATCH];
-#pragma unroll
-                for (int j = 0; j < O4BATCH; j++) {
-                    const int i = p0 + 64 * (kb + j);
-                    kk[j] = 0u;
-                    if (kb + j < KW && i < n) {
-                        while ((uint32_t)i >= cnext) {
-                            c++;
-                            cfirst = cnext;
-                            cnext = coff[c + 1];
-                            cbase = cbas[c];
-                        }
-                        kk[j] = cand[cbase + ((uint32_t)i - cfirst)];
-                    }
+            for (int j = 0; j < O4BATCH; j++) {
+                const int i = p0 + 64 * (kb + j);
+                if (kb + j < KW && i < n) {
+                    atomicAdd(&PS[ff[j]], 1u);
+                    atomicMax(&Bst[ff[j]], OCT_BEST(kk[j], i));
+                    pa[i] = kk[j];
                 }
-#pragma unroll
-                for (int j = 0; j < O4BATCH; j++)
-                    ff[j] = (kb + j < KW && p0 + 64 * (kb + j) < n) ? xs[kk[j] & 0xFFF] | ys[(kk[j] >> 12) & 0xFFF] : 0u;
-#pragma unroll
-                for (int j = 0; j < O4BATCH; j++)
-                    if (kb + j < KW && p0 + 64 * (kb + j) < n) ff[j] |= atomicAdd(&Hc[ff[j]], 1u) << 16;
-#pragma unroll
-                for (int j = 0; j < O4BATCH; j++)
-                    if (kb + j < KW && p0 + 64 * (kb + j) < n) {
-                        pa[p0 + 64 * (kb + j)] = kk[j];
-                        aux[p0 + 64 * (kb + j)] = ff[j];
-                    }
             }
         }
     }
     asm volatile("" ::"v"(warm));
-    __syncthreads(); /* coff (in the node arrays) is free again; the counters are complete */
+    __syncthreads(); /* coff (in the node arrays) is free again; the counters and the best keys are complete */
     STAMP3();
-    {   /* exclusive prefix sums of the fine counts, LDS to LDS */
+    {   /* exclusive prefix sums of the fine counts, in place */
         const int ntile = (cells + 63) >> 6, tpw = (ntile + OTV / 64 - 1) / (OTV / 64); /* tiles per wave */
         const int t1 = min((wv + 1) * tpw, ntile);
         uint32_t carry = 0;
         for (int t = wv * tpw; t < t1; t++) {
             const int c = t * 64 + lane;
-            const uint32_t h = c < cells ? Hc[c] : 0u;
-            /* a key's rank inside its fine cell travels in 16 bits next to the cell index (walk 1); the host sizes the
-             * grid so that no cell can hold that many keys, this is the runtime guard behind that bound: the pass is
-             * reported (VSLAM_ERR_CAPACITY), never silently mis-sorted */
-            if (h >= 65536u) atomicOr(err_flag, 1);
+            const uint32_t h = c < cells ? PS[c] : 0u;
             const uint32_t inc = wave_incl_add(h);
             if (c < cells) PS[c] = carry + inc - h;
             carry += (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
@@ -343,30 +326,6 @@ k_octree_v4(const uint8_t* __restrict__ cand_region, size_t cand_stride, int nce
     __syncthreads();
     STAMP3();
 
-    /* ---- 2. walk 2: the keys sorted by fine cell (order inside a cell: whatever the atomics gave; the selection below
-     * decides by original position, which travels with the key) */
-    if (inReg) {
-#pragma unroll
-        for (int k = 0; k < OKPT; k++) {
-            const int i = wbeg + lane + 64 * k;
-            if (k < KW && i < n) sorted[PS[auxR[k] & 0xFFFFu] + (auxR[k] >> 16)] = make_uint2(keyR[k], (uint32_t)i);
-        }
-    } else {
-        for (int base = tid; base < n; base += O4BATCH * OTV) {
-            uint32_t kk[O4BATCH], ff[O4BATCH];
-#pragma unroll
-            for (int j = 0; j < O4BATCH; j++) {
-                const int i = base + j * OTV;
-                kk[j] = i < n ? pa[i] : 0u;
-                ff[j] = i < n ? aux[i] : 0u;
-            }
-#pragma unroll
-            for (int j = 0; j < O4BATCH; j++) {
-                const int i = base + j * OTV;
-                if (i < n) sorted[PS[ff[j] & 0xFFFFu] + (ff[j] >> 16)] = make_uint2(kk[j], (uint32_t)i);
-            }
-        }
-    }
     /* initial nodes; ONode.begin = path code of the node (root << 2 depth | quadrants), depth in cf[31:28] */
     if (tid == 0) {
         int li = 0;
@@ -385,11 +344,12 @@ k_octree_v4(const uint8_t* __restrict__ cand_region, size_t cand_stride, int nce
         }
         s_size = li;
     }
-    __syncthreads(); /* also: the sorted keys (global memory, this CU's stores) are complete for the whole workgroup */
+    __syncthreads(); /* also: the keys in key order (global memory, this CU's stores) are complete for the whole workgroup */
     STAMP3();
 
     /* ---- 3. split passes: the reference's list logic; the children's key counts come from the prefix sums */
     int phase = 1;
+    bool haveSorted = false; /* uniform: the keys sorted by fine cell exist (only a problem that splits below the grid builds them) */
     const int KN = (MAXN + OTV - 1) / OTV;
     for (int iter = 0; iter < P.maxIter; iter++) {
         const int size0 = s_size;
@@ -408,12 +368,8 @@ k_octree_v4(const uint8_t* __restrict__ cand_region, size_t cand_stride, int nce
                         const uint32_t p0 = PS[cb0], p1 = PS[cb0 + q4], p2 = PS[cb0 + 2 * q4], p3 = PS[cb0 + 3 * q4];
                         c = (u64)(p1 - p0) | ((u64)(p2 - p1) << FB) | ((u64)(p3 - p2) << (2 * FB));
                     } else { /* finer than the grid: the node's keys are among the few of ONE fine cell */
-                        s_deep = 1; /* statistics only (benign race: all writers store 1) */
-                        const uint32_t f = path >> (2 * (depth - D));
-                        for (uint32_t j = PS[f]; j < PS[f + 1]; j++) {
-                            const uint32_t kp = oct_key_path(sorted[j].x, hX, nIni, Hh, depth + 1);
-                            if ((kp >> 2) == path) c += onehot((int)(kp & 3u));
-                        }
+                        s_deep = 1; /* benign race: all writers store 1, all readers wait for the barrier below */
+                        if (haveSorted) c = deep_child_counts(sorted, PS, path, depth, D, hX, nIni, Hh);
                     }
                     /* descending (count, "created later" == smaller list index): one unsigned compare */
                     kq = (ND4_COUNT(nd) << 12) | (uint32_t)(4095 - v);
@@ -425,6 +381,38 @@ k_octree_v4(const uint8_t* __restrict__ cand_region, size_t cand_stride, int nce
         /* pad the sort keys to a multiple of four (the rank loop reads them four at a time) */
         if (tid < 4 && size0 + tid < ((size0 + 3) & ~3)) Kq[size0 + tid] = 0u;
         __syncthreads();
+        if (s_deep && !haveSorted) {
+            /* The first pass that meets a node below the grid sorts the keys by fine cell: {key, position} at
+             * sorted[PS[cell] + rank], the rank from a returning LDS atomic on counters that take the place of the cells'
+             * best keys (the select then reads the sorted runs instead).  Order inside a cell: whatever the atomics give;
+             * the select decides by original position, which travels with the key.  s_deep only ever goes from 0 to 1 and
+             * is written in front of the barrier above: the decision is uniform. */
+            for (int i = tid; i < cells; i += OTV) Bst[i] = 0u;
+            __syncthreads();
+            for (int base = tid; base < n; base += O4BATCH * OTV) {
+                uint32_t kk[O4BATCH], ff[O4BATCH];
+#pragma unroll
+                for (int j = 0; j < O4BATCH; j++) kk[j] = base + j * OTV < n ? pa[base + j * OTV] : 0u;
+#pragma unroll
+                for (int j = 0; j < O4BATCH; j++) ff[j] = base + j * OTV < n ? xs[kk[j] & 0xFFF] | ys[(kk[j] >> 12) & 0xFFF] : 0u;
+#pragma unroll
+                for (int j = 0; j < O4BATCH; j++) {
+                    const int i = base + j * OTV;
+                    if (i < n) sorted[PS[ff[j]] + atomicAdd(&Bst[ff[j]], 1u)] = make_uint2(kk[j], (uint32_t)i);
+                }
+            }
+            haveSorted = true;
+            __syncthreads();
+            for (int k = 0; k < KN; k++) { /* the counts that step A left open */
+                const int v = tid * KN + k;
+                if (v < size0) {
+                    const ONode nd = cur[v];
+                    if (!ND_NOMORE(nd) && ND4_DEPTH(nd) >= D)
+                        Cnt[v] = deep_child_counts(sorted, PS, nd.begin, ND4_DEPTH(nd), D, hX, nIni, Hh);
+                }
+            }
+            __syncthreads();
+        }
         /* D1. processing rank of every expandable node */
         uint32_t nexp_mine = 0;
         for (int k = 0; k < KN; k++) {
@@ -558,61 +546,86 @@ k_octree_v4(const uint8_t* __restrict__ cand_region, size_t cand_stride, int nce
     }
 
     STAMP3();
-    /* ---- 4. best response per node, first in key order wins (fextractor.cpp:732-751): four lanes per node reduce its
-     * run of the sorted keys on (response, ~position) */
+    /* ---- 4. best response per node, first in key order wins (fextractor.cpp:732-751).  A node of depth d <= D is a run of
+     * 4^(D-d) fine cells: four lanes reduce the cells' best keys (walk 1) to the winner's position, then all winners are
+     * gathered from the keys in key order with independent loads.  A problem that went below the grid has the sorted
+     * keys instead: four lanes per node reduce its run of them on (response, ~position). */
     const int size = s_size;
-    for (int v0 = 0; v0 < size; v0 += OTV / 4) {
-        const int v = v0 + (tid >> 2), sub = tid & 3;
-        u64 best = 0ull;
-        uint32_t bkey = 0u;
-        if (v < size) {
-            const ONode nd = cur[v];
-            const int depth = ND4_DEPTH(nd);
-            const uint32_t path = nd.begin;
-            if (depth <= D) {
-                const uint32_t lo = PS[path << (2 * (D - depth))], hi = PS[(path + 1u) << (2 * (D - depth))];
-                for (uint32_t j0 = lo + (uint32_t)sub; j0 < hi; j0 += 16) { /* four loads in flight per lane */
-                    uint2 r[4];
+    if (!haveSorted) {
+        /* A node of depth d reduces 4^(D-d) cells with four lanes: one or four cells for the nodes of a list that reached
+         * its quota, but 4^D for an initial node that was never split (a list that ended early: few nodes, each a long
+         * serial run of LDS reads, at most cells / 4 per lane in all).  Not dealt wider: such lists belong to the sparse
+         * top levels, whose workgroups finish long before level 0's. */
+        uint32_t* win = (uint32_t*)nxt; /* the list that is not current: position of every node's winner */
+        for (int v0 = 0; v0 < size; v0 += OTV / 4) {
+            const int v = v0 + (tid >> 2), sub = tid & 3;
+            uint32_t best = 0u;
+            if (v < size) {
+                const ONode nd = cur[v];
+                const int sh = 2 * (D - ND4_DEPTH(nd)); /* no node is deeper than the grid here */
+                const uint32_t lo = nd.begin << sh, hi = (nd.begin + 1u) << sh;
+                for (uint32_t j = lo + (uint32_t)sub; j < hi; j += 4) best = max(best, Bst[j]);
+            }
+            best = max(best, (uint32_t)__shfl_xor((int)best, 1, 64)); /* the node's four lanes are neighbours in the wave */
+            best = max(best, (uint32_t)__shfl_xor((int)best, 2, 64));
+            if (v < size && sub == 0) win[v] = OCT_BEST_POS(best); /* every listed node holds at least one key */
+        }
+        __syncthreads();
+        for (int v = tid; v < size; v += OTV) out[v] = pa[win[v]];
+    } else {
+        for (int v0 = 0; v0 < size; v0 += OTV / 4) {
+            const int v = v0 + (tid >> 2), sub = tid & 3;
+            u64 best = 0ull;
+            uint32_t bkey = 0u;
+            if (v < size) {
+                const ONode nd = cur[v];
+                const int depth = ND4_DEPTH(nd);
+                const uint32_t path = nd.begin;
+                if (depth <= D) {
+                    const uint32_t lo = PS[path << (2 * (D - depth))], hi = PS[(path + 1u) << (2 * (D - depth))];
+                    for (uint32_t j0 = lo + (uint32_t)sub; j0 < hi; j0 += 16) { /* four loads in flight per lane */
+                        uint2 r[4];
 #pragma unroll
-                    for (int u = 0; u < 4; u++) r[u] = j0 + 4 * u < hi ? sorted[j0 + 4 * u] : make_uint2(0u, 0xFFFFFFFFu);
+                        for (int u = 0; u < 4; u++) r[u] = j0 + 4 * u < hi ? sorted[j0 + 4 * u] : make_uint2(0u, 0xFFFFFFFFu);
 #pragma unroll
-                    for (int u = 0; u < 4; u++) {
-                        const u64 a = ((u64)(r[u].x >> 24) << 32) | (u64)(0xFFFFFFFFu - r[u].y);
-                        if (j0 + 4 * u < hi && a >= best) { /* >=: a key of response 0 at position 0xFFFFFFFF cannot exist, so 'best == 0' means none yet */
-                            best = a;
-                            bkey = r[u].x;
+                        for (int u = 0; u < 4; u++) {
+                            const u64 a = ((u64)(r[u].x >> 24) << 32) | (u64)(0xFFFFFFFFu - r[u].y);
+                            if (j0 + 4 * u < hi && a >= best) { /* >=: a key of response 0 at position 0xFFFFFFFF cannot exist, so 'best == 0' means none yet */
+                                best = a;
+                                bkey = r[u].x;
+                            }
                         }
                     }
-                }
-            } else { /* a node inside one fine cell: test the cell's keys against the node's path */
-                const uint32_t f = path >> (2 * (depth - D));
-                for (uint32_t j = PS[f] + (uint32_t)sub; j < PS[f + 1]; j += 4) {
-                    const uint2 r = sorted[j];
-                    if (oct_key_path(r.x, hX, nIni, Hh, depth) == path) {
-                        const u64 a = ((u64)(r.x >> 24) << 32) | (u64)(0xFFFFFFFFu - r.y);
-                        if (a >= best) {
-                            best = a;
-                            bkey = r.x;
+                } else { /* a node inside one fine cell: test the cell's keys against the node's path */
+                    const uint32_t f = path >> (2 * (depth - D));
+                    for (uint32_t j = PS[f] + (uint32_t)sub; j < PS[f + 1]; j += 4) {
+                        const uint2 r = sorted[j];
+                        if (oct_key_path(r.x, hX, nIni, Hh, depth) == path) {
+                            const u64 a = ((u64)(r.x >> 24) << 32) | (u64)(0xFFFFFFFFu - r.y);
+                            if (a >= best) {
+                                best = a;
+                                bkey = r.x;
+                            }
                         }
                     }
                 }
             }
-        }
 #pragma unroll
-        for (int o = 1; o < 4; o <<= 1) { /* the node's four lanes are neighbours in the wave */
-            const u64 ob = __shfl_xor(best, o, 64);
-            const uint32_t ok = __shfl_xor(bkey, o, 64);
-            if (ob > best) {
-                best = ob;
-                bkey = ok;
+            for (int o = 1; o < 4; o <<= 1) { /* the node's four lanes are neighbours in the wave */
+                const u64 ob = __shfl_xor(best, o, 64);
+                const uint32_t ok = __shfl_xor(bkey, o, 64);
+                if (ob > best) {
+                    best = ob;
+                    bkey = ok;
+                }
             }
+            if (v < size && sub == 0) out[v] = bkey; /* every listed node holds at least one key */
         }
-        if (v < size && sub == 0) out[v] = bkey; /* every listed node holds at least one key */
     }
 #ifdef VSLAM_OCT_STAMPS
     __syncthreads();
     STAMP3();
-    if (DBG3 && tid == 0 && level == 0 && slot == 0) DBG3[63] = dbgn3;
+    if (DBG3 && tid == 0 && level == VSLAM_OCT_STAMP_LEVEL && slot == 0) DBG3[63] = dbgn3;
 #endif
     if (tid == 0) {
         *ocnt = size;
@@ -702,27 +715,28 @@ k_assign_out(OctParams P, PyramidGeom g, uint32_t* sel_xyr, int32_t* sel_cnt,
 size_t vk_octree_lds_bytes(int maxNodes) { return (size_t)maxNodes * (16 + 16 + 8 + 8 + 2 + 2 + 2 + 2) + 64; }
 
 void vk_octree(hipStream_t st, const uint8_t* cand_region, size_t cand_stride, int ncells, const OctParams& P,
-               uint32_t* keys_a, uint32_t* aux_a, void* sorted_a, size_t pts_stride,
+               uint32_t* keys_a, void* sorted_a, size_t pts_stride,
                uint32_t* sel_xyr, int32_t* sel_cnt, int32_t* err_flag, int nlevels, int nslots, int32_t* deep_flags,
                int regkeys /* vslam_tuning.oct_regkeys: -1 by batch size, 0 | 1 forced */, int threads /* 256 | 512 | 1024 */) {
     const dim3 grid(nslots, nlevels);
-    /* Keys in registers save walk 2 its re-read, at 32 VGPRs per thread; a 1024-thread workgroup then leaves less room
-     * for foreign waves on its CU.  With several contexts in flight the neighbours matter more than the re-read
-     * (default: registers only for one or two images, where latency is what counts). */
+    /* oct_regkeys is a deprecated alias: it used to keep the keys in registers between two walks, in a 1024-thread
+     * workgroup.  There is one walk now and nothing to keep; 1 means what oct_threads = 1024 means, 0 and -1 leave the
+     * choice to oct_threads (whose default is 1024 for one or two images, where latency is what counts). */
     const bool rk = regkeys < 0 ? nslots <= 2 : regkeys == 1;
     const size_t lds = (size_t)P.fineLdsOff + (size_t)P.fineLdsBytes;
-    /* Threads per problem.  1024 finish a single frame's level-0 problem soonest (and hold its keys in registers); in a
+    /* Threads per problem.  1024 finish a single frame's level-0 problem soonest; in a
      * batch every (slot, level) problem has a workgroup of its own anyway, and a SMALL workgroup leaves the CU's wave
      * slots and issue cycles to the other contexts' kernels: 256 instead of 1024 threads is +4 % mono, +7 % stereo,
-     * +13 % mono at 2000 features in the pipeline; 1080p, with 65 k keys on level 0, wants 512 (+2 %; 256: -2 %) */
+     * +13 % mono at 2000 features in the pipeline (measured with the two-walk kernel).  1080p, with 65 k keys on level 0,
+     * wanted 512 then (+2 %); with one walk 512 alone is the shortest stage and LOSES 4 % in the pipeline against the
+     * two-walk kernel, while 256 gains 3-5 % (profiles/octree_critical_path_ab.txt): 256 for every batch. */
     const int th = rk ? 1024 : (threads == 256 || threads == 512) ? threads : 1024;
-#define OCT4_LAUNCH(RK, TH)                                                                                             \
-    hipLaunchKernelGGL((k_octree_v4<RK, TH>), grid, dim3(TH), lds, st, cand_region, cand_stride, ncells, P, keys_a, aux_a, \
+#define OCT4_LAUNCH(TH)                                                                                          \
+    hipLaunchKernelGGL((k_octree_v4<TH>), grid, dim3(TH), lds, st, cand_region, cand_stride, ncells, P, keys_a, \
                        (uint2*)sorted_a, pts_stride, sel_xyr, sel_cnt, err_flag, deep_flags)
-    if (rk) OCT4_LAUNCH(true, 1024);
-    else if (th == 256) OCT4_LAUNCH(false, 256);
-    else if (th == 512) OCT4_LAUNCH(false, 512);
-    else OCT4_LAUNCH(false, 1024);
+    if (th == 256) OCT4_LAUNCH(256);
+    else if (th == 512) OCT4_LAUNCH(512);
+    else OCT4_LAUNCH(1024);
 #undef OCT4_LAUNCH
 }
 
@@ -745,9 +759,8 @@ int vk_octree_set_max_lds(size_t bytes) {
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return (int)hipErrorInvalidDevice;
     size_t& have = have_dev[dev];
     if (bytes <= have) return 0;
-    const void* fns[4] = {(const void*)k_octree_v4<true, 1024>, (const void*)k_octree_v4<false, 1024>,
-                          (const void*)k_octree_v4<false, 512>, (const void*)k_octree_v4<false, 256>};
-    for (int i = 0; i < 4; i++) {
+    const void* fns[3] = {(const void*)k_octree_v4<1024>, (const void*)k_octree_v4<512>, (const void*)k_octree_v4<256>};
+    for (int i = 0; i < 3; i++) {
         const int rc = (int)hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
         if (rc) return rc;
     }
