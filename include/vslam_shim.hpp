@@ -29,6 +29,7 @@
 
 #include "vslam_fe.h"
 #include "vslam_fastgrid.h"
+#include "vslam_harrisgrid.h"
 
 #ifdef VSLAM_SHIM_WITH_OPENCV
 #include <opencv2/core/core.hpp>
@@ -688,6 +689,87 @@ public:
 private:
     std::unique_ptr<FASTGPU> det_;
     int w_ = 0, h_ = 0;
+};
+
+/* ---------------------------------------------------------------------------------------------------
+ * The grid Harris / Shi-Tomasi detector, the sibling of FASTGPU over the same DetectorBaseGPU.  HarrisGPU carries
+ * vilib::HarrisGPU's constructor (harris_gpu.h; harris_gpu.cpp:63-74) and DetectorBase's read side: detect() on an
+ * 8-bit image replaces `Frame(image, 0, levels)` + `detect(frame->pyramid_)` and ends, as the reference's does, in
+ * processGridAndThreshold(quality_level) (detector_base_gpu.cpp:228-248): getPoints() holds one FeaturePoint per grid
+ * cell and isOccupied(i) says whether cell i scored above max score * quality_level.
+ * ------------------------------------------------------------------------------------------------- */
+typedef int conv_filter_border_type_t; /* VSLAM_HG_BORDER_*: vilib::conv_filter_border_type in its order */
+
+class HarrisGPU {
+public:
+    typedef FASTGPU::FeaturePoint FeaturePoint;
+    HarrisGPU(std::size_t image_width, std::size_t image_height, std::size_t cell_size_width, std::size_t cell_size_height,
+              std::size_t min_level, std::size_t max_level, std::size_t horizontal_border, std::size_t vertical_border,
+              conv_filter_border_type_t filter_border_type, bool use_harris, float harris_k, float quality_level,
+              int device = 0) {
+        vslam_hg_params p;
+        std::memset(&p, 0, sizeof(p));
+        p.image_width = (int32_t)image_width;
+        p.image_height = (int32_t)image_height;
+        p.cell_size_width = (int32_t)cell_size_width;
+        p.cell_size_height = (int32_t)cell_size_height;
+        p.min_level = (int32_t)min_level;
+        p.max_level = (int32_t)max_level;
+        p.horizontal_border = (int32_t)horizontal_border;
+        p.vertical_border = (int32_t)vertical_border;
+        p.filter_border_type = filter_border_type;
+        p.use_harris = use_harris ? 1 : 0;
+        p.harris_k = harris_k;
+        p.quality_level = quality_level;
+        p.tie_rule = 0;
+        p.device = device;
+        p.max_batch = 1;
+        check(vslam_hg_create(&p, &hg_));
+        int nc = 0, nr = 0;
+        vslam_hg_grid(hg_, &nc, &nr);
+        n_cols_ = (std::size_t)nc;
+        n_rows_ = (std::size_t)nr;
+        reset();
+    }
+    ~HarrisGPU() { vslam_hg_destroy(hg_); }
+    HarrisGPU(const HarrisGPU&) = delete;
+    HarrisGPU& operator=(const HarrisGPU&) = delete;
+
+    void reset() { /* DetectorBase::reset + the constructor's keypoints_ fill (detector_base.cpp:67,76-84) */
+        keypoints_.assign(n_cols_ * n_rows_, FeaturePoint{0.0, 0.0, 0.0, (unsigned int)-1});
+        occupied_.assign(n_cols_ * n_rows_, 0);
+    }
+    void detect(const uint8_t* image, std::size_t pitch) { /* detectBase + processGridAndThreshold, harris_gpu.cpp:195-198 */
+        const std::size_t n = n_cols_ * n_rows_;
+        pos_.resize(2 * n);
+        score_.resize(n);
+        level_.resize(n);
+        keep_.resize(n);
+        int32_t n_keep = 0;
+        check(vslam_hg_detect(hg_, image, pitch, pos_.data(), score_.data(), level_.data(), keep_.data(), &n_keep));
+        for (std::size_t i = 0; i < n; i++)
+            if (keep_[i]) {
+                keypoints_[i] = FeaturePoint{(double)pos_[2 * i], (double)pos_[2 * i + 1], (double)score_[i], (unsigned int)level_[i]};
+                occupied_[i] = 1;
+            }
+    }
+    const std::vector<FeaturePoint>& getPoints() const { return keypoints_; }
+    bool isOccupied(std::size_t i) const { return occupied_[i] != 0; }
+    std::size_t count() const {
+        std::size_t c = 0;
+        for (uint8_t o : occupied_) c += o;
+        return c;
+    }
+    std::size_t getCellCountHorizontal() const { return n_cols_; }
+    std::size_t getCellCountVertical() const { return n_rows_; }
+
+private:
+    vslam_hg* hg_ = nullptr;
+    std::size_t n_cols_ = 0, n_rows_ = 0;
+    std::vector<FeaturePoint> keypoints_;
+    std::vector<uint8_t> occupied_, keep_;
+    std::vector<float> pos_, score_;
+    std::vector<int32_t> level_;
 };
 
 /* ---------------------------------------------------------------------------------------------------

@@ -19,23 +19,13 @@
  */
 #include "../../include/vslam_fastgrid.h"
 #include "vslam_ctx.h"
+#include "vslam_gridpyr.h"
 #include "vslam_wave.h"
 
-#define FG_MAX_LEVELS 8
-#define FG_MAX_BATCH 64
-
-struct FgLevel {
-    int32_t w, h, pitch;
-    uint32_t pad;
-    size_t base, bytes; /* level-major layout: image s of level l starts at base + s * bytes */
-};
 struct FgGeom {
     FgLevel lv[FG_MAX_LEVELS];
     int32_t cw, ch, n_cols, n_rows, min_level, max_level, hb, vb, dhb, dvb, arc, score, tie;
     float thr;
-};
-struct FgPtrs {
-    const uint8_t* p[FG_MAX_BATCH];
 };
 
 struct vslam_fg {
@@ -299,6 +289,34 @@ k_fg_detect(const uint8_t* __restrict__ pyr, FgGeom G, uint8_t* grid, float* res
 }
 
 /* ---------------------------------------------------------------------------------------------- host */
+size_t fg_pyramid_layout(FgLevel* lv, int w, int h, int levels, int max_batch) {
+    size_t off = 0;
+    for (int l = 0; l < levels; l++) {
+        FgLevel& L = lv[l];
+        L.w = w >> l; /* pyramid_pool.cpp:61-62 */
+        L.h = h >> l;
+        L.pitch = (L.w + 8 + 63) & ~63;
+        L.bytes = (size_t)L.pitch * L.h;
+        L.base = off;
+        off += L.bytes * max_batch;
+    }
+    return off + 256;
+}
+
+void fg_pyramid_gather(hipStream_t st, const uint8_t* const* imgs, int n, size_t src_pitch, uint8_t* pyr, const FgLevel& L0) {
+    FgPtrs P;
+    memset(&P, 0, sizeof(P));
+    for (int s = 0; s < n; s++) P.p[s] = imgs[s];
+    hipLaunchKernelGGL(k_fg_gather, dim3(((L0.w + 15) / 16 + 63) / 64, (L0.h + 3) / 4, n), dim3(256), 0, st, P, src_pitch, pyr, L0);
+}
+
+void fg_pyramid_halfsample(hipStream_t st, uint8_t* pyr, const FgLevel* lv, int levels, int n) {
+    for (int l = 1; l < levels; l++) {
+        const FgLevel& D = lv[l];
+        hipLaunchKernelGGL(k_fg_halfsample, dim3(((D.w + 3) / 4 + 63) / 64, (D.h + 3) / 4, n), dim3(256), 0, st, pyr, lv[l - 1], D);
+    }
+}
+
 static size_t fg_lds_bytes(const FgGeom& G) {
     size_t m = 0;
     for (int l = G.min_level; l < G.max_level; l++) {
@@ -349,17 +367,7 @@ extern "C" int vslam_fg_create(const vslam_fg_params* p, vslam_fg** out) {
     G.tie = p->tie_rule;
     G.thr = p->threshold;
     fg->cells = G.n_cols * G.n_rows;
-    size_t off = 0;
-    for (int l = 0; l < G.max_level; l++) {
-        FgLevel& L = G.lv[l];
-        L.w = p->image_width >> l; /* pyramid_pool.cpp:61-62 */
-        L.h = p->image_height >> l;
-        L.pitch = (L.w + 8 + 63) & ~63;
-        L.bytes = (size_t)L.pitch * L.h;
-        L.base = off;
-        off += L.bytes * p->max_batch;
-    }
-    fg->pyr_bytes = off + 256;
+    fg->pyr_bytes = fg_pyramid_layout(G.lv, p->image_width, p->image_height, G.max_level, p->max_batch);
 #define FG_TRY(call)                                                      \
     do {                                                                  \
         hipError_t e_ = (call);                                           \
@@ -444,11 +452,7 @@ extern "C" int vslam_fg_detect_batch(vslam_fg* fg, int n, const uint8_t* const* 
     const FgLevel& L0 = G.lv[0];
     hipStream_t st = fg->stream;
     if (on_device) {
-        FgPtrs P;
-        memset(&P, 0, sizeof(P));
-        for (int s = 0; s < n; s++) P.p[s] = imgs[s];
-        hipLaunchKernelGGL(k_fg_gather, dim3(((L0.w + 15) / 16 + 63) / 64, (L0.h + 3) / 4, n), dim3(256), 0, st, P, pitch,
-                           fg->d_pyr, L0);
+        fg_pyramid_gather(st, imgs, n, pitch, fg->d_pyr, L0);
     } else { /* pageable rows -> pinned staging in the device layout -> one copy kernel (see vslam_fe.hip) */
         for (int s = 0; s < n; s++)
             for (int y = 0; y < L0.h; y++) memcpy(fg->h_img + (size_t)s * L0.bytes + (size_t)y * L0.pitch, imgs[s] + (size_t)y * pitch, L0.w);
@@ -460,11 +464,7 @@ extern "C" int vslam_fg_detect_batch(vslam_fg* fg, int n, const uint8_t* const* 
         R.n = 1;
         vk_copy_ranges(st, R);
     }
-    for (int l = 1; l < G.max_level; l++) {
-        const FgLevel& D = G.lv[l];
-        hipLaunchKernelGGL(k_fg_halfsample, dim3(((D.w + 3) / 4 + 63) / 64, (D.h + 3) / 4, n), dim3(256), 0, st, fg->d_pyr,
-                           G.lv[l - 1], D);
-    }
+    fg_pyramid_halfsample(st, fg->d_pyr, G.lv, G.max_level, n);
     fg_launch_detect(fg, n, nullptr, -1, -1);
     CopyRanges R;
     memset(&R, 0, sizeof(R));
