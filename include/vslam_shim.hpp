@@ -585,57 +585,17 @@ inline void ComputeStereoMatches(const FExtractor& left, const FExtractor& right
  * cells, epsilon 10, arc 10, SUM_OF_ABS_DIFF_ON_ARC); unlike the reference, which prints the grid and leaves
  * `keypoints` empty, it returns the occupied cells as key points (pt, response = score, octave = level).
  * ------------------------------------------------------------------------------------------------- */
-class FASTGPU {
+namespace detail {
+/* DetectorBase's read side (detector_base.h:48-57,75-80) and the buffers a detect() call fills, for FASTGPU and HarrisGPU */
+class GridDetectorBase {
 public:
     struct FeaturePoint {
         double x_, y_, score_;
         unsigned int level_;
     };
-    FASTGPU(std::size_t image_width, std::size_t image_height, std::size_t cell_size_width, std::size_t cell_size_height,
-            std::size_t min_level, std::size_t max_level, std::size_t horizontal_border, std::size_t vertical_border,
-            float threshold, int min_arc_length, int score, int device = 0) {
-        vslam_fg_params p;
-        std::memset(&p, 0, sizeof(p));
-        p.image_width = (int32_t)image_width;
-        p.image_height = (int32_t)image_height;
-        p.cell_size_width = (int32_t)cell_size_width;
-        p.cell_size_height = (int32_t)cell_size_height;
-        p.min_level = (int32_t)min_level;
-        p.max_level = (int32_t)max_level;
-        p.horizontal_border = (int32_t)horizontal_border;
-        p.vertical_border = (int32_t)vertical_border;
-        p.threshold = threshold;
-        p.min_arc_length = min_arc_length;
-        p.score = score;
-        p.tie_rule = 0;
-        p.device = device;
-        p.max_batch = 1;
-        check(vslam_fg_create(&p, &fg_));
-        int nc = 0, nr = 0;
-        vslam_fg_grid(fg_, &nc, &nr);
-        n_cols_ = (std::size_t)nc;
-        n_rows_ = (std::size_t)nr;
-        reset();
-    }
-    ~FASTGPU() { vslam_fg_destroy(fg_); }
-    FASTGPU(const FASTGPU&) = delete;
-    FASTGPU& operator=(const FASTGPU&) = delete;
-
     void reset() { /* DetectorBase::reset + the constructor's keypoints_ fill (detector_base.cpp:67,76-84) */
         keypoints_.assign(n_cols_ * n_rows_, FeaturePoint{0.0, 0.0, 0.0, (unsigned int)-1});
         occupied_.assign(n_cols_ * n_rows_, 0);
-    }
-    void detect(const uint8_t* image, std::size_t pitch) { /* detectBase + processGrid, detector_base_gpu.cpp:204-218 */
-        const std::size_t n = n_cols_ * n_rows_;
-        pos_.resize(2 * n);
-        score_.resize(n);
-        level_.resize(n);
-        check(vslam_fg_detect(fg_, image, pitch, pos_.data(), score_.data(), level_.data()));
-        for (std::size_t i = 0; i < n; i++)
-            if (score_[i] > 0.0f) {
-                keypoints_[i] = FeaturePoint{(double)pos_[2 * i], (double)pos_[2 * i + 1], (double)score_[i], (unsigned int)level_[i]};
-                occupied_[i] = 1;
-            }
     }
     const std::vector<FeaturePoint>& getPoints() const { return keypoints_; }
     bool isOccupied(std::size_t i) const { return occupied_[i] != 0; }
@@ -647,13 +607,74 @@ public:
     std::size_t getCellCountHorizontal() const { return n_cols_; }
     std::size_t getCellCountVertical() const { return n_rows_; }
 
-private:
-    vslam_fg* fg_ = nullptr;
+protected:
+    GridDetectorBase() {}
+    GridDetectorBase(const GridDetectorBase&) = delete;
+    GridDetectorBase& operator=(const GridDetectorBase&) = delete;
+    /* the fields every vslam_*_params has; one image per call, the reference's tie order */
+    template <class P>
+    static void fill_common(P& p, std::size_t image_width, std::size_t image_height, std::size_t cell_size_width,
+                            std::size_t cell_size_height, std::size_t min_level, std::size_t max_level,
+                            std::size_t horizontal_border, std::size_t vertical_border, int device) {
+        std::memset(&p, 0, sizeof(p));
+        p.image_width = (int32_t)image_width;
+        p.image_height = (int32_t)image_height;
+        p.cell_size_width = (int32_t)cell_size_width;
+        p.cell_size_height = (int32_t)cell_size_height;
+        p.min_level = (int32_t)min_level;
+        p.max_level = (int32_t)max_level;
+        p.horizontal_border = (int32_t)horizontal_border;
+        p.vertical_border = (int32_t)vertical_border;
+        p.tie_rule = 0;
+        p.device = device;
+        p.max_batch = 1;
+    }
+    void set_grid(int n_cols, int n_rows) {
+        n_cols_ = (std::size_t)n_cols;
+        n_rows_ = (std::size_t)n_rows;
+        pos_.resize(2 * n_cols_ * n_rows_);
+        score_.resize(n_cols_ * n_rows_);
+        level_.resize(n_cols_ * n_rows_);
+        reset();
+    }
+    void occupy(std::size_t i) { /* cell i of the last grid is a feature */
+        keypoints_[i] = FeaturePoint{(double)pos_[2 * i], (double)pos_[2 * i + 1], (double)score_[i], (unsigned int)level_[i]};
+        occupied_[i] = 1;
+    }
     std::size_t n_cols_ = 0, n_rows_ = 0;
     std::vector<FeaturePoint> keypoints_;
     std::vector<uint8_t> occupied_;
     std::vector<float> pos_, score_;
     std::vector<int32_t> level_;
+};
+} /* namespace detail */
+
+class FASTGPU : public detail::GridDetectorBase {
+public:
+    FASTGPU(std::size_t image_width, std::size_t image_height, std::size_t cell_size_width, std::size_t cell_size_height,
+            std::size_t min_level, std::size_t max_level, std::size_t horizontal_border, std::size_t vertical_border,
+            float threshold, int min_arc_length, int score, int device = 0) {
+        vslam_fg_params p;
+        fill_common(p, image_width, image_height, cell_size_width, cell_size_height, min_level, max_level, horizontal_border,
+                    vertical_border, device);
+        p.threshold = threshold;
+        p.min_arc_length = min_arc_length;
+        p.score = score;
+        check(vslam_fg_create(&p, &fg_));
+        int nc = 0, nr = 0;
+        vslam_fg_grid(fg_, &nc, &nr);
+        set_grid(nc, nr);
+    }
+    ~FASTGPU() { vslam_fg_destroy(fg_); }
+
+    void detect(const uint8_t* image, std::size_t pitch) { /* detectBase + processGrid, detector_base_gpu.cpp:204-218 */
+        check(vslam_fg_detect(fg_, image, pitch, pos_.data(), score_.data(), level_.data()));
+        for (std::size_t i = 0; i < score_.size(); i++)
+            if (score_[i] > 0.0f) occupy(i);
+    }
+
+private:
+    vslam_fg* fg_ = nullptr;
 };
 
 class FAST {
@@ -700,76 +721,37 @@ private:
  * ------------------------------------------------------------------------------------------------- */
 typedef int conv_filter_border_type_t; /* VSLAM_HG_BORDER_*: vilib::conv_filter_border_type in its order */
 
-class HarrisGPU {
+class HarrisGPU : public detail::GridDetectorBase {
 public:
-    typedef FASTGPU::FeaturePoint FeaturePoint;
     HarrisGPU(std::size_t image_width, std::size_t image_height, std::size_t cell_size_width, std::size_t cell_size_height,
               std::size_t min_level, std::size_t max_level, std::size_t horizontal_border, std::size_t vertical_border,
               conv_filter_border_type_t filter_border_type, bool use_harris, float harris_k, float quality_level,
               int device = 0) {
         vslam_hg_params p;
-        std::memset(&p, 0, sizeof(p));
-        p.image_width = (int32_t)image_width;
-        p.image_height = (int32_t)image_height;
-        p.cell_size_width = (int32_t)cell_size_width;
-        p.cell_size_height = (int32_t)cell_size_height;
-        p.min_level = (int32_t)min_level;
-        p.max_level = (int32_t)max_level;
-        p.horizontal_border = (int32_t)horizontal_border;
-        p.vertical_border = (int32_t)vertical_border;
+        fill_common(p, image_width, image_height, cell_size_width, cell_size_height, min_level, max_level, horizontal_border,
+                    vertical_border, device);
         p.filter_border_type = filter_border_type;
         p.use_harris = use_harris ? 1 : 0;
         p.harris_k = harris_k;
         p.quality_level = quality_level;
-        p.tie_rule = 0;
-        p.device = device;
-        p.max_batch = 1;
         check(vslam_hg_create(&p, &hg_));
         int nc = 0, nr = 0;
         vslam_hg_grid(hg_, &nc, &nr);
-        n_cols_ = (std::size_t)nc;
-        n_rows_ = (std::size_t)nr;
-        reset();
+        set_grid(nc, nr);
+        keep_.resize(score_.size());
     }
     ~HarrisGPU() { vslam_hg_destroy(hg_); }
-    HarrisGPU(const HarrisGPU&) = delete;
-    HarrisGPU& operator=(const HarrisGPU&) = delete;
 
-    void reset() { /* DetectorBase::reset + the constructor's keypoints_ fill (detector_base.cpp:67,76-84) */
-        keypoints_.assign(n_cols_ * n_rows_, FeaturePoint{0.0, 0.0, 0.0, (unsigned int)-1});
-        occupied_.assign(n_cols_ * n_rows_, 0);
-    }
     void detect(const uint8_t* image, std::size_t pitch) { /* detectBase + processGridAndThreshold, harris_gpu.cpp:195-198 */
-        const std::size_t n = n_cols_ * n_rows_;
-        pos_.resize(2 * n);
-        score_.resize(n);
-        level_.resize(n);
-        keep_.resize(n);
         int32_t n_keep = 0;
         check(vslam_hg_detect(hg_, image, pitch, pos_.data(), score_.data(), level_.data(), keep_.data(), &n_keep));
-        for (std::size_t i = 0; i < n; i++)
-            if (keep_[i]) {
-                keypoints_[i] = FeaturePoint{(double)pos_[2 * i], (double)pos_[2 * i + 1], (double)score_[i], (unsigned int)level_[i]};
-                occupied_[i] = 1;
-            }
+        for (std::size_t i = 0; i < keep_.size(); i++)
+            if (keep_[i]) occupy(i);
     }
-    const std::vector<FeaturePoint>& getPoints() const { return keypoints_; }
-    bool isOccupied(std::size_t i) const { return occupied_[i] != 0; }
-    std::size_t count() const {
-        std::size_t c = 0;
-        for (uint8_t o : occupied_) c += o;
-        return c;
-    }
-    std::size_t getCellCountHorizontal() const { return n_cols_; }
-    std::size_t getCellCountVertical() const { return n_rows_; }
 
 private:
     vslam_hg* hg_ = nullptr;
-    std::size_t n_cols_ = 0, n_rows_ = 0;
-    std::vector<FeaturePoint> keypoints_;
-    std::vector<uint8_t> occupied_, keep_;
-    std::vector<float> pos_, score_;
-    std::vector<int32_t> level_;
+    std::vector<uint8_t> keep_;
 };
 
 /* ---------------------------------------------------------------------------------------------------

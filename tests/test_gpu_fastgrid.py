@@ -76,6 +76,33 @@ def test_pyramid_and_response_images():
             d.close()
 
 
+def _blocks():
+    """256 x 256 in 32-pixel blocks of random grey: level 5 is the 8 x 8 image of the blocks, so that the reference's response
+    has non-zero values on every level up to there"""
+    grey = np.random.default_rng(24).integers(0, 256, (8, 8)).astype(np.uint8)
+    return np.ascontiguousarray(np.kron(grey, np.ones((32, 32), np.uint8)))
+
+
+@pytest.mark.parametrize("cell", [32, 64])
+def test_six_levels_down_to_one_and_two_pixel_cells(cell):
+    """Levels 4 and 5 of 32 x 32 cells and level 5 of 64 x 64 cells have 2- and 1-pixel cells: the window is staged byte by
+    byte there, dword by dword above."""
+    img = _blocks()
+    d = FASTGPU(256, 256, cell, cell, 0, 6)
+    try:
+        _same(d.detect(img), orbo.fg_detect(img, (cell, cell), 0, 6))
+        cur = img
+        for l in range(1, 6):
+            cur = orbo.fg_halfsample(cur)
+            if l < 3:
+                continue
+            want = orbo.fg_response(cur, 3, 3, 10.0, 10, SUM_OF_ABS_DIFF_ON_ARC)
+            assert np.any(want != 0), l
+            assert np.array_equal(d.response(0, l).view(np.uint32), want.view(np.uint32)), l
+    finally:
+        d.close()
+
+
 def test_golden_grids():
     crops = _crops()
     z = np.load(os.path.join(GOLD, "fastgrid.npz"))

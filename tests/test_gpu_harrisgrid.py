@@ -103,6 +103,34 @@ def test_pyramid_levels_and_response_images(use_harris):
             d.close()
 
 
+def _blocks():
+    """256 x 256 in 32-pixel blocks of random grey: level 5 is the 8 x 8 image of the blocks, so that the restatement's
+    response has non-zero values on every level up to there"""
+    grey = np.random.default_rng(24).integers(0, 256, (8, 8)).astype(np.uint8)
+    return np.ascontiguousarray(np.kron(grey, np.ones((32, 32), np.uint8)))
+
+
+@pytest.mark.parametrize("border", [hr.BORDER_SKIP, hr.BORDER_REFLECT_101])
+@pytest.mark.parametrize("cell", [32, 64])
+def test_six_levels_down_to_one_and_two_pixel_cells(cell, border):
+    """Levels 4 and 5 of 32 x 32 cells and level 5 of 64 x 64 cells have 2- and 1-pixel cells: the window is staged byte by
+    byte there, dword by dword above; the border rule is applied to either."""
+    img = _blocks()
+    d = HarrisGPU(256, 256, cell, cell, 0, 6, filter_border_type=border)
+    try:
+        _same(d.detect(img), hr.detect(img, (cell, cell), 0, 6, filter_border=border))
+        cur = img
+        for l in range(1, 6):
+            cur = hr.halfsample(cur)
+            if l < 3:
+                continue
+            want = hr.response(cur, border, True, 0.04)
+            assert np.any(want != 0), l
+            assert np.array_equal(_u32(d.response(0, l)), _u32(want)), l
+    finally:
+        d.close()
+
+
 def test_golden_grids():
     crops = HC.crops()
     z = np.load(os.path.join(HC.GOLD, "harrisgrid.npz"))
