@@ -30,6 +30,7 @@
 #include "vslam_fe.h"
 #include "vslam_fastgrid.h"
 #include "vslam_harrisgrid.h"
+#include "vslam_featuretracker.h"
 
 #ifdef VSLAM_SHIM_WITH_OPENCV
 #include <opencv2/core/core.hpp>
@@ -606,6 +607,9 @@ public:
     }
     std::size_t getCellCountHorizontal() const { return n_cols_; }
     std::size_t getCellCountVertical() const { return n_rows_; }
+    /* what FeatureTrackerGPU::setDetectorGPU binds to: the C handle and which of VSLAM_FT_DETECTOR_* it is */
+    void* handle() const { return handle_; }
+    int kind() const { return kind_; }
 
 protected:
     GridDetectorBase() {}
@@ -641,6 +645,8 @@ protected:
         keypoints_[i] = FeaturePoint{(double)pos_[2 * i], (double)pos_[2 * i + 1], (double)score_[i], (unsigned int)level_[i]};
         occupied_[i] = 1;
     }
+    void* handle_ = nullptr;
+    int kind_ = VSLAM_FT_DETECTOR_FAST;
     std::size_t n_cols_ = 0, n_rows_ = 0;
     std::vector<FeaturePoint> keypoints_;
     std::vector<uint8_t> occupied_;
@@ -661,6 +667,7 @@ public:
         p.min_arc_length = min_arc_length;
         p.score = score;
         check(vslam_fg_create(&p, &fg_));
+        handle_ = fg_;
         int nc = 0, nr = 0;
         vslam_fg_grid(fg_, &nc, &nr);
         set_grid(nc, nr);
@@ -735,6 +742,8 @@ public:
         p.harris_k = harris_k;
         p.quality_level = quality_level;
         check(vslam_hg_create(&p, &hg_));
+        handle_ = hg_;
+        kind_ = VSLAM_FT_DETECTOR_HARRIS;
         int nc = 0, nr = 0;
         vslam_hg_grid(hg_, &nc, &nr);
         set_grid(nc, nr);
@@ -752,6 +761,103 @@ public:
 private:
     vslam_hg* hg_ = nullptr;
     std::vector<uint8_t> keep_;
+};
+
+/* ---------------------------------------------------------------------------------------------------
+ * The pyramidal Lucas-Kanade feature tracker, the one consumer of the two grid detectors.  FeatureTrackerGPU carries
+ * vilib::FeatureTrackerGPU's constructor options (feature_tracker_options.h:50-98) and its methods
+ * (feature_tracker_gpu.h, feature_tracker_base.h): setDetectorGPU, track, reset, setBestNFeatures,
+ * setMinTracksToDetect, getDisparity.  track() on an 8-bit image replaces `Frame(image, 0, pyramid_levels)` in a
+ * FrameBundle of one + `track(bundle, tracked, detected)`; features() is what the reference leaves in the frame
+ * (px_vec_, score_vec_, level_vec_, track_id_vec_ up to num_features_).  One camera per tracker.
+ * ------------------------------------------------------------------------------------------------- */
+struct FeatureTrackerOptions {
+    int klt_max_level = 4;
+    int klt_min_level = 0;
+    std::vector<int> klt_patch_sizes = {16, 16, 16, 8, 8};
+    int klt_max_iter = VSLAM_FT_MAX_ITER; /* a compile-time constant, as in the reference */
+    double klt_min_update_squared = 0.0005;
+    std::size_t min_tracks_to_detect_new_features = 100;
+    bool reset_before_detection = true;
+    int use_best_n_features = -1;
+    bool klt_template_is_first_observation = true;
+    bool affine_est_offset = false;
+    bool affine_est_gain = false;
+    int pyramid_levels = 5; /* vilib::Frame's n_pyr_levels */
+};
+
+class FeatureTrackerGPU {
+public:
+    explicit FeatureTrackerGPU(const FeatureTrackerOptions& options, const std::size_t& camera_num = 1) : options_(options) {
+        if (camera_num != 1) throw std::invalid_argument("FeatureTrackerGPU: one camera per tracker");
+    }
+    ~FeatureTrackerGPU() { vslam_ft_destroy(ft_); }
+    FeatureTrackerGPU(const FeatureTrackerGPU&) = delete;
+    FeatureTrackerGPU& operator=(const FeatureTrackerGPU&) = delete;
+
+    /* the tracker shares the detector's stream and keeps the detector alive */
+    void setDetectorGPU(const std::shared_ptr<detail::GridDetectorBase>& detector, const std::size_t& camera_id = 0) {
+        if (camera_id != 0 || !detector) throw std::invalid_argument("FeatureTrackerGPU::setDetectorGPU");
+        vslam_ft_destroy(ft_);
+        ft_ = nullptr;
+        vslam_ft_params p;
+        std::memset(&p, 0, sizeof(p));
+        p.klt_min_level = options_.klt_min_level;
+        p.klt_max_level = options_.klt_max_level;
+        for (std::size_t i = 0; i < options_.klt_patch_sizes.size() && i < VSLAM_FT_MAX_LEVELS; i++)
+            p.klt_patch_sizes[i] = options_.klt_patch_sizes[i];
+        p.klt_min_update_squared = (float)options_.klt_min_update_squared;
+        p.min_tracks_to_detect_new_features = (int32_t)options_.min_tracks_to_detect_new_features;
+        p.reset_before_detection = options_.reset_before_detection ? 1 : 0;
+        p.use_best_n_features = options_.use_best_n_features;
+        p.klt_template_is_first_observation = options_.klt_template_is_first_observation ? 1 : 0;
+        p.affine_est_offset = options_.affine_est_offset ? 1 : 0;
+        p.affine_est_gain = options_.affine_est_gain ? 1 : 0;
+        p.pyramid_levels = options_.pyramid_levels;
+        check(vslam_ft_create(&p, detector->kind(), detector->handle(), &ft_));
+        detector_ = detector;
+        features_.resize((std::size_t)vslam_ft_capacity(ft_));
+        n_features_ = 0;
+    }
+
+    void track(const uint8_t* image, std::size_t pitch, std::size_t& total_tracked_features_num, std::size_t& total_detected_features_num) {
+        int32_t tracked = 0, detected = 0;
+        int n = 0;
+        check(vslam_ft_track(ft_, image, pitch, 0, &tracked, &detected));
+        check(vslam_ft_features(ft_, features_.data(), (int)features_.size(), &n));
+        n_features_ = (std::size_t)n;
+        total_tracked_features_num = (std::size_t)tracked;
+        total_detected_features_num = (std::size_t)detected;
+    }
+    void reset() { check(vslam_ft_reset(ft_)); }
+    void setBestNFeatures(int n) {
+        options_.use_best_n_features = n;
+        if (ft_) check(vslam_ft_set_best_n(ft_, n));
+    }
+    void setMinTracksToDetect(int n) {
+        options_.min_tracks_to_detect_new_features = (std::size_t)n;
+        if (ft_) check(vslam_ft_set_min_tracks(ft_, n));
+    }
+    void getDisparity(const double& pivot_ratio, double& total_avg_disparity) const {
+        check(vslam_ft_disparity(ft_, pivot_ratio, &total_avg_disparity));
+    }
+    /* the current frame's features in addFeature order */
+    std::size_t num_features() const { return n_features_; }
+    const vslam_ft_feature& feature(std::size_t i) const { return features_[i]; }
+    std::vector<vslam_ft_track_info> tracks() const {
+        std::vector<vslam_ft_track_info> t(features_.size());
+        int n = 0;
+        check(vslam_ft_tracks(ft_, t.data(), (int)t.size(), &n));
+        t.resize((std::size_t)n);
+        return t;
+    }
+
+private:
+    FeatureTrackerOptions options_;
+    std::shared_ptr<detail::GridDetectorBase> detector_;
+    vslam_ft* ft_ = nullptr;
+    std::vector<vslam_ft_feature> features_;
+    std::size_t n_features_ = 0;
 };
 
 /* ---------------------------------------------------------------------------------------------------

@@ -247,6 +247,11 @@ int gd_grid(const GdHost* h, int* n_cols, int* n_rows);
 /* upload or gather, halfsample, launch, grid copy, unpack into pos / score / level */
 int gd_detect_batch(GdHost* h, int n, const uint8_t* const* imgs, size_t pitch, int on_device, float* pos, float* score,
                     int32_t* level);
+/* The two halves of gd_detect_batch, for a caller that brings a pyramid of its own in h's layout (the feature tracker,
+ * whose pyramid has more levels): n images -> level 0 of pyr, and the bound detector's launch, grid copy and unpacking
+ * on an already built pyramid.  Both work on h's stream; the second waits for it. */
+void gd_stage_images(GdHost* h, int n, const uint8_t* const* imgs, size_t pitch, int on_device, uint8_t* pyr);
+int gd_detect_pyramid(GdHost* h, int n, uint8_t* pyr, float* pos, float* score, int32_t* level);
 int gd_level_copy(GdHost* h, int slot, int level, uint8_t* dst, size_t dst_pitch, int* w, int* h_out);
 int gd_response_copy(GdHost* h, int slot, int level, float* dst);
 int gd_nt(); /* threads per cell, see vk_fast_cells_v3; VSLAM_FG_NT = 64 | 128 | 256 for A/B runs, for both detectors */

@@ -104,6 +104,47 @@ int gd_nt() {
     return (v == 64 || v == 128 || v == 256) ? v : 128;
 }
 
+void gd_stage_images(GdHost* h, int n, const uint8_t* const* imgs, size_t pitch, int on_device, uint8_t* pyr) {
+    const FgLevel& L0 = h->G.lv[0];
+    if (on_device) {
+        fg_pyramid_gather(h->stream, imgs, n, pitch, pyr, L0);
+    } else { /* pageable rows -> pinned staging in the device layout -> one copy kernel (see vslam_fe.hip) */
+        for (int s = 0; s < n; s++)
+            for (int y = 0; y < L0.h; y++) memcpy(h->h_img + (size_t)s * L0.bytes + (size_t)y * L0.pitch, imgs[s] + (size_t)y * pitch, L0.w);
+        CopyRanges R;
+        memset(&R, 0, sizeof(R));
+        R.n = 1;
+        R.dst[0] = pyr + L0.base;
+        R.src[0] = h->h_img;
+        R.bytes[0] = L0.bytes * n;
+        vk_copy_ranges(h->stream, R);
+    }
+}
+
+int gd_detect_pyramid(GdHost* h, int n, uint8_t* pyr, float* pos, float* score, int32_t* level) {
+    uint8_t* const own = h->d_pyr; /* the launch reads the object's pyramid pointer */
+    h->d_pyr = pyr;
+    h->launch(h, n, nullptr, -1, -1);
+    h->d_pyr = own;
+    CopyRanges R;
+    memset(&R, 0, sizeof(R));
+    R.n = 1;
+    R.dst[0] = h->h_grid;
+    R.src[0] = h->d_grid;
+    R.bytes[0] = (size_t)h->cells * 16 * n;
+    vk_copy_ranges(h->stream, R);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const int C = h->cells;
+    for (int s = 0; s < n; s++) {
+        const uint8_t* g = h->h_grid + (size_t)s * C * 16;
+        memcpy(pos + (size_t)s * C * 2, g, (size_t)C * 8);
+        memcpy(score + (size_t)s * C, g + (size_t)C * 8, (size_t)C * 4);
+        memcpy(level + (size_t)s * C, g + (size_t)C * 12, (size_t)C * 4);
+    }
+    return VSLAM_OK;
+}
+
 int gd_detect_batch(GdHost* h, int n, const uint8_t* const* imgs, size_t pitch, int on_device, float* pos, float* score,
                     int32_t* level) {
     if (!h || n < 1 || n > h->max_batch || !imgs || !pos || !score || !level || pitch < (size_t)h->G.lv[0].w) {
@@ -116,39 +157,11 @@ int gd_detect_batch(GdHost* h, int n, const uint8_t* const* imgs, size_t pitch, 
             return VSLAM_ERR_INVALID;
         }
     HIPCHK(hipSetDevice(h->device));
-    const GdGeom& G = h->G;
-    const FgLevel& L0 = G.lv[0];
-    hipStream_t st = h->stream;
-    CopyRanges R;
-    memset(&R, 0, sizeof(R));
-    R.n = 1;
-    if (on_device) {
-        fg_pyramid_gather(st, imgs, n, pitch, h->d_pyr, L0);
-    } else { /* pageable rows -> pinned staging in the device layout -> one copy kernel (see vslam_fe.hip) */
-        for (int s = 0; s < n; s++)
-            for (int y = 0; y < L0.h; y++) memcpy(h->h_img + (size_t)s * L0.bytes + (size_t)y * L0.pitch, imgs[s] + (size_t)y * pitch, L0.w);
-        R.dst[0] = h->d_pyr + L0.base;
-        R.src[0] = h->h_img;
-        R.bytes[0] = L0.bytes * n;
-        vk_copy_ranges(st, R);
-    }
-    fg_pyramid_halfsample(st, h->d_pyr, G.lv, G.max_level, n);
-    h->launch(h, n, nullptr, -1, -1);
-    R.dst[0] = h->h_grid;
-    R.src[0] = h->d_grid;
-    R.bytes[0] = (size_t)h->cells * 16 * n;
-    vk_copy_ranges(st, R);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st));
-    h->last_n = n;
-    const int C = h->cells;
-    for (int s = 0; s < n; s++) {
-        const uint8_t* g = h->h_grid + (size_t)s * C * 16;
-        memcpy(pos + (size_t)s * C * 2, g, (size_t)C * 8);
-        memcpy(score + (size_t)s * C, g + (size_t)C * 8, (size_t)C * 4);
-        memcpy(level + (size_t)s * C, g + (size_t)C * 12, (size_t)C * 4);
-    }
-    return VSLAM_OK;
+    gd_stage_images(h, n, imgs, pitch, on_device, h->d_pyr);
+    fg_pyramid_halfsample(h->stream, h->d_pyr, h->G.lv, h->G.max_level, n);
+    const int rc = gd_detect_pyramid(h, n, h->d_pyr, pos, score, level);
+    if (rc == VSLAM_OK) h->last_n = n;
+    return rc;
 }
 
 int gd_level_copy(GdHost* h, int slot, int level, uint8_t* dst, size_t dst_pitch, int* w, int* h_out) {
