@@ -610,16 +610,19 @@ public:
     /* what FeatureTrackerGPU::setDetectorGPU binds to: the C handle and which of VSLAM_FT_DETECTOR_* it is */
     void* handle() const { return handle_; }
     int kind() const { return kind_; }
+    /* how many image slots the detector's launch can take: the cameras of a FeatureTrackerGPU bound to it */
+    std::size_t max_batch() const { return max_batch_; }
 
 protected:
     GridDetectorBase() {}
     GridDetectorBase(const GridDetectorBase&) = delete;
     GridDetectorBase& operator=(const GridDetectorBase&) = delete;
-    /* the fields every vslam_*_params has; one image per call, the reference's tie order */
+    /* the fields every vslam_*_params has; the reference's tie order.  detect() takes one image per call; max_batch > 1
+     * is for a FeatureTrackerGPU of several cameras */
     template <class P>
-    static void fill_common(P& p, std::size_t image_width, std::size_t image_height, std::size_t cell_size_width,
-                            std::size_t cell_size_height, std::size_t min_level, std::size_t max_level,
-                            std::size_t horizontal_border, std::size_t vertical_border, int device) {
+    void fill_common(P& p, std::size_t image_width, std::size_t image_height, std::size_t cell_size_width,
+                     std::size_t cell_size_height, std::size_t min_level, std::size_t max_level,
+                     std::size_t horizontal_border, std::size_t vertical_border, int device, int max_batch) {
         std::memset(&p, 0, sizeof(p));
         p.image_width = (int32_t)image_width;
         p.image_height = (int32_t)image_height;
@@ -631,7 +634,8 @@ protected:
         p.vertical_border = (int32_t)vertical_border;
         p.tie_rule = 0;
         p.device = device;
-        p.max_batch = 1;
+        p.max_batch = max_batch;
+        max_batch_ = (std::size_t)(max_batch > 0 ? max_batch : 0);
     }
     void set_grid(int n_cols, int n_rows) {
         n_cols_ = (std::size_t)n_cols;
@@ -647,7 +651,7 @@ protected:
     }
     void* handle_ = nullptr;
     int kind_ = VSLAM_FT_DETECTOR_FAST;
-    std::size_t n_cols_ = 0, n_rows_ = 0;
+    std::size_t n_cols_ = 0, n_rows_ = 0, max_batch_ = 1;
     std::vector<FeaturePoint> keypoints_;
     std::vector<uint8_t> occupied_;
     std::vector<float> pos_, score_;
@@ -659,10 +663,10 @@ class FASTGPU : public detail::GridDetectorBase {
 public:
     FASTGPU(std::size_t image_width, std::size_t image_height, std::size_t cell_size_width, std::size_t cell_size_height,
             std::size_t min_level, std::size_t max_level, std::size_t horizontal_border, std::size_t vertical_border,
-            float threshold, int min_arc_length, int score, int device = 0) {
+            float threshold, int min_arc_length, int score, int device = 0, int max_batch = 1) {
         vslam_fg_params p;
         fill_common(p, image_width, image_height, cell_size_width, cell_size_height, min_level, max_level, horizontal_border,
-                    vertical_border, device);
+                    vertical_border, device, max_batch);
         p.threshold = threshold;
         p.min_arc_length = min_arc_length;
         p.score = score;
@@ -733,10 +737,10 @@ public:
     HarrisGPU(std::size_t image_width, std::size_t image_height, std::size_t cell_size_width, std::size_t cell_size_height,
               std::size_t min_level, std::size_t max_level, std::size_t horizontal_border, std::size_t vertical_border,
               conv_filter_border_type_t filter_border_type, bool use_harris, float harris_k, float quality_level,
-              int device = 0) {
+              int device = 0, int max_batch = 1) {
         vslam_hg_params p;
         fill_common(p, image_width, image_height, cell_size_width, cell_size_height, min_level, max_level, horizontal_border,
-                    vertical_border, device);
+                    vertical_border, device, max_batch);
         p.filter_border_type = filter_border_type;
         p.use_harris = use_harris ? 1 : 0;
         p.harris_k = harris_k;
@@ -767,9 +771,11 @@ private:
  * The pyramidal Lucas-Kanade feature tracker, the one consumer of the two grid detectors.  FeatureTrackerGPU carries
  * vilib::FeatureTrackerGPU's constructor options (feature_tracker_options.h:50-98) and its methods
  * (feature_tracker_gpu.h, feature_tracker_base.h): setDetectorGPU, track, reset, setBestNFeatures,
- * setMinTracksToDetect, getDisparity.  track() on an 8-bit image replaces `Frame(image, 0, pyramid_levels)` in a
- * FrameBundle of one + `track(bundle, tracked, detected)`; features() is what the reference leaves in the frame
- * (px_vec_, score_vec_, level_vec_, track_id_vec_ up to num_features_).  One camera per tracker.
+ * setMinTracksToDetect, getDisparity.  track() on 8-bit images, one per camera, replaces `Frame(image, 0, pyramid_levels)`
+ * per camera of a FrameBundle + `track(bundle, tracked, detected)`; the form on one image is the bundle of one.
+ * feature(i, camera_id) is what the reference leaves in that camera's frame (px_vec_, score_vec_, level_vec_,
+ * track_id_vec_ up to num_features_).  The cameras of a tracker bind ONE detector object (one image size, one grid, one
+ * stream) whose max_batch is at least camera_num; a rig whose cameras differ in image size is several trackers.
  * ------------------------------------------------------------------------------------------------- */
 struct FeatureTrackerOptions {
     int klt_max_level = 4;
@@ -788,16 +794,26 @@ struct FeatureTrackerOptions {
 
 class FeatureTrackerGPU {
 public:
-    explicit FeatureTrackerGPU(const FeatureTrackerOptions& options, const std::size_t& camera_num = 1) : options_(options) {
-        if (camera_num != 1) throw std::invalid_argument("FeatureTrackerGPU: one camera per tracker");
+    explicit FeatureTrackerGPU(const FeatureTrackerOptions& options, const std::size_t& camera_num = 1)
+        : options_(options), camera_num_(camera_num), bound_(camera_num) {
+        if (camera_num < 1) throw std::invalid_argument("FeatureTrackerGPU: at least one camera");
     }
     ~FeatureTrackerGPU() { vslam_ft_destroy(ft_); }
     FeatureTrackerGPU(const FeatureTrackerGPU&) = delete;
     FeatureTrackerGPU& operator=(const FeatureTrackerGPU&) = delete;
 
-    /* the tracker shares the detector's stream and keeps the detector alive */
+    /* The tracker shares the detector's stream and keeps the detector alive.  Every camera binds the same detector
+     * object; the tracker exists once the last camera is bound (binding one again builds it anew). */
     void setDetectorGPU(const std::shared_ptr<detail::GridDetectorBase>& detector, const std::size_t& camera_id = 0) {
-        if (camera_id != 0 || !detector) throw std::invalid_argument("FeatureTrackerGPU::setDetectorGPU");
+        if (camera_id >= camera_num_ || !detector) throw std::invalid_argument("FeatureTrackerGPU::setDetectorGPU");
+        if (detector->max_batch() < camera_num_)
+            throw std::invalid_argument("FeatureTrackerGPU::setDetectorGPU: the detector's max_batch is below camera_num");
+        for (std::size_t c = 0; c < camera_num_; c++)
+            if (c != camera_id && bound_[c] && bound_[c] != detector)
+                throw std::invalid_argument("FeatureTrackerGPU::setDetectorGPU: the cameras of a tracker share one detector object");
+        bound_[camera_id] = detector;
+        for (const std::shared_ptr<detail::GridDetectorBase>& d : bound_)
+            if (!d) return;
         vslam_ft_destroy(ft_);
         ft_ = nullptr;
         vslam_ft_params p;
@@ -814,20 +830,28 @@ public:
         p.affine_est_offset = options_.affine_est_offset ? 1 : 0;
         p.affine_est_gain = options_.affine_est_gain ? 1 : 0;
         p.pyramid_levels = options_.pyramid_levels;
-        check(vslam_ft_create(&p, detector->kind(), detector->handle(), &ft_));
-        detector_ = detector;
-        features_.resize((std::size_t)vslam_ft_capacity(ft_));
-        n_features_ = 0;
+        check(vslam_ft_create_bundle(&p, detector->kind(), detector->handle(), (int)camera_num_, &ft_));
+        features_.assign(camera_num_, std::vector<vslam_ft_feature>((std::size_t)vslam_ft_capacity(ft_)));
+        n_features_.assign(camera_num_, 0);
     }
 
+    /* one image per camera, all of one pitch; the two totals are the reference's, summed over the cameras */
+    void track(const std::vector<const uint8_t*>& images, std::size_t pitch, std::size_t& total_tracked_features_num,
+               std::size_t& total_detected_features_num) {
+        if (images.size() != camera_num_) throw std::invalid_argument("FeatureTrackerGPU::track: one image per camera");
+        std::vector<int32_t> tracked(camera_num_, 0), detected(camera_num_, 0);
+        check(vslam_ft_track_bundle(ft_, images.data(), pitch, 0, tracked.data(), detected.data()));
+        total_tracked_features_num = total_detected_features_num = 0;
+        for (std::size_t c = 0; c < camera_num_; c++) {
+            int n = 0;
+            check(vslam_ft_features_cam(ft_, (int)c, features_[c].data(), (int)features_[c].size(), &n));
+            n_features_[c] = (std::size_t)n;
+            total_tracked_features_num += (std::size_t)tracked[c];
+            total_detected_features_num += (std::size_t)detected[c];
+        }
+    }
     void track(const uint8_t* image, std::size_t pitch, std::size_t& total_tracked_features_num, std::size_t& total_detected_features_num) {
-        int32_t tracked = 0, detected = 0;
-        int n = 0;
-        check(vslam_ft_track(ft_, image, pitch, 0, &tracked, &detected));
-        check(vslam_ft_features(ft_, features_.data(), (int)features_.size(), &n));
-        n_features_ = (std::size_t)n;
-        total_tracked_features_num = (std::size_t)tracked;
-        total_detected_features_num = (std::size_t)detected;
+        track(std::vector<const uint8_t*>(1, image), pitch, total_tracked_features_num, total_detected_features_num);
     }
     void reset() { check(vslam_ft_reset(ft_)); }
     void setBestNFeatures(int n) {
@@ -838,26 +862,28 @@ public:
         options_.min_tracks_to_detect_new_features = (std::size_t)n;
         if (ft_) check(vslam_ft_set_min_tracks(ft_, n));
     }
-    void getDisparity(const double& pivot_ratio, double& total_avg_disparity) const {
-        check(vslam_ft_disparity(ft_, pivot_ratio, &total_avg_disparity));
+    void getDisparity(const double& pivot_ratio, double& total_avg_disparity, std::size_t camera_id = 0) const {
+        check(vslam_ft_disparity_cam(ft_, (int)camera_id, pivot_ratio, &total_avg_disparity));
     }
-    /* the current frame's features in addFeature order */
-    std::size_t num_features() const { return n_features_; }
-    const vslam_ft_feature& feature(std::size_t i) const { return features_[i]; }
-    std::vector<vslam_ft_track_info> tracks() const {
-        std::vector<vslam_ft_track_info> t(features_.size());
+    std::size_t camera_num() const { return camera_num_; }
+    /* the current frame's features of one camera in addFeature order */
+    std::size_t num_features(std::size_t camera_id = 0) const { return n_features_.at(camera_id); }
+    const vslam_ft_feature& feature(std::size_t i, std::size_t camera_id = 0) const { return features_.at(camera_id)[i]; }
+    std::vector<vslam_ft_track_info> tracks(std::size_t camera_id = 0) const {
+        std::vector<vslam_ft_track_info> t(ft_ ? (std::size_t)vslam_ft_capacity(ft_) : 0);
         int n = 0;
-        check(vslam_ft_tracks(ft_, t.data(), (int)t.size(), &n));
+        check(vslam_ft_tracks_cam(ft_, (int)camera_id, t.data(), (int)t.size(), &n));
         t.resize((std::size_t)n);
         return t;
     }
 
 private:
     FeatureTrackerOptions options_;
-    std::shared_ptr<detail::GridDetectorBase> detector_;
+    std::size_t camera_num_;
+    std::vector<std::shared_ptr<detail::GridDetectorBase>> bound_; /* per camera; all the same object */
     vslam_ft* ft_ = nullptr;
-    std::vector<vslam_ft_feature> features_;
-    std::size_t n_features_ = 0;
+    std::vector<std::vector<vslam_ft_feature>> features_;
+    std::vector<std::size_t> n_features_;
 };
 
 /* ---------------------------------------------------------------------------------------------------

@@ -9,14 +9,20 @@
  *                                         (perform_lk), at most 30 iterations per level
  *   over track metadata in mapped host memory (feature_tracker_gpu.cpp:418-470).
  * What runs here:
- *   k_ft_update<offset, gain>, k_ft_track<offset, gain>: one wave64 per workgroup, one candidate per 32-lane half.  The two
- *     halves diverge in level, iteration count and exit; every cross-lane read stays inside its half (__shfl_xor and
- *     __shfl_down with width 32), and all 32 lanes of a half are uniform in control flow by construction: the reduced
- *     Jres is the same word in every lane of the half, and everything else that steers a branch is per candidate.
- *   Track metadata lives in HBM (64 bytes per buffer id, the reference's layout).  Per frame there is one upload -- the
- *     indirection list and the positions of the new tracks; k_ft_update initialises their metadata -- and one result copy
- *     (cur_px, disparity per candidate).  Whether kernels that read and write pinned host memory directly, as the
- *     reference's do, would be faster is unmeasured.
+ *   k_ft_update<offset, gain, bundle>, k_ft_track<offset, gain, bundle>: one wave64 per workgroup, one candidate per
+ *     32-lane half.  The two halves diverge in level, iteration count and exit -- and, in a bundle, in the camera --; every
+ *     cross-lane read stays inside its half (__shfl_xor and __shfl_down with width 32), and all 32 lanes of a half are
+ *     uniform in control flow by construction: the reduced Jres is the same word in every lane of the half, and
+ *     everything else that steers a branch is per candidate.
+ *   A tracker object serves C cameras (a FrameBundle) that share the detector, its stream and the options.  Each step of
+ *     the reference's track() runs once for the bundle: one pyramid build over C image slots, one k_ft_track launch over
+ *     the cameras' live tracks one camera after the other, one result copy, one detector launch over the slots [0, hi),
+ *     one upload, one k_ft_update launch.  A candidate is one word (FT_CAND_*): its camera slot and its buffer id within
+ *     that camera's block of max_ftr buffers; the image of slot s on a level is base + s * bytes.
+ *   Track metadata lives in HBM (64 bytes per buffer id, the reference's layout).  Per call there is one upload -- the
+ *     candidate words of both kernels and the positions of the new tracks; k_ft_update initialises their metadata -- and
+ *     one result copy (cur_px, disparity per candidate).  Whether kernels that read and write pinned host memory
+ *     directly, as the reference's do, would be faster is unmeasured.
  *   Templates are int32 in the reference's layout (max_area per level, max_level first), so vslam_ft_template_copy is a
  *     plain copy.  k_ft_update sums the Hessian from the image bytes it has just copied rather than from the patch in
  *     global memory: the same integers, and no store-to-load round trip inside a wave.
@@ -32,12 +38,23 @@
 #define FT_META 16
 enum { FT_TEMPLATE = 4, FT_FIRST = 6, FT_CUR = 8, FT_AB = 10, FT_DISP = 12 };
 #define FT_NAN 0x7fffffffu
+/* BUNDLE: the object has more than one camera.  With one, the slot is the constant 0 and the kernels are, register for
+ * register, the single-camera kernels they were; with the slot a per-candidate value, two of the four k_ft_track and one
+ * of the k_ft_update variants would give up a wave of occupancy, which a single camera need not pay.
+ * A candidate word: bits 0-19 the buffer id within its camera (vslam_ftbook_create caps max_ftr at 2^20), bits 20-25 the
+ * camera slot (FG_MAX_BATCH = 64), bit 31 (k_ft_update only) a new track, whose position is newpx[candidate]. */
+#define FT_CAND_ID 0xFFFFFu
+#define FT_CAND_SLOT_SHIFT 20
+#define FT_CAND_SLOT 63u
+#define FT_CAND_NEW 0x80000000u
+static_assert(FG_MAX_BATCH - 1 <= FT_CAND_SLOT, "a candidate word has six bits for the camera slot");
 
 struct FtGeom {
     FgLevel lv[FG_MAX_LEVELS];
     int32_t ps[FG_MAX_LEVELS];
     int32_t min_level, max_level, max_area, nlev;
     float min_update_squared;
+    int32_t max_ftr; /* buffers per camera: camera s owns buffers s * max_ftr .. */
 };
 
 /* int u = floorf(v): the conversion saturates, as CUDA's does.  A clamped value fails every bounds test below just as
@@ -111,20 +128,22 @@ struct FtDim { /* parameters of the update, entries of the symmetric Hessian */
     static constexpr int NH = NP * (NP + 1) / 2;
 };
 
-/* K10.  Candidates 0 .. n-1 are indir[0 .. n); the last n_new of them are new tracks whose metadata is set up here from
- * newpx, the others (klt_template_is_first_observation == false) take their converged position as the new template. */
-template <bool OFF, bool GAIN>
+/* K10.  Candidates 0 .. n-1 are cand[0 .. n), every camera's "last n" tracks one camera after the other.  A word with
+ * FT_CAND_NEW is a new track whose metadata is set up here from newpx[candidate], the others
+ * (klt_template_is_first_observation == false) take their converged position as the new template. */
+template <bool OFF, bool GAIN, bool BUNDLE>
 __global__ void __launch_bounds__(64)
-k_ft_update(int n, int n_new, const int32_t* __restrict__ indir, const float2* __restrict__ newpx, const uint8_t* __restrict__ pyr, FtGeom G,
+k_ft_update(int n, const uint32_t* __restrict__ cand, const float2* __restrict__ newpx, const uint8_t* __restrict__ pyr, FtGeom G,
             float* __restrict__ meta, int32_t* __restrict__ patches, float* __restrict__ invh) {
     constexpr int NH = FtDim<OFF, GAIN>::NH;
     const int t = threadIdx.x & 31, cx = blockIdx.x * 2 + (threadIdx.x >> 5);
     if (cx >= n) return; /* an idle half */
-    const int bx = indir[cx];
+    const uint32_t cw = cand[cx];
+    const int slot = BUNDLE ? (int)((cw >> FT_CAND_SLOT_SHIFT) & FT_CAND_SLOT) : 0, bx = slot * G.max_ftr + (int)(cw & FT_CAND_ID);
     float* m = meta + (size_t)bx * FT_META;
     float2 ref;
-    if (cx >= n - n_new) { /* addTrack, feature_tracker_gpu.cpp:338-350 */
-        ref = newpx[cx - (n - n_new)];
+    if (cw & FT_CAND_NEW) { /* addTrack, feature_tracker_gpu.cpp:338-350 */
+        ref = newpx[cx];
         if (t == 0) {
             m[FT_TEMPLATE] = m[FT_FIRST] = m[FT_CUR] = ref.x;
             m[FT_TEMPLATE + 1] = m[FT_FIRST + 1] = m[FT_CUR + 1] = ref.y;
@@ -150,7 +169,8 @@ k_ft_update(int n, int n_new, const int32_t* __restrict__ indir, const float2* _
             if (t == 0) hb[0] = __uint_as_float(FT_NAN);
             continue;
         }
-        const uint8_t* tl = pyr + lg.base + (size_t)y_tl * lg.pitch + x_tl;
+        /* image `slot` of the level starts slot * bytes = slot * h rows behind the level's base (fg_pyramid_layout) */
+        const uint8_t* tl = pyr + lg.base + (size_t)(slot * lg.h + y_tl) * lg.pitch + x_tl;
         for (int id = t; id < stride * stride; id += 32) {
             const int yy = id / stride, xx = id - yy * stride;
             pb[id] = (int32_t)tl[yy * lg.pitch + xx];
@@ -204,14 +224,16 @@ k_ft_update(int n, int n_new, const int32_t* __restrict__ indir, const float2* _
 }
 
 /* K11.  result[cx] = (cur_px, disparity) of candidate cx, or the NaN word twice where it did not converge. */
-template <bool OFF, bool GAIN>
+template <bool OFF, bool GAIN, bool BUNDLE>
 __global__ void __launch_bounds__(64)
-k_ft_track(int n, const int32_t* __restrict__ indir, const uint8_t* __restrict__ pyr, FtGeom G, float* __restrict__ meta,
+k_ft_track(int n, const uint32_t* __restrict__ cand, const uint8_t* __restrict__ pyr, FtGeom G, float* __restrict__ meta,
            const int32_t* __restrict__ patches, const float* __restrict__ invh, float4* __restrict__ result) {
     constexpr int NP = FtDim<OFF, GAIN>::NP, NH = FtDim<OFF, GAIN>::NH;
     const int t = threadIdx.x & 31, cx = blockIdx.x * 2 + (threadIdx.x >> 5);
     if (cx >= n) return; /* an idle half */
-    const int bx = indir[cx];
+    const uint32_t cw = cand[cx];
+    const int slot = BUNDLE ? (int)((cw >> FT_CAND_SLOT_SHIFT) & FT_CAND_SLOT) : 0;
+    const int bx = BUNDLE ? slot * G.max_ftr + (int)(cw & FT_CAND_ID) : (int)cw; /* one camera: the word is the buffer id */
     float* m = meta + (size_t)bx * FT_META;
     const int32_t* pb = patches + (size_t)bx * G.nlev * G.max_area;
     const float* hb = invh + (size_t)bx * G.nlev * 10;
@@ -233,7 +255,10 @@ k_ft_track(int n, const int32_t* __restrict__ indir, const uint8_t* __restrict__
         const int sh = 31 - __clz(ps), rstep = 32 >> sh, ppt = (ps * ps) >> 5;
         const int px = t & (ps - 1), py = t >> sh;
         const int32_t* ref0 = pb + (py + 1) * stride + px + 1;
+        /* image `slot` of the level starts slot * bytes = slot * h rows behind the level's base (fg_pyramid_layout): the
+         * lane's row within the patch, counted from the base */
         const uint8_t* img = pyr + lg.base;
+        const int row0 = slot * lg.h + py;
         float iH[NH];
 #pragma unroll
         for (int k = 0; k < NH; k++) iH[k] = hb[k];
@@ -249,7 +274,7 @@ k_ft_track(int n, const int32_t* __restrict__ indir, const uint8_t* __restrict__
             const float wTL = __fmul_rn(__fsub_rn(1.0f, sx), __fsub_rn(1.0f, sy)), wTR = __fmul_rn(sx, __fsub_rn(1.0f, sy));
             const float wBL = __fmul_rn(__fsub_rn(1.0f, sx), sy), wBR = __fmul_rn(sx, sy);
             const float gain1 = __fadd_rn(1.0f, alpha);
-            const uint8_t* it = img + (size_t)(v - half + py) * lg.pitch + (u - half + px);
+            const uint8_t* it = img + (size_t)(v - half + row0) * lg.pitch + (u - half + px);
             const int32_t* r = ref0;
             float J[NP];
 #pragma unroll
@@ -326,17 +351,24 @@ k_ft_track(int n, const int32_t* __restrict__ indir, const uint8_t* __restrict__
 struct vslam_ft {
     vslam_ft_params p;
     GdHost* det = nullptr;
-    vslam_ftbook* book = nullptr;
+    int n_cam = 0;
+    std::vector<vslam_ftbook*> book; /* one per camera; the track-id counter is threaded through them (next_id) */
+    int next_id = 0;
     FtGeom G;
-    int max_ftr = 0;
+    int max_ftr = 0; /* per camera */
+    size_t cap = 0;  /* n_cam * max_ftr: candidates, buffers */
     size_t pyr_bytes = 0;
-    uint8_t *d_pyr = nullptr, *d_stage = nullptr, *h_stage = nullptr; /* stage: int32 indir[max_ftr] | float2 newpx[max_ftr] */
+    /* stage, packed anew in every call so that it goes up as one range: float2 newpx[n_upd] (per entry of ucand) |
+     * uint32 cand[n] (the next call's k_ft_track; cand_off bytes in) | uint32 ucand[n_upd] (k_ft_update); n, n_upd <= cap */
+    uint8_t *d_pyr = nullptr, *d_stage = nullptr, *h_stage = nullptr;
+    size_t cand_off = 0;
     float *d_meta = nullptr, *d_invh = nullptr, *h_res = nullptr;
     float4* d_res = nullptr;
     int32_t* d_patch = nullptr;
-    std::vector<float> pos, score;
+    std::vector<float> pos, score; /* the detector's grids of slots 0 .. n_cam - 1 */
     std::vector<int32_t> level;
     std::vector<vslam_ft_track_info> info;
+    std::vector<int32_t> n_live, tracked, detected; /* per camera, within a call */
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr}; /* vslam_ft_profile: around k_ft_track, around k_ft_update */
     bool profile = false, ran_track = false, ran_update = false;
 };
@@ -345,6 +377,9 @@ template <class K>
 static K* ft_pick(const vslam_ft* ft, K* k00, K* k10, K* k01, K* k11) {
     return ft->p.affine_est_offset ? (ft->p.affine_est_gain ? k11 : k10) : (ft->p.affine_est_gain ? k01 : k00);
 }
+#define FT_KERNEL(ft, k) \
+    ((ft)->n_cam > 1 ? ft_pick(ft, k<false, false, true>, k<true, false, true>, k<false, true, true>, k<true, true, true>) \
+                     : ft_pick(ft, k<false, false, false>, k<true, false, false>, k<false, true, false>, k<true, true, false>))
 
 extern "C" void vslam_ft_destroy(vslam_ft* ft) {
     if (!ft) return;
@@ -362,18 +397,18 @@ extern "C" void vslam_ft_destroy(vslam_ft* ft) {
     if (ft->h_res) (void)hipHostFree(ft->h_res);
     if (ft->d_res) (void)hipFree(ft->d_res);
     if (ft->d_patch) (void)hipFree(ft->d_patch);
-    vslam_ftbook_destroy(ft->book);
+    for (vslam_ftbook* b : ft->book) vslam_ftbook_destroy(b);
     delete ft;
 }
 
 static int ft_alloc(vslam_ft* ft) {
-    const size_t n = (size_t)ft->max_ftr;
+    const size_t n = ft->cap;
     HIPCHK(hipSetDevice(ft->det->device));
     HIPCHK(hipMalloc((void**)&ft->d_pyr, ft->pyr_bytes));
     HIPCHK(hipMemset(ft->d_pyr, 0, ft->pyr_bytes));
-    HIPCHK(hipMalloc((void**)&ft->d_stage, n * 12));
-    HIPCHK((hipError_t)vslam_pinned_alloc((void**)&ft->h_stage, n * 12));
-    memset(ft->h_stage, 0, n * 12);
+    HIPCHK(hipMalloc((void**)&ft->d_stage, n * 16));
+    HIPCHK((hipError_t)vslam_pinned_alloc((void**)&ft->h_stage, n * 16));
+    memset(ft->h_stage, 0, n * 16);
     HIPCHK(hipMalloc((void**)&ft->d_meta, n * FT_META * 4));
     HIPCHK(hipMemset(ft->d_meta, 0, n * FT_META * 4));
     HIPCHK(hipMalloc((void**)&ft->d_patch, n * ft->G.nlev * ft->G.max_area * 4));
@@ -386,7 +421,7 @@ static int ft_alloc(vslam_ft* ft) {
     return VSLAM_OK;
 }
 
-extern "C" int vslam_ft_create(const vslam_ft_params* p, int detector_kind, void* detector, vslam_ft** out) {
+extern "C" int vslam_ft_create_bundle(const vslam_ft_params* p, int detector_kind, void* detector, int n_cameras, vslam_ft** out) {
     if (!p || !out || !detector || (detector_kind != VSLAM_FT_DETECTOR_FAST && detector_kind != VSLAM_FT_DETECTOR_HARRIS)) {
         g_err = "invalid arguments";
         return VSLAM_ERR_INVALID;
@@ -395,6 +430,10 @@ extern "C" int vslam_ft_create(const vslam_ft_params* p, int detector_kind, void
     /* vslam_fg and vslam_hg derive from GdHost and from nothing else (vslam_fastgrid.hip, vslam_harrisgrid.hip), so either
      * handle is the address of its GdHost: the tracker needs no more of a detector than DetectorBaseGPU offers */
     GdHost* det = reinterpret_cast<GdHost*>(detector);
+    if (n_cameras < 1 || n_cameras > det->max_batch) {
+        g_err = "vslam_ft_create_bundle: 1 <= n_cameras <= the detector's max_batch";
+        return VSLAM_ERR_INVALID;
+    }
     const FgLevel& L0 = det->G.lv[0];
     bool ok = det->launch && p->klt_min_level >= 0 && p->klt_max_level > p->klt_min_level && p->klt_max_level < VSLAM_FT_MAX_LEVELS &&
               p->pyramid_levels >= p->klt_max_level + 1 && p->pyramid_levels >= det->G.max_level && p->pyramid_levels <= FG_MAX_LEVELS &&
@@ -417,16 +456,22 @@ extern "C" int vslam_ft_create(const vslam_ft_params* p, int detector_kind, void
     vslam_ft* ft = new vslam_ft();
     ft->p = *p;
     ft->det = det;
-    if (vslam_ftbook_create(p, det->G.n_cols, det->G.n_rows, det->G.cw, det->G.ch, &ft->book) != 0) {
-        delete ft;
-        g_err = "vslam_ft_create: min_tracks_to_detect_new_features and use_best_n_features leave no room for a track";
-        return VSLAM_ERR_INVALID;
+    ft->n_cam = n_cameras;
+    for (int c = 0; c < n_cameras; c++) {
+        vslam_ftbook* b = nullptr;
+        if (vslam_ftbook_create(p, det->G.n_cols, det->G.n_rows, det->G.cw, det->G.ch, &b) != 0) {
+            vslam_ft_destroy(ft);
+            g_err = "vslam_ft_create: min_tracks_to_detect_new_features and use_best_n_features leave no room for a track";
+            return VSLAM_ERR_INVALID;
+        }
+        ft->book.push_back(b);
     }
-    ft->max_ftr = vslam_ftbook_capacity(ft->book);
+    ft->max_ftr = vslam_ftbook_capacity(ft->book[0]); /* at most 2^20 (vslam_ftbook_create): FT_CAND_ID holds a buffer id */
+    ft->cap = (size_t)ft->max_ftr * n_cameras;
     FtGeom& G = ft->G;
     memset(&G, 0, sizeof(G));
     /* the detector's level-major layout, continued: a level's base does not depend on how many levels follow, so the
-     * detector's kernel finds its levels in this pyramid where it finds them in its own */
+     * detector's kernel finds its levels, and every image slot of them, in this pyramid where it finds them in its own */
     ft->pyr_bytes = fg_pyramid_layout(G.lv, L0.w, L0.h, p->pyramid_levels, det->max_batch);
     for (int l = 0; l < VSLAM_FT_MAX_LEVELS; l++) G.ps[l] = p->klt_patch_sizes[l];
     G.min_level = p->klt_min_level;
@@ -434,10 +479,14 @@ extern "C" int vslam_ft_create(const vslam_ft_params* p, int detector_kind, void
     G.nlev = p->klt_max_level - p->klt_min_level + 1;
     G.max_area = (max_ps + 2) * (max_ps + 2); /* feature_tracker_gpu.cpp:68-76, over the levels in use */
     G.min_update_squared = p->klt_min_update_squared;
-    ft->pos.resize((size_t)det->cells * 2);
-    ft->score.resize((size_t)det->cells);
-    ft->level.resize((size_t)det->cells);
+    G.max_ftr = ft->max_ftr;
+    ft->pos.resize((size_t)det->cells * 2 * n_cameras);
+    ft->score.resize((size_t)det->cells * n_cameras);
+    ft->level.resize((size_t)det->cells * n_cameras);
     ft->info.resize((size_t)ft->max_ftr);
+    ft->n_live.resize((size_t)n_cameras);
+    ft->tracked.resize((size_t)n_cameras);
+    ft->detected.resize((size_t)n_cameras);
     if (ft_alloc(ft) != VSLAM_OK) {
         vslam_ft_destroy(ft);
         return VSLAM_ERR_HIP;
@@ -446,33 +495,48 @@ extern "C" int vslam_ft_create(const vslam_ft_params* p, int detector_kind, void
     return VSLAM_OK;
 }
 
-extern "C" int vslam_ft_capacity(const vslam_ft* ft) { return ft ? ft->max_ftr : -1; }
+extern "C" int vslam_ft_create(const vslam_ft_params* p, int detector_kind, void* detector, vslam_ft** out) {
+    return vslam_ft_create_bundle(p, detector_kind, detector, 1, out);
+}
 
-extern "C" int vslam_ft_track(vslam_ft* ft, const uint8_t* img, size_t pitch, int on_device, int32_t* n_tracked, int32_t* n_detected) {
-    if (!ft || !img || pitch < (size_t)ft->G.lv[0].w) {
+extern "C" int vslam_ft_capacity(const vslam_ft* ft) { return ft ? ft->max_ftr : -1; }
+extern "C" int vslam_ft_cameras(const vslam_ft* ft) { return ft ? ft->n_cam : -1; }
+
+extern "C" int vslam_ft_track_bundle(vslam_ft* ft, const uint8_t* const* imgs, size_t pitch, int on_device, int32_t* n_tracked,
+                                     int32_t* n_detected) {
+    if (!ft || !imgs || pitch < (size_t)ft->G.lv[0].w) {
         g_err = "invalid arguments";
         return VSLAM_ERR_INVALID;
     }
+    const int C = ft->n_cam;
+    for (int c = 0; c < C; c++)
+        if (!imgs[c]) {
+            g_err = "null image";
+            return VSLAM_ERR_INVALID;
+        }
     GdHost* det = ft->det;
     HIPCHK(hipSetDevice(det->device));
     hipStream_t st = det->stream;
     CopyRanges R;
     memset(&R, 0, sizeof(R));
-    R.n = 1;
-    /* 00) the frame's pyramid, once for the tracker and the detector */
-    const uint8_t* one[1] = {img};
-    gd_stage_images(det, 1, one, pitch, on_device, ft->d_pyr);
-    fg_pyramid_halfsample(st, ft->d_pyr, ft->G.lv, ft->p.pyramid_levels, 1);
-    /* 01) + 02) track what there is; its indirection list went up at the end of the previous call */
-    int n = 0, tracked = 0, detected = 0;
-    vslam_ftbook_tracks(ft->book, nullptr, 0, &n);
+    /* 00) the bundle's pyramids, once for the tracker and the detector: camera c is image slot c of every level */
+    gd_stage_images(det, C, imgs, pitch, on_device, ft->d_pyr);
+    fg_pyramid_halfsample(st, ft->d_pyr, ft->G.lv, ft->p.pyramid_levels, C);
+    /* 01) + 02) track what there is, one camera's tracks after the other's; the candidate words went up at the end of the
+     * previous call */
+    int n = 0;
+    for (int c = 0; c < C; c++) {
+        vslam_ftbook_tracks(ft->book[c], nullptr, 0, &ft->n_live[c]);
+        n += ft->n_live[c];
+    }
     ft->ran_track = n > 0;
     if (n > 0) {
         if (ft->profile) HIPCHK(hipEventRecord(ft->ev[0], st));
-        hipLaunchKernelGGL(ft_pick(ft, k_ft_track<false, false>, k_ft_track<true, false>, k_ft_track<false, true>, k_ft_track<true, true>),
-                           dim3((n + 1) / 2), dim3(64), 0, st, n, (const int32_t*)ft->d_stage, ft->d_pyr, ft->G, ft->d_meta, ft->d_patch,
+        hipLaunchKernelGGL(FT_KERNEL(ft, k_ft_track),
+                           dim3((n + 1) / 2), dim3(64), 0, st, n, (const uint32_t*)(ft->d_stage + ft->cand_off), ft->d_pyr, ft->G, ft->d_meta, ft->d_patch,
                            ft->d_invh, ft->d_res);
         if (ft->profile) HIPCHK(hipEventRecord(ft->ev[1], st));
+        R.n = 1;
         R.dst[0] = ft->h_res;
         R.src[0] = ft->d_res;
         R.bytes[0] = (size_t)n * 16;
@@ -480,44 +544,90 @@ extern "C" int vslam_ft_track(vslam_ft* ft, const uint8_t* img, size_t pitch, in
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(st));
     }
-    vslam_ftbook_results(ft->book, ft->h_res, n);
-    vslam_ftbook_tracks(ft->book, nullptr, 0, &tracked);
-    /* 03) detect on the same pyramid where too few tracks are left */
-    if (vslam_ftbook_need_detect(ft->book)) {
-        const int rc = gd_detect_pyramid(det, 1, ft->d_pyr, ft->pos.data(), ft->score.data(), ft->level.data());
-        if (rc != VSLAM_OK) return rc;
-        vslam_ftbook_detect(ft->book, ft->pos.data(), ft->score.data(), ft->level.data(), &detected);
-        if (ft->p.reset_before_detection) tracked = 0;
+    int hi = 0; /* one more than the highest camera that wants new features */
+    for (int c = 0, at = 0; c < C; at += ft->n_live[c], c++) {
+        vslam_ftbook_results(ft->book[c], ft->h_res + (size_t)at * 4, ft->n_live[c]);
+        vslam_ftbook_tracks(ft->book[c], nullptr, 0, &ft->tracked[c]);
+        ft->detected[c] = 0;
+        if (vslam_ftbook_need_detect(ft->book[c])) hi = c + 1;
     }
-    /* 04) one upload: every track's buffer id, then the new tracks' positions; templates for the last `last_n` tracks */
-    vslam_ftbook_tracks(ft->book, ft->info.data(), ft->max_ftr, &n);
-    const int last_n = vslam_ftbook_update_count(ft->book);
-    int32_t* indir = (int32_t*)ft->h_stage;
-    float* newpx = (float*)(ft->h_stage + (size_t)ft->max_ftr * 4);
-    for (int i = 0; i < n; i++) indir[i] = ft->info[i].buffer_id;
-    for (int i = 0; i < detected; i++) {
-        newpx[2 * i] = ft->info[n - detected + i].first_pos[0];
-        newpx[2 * i + 1] = ft->info[n - detected + i].first_pos[1];
+    /* 03) detect on the same pyramids where too few tracks are left: one launch over the slots [0, hi).  Detection keeps
+     * no state, so the grid of a camera below hi that did not ask is computed and not read.  Ids go camera by camera. */
+    if (hi > 0) {
+        const int rc = gd_detect_pyramid(det, hi, ft->d_pyr, ft->pos.data(), ft->score.data(), ft->level.data());
+        if (rc != VSLAM_OK) return rc;
+        const size_t cells = (size_t)det->cells;
+        for (int c = 0; c < hi; c++) {
+            vslam_ftbook* b = ft->book[c];
+            if (!vslam_ftbook_need_detect(b)) continue;
+            vslam_ftbook_set_next_id(b, ft->next_id);
+            int d = 0;
+            vslam_ftbook_detect(b, ft->pos.data() + cells * 2 * c, ft->score.data() + cells * c, ft->level.data() + cells * c, &d);
+            ft->next_id = vslam_ftbook_next_id(b);
+            ft->detected[c] = d;
+            if (ft->p.reset_before_detection) ft->tracked[c] = 0;
+        }
+    }
+    /* 04) one upload, one range: the positions of the update candidates that are new tracks, every track's candidate word
+     * for the next call's k_ft_track, and the candidate words of every camera's last `last_n` tracks, which get templates */
+    int n_upd = 0;
+    n = 0;
+    for (int c = 0; c < C; c++) {
+        vslam_ftbook_tracks(ft->book[c], nullptr, 0, &ft->n_live[c]);
+        n += ft->n_live[c];
+        n_upd += std::min(ft->n_live[c], vslam_ftbook_update_count(ft->book[c]));
+    }
+    float* newpx = (float*)ft->h_stage;
+    uint32_t *cand = (uint32_t*)ft->h_stage + 2 * (size_t)n_upd, *ucand = cand + n;
+    ft->cand_off = 8 * (size_t)n_upd;
+    for (int c = 0, at = 0, u = 0; c < C; at += ft->n_live[c], c++) {
+        const int nc = ft->n_live[c], first_upd = nc - std::min(nc, vslam_ftbook_update_count(ft->book[c]));
+        vslam_ftbook_tracks(ft->book[c], ft->info.data(), ft->max_ftr, nullptr);
+        for (int i = 0; i < nc; i++) {
+            const uint32_t w = ((uint32_t)c << FT_CAND_SLOT_SHIFT) | (uint32_t)ft->info[i].buffer_id;
+            cand[at + i] = w;
+            if (i < first_upd) continue;
+            if (i >= nc - ft->detected[c]) { /* the new tracks are the last `detected` of the camera's list */
+                ucand[u] = w | FT_CAND_NEW;
+                newpx[2 * u] = ft->info[i].first_pos[0];
+                newpx[2 * u + 1] = ft->info[i].first_pos[1];
+            } else {
+                ucand[u] = w;
+            }
+            u++;
+        }
     }
     if (n > 0) {
+        R.n = 1;
         R.dst[0] = ft->d_stage;
         R.src[0] = ft->h_stage;
-        R.bytes[0] = (size_t)ft->max_ftr * 12;
+        R.bytes[0] = ((size_t)n + 3 * (size_t)n_upd) * 4;
         vk_copy_ranges(st, R);
     }
-    ft->ran_update = last_n > 0;
-    if (last_n > 0) {
+    ft->ran_update = n_upd > 0;
+    if (n_upd > 0) {
         if (ft->profile) HIPCHK(hipEventRecord(ft->ev[2], st));
-        hipLaunchKernelGGL(ft_pick(ft, k_ft_update<false, false>, k_ft_update<true, false>, k_ft_update<false, true>, k_ft_update<true, true>),
-                           dim3((last_n + 1) / 2), dim3(64), 0, st, last_n, detected, (const int32_t*)ft->d_stage + (n - last_n),
-                           (const float2*)(ft->d_stage + (size_t)ft->max_ftr * 4), ft->d_pyr, ft->G, ft->d_meta, ft->d_patch, ft->d_invh);
+        hipLaunchKernelGGL(FT_KERNEL(ft, k_ft_update),
+                           dim3((n_upd + 1) / 2), dim3(64), 0, st, n_upd, (const uint32_t*)(ft->d_stage + ft->cand_off) + n,
+                           (const float2*)ft->d_stage, ft->d_pyr, ft->G, ft->d_meta, ft->d_patch, ft->d_invh);
         if (ft->profile) HIPCHK(hipEventRecord(ft->ev[3], st));
     }
     HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st)); /* the staging blocks and the caller's image are free again */
-    if (n_tracked) *n_tracked = tracked;
-    if (n_detected) *n_detected = detected;
+    HIPCHK(hipStreamSynchronize(st)); /* the staging blocks and the caller's images are free again */
+    for (int c = 0; c < C; c++) {
+        if (n_tracked) n_tracked[c] = ft->tracked[c];
+        if (n_detected) n_detected[c] = ft->detected[c];
+    }
     return VSLAM_OK;
+}
+
+extern "C" int vslam_ft_track(vslam_ft* ft, const uint8_t* img, size_t pitch, int on_device, int32_t* n_tracked, int32_t* n_detected) {
+    if (!ft || !img || ft->n_cam != 1) {
+        g_err = ft && ft->n_cam != 1 ? "vslam_ft_track: a bundle of several cameras takes vslam_ft_track_bundle" : "invalid arguments";
+        return VSLAM_ERR_INVALID;
+    }
+    const uint8_t* one[1] = {img};
+    return vslam_ft_track_bundle(ft, one, pitch, on_device, n_tracked, n_detected);
 }
 
 extern "C" int vslam_ft_profile(vslam_ft* ft, int enable) {
@@ -551,32 +661,52 @@ static int ft_book_rc(int rc) {
     g_err = "invalid arguments";
     return VSLAM_ERR_INVALID;
 }
+static const vslam_ftbook* ft_book(const vslam_ft* ft, int camera) { /* nullptr, which every vslam_ftbook_* rejects */
+    return ft && camera >= 0 && camera < ft->n_cam ? ft->book[camera] : nullptr;
+}
 
-extern "C" int vslam_ft_features(const vslam_ft* ft, vslam_ft_feature* out, int cap, int* n) {
-    return ft_book_rc(ft ? vslam_ftbook_features(ft->book, out, cap, n) : -1);
+extern "C" int vslam_ft_features_cam(const vslam_ft* ft, int camera, vslam_ft_feature* out, int cap, int* n) {
+    return ft_book_rc(vslam_ftbook_features(ft_book(ft, camera), out, cap, n));
 }
-extern "C" int vslam_ft_tracks(const vslam_ft* ft, vslam_ft_track_info* out, int cap, int* n) {
-    return ft_book_rc(ft ? vslam_ftbook_tracks(ft->book, out, cap, n) : -1);
+extern "C" int vslam_ft_tracks_cam(const vslam_ft* ft, int camera, vslam_ft_track_info* out, int cap, int* n) {
+    return ft_book_rc(vslam_ftbook_tracks(ft_book(ft, camera), out, cap, n));
 }
-extern "C" int vslam_ft_disparity(const vslam_ft* ft, double pivot_ratio, double* out) {
-    return ft_book_rc(ft ? vslam_ftbook_disparity(ft->book, pivot_ratio, out) : -1);
+extern "C" int vslam_ft_disparity_cam(const vslam_ft* ft, int camera, double pivot_ratio, double* out) {
+    return ft_book_rc(vslam_ftbook_disparity(ft_book(ft, camera), pivot_ratio, out));
 }
-extern "C" int vslam_ft_reset(vslam_ft* ft) { return ft_book_rc(ft ? vslam_ftbook_reset(ft->book) : -1); }
-extern "C" int vslam_ft_set_best_n(vslam_ft* ft, int n) { return ft_book_rc(ft ? vslam_ftbook_set_best_n(ft->book, n) : -1); }
-extern "C" int vslam_ft_set_min_tracks(vslam_ft* ft, int n) { return ft_book_rc(ft ? vslam_ftbook_set_min_tracks(ft->book, n) : -1); }
+extern "C" int vslam_ft_features(const vslam_ft* ft, vslam_ft_feature* out, int cap, int* n) { return vslam_ft_features_cam(ft, 0, out, cap, n); }
+extern "C" int vslam_ft_tracks(const vslam_ft* ft, vslam_ft_track_info* out, int cap, int* n) { return vslam_ft_tracks_cam(ft, 0, out, cap, n); }
+extern "C" int vslam_ft_disparity(const vslam_ft* ft, double pivot_ratio, double* out) { return vslam_ft_disparity_cam(ft, 0, pivot_ratio, out); }
 
-extern "C" int vslam_ft_template_copy(vslam_ft* ft, int track, int level, int32_t* patch, float* invH) {
+/* the options are the bundle's: every camera's book gets the call; the first refusal is returned */
+template <class F>
+static int ft_all_books(vslam_ft* ft, F f) {
+    int rc = ft ? 0 : -1;
+    for (int c = 0; ft && c < ft->n_cam; c++)
+        if (f(ft->book[c]) != 0) rc = -1;
+    return ft_book_rc(rc);
+}
+extern "C" int vslam_ft_reset(vslam_ft* ft) { return ft_all_books(ft, [](vslam_ftbook* b) { return vslam_ftbook_reset(b); }); }
+extern "C" int vslam_ft_set_best_n(vslam_ft* ft, int n) { return ft_all_books(ft, [n](vslam_ftbook* b) { return vslam_ftbook_set_best_n(b, n); }); }
+extern "C" int vslam_ft_set_min_tracks(vslam_ft* ft, int n) { return ft_all_books(ft, [n](vslam_ftbook* b) { return vslam_ftbook_set_min_tracks(b, n); }); }
+
+extern "C" int vslam_ft_template_copy_cam(vslam_ft* ft, int camera, int track, int level, int32_t* patch, float* invH) {
     int n = 0;
-    if (ft) vslam_ftbook_tracks(ft->book, ft->info.data(), ft->max_ftr, &n);
-    if (!ft || track < 0 || track >= n || level < ft->G.min_level || level > ft->G.max_level || (!patch && !invH)) {
+    const vslam_ftbook* b = ft_book(ft, camera);
+    if (b) vslam_ftbook_tracks(b, ft->info.data(), ft->max_ftr, &n);
+    if (!b || track < 0 || track >= n || level < ft->G.min_level || level > ft->G.max_level || (!patch && !invH)) {
         g_err = "invalid arguments";
         return VSLAM_ERR_INVALID;
     }
-    const size_t slot = (size_t)ft->info[track].buffer_id * ft->G.nlev + (size_t)(ft->G.max_level - level); /* max_level first */
+    const size_t buf = (size_t)camera * ft->max_ftr + (size_t)ft->info[track].buffer_id;
+    const size_t slot = buf * ft->G.nlev + (size_t)(ft->G.max_level - level); /* max_level first */
     const int side = ft->G.ps[level] + 2;
     HIPCHK(hipSetDevice(ft->det->device));
     if (patch) HIPCHK(hipMemcpyAsync(patch, ft->d_patch + slot * ft->G.max_area, (size_t)side * side * 4, hipMemcpyDeviceToHost, ft->det->stream));
     if (invH) HIPCHK(hipMemcpyAsync(invH, ft->d_invh + slot * 10, 40, hipMemcpyDeviceToHost, ft->det->stream));
     HIPCHK(hipStreamSynchronize(ft->det->stream));
     return VSLAM_OK;
+}
+extern "C" int vslam_ft_template_copy(vslam_ft* ft, int track, int level, int32_t* patch, float* invH) {
+    return vslam_ft_template_copy_cam(ft, 0, track, level, patch, invH);
 }

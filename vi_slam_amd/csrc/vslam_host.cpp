@@ -1469,3 +1469,12 @@ extern "C" int vslam_ftbook_set_min_tracks(vslam_ftbook* b, int n) {
     b->p.min_tracks_to_detect_new_features = n;
     return 0;
 }
+
+/* Point::getNewId is one counter for every camera of a FrameBundle: a tracker over several books reads it from one book
+ * after step 03 and hands it to the next before */
+extern "C" int vslam_ftbook_next_id(const vslam_ftbook* b) { return b ? b->next_id : -1; }
+extern "C" int vslam_ftbook_set_next_id(vslam_ftbook* b, int id) {
+    if (!b || id < 0) return -1;
+    b->next_id = id;
+    return 0;
+}

@@ -1,7 +1,8 @@
 """Host-side mirror of the pyramidal Lucas-Kanade feature tracker, vilib::FeatureTrackerGPU
 (thirdparty/vilib/visual_lib/src/feature_tracker/feature_tracker_gpu.cpp, feature_tracker_base.cpp) over the C ABI of
 include/vslam_featuretracker.h.  The constructor takes vilib::FeatureTrackerOptions' fields and the bound detector
-(setDetectorGPU): a fastgrid.FASTGPU or a harrisgrid.HarrisGPU.  Book is the bookkeeping alone, from the GPU-free
+(setDetectorGPU): a fastgrid.FASTGPU or a harrisgrid.HarrisGPU, and how many cameras the object serves (a FrameBundle:
+all of the detector's image size, at most its max_batch).  Book is the bookkeeping alone, from the GPU-free
 libvslam_host.so."""
 import ctypes as C
 
@@ -68,6 +69,13 @@ def _bind(L, prefix):
     f("set_min_tracks").argtypes = [vp, i]
     if prefix == "ft":
         L.vslam_ft_create.argtypes = [C.POINTER(FtParams), i, vp, C.POINTER(vp)]
+        L.vslam_ft_create_bundle.argtypes = [C.POINTER(FtParams), i, vp, i, C.POINTER(vp)]
+        L.vslam_ft_cameras.argtypes = [vp]
+        L.vslam_ft_track_bundle.argtypes = [vp, vp, C.c_size_t, i, vp, vp]
+        L.vslam_ft_features_cam.argtypes = [vp, i, vp, i, C.POINTER(i)]
+        L.vslam_ft_tracks_cam.argtypes = [vp, i, vp, i, C.POINTER(i)]
+        L.vslam_ft_disparity_cam.argtypes = [vp, i, C.c_double, C.POINTER(C.c_double)]
+        L.vslam_ft_template_copy_cam.argtypes = [vp, i, i, i, vp, vp]
         L.vslam_ft_track.argtypes = [vp, vp, C.c_size_t, i, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.vslam_ft_template_copy.argtypes = [vp, i, i, vp, vp]
         L.vslam_ft_profile.argtypes = [vp, i]
@@ -78,6 +86,8 @@ def _bind(L, prefix):
         L.vslam_ftbook_need_detect.argtypes = [vp]
         L.vslam_ftbook_detect.argtypes = [vp, vp, vp, vp, C.POINTER(i)]
         L.vslam_ftbook_update_count.argtypes = [vp]
+        L.vslam_ftbook_next_id.argtypes = [vp]
+        L.vslam_ftbook_set_next_id.argtypes = [vp, i]
     _bound.add(key)
 
 
@@ -104,23 +114,33 @@ class _ReadSide:
         except Exception:
             pass
 
-    def _list(self, name, dtype):
+    def _cam(self, name, camera):
+        """the function and its leading arguments; a tracker's read side names the camera, a book is one camera"""
+        if self._prefix == "ft":
+            return self._fn(name + "_cam"), (self._h, camera)
+        if camera != 0:
+            raise ValueError("vslam_ftbook: a book is one camera")
+        return self._fn(name), (self._h,)
+
+    def _list(self, name, dtype, camera):
         out = np.zeros(self.capacity, dtype)
         n = C.c_int()
-        self._ok(self._fn(name)(self._h, _p(out), self.capacity, C.byref(n)))
+        f, head = self._cam(name, camera)
+        self._ok(f(*head, _p(out), self.capacity, C.byref(n)))
         return out[:n.value]
 
-    def features(self):
+    def features(self, camera=0):
         """the frame's feature list in addFeature order: px, score, level, track_id"""
-        return self._list("features", FEATURE_DTYPE)
+        return self._list("features", FEATURE_DTYPE, camera)
 
-    def tracks(self):
+    def tracks(self, camera=0):
         """the live tracks: first_pos, cur_pos, cur_disparity, life, track_id, buffer_id"""
-        return self._list("tracks", TRACK_DTYPE)
+        return self._list("tracks", TRACK_DTYPE, camera)
 
-    def getDisparity(self, pivot_ratio):
+    def getDisparity(self, pivot_ratio, camera=0):
         d = C.c_double()
-        self._ok(self._fn("disparity")(self._h, pivot_ratio, C.byref(d)))
+        f, head = self._cam("disparity", camera)
+        self._ok(f(*head, pivot_ratio, C.byref(d)))
         return d.value
 
     def reset(self):
@@ -134,10 +154,12 @@ class _ReadSide:
 
 
 class FeatureTrackerGPU(_ReadSide):
-    """vilib::FeatureTrackerGPU(options, 1) + setDetectorGPU(detector, 0).  Keep the detector alive as long as the tracker."""
+    """vilib::FeatureTrackerGPU(options, cameras) + setDetectorGPU(detector, c) for every camera c: the cameras share the
+    detector (image size, grid, stream; cameras <= its max_batch) and the options, and nothing else but the track-id counter.
+    Keep the detector alive as long as the tracker.  capacity is per camera."""
     _prefix = "ft"
 
-    def __init__(self, detector, **options):
+    def __init__(self, detector, cameras=1, **options):
         self._h = None
         self.L = lib()
         _bind(self.L, "ft")
@@ -145,9 +167,10 @@ class FeatureTrackerGPU(_ReadSide):
         self.params = make_params(**options)
         h = C.c_void_p()
         kind = DETECTOR_HARRIS if detector._prefix == "hg" else DETECTOR_FAST
-        _check(self.L.vslam_ft_create(C.byref(self.params), kind, detector._h, C.byref(h)))
+        _check(self.L.vslam_ft_create_bundle(C.byref(self.params), kind, detector._h, cameras, C.byref(h)))
         self._h = h
         self.capacity = self.L.vslam_ft_capacity(h)
+        self.cameras = self.L.vslam_ft_cameras(h)
 
     def track(self, image=None, dev_ptr=None, pitch=None):
         """FeatureTrackerGPU::track on one frame: a host array, or a device address (dev_ptr, pitch) -> (n_tracked, n_detected)"""
@@ -160,6 +183,22 @@ class FeatureTrackerGPU(_ReadSide):
             _check(self.L.vslam_ft_track(self._h, C.c_void_p(dev_ptr), pitch, 1, C.byref(nt), C.byref(nd)))
         return nt.value, nd.value
 
+    def track_bundle(self, images=None, dev_ptrs=None, pitch=None):
+        """FeatureTrackerGPU::track on a FrameBundle: one host array per camera, or one device address per camera
+        (dev_ptrs, pitch) -> [(n_tracked, n_detected)] per camera"""
+        n = self.cameras
+        nt, nd = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        if dev_ptrs is None:
+            images = [np.ascontiguousarray(im, np.uint8) for im in images]
+            assert len(images) == n and all(im.shape == (self.detector.height, self.detector.width) for im in images)
+            ptrs = (C.c_void_p * n)(*[im.ctypes.data for im in images])
+            _check(self.L.vslam_ft_track_bundle(self._h, ptrs, images[0].strides[0], 0, _p(nt), _p(nd)))
+        else:
+            assert len(dev_ptrs) == n
+            ptrs = (C.c_void_p * n)(*dev_ptrs)
+            _check(self.L.vslam_ft_track_bundle(self._h, ptrs, pitch, 1, _p(nt), _p(nd)))
+        return [(int(a), int(b)) for a, b in zip(nt, nd)]
+
     def profile(self, enable=True):
         """diagnostic: bracket the two kernels of every track() with HIP events"""
         _check(self.L.vslam_ft_profile(self._h, 1 if enable else 0))
@@ -170,11 +209,11 @@ class FeatureTrackerGPU(_ReadSide):
         _check(self.L.vslam_ft_kernel_ms(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
-    def template(self, track, level):
-        """diagnostic: (patch[(ps+2), (ps+2)] int32, invH[10] float32) of live track `track` on pyramid level `level`"""
+    def template(self, track, level, camera=0):
+        """diagnostic: (patch[(ps+2), (ps+2)] int32, invH[10] float32) of camera `camera`'s live track `track` on pyramid level `level`"""
         side = self.params.klt_patch_sizes[level] + 2
         patch, inv = np.zeros((side, side), np.int32), np.zeros(10, np.float32)
-        _check(self.L.vslam_ft_template_copy(self._h, track, level, _p(patch), _p(inv)))
+        _check(self.L.vslam_ft_template_copy_cam(self._h, camera, track, level, _p(patch), _p(inv)))
         return patch, inv
 
 
@@ -207,3 +246,12 @@ class Book(_ReadSide):
 
     def update_count(self):
         return self.L.vslam_ftbook_update_count(self._h)
+
+    @property
+    def next_id(self):
+        """the id the next new track gets; a tracker over several books threads one counter through them"""
+        return self.L.vslam_ftbook_next_id(self._h)
+
+    @next_id.setter
+    def next_id(self, value):
+        self._ok(self.L.vslam_ftbook_set_next_id(self._h, value))
