@@ -64,7 +64,8 @@ typedef struct vslam_kp {
  * unsynchronised statics, so two threads creating and using two contexts (frame.cpp:107-108) share no mutable state. */
 typedef struct vslam_tuning {
     int32_t pyramid_per_level;    /* VSLAM_PYRAMID=levels: 1 = one launch per pyramid level instead of the fused groups */
-    int32_t pyr_rows;             /* VSLAM_PYR_ROWS: rows of the first computed level per fused-pyramid tile (4..64, default 28) */
+    int32_t pyr_rows;             /* VSLAM_PYR_ROWS: rows of the first computed level per fused-pyramid tile (4..64; default 16 for contexts of
+                                     one or two images, else 32 with pyr_pingpong, 48 / 40 above a megapixel without)  */
     int32_t pyr_threads;          /* retired: accepted and ignored (the fused pyramid runs 256 threads per tile) */
     int32_t blur_rows;            /* VSLAM_BLUR_ROWS: output rows per wave task of the blur (8..512, default 32) */
     int32_t fast_threads;         /* retired: accepted and ignored (128 threads per FAST cell) */
@@ -108,6 +109,11 @@ typedef struct vslam_tuning {
     int32_t oct_precount;         /* retired: accepted and ignored */
     int32_t desc_kpw;             /* VSLAM_DESC_KPW: 1 | 4 keypoints per wave of the descriptor kernel (default: 1 for contexts of one or
                                      two images, else 4) */
+    int32_t pyr_pingpong;         /* VSLAM_PYR_PINGPONG: LDS layout of a fused-pyramid tile.  1 = two regions that alternate levels
+                                     reuse, at most 20 KB per tile, so a tile fits where a k_fast_bands workgroup retired; 0 = every
+                                     level of the group resident, up to 64 KB.  Default: contexts of more than two images of up to a megapixel
+                                     run 1, except for the passes of the stereo-frame entry, which run 0; everything else 0.  A value
+                                     set here holds for every entry */
     int32_t reserved[1];
 } vslam_tuning;
 void vslam_tuning_init(vslam_tuning* t); /* every field = -1 (library default) */

@@ -67,9 +67,14 @@ struct vslam_fe {
     struct PyrGroupCtx {
         PyrGroupDev dev;
         size_t lds_bytes;
+        bool fit; /* ping-pong plan: k_pyramid_group<.., true> */
         PyrTileDev* d_tiles;
     };
     std::vector<PyrGroupCtx> pyr_groups;
+    /* the resident plan beside a default ping-pong one, for the passes of the stereo-frame entry (empty: pyr_groups serves every
+     * entry -- a shape set through vslam_tuning, contexts of one or two images, frames above a megapixel) */
+    std::vector<PyrGroupCtx> pyr_groups_resident;
+    bool pyr_resident_hint = false;   /* the pass being enqueued takes pyr_groups_resident (set by the stereo-frame entry) */
     /* FAST cells */
     std::vector<vslam::HostCell> cells;
     int level_cell_first[VSLAM_MAX_LEVELS + 1] = {};

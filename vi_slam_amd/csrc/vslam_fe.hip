@@ -50,6 +50,7 @@ static void free_ctx(vslam_fe* fe) {
         hipFree(fe->d_quads[l]);
     }
     for (auto& g : fe->pyr_groups) hipFree(g.d_tiles);
+    for (auto& g : fe->pyr_groups_resident) hipFree(g.d_tiles);
     hipFree(fe->d_cells);
     hipFree(fe->d_bands);
     hipFree(fe->d_band_classes);
@@ -209,47 +210,63 @@ static int create_pyramid(vslam_fe* fe) {
     static_assert(sizeof(PyrTileDev) == sizeof(vslam::PyrTileLevel), "planner and kernel share the tile record");
     /* tile height: 16 rows for contexts of one or two images, where a frame's latency counts and more workgroups per image
      * finish sooner (batch-1 latency through the C ABI: 0.135 ms with 12-16 rows, 0.137 with 20-28, 0.142 with 36, 0.146 with
-     * 48); 48 for batches, where the pyramid competes for issue slots -- least halo and fewest prologues, which is what
-     * counts in a VALU-bound pipeline -- and 40 above a megapixel, where the step is the sum of the wide kernels'
-     * single-context times and the pyramid alone is 7 % shorter with smaller tiles
-     * (profiles/r04_pyramid_tile_sweep.txt: 1080p +1.8 %) */
-    const int pyr_rows = fe->tune.pyr_rows >= 0 ? fe->tune.pyr_rows
-                         : fe->B <= 2 ? 16 : (size_t)p.width * p.height > 1000000 ? 40 : 48;
-#ifndef VSLAM_PYR_LDS_KB
-#define VSLAM_PYR_LDS_KB 64 /* LDS a pyramid tile's cascade may take (32 / 48 / 96 measured) */
-#endif
-    for (int l0 = 0; fused && l0 + 1 < p.nlevels;) {
-        const int nl = std::min(l0 == 0 ? 3 : VSLAM_PYR_GROUP_LEVELS, p.nlevels - 1 - l0);
-        std::vector<const vslam::PyrLevelTables*> gt;
-        for (int j = 1; j <= nl; j++) gt.push_back(&pyr_tabs[l0 + j]);
-        vslam::PyrGroupPlan plan;
-        if (!vslam::build_pyramid_group(gt, l0, VSLAM_PYR_LDS_KB * 1024, plan, pyr_rows)) {
-            fused = false;
-            break;
+     * 48); for batches see vslam::pyramid_tile_shape */
+    /* one plan set (a vector of groups) per tile shape; false: some group has no plan at that shape */
+    auto plan_groups = [&](int tune_pingpong, std::vector<vslam_fe::PyrGroupCtx>& out, bool* is_pingpong) -> int {
+        int pyr_rows;
+        bool pyr_pingpong;
+        size_t pyr_lds;
+        vslam::pyramid_tile_shape(p.width, p.height, fe->B, fe->tune.pyr_rows, tune_pingpong, &pyr_rows, &pyr_pingpong, &pyr_lds);
+        if (is_pingpong) *is_pingpong = pyr_pingpong;
+        bool ok = true;
+        for (int l0 = 0; ok && l0 + 1 < p.nlevels;) {
+            const int nl = std::min(l0 == 0 ? 3 : VSLAM_PYR_GROUP_LEVELS, p.nlevels - 1 - l0);
+            std::vector<const vslam::PyrLevelTables*> gt;
+            for (int j = 1; j <= nl; j++) gt.push_back(&pyr_tabs[l0 + j]);
+            vslam::PyrGroupPlan plan;
+            if (!vslam::build_pyramid_group(gt, l0, pyr_lds, plan, pyr_rows, pyr_pingpong)) {
+                ok = false;
+                break;
+            }
+            vslam_fe::PyrGroupCtx g;
+            memset(&g.dev, 0, sizeof(g.dev));
+            g.dev.l0 = l0;
+            g.dev.nl = nl;
+            g.dev.ntiles = plan.ntx * plan.nty;
+            g.dev.readable_w0 = p.width;
+            g.lds_bytes = plan.lds_bytes;
+            g.fit = pyr_pingpong;
+            g.d_tiles = nullptr;
+            UPLOAD(g.d_tiles, plan.tiles.data(), plan.tiles.size() * sizeof(PyrTileDev));
+            g.dev.tiles = g.d_tiles;
+            for (int j = 0; j <= nl; j++) g.dev.lg[j] = fe->geom.lv[l0 + j];
+            for (int j = 1; j <= nl; j++) {
+                g.dev.qbase[j - 1] = fe->d_qbase[l0 + j];
+                g.dev.quads[j - 1] = fe->d_quads[l0 + j];
+                g.dev.ytab[j - 1] = fe->d_ytab[l0 + j];
+                g.dev.yb[j - 1] = fe->d_yb[l0 + j];
+            }
+            out.push_back(g);
+            l0 += nl;
         }
-        vslam_fe::PyrGroupCtx g;
-        memset(&g.dev, 0, sizeof(g.dev));
-        g.dev.l0 = l0;
-        g.dev.nl = nl;
-        g.dev.ntiles = plan.ntx * plan.nty;
-        g.dev.readable_w0 = p.width;
-        g.lds_bytes = plan.lds_bytes;
-        g.d_tiles = nullptr;
-        UPLOAD(g.d_tiles, plan.tiles.data(), plan.tiles.size() * sizeof(PyrTileDev));
-        g.dev.tiles = g.d_tiles;
-        for (int j = 0; j <= nl; j++) g.dev.lg[j] = fe->geom.lv[l0 + j];
-        for (int j = 1; j <= nl; j++) {
-            g.dev.qbase[j - 1] = fe->d_qbase[l0 + j];
-            g.dev.quads[j - 1] = fe->d_quads[l0 + j];
-            g.dev.ytab[j - 1] = fe->d_ytab[l0 + j];
-            g.dev.yb[j - 1] = fe->d_yb[l0 + j];
+        if (!ok) {
+            for (auto& g : out) hipFree(g.d_tiles);
+            out.clear();
         }
-        fe->pyr_groups.push_back(g);
-        l0 += nl;
-    }
-    if (!fused) {
-        for (auto& g : fe->pyr_groups) hipFree(g.d_tiles);
-        fe->pyr_groups.clear();
+        return VSLAM_OK;
+    };
+    if (fused) {
+        bool is_pingpong = false;
+        const int rc = plan_groups(fe->tune.pyr_pingpong, fe->pyr_groups, &is_pingpong);
+        if (rc != VSLAM_OK) return rc;
+        /* The default ping-pong shape is the mono entries': beside the init matcher's coupled contexts it gains 3.7 % at KITTI
+         * size.  Stereo frames lose 2.7 % with it (their step is the sum of the wide kernels' single-context times; FAST beside
+         * a co-resident pyramid is longer), so the stereo-frame entry keeps the resident plan -- chosen per pass, like desc_kpw
+         * (profiles/pyramid_beside_fast_ab.txt).  A shape set through vslam_tuning.pyr_pingpong holds for every entry. */
+        if (is_pingpong && fe->tune.pyr_pingpong < 0 && !fe->pyr_groups.empty()) {
+            const int rc2 = plan_groups(0, fe->pyr_groups_resident, nullptr);
+            if (rc2 != VSLAM_OK) return rc2;
+        }
     }
     return VSLAM_OK;
 }
@@ -893,8 +910,8 @@ static int enqueue_front(vslam_fe* fe, int nimg, const uint8_t* const* imgs, siz
     const bool prof = fe->profiling;
     if (prof) HIPCHK(hipEventRecord(fe->ev_prof[0], st));
     bool first_group = true;
-    for (const auto& g : fe->pyr_groups) {
-        vk_pyramid_group(st, fe->d_pyr, fe->slot_stride, fe->src, g.dev, g.lds_bytes, nimg,
+    for (const auto& g : (fe->pyr_resident_hint && !fe->pyr_groups_resident.empty()) ? fe->pyr_groups_resident : fe->pyr_groups) {
+        vk_pyramid_group(st, fe->d_pyr, fe->slot_stride, fe->src, g.dev, g.lds_bytes, g.fit, nimg,
                          first_group ? fe->d_cand : nullptr, fe->cand_stride, first_group ? d_errw : nullptr);
         first_group = false;
     }
@@ -1130,6 +1147,7 @@ static int enqueue_extract_impl(vslam_fe* fe, int nimg, const uint8_t* const* im
                     (long long)(want_host & 3) ^ ((long long)(lap0 >> 16) << 40) ^ ((long long)(lap1 >> 16) << 24) ^
                     ((long long)on_device << 56); /* host / pinned / staged passes capture different launches */
     if (on_device == VSLAM_IMGS_HOST && fe->h_img_pitch != (size_t)fe->geom.lv[0].pitch) key ^= 1ll << 59; /* dense staging rows */
+    if (fe->pyr_resident_hint && !fe->pyr_groups_resident.empty()) key ^= 1ll << 58; /* the entry's pyramid plan is part of the capture */
     if (on_device == VSLAM_IMGS_PINNED) {
         /* the caller's pointers are kernel arguments of the captured pull: a different set of images is a different
          * graph (a capture-card ring of a few buffers per context hits the cache every time) */

@@ -145,7 +145,7 @@ bool build_resize_quads(const ResizeTables& r, int sw, int dw, std::vector<uint1
 static inline int div_floor4(int x) { return x >> 2; }
 
 static bool plan_with(const std::vector<const PyrLevelTables*>& tabs, int l0, int ntx, int nty, size_t max_lds,
-                      PyrGroupPlan& plan) {
+                      bool pingpong, PyrGroupPlan& plan) {
     const int nl = (int)tabs.size();
     plan.l0 = l0;
     plan.nl = nl;
@@ -189,17 +189,37 @@ static bool plan_with(const std::vector<const PyrLevelTables*>& tabs, int l0, in
                     nr1 = t.r.ytab[2 * (cr1[j] - 1) + 1] + 1;
                 }
             }
-            size_t off = 0;
+            /* LDS layout.  Every level resident: the tiles follow each other.  Ping-pong: level j reads only level j-1, and
+             * the barrier after level j-1 ends the last read of level j-2, so two regions are enough -- the even entries
+             * (source, level 2, ...) share region 0, the odd ones region 1, each as large as its largest tenant. */
+            size_t region[2] = {0, 0};
             for (int j = 0; j <= nl; j++) {
                 T[j].c0 = (int16_t)(4 * cq0[j]);
                 T[j].nc = (int16_t)(4 * (cq1[j] - cq0[j]));
                 T[j].r0 = (int16_t)cr0[j];
                 T[j].nr = (int16_t)(cr1[j] - cr0[j]);
                 T[j].pitch = (uint32_t)((T[j].nc + 8 + 15) & ~15);
-                T[j].lds_off = (uint32_t)off;
-                off += (size_t)T[j].pitch * T[j].nr;
+                region[j & 1] = std::max(region[j & 1], (size_t)T[j].pitch * T[j].nr);
                 if (j >= 1 && T[j].nc / 4 > 64) return false; /* lane = quad */
                 if (j == 0 && T[j].pitch / 16 > 64) return false; /* staging: lane = 16-byte chunk of a row */
+            }
+            size_t off = 0;
+            for (int j = 0; j <= nl; j++) {
+                if (pingpong) T[j].lds_off = (uint32_t)((j & 1) ? region[0] : 0);
+                else {
+                    T[j].lds_off = (uint32_t)off;
+                    off += (size_t)T[j].pitch * T[j].nr;
+                }
+            }
+            if (pingpong) {
+                off = region[0] + region[1];
+                /* what level j overwrites must be dead: its tile may not touch the level it is computed from (each region
+                 * is as large as its largest tenant, so a tile cannot leave its region) */
+                for (int j = 1; j <= nl; j++) {
+                    const size_t d0 = T[j].lds_off, d1 = d0 + (size_t)T[j].pitch * T[j].nr;
+                    const size_t s0 = T[j - 1].lds_off, s1 = s0 + (size_t)T[j - 1].pitch * T[j - 1].nr;
+                    if (d0 < s1 && s0 < d1) return false;
+                }
             }
             for (int j = 1; j <= nl; j++) {
                 T[j].rt_off = (uint32_t)off;
@@ -211,7 +231,20 @@ static bool plan_with(const std::vector<const PyrLevelTables*>& tabs, int l0, in
     return lds_max <= max_lds;
 }
 
-bool build_pyramid_group(const std::vector<const PyrLevelTables*>& tabs, int l0, size_t max_lds, PyrGroupPlan& plan, int rows_override) {
+void pyramid_tile_shape(int width, int height, int batch, int tune_rows, int tune_pingpong, int* rows, bool* pingpong,
+                        size_t* max_lds) {
+    /* contexts of one or two images keep every level resident: their 16-row tiles are small anyway and nothing runs beside
+     * them; so do frames above a megapixel, whose step lost 4 % with the ping-pong tiles (KITTI mono +4 %, 32 rows the best
+     * of 24 / 28 / 32 / 36 / 40: profiles/pyramid_beside_fast_ab.txt).  vslam_fe_create plans the resident shape as well for
+     * the passes of the stereo-frame entry */
+    *pingpong = tune_pingpong >= 0 ? tune_pingpong != 0 : batch > 2 && (size_t)width * height <= 1000000;
+    *rows = tune_rows >= 0 ? tune_rows
+            : batch <= 2 ? 16 : *pingpong ? 32 : (size_t)width * height > 1000000 ? 40 : 48;
+    *max_lds = *pingpong ? (size_t)VSLAM_PYR_PINGPONG_LDS : (size_t)VSLAM_PYR_LDS_KB * 1024;
+}
+
+bool build_pyramid_group(const std::vector<const PyrLevelTables*>& tabs, int l0, size_t max_lds, PyrGroupPlan& plan, int rows_override,
+                         bool pingpong) {
     if (tabs.empty() || tabs.size() > VSLAM_MAX_LEVELS) return false;
     for (const PyrLevelTables* t : tabs)
         if (!t || t->qbase.empty()) return false; /* a level without the quad table: per-level launches */
@@ -226,7 +259,7 @@ bool build_pyramid_group(const std::vector<const PyrLevelTables*>& tabs, int l0,
 #define VSLAM_PYR_TILE_QUADS 52 /* widest tile tried first: quads of the first computed level (a wave's lanes, halo included) */
 #endif
     for (int ntx = std::max(1, (nq1 + VSLAM_PYR_TILE_QUADS - 1) / VSLAM_PYR_TILE_QUADS); ntx <= std::max(1, nq1 / 8); ntx++)
-        if (plan_with(tabs, l0, ntx, nty, max_lds, plan)) return true;
+        if (plan_with(tabs, l0, ntx, nty, max_lds, pingpong, plan)) return true;
     return false;
 }
 
@@ -254,6 +287,17 @@ int emulate_pyramid_group(const PyrGroupPlan& plan, const std::vector<const PyrL
         for (int j = 1; j <= nl; j++) {
             const PyrLevelTables& t = *tabs[j - 1];
             const PyrTileLevel &S = T[j - 1], &D = T[j];
+            {   /* the level's tile may lie over an earlier level's (ping-pong layout): not over the one it reads, not over
+                 * a row table, and what the earlier tenant left there does not count as computed */
+                const size_t d0 = D.lds_off, d1 = d0 + (size_t)D.pitch * D.nr;
+                const size_t s0 = S.lds_off, s1 = s0 + (size_t)S.pitch * S.nr;
+                if (d1 > lds.size()) return -7;
+                if (d0 < s1 && s0 < d1) return -8;
+                for (int k = 1; k <= nl; k++)
+                    if (T[k].nr > 0 && d1 > T[k].rt_off) return -9;
+                std::fill(ok.begin() + d0, ok.begin() + d1, (uint8_t)0);
+                std::fill(lds.begin() + d0, lds.begin() + d1, (uint8_t)0xCD);
+            }
             for (int r = D.r0; r < D.r0 + D.nr; r++) {
                 const int sy0 = t.r.ytab[2 * r], sy1 = t.r.ytab[2 * r + 1], b0 = t.r.yb[2 * r], b1 = t.r.yb[2 * r + 1];
                 if (sy0 < S.r0 || sy1 >= S.r0 + S.nr) return -2;
@@ -878,9 +922,12 @@ int vslamh_resize_with_tables(const uint8_t* src, int sw, int sh, size_t sstride
 
 /* The fused pyramid plan evaluated on the CPU: builds the tables and group plans exactly as vslam_fe_create does
  * (groups of levels 1-3, 4-7, ...) and runs emulate_pyramid_group.  out = all levels >= 1 back to back, level l at
- * offset sum of w*h of the levels before it, tightly packed.  Returns the number of groups, or a negative code. */
-int vslamh_pyramid_fused(const uint8_t* img, int w, int h, size_t stride, int nfeatures, float scale, int nlevels,
-                         uint8_t* out, int* lds_bytes_max, int* tiles_total) {
+ * offset sum of w*h of the levels before it, tightly packed.  Returns the number of groups, or a negative code.
+ * recs (may be null): one row of 16 int32 per (group, tile, entry j) -- group, tile, j, nl, c0, nc, r0, nr, sq0, sq1, sr0,
+ * sr1, lds_off, pitch, rt_off, the plan's lds_bytes -- at most recs_cap rows; *nrecs = rows the plan has. */
+static int pyramid_fused_with(const uint8_t* img, int w, int h, size_t stride, int nfeatures, float scale, int nlevels,
+                              int rows, bool pingpong, size_t max_lds, uint8_t* out, int* lds_bytes_max, int* tiles_total,
+                              int32_t* recs, int recs_cap, int* nrecs) {
     vslam::ExtractorTables t;
     vslam::build_tables(nfeatures, scale, nlevels, t);
     std::vector<vslam::PyrLevelTables> tabs(nlevels);
@@ -900,7 +947,7 @@ int vslamh_pyramid_fused(const uint8_t* img, int w, int h, size_t stride, int nf
         lv[l].assign((size_t)pitch[l] * lh[l], 0xEE);
     }
     for (int y = 0; y < h; y++) memcpy(&lv[0][(size_t)y * pitch[0]], img + (size_t)y * stride, w);
-    int ngroups = 0;
+    int ngroups = 0, nr = 0;
     *lds_bytes_max = 0;
     *tiles_total = 0;
     for (int l0 = 0; l0 + 1 < nlevels;) {
@@ -908,18 +955,27 @@ int vslamh_pyramid_fused(const uint8_t* img, int w, int h, size_t stride, int nf
         std::vector<const vslam::PyrLevelTables*> gt;
         for (int j = 1; j <= nl; j++) gt.push_back(&tabs[l0 + j]);
         vslam::PyrGroupPlan plan;
-        if (!vslam::build_pyramid_group(gt, l0, 64 * 1024, plan)) return -101;
+        if (!vslam::build_pyramid_group(gt, l0, max_lds, plan, rows, pingpong)) return -101;
         std::vector<uint8_t*> dst(nl + 1, nullptr);
         std::vector<int> ds(nl + 1, 0);
         for (int j = 1; j <= nl; j++) { dst[j] = lv[l0 + j].data(); ds[j] = pitch[l0 + j]; }
         /* level 0 may be the caller's image (readable up to w only); internal levels are readable up to their pitch */
         const int rc = vslam::emulate_pyramid_group(plan, gt, lv[l0].data(), pitch[l0], l0 == 0 ? w : pitch[l0], dst, ds);
         if (rc) return rc;
+        for (int tile = 0; tile < plan.ntx * plan.nty; tile++)
+            for (int j = 0; j <= nl; j++, nr++) {
+                if (!recs || nr >= recs_cap) continue;
+                const vslam::PyrTileLevel& T = plan.tiles[(size_t)tile * (nl + 1) + j];
+                const int32_t row[16] = {ngroups, tile, j, nl, T.c0, T.nc, T.r0, T.nr, T.sq0, T.sq1, T.sr0, T.sr1,
+                                         (int32_t)T.lds_off, (int32_t)T.pitch, (int32_t)T.rt_off, (int32_t)plan.lds_bytes};
+                memcpy(recs + (size_t)nr * 16, row, sizeof(row));
+            }
         *lds_bytes_max = std::max(*lds_bytes_max, (int)plan.lds_bytes);
         *tiles_total += plan.ntx * plan.nty;
         ngroups++;
         l0 += nl;
     }
+    if (nrecs) *nrecs = nr;
     size_t o = 0;
     for (int l = 1; l < nlevels; l++)
         for (int y = 0; y < lh[l]; y++) {
@@ -927,6 +983,26 @@ int vslamh_pyramid_fused(const uint8_t* img, int w, int h, size_t stride, int nf
             o += lw[l];
         }
     return ngroups;
+}
+
+int vslamh_pyramid_fused(const uint8_t* img, int w, int h, size_t stride, int nfeatures, float scale, int nlevels,
+                         uint8_t* out, int* lds_bytes_max, int* tiles_total) {
+    return pyramid_fused_with(img, w, h, stride, nfeatures, scale, nlevels, -1, false, 64 * 1024, out, lds_bytes_max, tiles_total,
+                              nullptr, 0, nullptr);
+}
+
+/* The same with the tile shape a context of `batch` images gets from vslam_tuning.pyr_rows / pyr_pingpong (-1: default),
+ * and with the plan's tile records (see pyramid_fused_with).  *shape = {rows, pingpong, LDS limit} as resolved. */
+int vslamh_pyramid_fused_shape(const uint8_t* img, int w, int h, size_t stride, int nfeatures, float scale, int nlevels, int batch,
+                               int tune_rows, int tune_pingpong, uint8_t* out, int* lds_bytes_max, int* tiles_total, int32_t* shape,
+                               int32_t* recs, int recs_cap, int* nrecs) {
+    int rows;
+    bool pingpong;
+    size_t max_lds;
+    vslam::pyramid_tile_shape(w, h, batch, tune_rows, tune_pingpong, &rows, &pingpong, &max_lds);
+    if (shape) { shape[0] = rows; shape[1] = pingpong; shape[2] = (int32_t)max_lds; }
+    return pyramid_fused_with(img, w, h, stride, nfeatures, scale, nlevels, rows, pingpong, max_lds, out, lds_bytes_max, tiles_total,
+                              recs, recs_cap, nrecs);
 }
 
 int vslamh_cells(int level, int lw, int lh, uint16_t* out5, int cap) {

@@ -73,9 +73,22 @@ struct PyrLevelTables {   /* tables of destination level l (source l-1), as the 
     std::vector<uint32_t> quads;
 };
 /* Plan for levels l0+1 .. l0+nl (tabs[j-1] = tables of level l0+j).  Returns false if a tile would need more than 64
- * quads per row (lane = quad) or more LDS than max_lds -- the caller then keeps the per-level launches. */
+ * quads per row (lane = quad) or more LDS than max_lds -- the caller then keeps the per-level launches.
+ * pingpong = false: every level of the group has LDS of its own.  pingpong = true: two regions, the even entries of a
+ * tile (source, level 2, level 4) in the first and the odd ones in the second -- level j is computed from level j-1 alone,
+ * so it may overwrite level j-2; the planner checks that a level's tile never touches the one it is computed from. */
 bool build_pyramid_group(const std::vector<const PyrLevelTables*>& tabs, int l0, size_t max_lds, PyrGroupPlan& plan,
-                         int rows_override = -1 /* vslam_tuning.pyr_rows */);
+                         int rows_override = -1 /* vslam_tuning.pyr_rows */, bool pingpong = false);
+#ifndef VSLAM_PYR_LDS_KB
+#define VSLAM_PYR_LDS_KB 64 /* LDS a pyramid tile's cascade may take with every level resident (32 / 48 / 96 measured) */
+#endif
+/* LDS of a ping-pong tile, row tables included: what one k_fast_bands workgroup holds (8 of them fill a CU's 160 KB), so a
+ * pyramid workgroup fits where a FAST workgroup retired */
+#define VSLAM_PYR_PINGPONG_LDS (20 * 1024)
+/* The tile shape vslam_fe_create plans with: rows of the first computed level per tile, the LDS layout and its limit, from
+ * the frame size, the context's batch and vslam_tuning.pyr_rows / pyr_pingpong (-1: default). */
+void pyramid_tile_shape(int width, int height, int batch, int tune_rows, int tune_pingpong, int* rows, bool* pingpong,
+                        size_t* max_lds);
 /* CPU emulation of k_pyramid_group with the SAME plan and indexing (LDS tiles as arrays); used by the CPU tests to
  * validate a plan before it ever runs on the GPU.  levels[j] = image of level l0+j (j = 0 input, j >= 1 output,
  * pitch = stride[j]).  Returns 0, or a negative code if an access leaves a tile (the GPU would read garbage). */

@@ -24,7 +24,8 @@ void vk_blur7_v2(hipStream_t st, const uint8_t* pyr, size_t slot_stride, const B
                  uint8_t* blur, const uint32_t* tasks, int ntasks, const int32_t taps[7], int rows_per_task,
                  int nslots);
 void vk_pyramid_group(hipStream_t st, uint8_t* pyr, size_t slot_stride, const BatchSrc& src, const PyrGroupDev& G,
-                      size_t lds_bytes, int nslots, uint8_t* reset_cand = nullptr, size_t cand_stride = 0,
+                      size_t lds_bytes, bool fit /* a ping-pong plan: the kernel that sits where a FAST workgroup sat */, int nslots,
+                      uint8_t* reset_cand = nullptr, size_t cand_stride = 0,
                       int32_t* reset_err = nullptr);
 void vk_fast_cells_v3(hipStream_t st, const uint8_t* pyr, size_t slot_stride, const BatchSrc& src,
                       const PyramidGeom& g, const CellDesc* cells, int ncells, uint8_t* cand_region,

@@ -163,8 +163,10 @@ extern "C" int vslam_frame_stereo_batch_async(vslam_fe* fe, int npairs, const ui
      * per SIMD) than with four (110 VGPRs, 4 waves, the trigonometry of four keypoints in one pass: fewer instructions, which
      * is what the VALU-bound mono pipeline wants): KITTI stereo +3.3 %, profiles/r04_describe_kpw_ab.txt */
     fe->desc_kpw_hint = 1;
+    fe->pyr_resident_hint = true; /* and the resident pyramid tiles: see create_pyramid */
     int rc = vslam_enqueue_extract(fe, 2 * npairs, imgs, pitch, imgs_on_device, 0, 0, blk ? 2 : (want_host != 0));
     fe->desc_kpw_hint = -1;
+    fe->pyr_resident_hint = false;
     if (rc == VSLAM_OK) {
         int sl[VSLAM_MAX_STEREO_JOBS], sr[VSLAM_MAX_STEREO_JOBS];
         for (int j = 0; j < npairs; j++) {

@@ -17,6 +17,7 @@ struct EnvField {
 const EnvField kEnv[] = {
     TF("VSLAM_PYRAMID", pyramid_per_level, "levels", nullptr),
     TF("VSLAM_PYR_ROWS", pyr_rows, nullptr, nullptr),
+    TF("VSLAM_PYR_PINGPONG", pyr_pingpong, nullptr, nullptr),
     TF("VSLAM_BLUR_ROWS", blur_rows, nullptr, nullptr),
     TF("VSLAM_OCT_FINE_D", oct_fine_depth, nullptr, nullptr),
     TF("VSLAM_OCT_LDS_BUDGET_KB", oct_lds_budget_kb, nullptr, nullptr),
