@@ -425,3 +425,109 @@ def test_band_tables_encode_the_bands(H):
                     seen[cell0 + k] += 1
                 assert np.array_equal(fl[:iw], want_fl) and np.all(bit[:iw] != 0)
             assert np.all(seen == 1)
+
+
+# ---- the carving of a staging block (vslam::layout_parts, vslam_staging.h) ----
+def _layout(H, align, sizes):
+    H.vslamh_layout.restype = C.c_uint64
+    H.vslamh_layout.argtypes = [C.c_uint64, C.c_void_p, C.c_int, C.c_void_p]
+    s = np.asarray(sizes, np.uint64)
+    off = np.zeros(len(s), np.uint64)
+    total = H.vslamh_layout(align, _p(s), len(s), _p(off))
+    return [int(o) for o in off], int(total)
+
+
+def test_staging_layout_properties(H):
+    rng = np.random.default_rng(7)
+    assert _layout(H, 16, []) == ([], 0)
+    for align in (16, 256):
+        for _ in range(300):
+            n = int(rng.integers(1, 20))
+            sizes = [int(v) for v in rng.integers(0, 5000, n) * (rng.random(n) > 0.3)]
+            if rng.random() < 0.2:
+                sizes[int(rng.integers(n))] = int(rng.integers(1 << 20, 1 << 33))
+            off, total = _layout(H, align, sizes)
+            assert off[0] == 0 and all(o % align == 0 for o in off) and total % align == 0
+            assert all(a <= b for a, b in zip(off, off[1:]))
+            assert all(off[i] + sizes[i] <= off[i + 1] for i in range(n - 1))
+            assert off[-1] + sizes[-1] <= total < off[-1] + sizes[-1] + align
+            # a part of no bytes takes no room, and no part takes more than its size rounded up
+            assert all(off[i + 1] - off[i] < sizes[i] + align for i in range(n - 1))
+            assert all(off[i + 1] == off[i] for i in range(n - 1) if sizes[i] == 0)
+
+
+SZ_KP, SZ_MAP_POINT, SZ_MP_TRACK = V.KP_DTYPE.itemsize, V.MAP_POINT_DTYPE.itemsize, V.MP_TRACK_DTYPE.itemsize
+SBP_M = 8
+
+
+def _sbp_scratch(n):  # vk_sbp_scratch_bytes: an SbpProj (32 bytes) and M candidate words per point
+    return n * (32 + 4 * SBP_M)
+
+
+def _parent_sbp_frame(n_last, n_cur, kf, normals):
+    """The offset chain sbp_frame_impl had before vslam::layout, restated."""
+    def al(v):
+        return (v + 15) & ~15
+    o_kps = 0
+    o_x = al(o_kps + n_last * SZ_KP)
+    o_d = al(o_x + n_last * 12)
+    o_f = al(o_d + n_last * 32)
+    o_u = al(o_f + n_last)
+    o_o = al(o_u + n_cur * 4)
+    o_mn = al(o_o + n_cur)
+    o_mx = al(o_mn + (n_last * 4 if kf else 0))
+    o_nr = al(o_mx + (n_last * 4 if kf else 0))
+    in_bytes = al(o_nr + (n_last * 12 if (kf and normals) else 0))
+    o_scr = in_bytes
+    o_m = al(o_scr + _sbp_scratch(n_last))
+    o_n = al(o_m + n_cur * 4)
+    return [o_kps, o_x, o_d, o_f, o_u, o_o, o_mn, o_mx, o_nr, o_scr, o_m, o_n], o_n + 16
+
+
+def _parent_local_points(n_mp, n_cur, from_host):
+    """The offset chain vslam_search_local_points_async had before vslam::layout, restated."""
+    def al(v):
+        return (v + 255) & ~255
+    cap, nchunks = min(n_mp, 4096), (n_mp + 255) // 256  # VSLAM_FRUSTUM_MAX_KEPT, VSLAM_FRUSTUM_CHUNK
+    o_u = 0
+    o_o = o_u + al(n_cur * 4)
+    o_pts = o_o + al(n_cur)
+    o_desc = o_pts + (al(n_mp * SZ_MAP_POINT) if from_host else 0)
+    in_bytes = o_desc + (al(n_mp * 32) if from_host else 0)
+    o_track = in_bytes
+    o_depth = o_track + al(n_mp * SZ_MP_TRACK)
+    o_cv = o_depth + al(n_mp * 4)
+    o_ck = o_cv + al(nchunks * 4)
+    o_tc = o_ck + al(nchunks * 4)
+    o_dc = o_tc + al(cap * SZ_MP_TRACK)
+    o_fc = o_dc + al(cap * 32)
+    o_scr = o_fc + al(cap)
+    o_m = o_scr + al(_sbp_scratch(cap))
+    o_cnt = o_m + al(n_cur * 4)
+    o_idx = o_cnt + 256
+    total = o_idx + al(cap * 4)
+    return [o_u, o_o, o_pts, o_desc, o_track, o_depth, o_cv, o_ck, o_tc, o_dc, o_fc, o_scr, o_m, o_cnt, o_idx], total
+
+
+STAGING_N = (1, 3, 15, 16, 17, 4096)
+
+
+def test_staging_layout_equals_parent_chain_of_search_by_projection_frame(H):
+    for n_last in STAGING_N:
+        for n_cur in STAGING_N:
+            for kf, normals in ((False, False), (True, False), (True, True)):
+                kfn = n_last if kf else 0
+                sizes = [n_last * SZ_KP, n_last * 12, n_last * 32, n_last, n_cur * 4, n_cur, kfn * 4, kfn * 4,
+                         n_last * 12 if (kf and normals) else 0, _sbp_scratch(n_last), n_cur * 4, 16]
+                assert _layout(H, 16, sizes) == _parent_sbp_frame(n_last, n_cur, kf, normals), (n_last, n_cur, kf, normals)
+
+
+def test_staging_layout_equals_parent_chain_of_search_local_points(H):
+    for n_mp in (1, 255, 256, 257, 65536):
+        for n_cur in STAGING_N:
+            for from_host in (True, False):
+                cap, nchunks, host_mp = min(n_mp, 4096), (n_mp + 255) // 256, n_mp if from_host else 0
+                sizes = [n_cur * 4, n_cur, host_mp * SZ_MAP_POINT, host_mp * 32, n_mp * SZ_MP_TRACK, n_mp * 4, nchunks * 4,
+                         nchunks * 4, cap * SZ_MP_TRACK, cap * 32, cap, _sbp_scratch(cap), n_cur * 4, 256, cap * 4]
+                assert _layout(H, 256, sizes) == _parent_local_points(n_mp, n_cur, from_host), (n_mp, n_cur, from_host)
+

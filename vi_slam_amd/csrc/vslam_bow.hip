@@ -166,26 +166,14 @@ extern "C" int vslam_voc_info(const vslam_voc* v, int* depth_levels, int* weight
     return VSLAM_OK;
 }
 
-static int bow_buffers(vslam_fe* fe, int nslots, int per) {
-    const size_t bytes = (size_t)nslots * per * 16;
-    int rc = vslam_ensure((void**)&fe->d_bow, &fe->bow_bytes, bytes);
-    if (rc) return rc;
-    if (fe->h_bow_bytes < bytes) {
-        if (fe->h_bow) HIPCHK(hipHostFree(fe->h_bow));
-        fe->h_bow = nullptr;
-        fe->h_bow_bytes = 0;
-        HIPCHK((hipError_t)vslam_pinned_alloc((void**)&fe->h_bow, bytes));
-        fe->h_bow_bytes = bytes;
-    }
-    return VSLAM_OK;
-}
+static int bow_buffers(vslam_fe* fe, int nslots, int per) { return fe->bow.ensure((size_t)nslots * per * 16); }
 
-/* layout of d_bow / h_bow for `nslots` jobs of `per` features: weight f64[nslots][per] | word i32[..] | nid i32[..] */
+/* layout of fe->bow for `nslots` jobs of `per` features: weight f64[nslots][per] | word i32[..] | nid i32[..] */
 static void bow_launch(vslam_fe* fe, const vslam_voc* v, int njobs, const uint8_t* const* desc, const int32_t* const* cnt,
                        const int* n, int per, int levelsup) {
     BowJobsDev J;
     memset(&J, 0, sizeof(J));
-    double* dw = (double*)fe->d_bow;
+    double* dw = (double*)fe->bow.d;
     int32_t* dword = (int32_t*)(dw + (size_t)njobs * per);
     int32_t* dnid = dword + (size_t)njobs * per;
     int maxn = 0;
@@ -201,13 +189,7 @@ static void bow_launch(vslam_fe* fe, const vslam_voc* v, int njobs, const uint8_
     if (maxn > 0)
         hipLaunchKernelGGL(k_bow_descend, dim3((maxn + 15) / 16, njobs), dim3(256), 0, fe->stream, J, v->d_childStart,
                            v->d_childCount, v->d_childIds, v->d_desc, v->d_weight, v->d_word, v->L, levelsup);
-    CopyRanges R;
-    memset(&R, 0, sizeof(R));
-    R.dst[0] = fe->h_bow;
-    R.src[0] = fe->d_bow;
-    R.bytes[0] = (size_t)njobs * per * 16;
-    R.n = 1;
-    vk_copy_ranges(fe->stream, R);
+    fe->bow.down(fe->stream, 0, (size_t)njobs * per * 16);
 }
 
 extern "C" int vslam_bow_transform(vslam_fe* fe, const vslam_voc* voc, const uint8_t* dev_desc, int n, int levelsup,
@@ -224,7 +206,7 @@ extern "C" int vslam_bow_transform(vslam_fe* fe, const vslam_voc* voc, const uin
     bow_launch(fe, voc, 1, d, nullptr, &n, n, levelsup);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(fe->stream));
-    const double* hw = (const double*)fe->h_bow;
+    const double* hw = (const double*)fe->bow.h;
     const int32_t* hword = (const int32_t*)(hw + n);
     memcpy(weight, hw, (size_t)n * 8);
     memcpy(word_id, hword, (size_t)n * 4);
@@ -264,7 +246,7 @@ extern "C" int vslam_bow_transform_slots_wait(vslam_fe* fe, const int* n, int32_
     HIPCHK(hipSetDevice(fe->p.device));
     HIPCHK(hipStreamSynchronize(fe->stream));
     const int nj = fe->bow_jobs, per = fe->cap;
-    const double* hw = (const double*)fe->h_bow;
+    const double* hw = (const double*)fe->bow.h;
     const int32_t* hword = (const int32_t*)(hw + (size_t)nj * per);
     const int32_t* hnid = hword + (size_t)nj * per;
     for (int j = 0; j < nj; j++) {
@@ -457,18 +439,14 @@ static int search_by_bow_impl(vslam_fe* fe, const vslam_kp* kf_kps_host, const u
                 return VSLAM_ERR_INVALID;
             }
     HIPCHK(hipSetDevice(fe->p.device));
-    auto al = [](size_t v) { return (v + 15) & ~(size_t)15; };
     const int tk = kf_fv_off[n_kf_nodes], tf = f_fv_off[n_f_nodes];
-    const size_t o_kfl = 0, o_ka = al(o_kfl + (size_t)n_kf), o_fa = al(o_ka + (size_t)n_kf * 4),
-                 o_kn = al(o_fa + (size_t)n_f * 4), o_ko = al(o_kn + (size_t)n_kf_nodes * 4),
-                 o_kf = al(o_ko + (size_t)(n_kf_nodes + 1) * 4), o_fn = al(o_kf + (size_t)tk * 4),
-                 o_fo = al(o_fn + (size_t)n_f_nodes * 4), o_ff = al(o_fo + (size_t)(n_f_nodes + 1) * 4),
-                 o_ffl = al(o_ff + (size_t)tf * 4), in_bytes = al(o_ffl + (size_t)n_f);
-    const size_t o_m = in_bytes, o_b = al(o_m + (size_t)n_out * 4), o_n = al(o_b + (size_t)n_out), total = o_n + 16;
-    int rc = vslam_ensure((void**)&fe->d_proj, &fe->proj_bytes, total);
+    const size_t nk = (size_t)n_kf, nf = (size_t)n_f, no = (size_t)n_out;
+    const auto [o_kfl, o_ka, o_fa, o_kn, o_ko, o_kf, o_fn, o_fo, o_ff, o_ffl, o_m, o_b, o_n, total] = vslam::layout(
+        16, {nk, nk * 4, nf * 4, (size_t)n_kf_nodes * 4, (size_t)(n_kf_nodes + 1) * 4, (size_t)tk * 4, (size_t)n_f_nodes * 4,
+             (size_t)(n_f_nodes + 1) * 4, (size_t)tf * 4, nf, no * 4, no, 16});
+    int rc = fe->proj.ensure(total);
     if (rc) return rc;
-    if ((rc = vslam_ensure_pinned(&fe->h_proj, &fe->h_proj_bytes, total))) return rc;
-    uint8_t *h = fe->h_proj, *d = fe->d_proj;
+    uint8_t *h = fe->proj.h, *d = fe->proj.d;
     memcpy(h + o_kfl, kf_flags_host, (size_t)n_kf);
     for (int i = 0; i < n_kf; i++) ((float*)(h + o_ka))[i] = kf_kps_host[i].angle;
     for (int i = 0; i < n_f; i++) ((float*)(h + o_fa))[i] = f_kps_host[i].angle;
@@ -480,13 +458,7 @@ static int search_by_bow_impl(vslam_fe* fe, const vslam_kp* kf_kps_host, const u
     memcpy(h + o_ff, f_fv_feat, (size_t)tf * 4);
     if (f_flags_host) memcpy(h + o_ffl, f_flags_host, (size_t)n_f);
     hipStream_t st = fe->stream;
-    CopyRanges R;
-    memset(&R, 0, sizeof(R));
-    R.dst[0] = d;
-    R.src[0] = h;
-    R.bytes[0] = in_bytes;
-    R.n = 1;
-    vk_copy_ranges(st, R);
+    fe->proj.up(st, 0, o_m);
     SbowArgs A;
     memset(&A, 0, sizeof(A));
     A.kfDesc = dev_kf_desc; A.fDesc = dev_f_desc; A.kfFlags = d + o_kfl;
@@ -502,10 +474,7 @@ static int search_by_bow_impl(vslam_fe* fe, const vslam_kp* kf_kps_host, const u
     hipLaunchKernelGGL(k_fill_i32, dim3(1), dim3(256), 0, st, A.nmatches, 4, 0);
     hipLaunchKernelGGL(k_sbow_nodes, dim3(n_kf_nodes), dim3(64), 0, st, A);
     hipLaunchKernelGGL(k_sbow_finish, dim3(1), dim3(256), 0, st, A);
-    R.dst[0] = h + o_m;
-    R.src[0] = d + o_m;
-    R.bytes[0] = (o_n + 16) - o_m;
-    vk_copy_ranges(st, R);
+    fe->proj.down(st, o_m, total - o_m);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));
     if (((const int32_t*)(h + o_n))[1]) {
@@ -669,19 +638,14 @@ extern "C" int vslam_search_for_triangulation(vslam_fe* fe, const vslam_tri_para
         return VSLAM_ERR_UNSUPPORTED;
     }
     HIPCHK(hipSetDevice(fe->p.device));
-    auto al = [](size_t v) { return (v + 15) & ~(size_t)15; };
     const int t1 = fv1_off[n1_nodes], t2 = fv2_off[n2_nodes];
-    const size_t o_k1 = 0, o_k2 = al(o_k1 + (size_t)n1 * sizeof(vslam_kp)), o_h1 = al(o_k2 + (size_t)n2 * sizeof(vslam_kp)),
-                 o_h2 = al(o_h1 + (size_t)n1), o_u1 = al(o_h2 + (size_t)n2), o_u2 = al(o_u1 + (size_t)n1 * 4),
-                 o_n1 = al(o_u2 + (size_t)n2 * 4), o_o1 = al(o_n1 + (size_t)n1_nodes * 4),
-                 o_f1 = al(o_o1 + (size_t)(n1_nodes + 1) * 4), o_n2 = al(o_f1 + (size_t)t1 * 4),
-                 o_o2 = al(o_n2 + (size_t)n2_nodes * 4), o_f2 = al(o_o2 + (size_t)(n2_nodes + 1) * 4),
-                 in_bytes = al(o_f2 + (size_t)t2 * 4);
-    const size_t o_m = in_bytes, o_b = al(o_m + (size_t)n1 * 4), o_n = al(o_b + (size_t)n1), total = o_n + 16;
-    int rc = vslam_ensure((void**)&fe->d_proj, &fe->proj_bytes, total);
+    const size_t z1 = (size_t)n1, z2 = (size_t)n2;
+    const auto [o_k1, o_k2, o_h1, o_h2, o_u1, o_u2, o_n1, o_o1, o_f1, o_n2, o_o2, o_f2, o_m, o_b, o_n, total] = vslam::layout(
+        16, {z1 * sizeof(vslam_kp), z2 * sizeof(vslam_kp), z1, z2, z1 * 4, z2 * 4, (size_t)n1_nodes * 4, (size_t)(n1_nodes + 1) * 4,
+             (size_t)t1 * 4, (size_t)n2_nodes * 4, (size_t)(n2_nodes + 1) * 4, (size_t)t2 * 4, z1 * 4, z1, 16});
+    int rc = fe->proj.ensure(total);
     if (rc) return rc;
-    if ((rc = vslam_ensure_pinned(&fe->h_proj, &fe->h_proj_bytes, total))) return rc;
-    uint8_t *h = fe->h_proj, *d = fe->d_proj;
+    uint8_t *h = fe->proj.h, *d = fe->proj.d;
     memcpy(h + o_k1, kps1_host, (size_t)n1 * sizeof(vslam_kp));
     memcpy(h + o_k2, kps2_host, (size_t)n2 * sizeof(vslam_kp));
     memcpy(h + o_h1, has_mp1_host, (size_t)n1);
@@ -695,13 +659,7 @@ extern "C" int vslam_search_for_triangulation(vslam_fe* fe, const vslam_tri_para
     memcpy(h + o_o2, fv2_off, (size_t)(n2_nodes + 1) * 4);
     memcpy(h + o_f2, fv2_feat, (size_t)t2 * 4);
     hipStream_t st = fe->stream;
-    CopyRanges R;
-    memset(&R, 0, sizeof(R));
-    R.dst[0] = d;
-    R.src[0] = h;
-    R.bytes[0] = in_bytes;
-    R.n = 1;
-    vk_copy_ranges(st, R);
+    fe->proj.up(st, 0, o_m);
     StriArgs A;
     memset(&A, 0, sizeof(A));
     A.desc1 = dev_desc1; A.desc2 = dev_desc2; A.hasMp1 = d + o_h1; A.hasMp2 = d + o_h2;
@@ -726,10 +684,7 @@ extern "C" int vslam_search_for_triangulation(vslam_fe* fe, const vslam_tri_para
     hipLaunchKernelGGL(k_fill_i32, dim3(1), dim3(256), 0, st, Fz.nmatches, 4, 0);
     if (t1 > 0) hipLaunchKernelGGL(k_stri_queries, dim3((t1 + 3) / 4), dim3(256), 0, st, A);
     hipLaunchKernelGGL(k_sbow_finish, dim3(1), dim3(256), 0, st, Fz);
-    R.dst[0] = h + o_m;
-    R.src[0] = d + o_m;
-    R.bytes[0] = (o_n + 16) - o_m;
-    vk_copy_ranges(st, R);
+    fe->proj.down(st, o_m, total - o_m);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));
     memcpy(match12, h + o_m, (size_t)n1 * 4);

@@ -1,5 +1,7 @@
 /* vslam_ctx.h -- private: the vslam_fe context (HBM layout, scratch, worker pool) shared by
- * vslam_fe.hip (extractor ABI) and vslam_match.hip (matcher ABI). */
+ * vslam_fe.hip (extractor ABI) and by the matcher ABI: vslam_stereo.hip (stereo, RGB-D), vslam_match.hip
+ * (SearchForInitialization), vslam_projection.hip (SearchByProjection family, Fuse, SearchLocalPoints), vslam_bow.hip
+ * and vslam_kfdb.hip. */
 #ifndef VSLAM_CTX_H
 #define VSLAM_CTX_H
 #include <hip/hip_runtime.h>
@@ -21,6 +23,7 @@
 #include "vslam_pool.h"
 #include "vslam_kernels.h"
 #include "vslam_tuning.h"
+#include "vslam_staging.h"
 
 std::string& vslam_err();
 #define g_err (vslam_err())
@@ -148,27 +151,17 @@ struct vslam_fe {
     uint8_t* d_init_scratch = nullptr; /* k_si_topm -> k_si_replay: compacted octave-0 lists + sorted prefixes */
     size_t init_scratch_bytes = 0;
     int* d_init_fb = nullptr; /* number of full re-scans in k_si_replay / k_sbp_replay (diagnostics) */
-    uint8_t* d_proj = nullptr;  /* SearchByProjection: uploaded last-frame arrays | scratch | results */
-    size_t proj_bytes = 0;
-    uint8_t* h_proj = nullptr;  /* pinned mirror (inputs, then results) */
-    size_t h_proj_bytes = 0;
+    /* one staging block for the single-call matchers (SearchByProjection, Fuse, ComputeDistinctiveDescriptors, SearchByBoW,
+     * SearchForTriangulation): inputs | scratch | results, carved anew by every call */
+    vslam_staging proj;
     bool proj_lds_set = false, dist_lds_set = false;
-    uint8_t* d_bow = nullptr;   /* ComputeBoW: per-feature weight | word | node for nslots x cap features */
-    size_t bow_bytes = 0;
-    uint8_t* h_bow = nullptr;   /* pinned mirror */
-    size_t h_bow_bytes = 0;
+    vslam_staging bow;          /* ComputeBoW: per-feature weight | word | node for nslots x cap features */
     int bow_jobs = 0;
-    uint8_t* d_kfdb = nullptr;  /* KeyFrameDatabase query: uploaded BowVectors | dense per-slot results (vslam_kfdb.hip) */
-    size_t kfdb_bytes = 0;
-    uint8_t* h_kfdb = nullptr;  /* pinned mirror (inputs, then results) */
-    size_t h_kfdb_bytes = 0;
-    uint8_t* d_lp = nullptr;    /* SearchLocalPoints: inputs | frustum records | compacted arrays | matcher scratch | results (vslam_match.hip) */
-    size_t lp_bytes = 0;
-    uint8_t* h_lp = nullptr;    /* pinned mirror (inputs, then results) */
-    size_t h_lp_bytes = 0;
+    vslam_staging kfdb;         /* KeyFrameDatabase query: uploaded BowVectors | dense per-slot results (vslam_kfdb.hip) */
+    vslam_staging lp;           /* SearchLocalPoints: inputs | frustum records | compacted arrays | matcher scratch | results (vslam_projection.hip) */
     int lp_state = 0;           /* 0: nothing enqueued, 1: a search is in flight, 2: an empty search (nothing launched) */
     int lp_n_mp = 0, lp_n_cur = 0, lp_cap = 0;
-    size_t lp_o_track = 0, lp_o_res = 0; /* where the records and the result block (matches | counts | indices) start */
+    size_t lp_o_track = 0, lp_o_res = 0, lp_o_cnt = 0, lp_o_idx = 0; /* where the records and the result block (matches | counts | indices) start */
     bool use_graph = true;          /* host-image passes replay a captured HIP graph (VSLAM_GRAPH=0 disables) */
     hipGraphExec_t graph_exec = nullptr;
     long long graph_key = 0;
@@ -179,11 +172,9 @@ struct vslam_fe {
     size_t h_img_pitch = 0;     /* row pitch of the images staged last: the level-0 pitch, or the width for dense sources */
     uint8_t* d_stage = nullptr; /* device staging of pinned caller images copied by the DMA engines (VSLAM_H2D=sdma) */
     size_t d_stage_bytes = 0;
-    uint8_t* d_sbp = nullptr;   /* batched device-resident SearchByProjection: scratch + results per job */
-    size_t sbp_bytes = 0;
-    uint8_t* h_sbp = nullptr;   /* pinned results */
-    size_t h_sbp_bytes = 0;
+    vslam_staging sbp;          /* batched device-resident SearchByProjection: scratch of every job | results of all jobs */
     int sbp_jobs = 0, sbp_M = 8;
+    size_t sbp_o_res = 0;       /* where the results (match tables | counts) start */
     float* d_x3dw = nullptr;    /* stereo points per pair: B x cap x 3 */
     uint8_t* d_mpflags = nullptr; /* B x cap */
     /* stereo scratch */
@@ -241,8 +232,6 @@ struct vslam_fe {
 static inline int vslam_pix_bpp(int fmt) { return fmt == VSLAM_PIX_GRAY8 ? 1 : fmt <= VSLAM_PIX_BGR8 ? 3 : 4; }
 static inline size_t vslam_row_bytes(const vslam_fe* fe) { return (size_t)fe->p.width * vslam_pix_bpp(fe->pix_fmt); }
 
-int vslam_ensure(void** p, size_t* have, size_t want);
-int vslam_ensure_pinned(uint8_t** p, size_t* have, size_t want); /* grow-only pinned host buffer */
 int vslam_pinned_alloc(void** p, size_t bytes);                  /* hipHostMalloc on the device's NUMA node; returns a hipError_t */
 int vslam_enqueue_extract(vslam_fe* fe, int nimg, const uint8_t* const* imgs, size_t pitch, int on_device,
                           int lap0, int lap1, int want_host);
@@ -272,19 +261,33 @@ static inline void vslam_count_delivery(vslam_fe* fe, int ops, const CopyRanges&
     fe->n_deliveries += (unsigned long long)ops;
     for (int r = 0; r < R.n; r++) fe->n_delivery_bytes += R.bytes[r];
 }
+static inline void vslam_count_delivery(vslam_fe* fe, int ops, size_t bytes) { /* a single range (vslam_copy_range) */
+    fe->n_deliveries += (unsigned long long)ops;
+    fe->n_delivery_bytes += bytes;
+}
 
 /* The result block -- counts | keypoints | descriptors -- and the `extra` bytes a matcher put behind them, from HBM to
  * the pinned mirror in ONE transfer on the context's stream. */
 static inline int vslam_deliver_block(vslam_fe* fe, size_t extra) {
-    CopyRanges R;
-    memset(&R, 0, sizeof(R));
-    R.dst[0] = fe->h_res;
-    R.src[0] = fe->d_res;
-    R.bytes[0] = fe->res_feat_bytes + extra;
-    R.n = 1;
-    vslam_count_delivery(fe, vk_copy_ranges(fe->stream, R, fe->tune), R);
+    const size_t bytes = fe->res_feat_bytes + extra;
+    vslam_count_delivery(fe, vslam_copy_range(fe->stream, fe->h_res, fe->d_res, bytes, fe->tune), bytes);
     HIPCHK(hipGetLastError());
     return VSLAM_OK;
+}
+
+/* the grid bounds of the _ex entry points: finite, non-empty (the reference divides by mnMaxX - mnMinX) */
+static inline bool bounds_ok(const vslam_bounds* b) {
+    return b && std::isfinite(b->min_x) && std::isfinite(b->max_x) && std::isfinite(b->min_y) && std::isfinite(b->max_y) &&
+           b->max_x > b->min_x && b->max_y > b->min_y;
+}
+/* The img_w / img_h entry points pass {0, (float)img_w, 0, (float)img_h}: with mnMinX = mnMinY = 0 every expression of
+ * the float-bounds matcher -- x - 0.0f, (float)W - 0.0f, the window and PosInGrid -- equals the integer-bounds one bit for
+ * bit, so their results do not change. */
+static inline SiBounds int_bounds(int img_w, int img_h) { return SiBounds{0.0f, (float)img_w, 0.0f, (float)img_h}; }
+/* SearchByProjection / Fuse / SearchBySim3: the context's grid bounds (vslam_fe_set_grid_bounds) while they are set, else
+ * the call's own img_w / img_h.  SearchForInitialization does not come here: its bounds are an argument. */
+static inline SiBounds matcher_bounds(const vslam_fe* fe, int img_w, int img_h) {
+    return fe->has_grid_bounds ? fe->grid_bounds : int_bounds(img_w, img_h);
 }
 
 #endif

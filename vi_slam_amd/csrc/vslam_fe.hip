@@ -80,22 +80,13 @@ static void free_ctx(vslam_fe* fe) {
     if (!fe->init_in_block) hipFree(fe->d_init);
     hipFree(fe->d_init_scratch);
     hipFree(fe->d_ukps);
-    hipFree(fe->d_proj);
-    hipFree(fe->d_sbp);
-    if (fe->h_sbp) hipHostFree(fe->h_sbp);
     hipFree(fe->d_x3dw);
     hipFree(fe->d_mpflags);
-    if (fe->h_proj) hipHostFree(fe->h_proj);
     if (fe->h_img) hipHostFree(fe->h_img);
     if (fe->h_depth) hipHostFree(fe->h_depth);
     hipFree(fe->d_stage);
     if (fe->graph_exec) hipGraphExecDestroy(fe->graph_exec);
-    hipFree(fe->d_bow);
-    if (fe->h_bow) hipHostFree(fe->h_bow);
-    hipFree(fe->d_kfdb);
-    if (fe->h_kfdb) hipHostFree(fe->h_kfdb);
-    hipFree(fe->d_lp);
-    if (fe->h_lp) hipHostFree(fe->h_lp);
+    for (vslam_staging* g : {&fe->proj, &fe->sbp, &fe->bow, &fe->kfdb, &fe->lp}) g->release();
     hipFree(fe->d_init_fb);
     if (fe->h_init && !fe->init_in_block) hipHostFree(fe->h_init);
     if (fe->ev_cand) hipEventDestroy(fe->ev_cand);

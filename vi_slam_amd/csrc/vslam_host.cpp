@@ -876,6 +876,15 @@ int search_for_initialization_replay(const vslam_kp* kps1, int n1, const vslam_k
     return nmatches;
 }
 
+size_t layout_parts(size_t align, const size_t* sizes, int n, size_t* off) {
+    size_t end = 0;
+    for (int i = 0; i < n; i++) {
+        off[i] = end;
+        end = (end + sizes[i] + align - 1) & ~(align - 1);
+    }
+    return end;
+}
+
 } // namespace vslam
 
 /* ---------------------------------------------------------------------------------------------
@@ -1130,6 +1139,13 @@ int vslamh_local_points_finish(const int32_t* match_compact, int n_cur, const in
         match_cur[i] = (k >= 0 && k < n_kept) ? orig_index[k] : -1;
     }
     return VSLAM_OK;
+}
+
+uint64_t vslamh_layout(uint64_t align, const uint64_t* sizes, int n, uint64_t* off) {
+    std::vector<size_t> s(sizes, sizes + n), o(n);
+    const size_t total = vslam::layout_parts((size_t)align, s.data(), n, o.data());
+    for (int i = 0; i < n; i++) off[i] = o[i];
+    return total;
 }
 
 /* quadtree path tables of k_octree_v4 against the literal halvings: returns the number of (x, y) whose table path differs */

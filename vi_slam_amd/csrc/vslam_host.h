@@ -6,6 +6,7 @@
 #ifndef VSLAM_HOST_H
 #define VSLAM_HOST_H
 
+#include <array>
 #include <cstdint>
 #include <functional>
 #include <vector>
@@ -202,8 +203,22 @@ int search_for_initialization_replay(const vslam_kp* kps1, int n1, const vslam_k
                                      int ncols, const float bounds[4], float* prevMatched, int32_t* matches12,
                                      int windowSize, float nnratio, bool checkOri);
 
+/* Carving of one staging block (vslam_staging.h): part 0 starts at 0 and part i at the end of part i - 1 rounded up to
+ * `align` (a power of two), so a part of no bytes takes no room.  off[0 .. n) receives the starts; returns the rounded
+ * end of the last part, the block's size. */
+size_t layout_parts(size_t align, const size_t* sizes, int n, size_t* off);
+/* the same for a braced list of sizes: {off[0], .., off[N - 1], total}, made for structured bindings */
+template <size_t N>
+std::array<size_t, N + 1> layout(size_t align, const size_t (&sizes)[N]) {
+    std::array<size_t, N + 1> o;
+    o[N] = layout_parts(align, sizes, (int)N, o.data());
+    return o;
+}
+
 } // namespace vslam
 
+/* vslam_host.cpp: layout_parts for the CPU suite (off: n entries); returns the total */
+extern "C" uint64_t vslamh_layout(uint64_t align, const uint64_t* sizes, int n, uint64_t* off);
 /* vslam_host.cpp: index map-back and over-capacity decision of vslam_search_local_points_wait */
 extern "C" int vslamh_local_points_finish(const int32_t* match_compact, int n_cur, const int32_t* orig_index, int n_kept,
                                           int capacity, int32_t* match_cur);

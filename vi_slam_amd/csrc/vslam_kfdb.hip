@@ -402,14 +402,10 @@ extern "C" int vslam_kfdb_query_async(vslam_kfdb* db, vslam_fe* fe, int nq, cons
     if (rc) return rc;
     db->q_fe = nullptr;
     const size_t S = db->slots.size();
-    auto al = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t o_vals = 0, o_ids = al(o_vals + total * 8), o_off = al(o_ids + total * 4),
-                 in_bytes = al(o_off + (size_t)(nq + 1) * 4);
-    const size_t o_score = in_bytes, o_words = al(o_score + (size_t)nq * S * 8), o_first = al(o_words + (size_t)nq * S * 4),
-                 bytes = al(o_first + (size_t)nq * S * 4);
-    if ((rc = vslam_ensure((void**)&fe->d_kfdb, &fe->kfdb_bytes, bytes))) return rc;
-    if ((rc = vslam_ensure_pinned(&fe->h_kfdb, &fe->h_kfdb_bytes, bytes))) return rc;
-    uint8_t *h = fe->h_kfdb, *d = fe->d_kfdb;
+    const auto [o_vals, o_ids, o_off, o_score, o_words, o_first, bytes] = vslam::layout(
+        16, {total * 8, total * 4, (size_t)(nq + 1) * 4, (size_t)nq * S * 8, (size_t)nq * S * 4, (size_t)nq * S * 4});
+    if ((rc = fe->kfdb.ensure(bytes))) return rc;
+    uint8_t *h = fe->kfdb.h, *d = fe->kfdb.d;
     int32_t* off = (int32_t*)(h + o_off);
     size_t at = 0;
     for (int q = 0; q < nq; q++) {
@@ -435,13 +431,7 @@ extern "C" int vslam_kfdb_query_async(vslam_kfdb* db, vslam_fe* fe, int nq, cons
     }
     hipStream_t st = fe->stream;
     if (S) {
-        CopyRanges R;
-        memset(&R, 0, sizeof(R));
-        R.dst[0] = d;
-        R.src[0] = h;
-        R.bytes[0] = in_bytes;
-        R.n = 1;
-        vk_copy_ranges(st, R);
+        fe->kfdb.up(st, 0, o_score);
         KfdbQueryArgs A;
         A.poolIds = db->d_ids;
         A.poolVals = db->d_vals;
@@ -455,10 +445,7 @@ extern "C" int vslam_kfdb_query_async(vslam_kfdb* db, vslam_fe* fe, int nq, cons
         A.first = (int32_t*)(d + o_first);
         hipLaunchKernelGGL(k_kfdb_query, dim3((unsigned)((S + KFDB_WAVES - 1) / KFDB_WAVES), (unsigned)nq),
                            dim3(64 * KFDB_WAVES), 0, st, A);
-        R.dst[0] = h + o_score;
-        R.src[0] = d + o_score;
-        R.bytes[0] = bytes - o_score;
-        vk_copy_ranges(st, R);
+        fe->kfdb.down(st, o_score, bytes - o_score);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipEventRecord(db->ev, st));
@@ -486,7 +473,7 @@ extern "C" int vslam_kfdb_query_wait(vslam_kfdb* db, vslam_fe* fe, int q, int ca
     HIPCHK(hipSetDevice(db->device));
     HIPCHK(hipEventSynchronize(db->ev));
     const size_t S = db->q_slots.size();
-    const uint8_t* h = fe->h_kfdb;
+    const uint8_t* h = fe->kfdb.h;
     const double* score = (const double*)(h + db->q_o_score) + (size_t)q * S;
     const int32_t* words = (const int32_t*)(h + db->q_o_words) + (size_t)q * S;
     const int32_t* first = (const int32_t*)(h + db->q_o_first) + (size_t)q * S;
