@@ -267,8 +267,8 @@ extern "C" int vslam_bow_transform_slots_wait(vslam_fe* fe, const int* n, int32_
  * minimum; TH_LOW and the ratio test as in the reference.  The rotation histogram spans all nodes: k_sbow_finish.
  * ================================================================================================== */
 #include "vslam_wave.h"
+#include "vslam_matchdev.h"
 #define SBOW_TH_LOW 50
-#define SBOW_HISTO 30
 #define SBOW_MAXC 32 /* candidates per lane: 2048 frame features under one node */
 
 struct SbowArgs {
@@ -305,7 +305,6 @@ __global__ void __launch_bounds__(64) k_sbow_nodes(SbowArgs A) {
         return;
     }
     uint32_t occ = 0; /* bit c: my c-th candidate already carries a MapPoint */
-    const float factor = 1.0f / SBOW_HISTO;
     for (int a = A.kfOff[kn]; a < A.kfOff[kn + 1]; a++) {
         const int realIdxKF = A.kfFeat[a];
         if (!A.kfFlags[realIdxKF]) continue; /* !pMP || pMP->isBad() */
@@ -340,13 +339,7 @@ __global__ void __launch_bounds__(64) k_sbow_nodes(SbowArgs A) {
                 const int oi = A.outByQuery ? realIdxKF : bestIdxF;
                 A.matchF[oi] = A.outByQuery ? bestIdxF : realIdxKF;
                 uint8_t bin = 255;
-                if (A.checkOri) {
-                    float rot = __fsub_rn(A.kfAngle[realIdxKF], A.fAngle[bestIdxF]);
-                    if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-                    int bi = (int)roundf(__fmul_rn(rot, factor));
-                    if (bi == SBOW_HISTO) bi = 0;
-                    bin = (uint8_t)bi;
-                }
+                if (A.checkOri) bin = (uint8_t)vslam_md::rot_bin(A.kfAngle[realIdxKF], A.fAngle[bestIdxF], VSLAM_HISTO_LENGTH);
                 A.matchBin[oi] = bin;
             }
         }
@@ -354,10 +347,10 @@ __global__ void __launch_bounds__(64) k_sbow_nodes(SbowArgs A) {
 }
 
 __global__ void __launch_bounds__(256) k_sbow_finish(SbowArgs A) {
-    __shared__ int s_hist[SBOW_HISTO];
+    __shared__ int s_hist[VSLAM_HISTO_LENGTH];
     __shared__ int s_n, s_removed;
     const int tid = threadIdx.x;
-    if (tid < SBOW_HISTO) s_hist[tid] = 0;
+    if (tid < VSLAM_HISTO_LENGTH) s_hist[tid] = 0;
     if (tid == 0) {
         s_n = 0;
         s_removed = 0;
@@ -372,27 +365,11 @@ __global__ void __launch_bounds__(256) k_sbow_finish(SbowArgs A) {
     atomicAdd(&s_n, mine);
     __syncthreads();
     if (A.checkOri) {
-        int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0; /* ComputeThreeMaxima, fmatcher.cpp:2813-2854 */
-        for (int i = 0; i < SBOW_HISTO; i++) {
-            const int sv = s_hist[i];
-            if (sv > max1) {
-                max3 = max2; max2 = max1; max1 = sv;
-                ind3 = ind2; ind2 = ind1; ind1 = i;
-            } else if (sv > max2) {
-                max3 = max2; max2 = sv;
-                ind3 = ind2; ind2 = i;
-            } else if (sv > max3) {
-                max3 = sv;
-                ind3 = i;
-            }
-        }
-        if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
-        else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) { ind3 = -1; }
+        const vslam_md::ThreeMaxima mx = vslam_md::three_maxima(s_hist, VSLAM_HISTO_LENGTH);
         int rem = 0;
         for (int i = tid; i < A.nOut; i += 256)
             if (A.matchF[i] >= 0) {
-                const int b = A.matchBin[i];
-                if (b != ind1 && b != ind2 && b != ind3) {
+                if (!vslam_md::keeps_bin(mx, A.matchBin[i])) {
                     A.matchF[i] = -1;
                     rem++;
                 }
@@ -551,7 +528,6 @@ __global__ void __launch_bounds__(256) k_stri_queries(StriArgs A) {
     }
     if (lo >= A.nNodes2 || A.nodes2[lo] != node) return;
     const int f0 = A.off2[lo], c2 = A.off2[lo + 1] - f0;
-    const float factor = 1.0f / SBOW_HISTO;
     const int idx1 = A.feat1[a1];
     if (A.hasMp1[idx1]) return; /* pMP1 */
     const bool bStereo1 = A.uRight1[idx1] >= 0.f;
@@ -593,13 +569,7 @@ __global__ void __launch_bounds__(256) k_stri_queries(StriArgs A) {
         const int bestIdx2 = A.feat2[f0 + (int)(0xFFFFFu - (g & 0xFFFFFu))];
         A.match12[idx1] = bestIdx2;
         uint8_t bin = 255;
-        if (A.checkOri) {
-            float rot = __fsub_rn(kp1.angle, A.kps2[bestIdx2].angle);
-            if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-            int bi = (int)roundf(__fmul_rn(rot, factor));
-            if (bi == SBOW_HISTO) bi = 0;
-            bin = (uint8_t)bi;
-        }
+        if (A.checkOri) bin = (uint8_t)vslam_md::rot_bin(kp1.angle, A.kps2[bestIdx2].angle, VSLAM_HISTO_LENGTH);
         A.matchBin[idx1] = bin;
     }
 }

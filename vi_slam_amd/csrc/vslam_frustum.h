@@ -17,9 +17,7 @@
  *   dist < min || dist > max
  *   viewCos = PO.dot(Pn) / dist    Matx::dot (matx.hpp, `_Tp s = 0; for i: s += val[i] * M.val[i]`): FLOAT accumulation from
  *                                  zero -- unlike cv::Mat::dot, which the Sim3 form (k_sbp_rank mode 3) accumulates in double
- *   PredictScale(dist, Frame*)     ceilf(logf(max / dist) / mfLogScaleFactor) with glibc's logf (vslam_trig.h); NaN and
- *                                  out-of-range quotients convert to INT_MIN on the reference's x86-64 build (cvttss2si) and
- *                                  so clamp to level 0, as in k_sbp_rank modes 2 and 3
+ *   PredictScale(dist, Frame*)     vslam_md::predict_level (vslam_matchdev.h), as in k_sbp_rank modes 2 and 3
  *   mTrackProjXR = uv.x - mbf * invz,  mTrackDepth = Pc_dist
  * The matx.hpp loops are quoted as recalled from OpenCV 4.2, not pinned against a build of it (oracle section).
  *
@@ -44,60 +42,11 @@
 #include <stdint.h>
 
 #include "../../include/vslam_fe.h"
-#include "vslam_trig.h"
+#include "vslam_matchdev.h"
 
 namespace vslam_fr {
 
-VSLAM_HD float fmul(float a, float b) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __fmul_rn(a, b);
-#else
-    return a * b;
-#endif
-}
-VSLAM_HD float fadd(float a, float b) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __fadd_rn(a, b);
-#else
-    return a + b;
-#endif
-}
-VSLAM_HD float fsub(float a, float b) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __fsub_rn(a, b);
-#else
-    return a - b;
-#endif
-}
-VSLAM_HD float fdvd(float a, float b) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __fdiv_rn(a, b);
-#else
-    return a / b;
-#endif
-}
-/* cv::norm of a Matx31f */
-VSLAM_HD float norm3(float a, float b, float c) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    double n2 = __dmul_rn((double)a, (double)a);
-    n2 = __dadd_rn(n2, __dmul_rn((double)b, (double)b));
-    n2 = __dadd_rn(n2, __dmul_rn((double)c, (double)c));
-    return (float)__dsqrt_rn(n2);
-#else
-    double n2 = (double)a * (double)a;
-    n2 = n2 + (double)b * (double)b;
-    n2 = n2 + (double)c * (double)c;
-    return (float)sqrt(n2);
-#endif
-}
-/* one row of a Matx product, or Matx::dot: float accumulation from zero */
-VSLAM_HD float dot3(const float* r, float x0, float x1, float x2) {
-    float s = 0.0f;
-    s = fadd(s, fmul(r[0], x0));
-    s = fadd(s, fmul(r[1], x1));
-    s = fadd(s, fmul(r[2], x2));
-    return s;
-}
+using namespace vslam_md; /* fmul .. fdvd, norm3, dot3_matx, predict_level */
 
 /* what one call of Frame::isInFrustum reads of the Frame */
 struct Frame {
@@ -144,9 +93,9 @@ VSLAM_HD void in_frustum(const Frame& F, const vslam_map_point& mp, vslam_mp_tra
     *out = t;
     if (!(mp.flags & 1u)) return;
     const float X = mp.pos[0], Y = mp.pos[1], Z = mp.pos[2];
-    const float PcX = fadd(dot3(F.Tcw + 0, X, Y, Z), F.Tcw[3]);
-    const float PcY = fadd(dot3(F.Tcw + 4, X, Y, Z), F.Tcw[7]);
-    const float PcZ = fadd(dot3(F.Tcw + 8, X, Y, Z), F.Tcw[11]);
+    const float PcX = fadd(dot3_matx(F.Tcw + 0, X, Y, Z), F.Tcw[3]);
+    const float PcY = fadd(dot3_matx(F.Tcw + 4, X, Y, Z), F.Tcw[7]);
+    const float PcZ = fadd(dot3_matx(F.Tcw + 8, X, Y, Z), F.Tcw[11]);
     const float Pc_dist = norm3(PcX, PcY, PcZ);
     const float invz = fdvd(1.0f, PcZ);
     if (PcZ < 0.0f) return;
@@ -160,14 +109,9 @@ VSLAM_HD void in_frustum(const Frame& F, const vslam_map_point& mp, vslam_mp_tra
     const float PO[3] = {fsub(X, F.Ow[0]), fsub(Y, F.Ow[1]), fsub(Z, F.Ow[2])};
     const float dist = norm3(PO[0], PO[1], PO[2]);
     if (dist < mp.min_dist || dist > mp.max_dist) return;
-    const float viewCos = fdvd(dot3(PO, mp.normal[0], mp.normal[1], mp.normal[2]), dist);
+    const float viewCos = fdvd(dot3_matx(PO, mp.normal[0], mp.normal[1], mp.normal[2]), dist);
     if (viewCos < F.viewingCosLimit) return;
-    const float lv = ceilf(fdvd(vslam_trig::glibc_logf(fdvd(mp.max_dist, dist)), F.logScaleFactor));
-    int level = 0;
-    if (!(lv != lv || lv >= 2147483648.0f || lv < 0.f)) {
-        level = (int)lv;
-        if (level > F.nlevels - 1) level = F.nlevels - 1;
-    }
+    const int level = predict_level(mp.max_dist, dist, F.logScaleFactor, F.nlevels);
     t.proj_xr = fsub(u, fmul(F.mbf, invz));
     t.view_cos = viewCos;
     t.level = level;

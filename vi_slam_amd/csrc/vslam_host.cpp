@@ -2,6 +2,7 @@
 #include "vslam_host.h"
 #include "vslam_undistort.h"
 #include "vslam_frustum.h"
+#include "vslam_matchdev.h"
 
 #include <algorithm>
 #include <climits>
@@ -729,25 +730,6 @@ void build_oct_lut(int W, int H, int D, std::vector<uint32_t>& xs, std::vector<u
     }
 }
 
-void compute_three_maxima(const int* hs, int L, int& ind1, int& ind2, int& ind3) {
-    int max1 = 0, max2 = 0, max3 = 0; /* fmatcher.cpp:2813-2854 */
-    for (int i = 0; i < L; i++) {
-        const int s = hs[i];
-        if (s > max1) {
-            max3 = max2; max2 = max1; max1 = s;
-            ind3 = ind2; ind2 = ind1; ind1 = i;
-        } else if (s > max2) {
-            max3 = max2; max2 = s;
-            ind3 = ind2; ind2 = i;
-        } else if (s > max3) {
-            max3 = s;
-            ind3 = i;
-        }
-    }
-    if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-    else if (max3 < 0.1f * (float)max1) { ind3 = -1; }
-}
-
 void FrameGrid::build(const vslam_kp* k, int n_, int imgW, int imgH) {
     const float b[4] = {0.0f, (float)imgW, 0.0f, (float)imgH}; /* frame.cpp:814-820 */
     build(k, n_, b);
@@ -807,11 +789,10 @@ int search_for_initialization_replay(const vslam_kp* kps1, int n1, const vslam_k
                                      int ncols, const float bounds[4], float* prevMatched, int32_t* vnMatches12,
                                      int windowSize, float mfNNratio, bool checkOri) {
     /* fmatcher.cpp:983-1098 */
-    const int TH_LOW = 50, HISTO_LENGTH = 30;
+    const int TH_LOW = 50, HISTO_LENGTH = VSLAM_HISTO_LENGTH;
     int nmatches = 0;
     for (int i = 0; i < n1; i++) vnMatches12[i] = -1;
-    std::vector<int> rotHist[30];
-    const float factor = 1.0f / HISTO_LENGTH;
+    std::vector<int> rotHist[HISTO_LENGTH];
     std::vector<int> vMatchedDistance(n2, INT_MAX), vnMatches21(n2, -1);
     FrameGrid grid2;
     grid2.build(kps2, n2, bounds);
@@ -844,23 +825,16 @@ int search_for_initialization_replay(const vslam_kp* kps1, int n1, const vslam_k
                 vnMatches21[bestIdx2] = i1;
                 vMatchedDistance[bestIdx2] = bestDist;
                 nmatches++;
-                if (checkOri) {
-                    float rot = kps1[i1].angle - kps2[bestIdx2].angle;
-                    if (rot < 0.0) rot += 360.0f;
-                    int bin = (int)std::round(rot * factor);
-                    if (bin == HISTO_LENGTH) bin = 0;
-                    rotHist[bin].push_back(i1);
-                }
+                if (checkOri) rotHist[vslam_md::rot_bin(kps1[i1].angle, kps2[bestIdx2].angle, HISTO_LENGTH)].push_back(i1);
             }
         }
     }
     if (checkOri) {
-        int ind1 = -1, ind2 = -1, ind3 = -1;
-        int sizes[30];
+        int sizes[HISTO_LENGTH];
         for (int i = 0; i < HISTO_LENGTH; i++) sizes[i] = (int)rotHist[i].size();
-        compute_three_maxima(sizes, HISTO_LENGTH, ind1, ind2, ind3);
+        const vslam_md::ThreeMaxima mx = vslam_md::three_maxima(sizes, HISTO_LENGTH); /* the kernels' text (vslam_matchdev.h) */
         for (int i = 0; i < HISTO_LENGTH; i++) {
-            if (i == ind1 || i == ind2 || i == ind3) continue;
+            if (vslam_md::keeps_bin(mx, i)) continue;
             for (int idx1 : rotHist[i])
                 if (vnMatches12[idx1] >= 0) {
                     vnMatches12[idx1] = -1;

@@ -178,9 +178,6 @@ bool distribute_octree(const Cand* cands, int n, int W, int H, int N, std::vecto
 void build_oct_lut(int W, int H, int D, std::vector<uint32_t>& xs, std::vector<uint32_t>& ys);
 uint32_t oct_key_path(int x, int y, int W, int H, int depth);
 
-/* FMatcher::ComputeThreeMaxima (fmatcher.cpp:2813-2854) on bin sizes. */
-void compute_three_maxima(const int* histo_sizes, int L, int& ind1, int& ind2, int& ind3);
-
 /* Frame::AssignFeaturesToGrid + GetFeaturesInArea (frame.cpp:386-414, 678-756), undistorted image. */
 struct FrameGrid {
     static const int COLS = 64, ROWS = 48; /* frame.h:42-43 */

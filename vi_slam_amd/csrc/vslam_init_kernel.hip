@@ -24,14 +24,10 @@
  */
 #include "vslam_kernels.h"
 #include "vslam_wave.h"
-#include "vslam_trig.h"
+#include "vslam_matchdev.h"
 
 #define SI_TH_LOW 50
-#define SI_HISTO 30
-#define SI_GRID_COLS 64 /* FRAME_GRID_COLS, frame.h:42 */
-#define SI_GRID_ROWS 48 /* FRAME_GRID_ROWS, frame.h:43 */
-#define SI_QPB_MAX 32   /* queries per k_si_topm workgroup: run-time (4 waves x 2..8), see vk_search_init */
-#define SI_MAX_M 16
+#define SI_QPB_MAX 32 /* queries per k_si_topm workgroup: run-time (4 waves x 2..8), see vk_search_init */
 
 struct SiCand { /* one octave-0 keypoint of frame 2 */
     float x, y, angle;
@@ -53,50 +49,6 @@ struct SiQuery { /* one octave-0 keypoint of frame 1 */
 /* per-pair scratch in HBM: [c1, c2, pad, pad] | SiCand[max_c2] | SiQuery[max_c2] | topm[max_c2][M] */
 __host__ __device__ inline size_t si_pair_bytes(int max_c2, int M) {
     return 16 + (size_t)max_c2 * (sizeof(SiCand) + sizeof(SiQuery) + 4 * (size_t)M);
-}
-
-struct SiWindow {
-    int minX, maxX, minY, maxY;
-    bool empty;
-};
-/* GetFeaturesInArea(x, y, r, ..): cell range over the grid bounds (frame.cpp:686-708 with mnMinX / mnMinY; KeyFrame's
- * copy, keyframe.cpp:655-699, is the same expression over its integer bounds: pass si_kf_bounds): floor((x - minX - r) *
- * inv), left to right.  With
- * minX = minY = 0 (the integer image, int_bounds() on the host) x - 0.0f == x, so every value equals the plain
- * floor((x - r) * inv) bit for bit. */
-/* A KeyFrame keeps the bounds as `const int mnMinX, mnMinY, mnMaxX, mnMaxY` (keyframe.h:255-258), initialised from the
- * Frame's floats (keyframe.cpp:44): truncated toward zero.  Its grid cells are the Frame's (binned with the float bounds,
- * keyframe.cpp:58-67) and its mfGridElement*Inv the Frame's floats (:36), but the window origin of
- * KeyFrame::GetFeaturesInArea (:663-675) and KeyFrame::IsInImage (:701-703) read the integers, converted back to float by
- * the comparison / subtraction.  {0, w, 0, h} is its own truncation. */
-__device__ __forceinline__ SiBounds si_kf_bounds(const SiBounds& b) {
-    return SiBounds{(float)(int)b.minX, (float)(int)b.maxX, (float)(int)b.minY, (float)(int)b.maxY};
-}
-__device__ __forceinline__ SiWindow si_window_b(float px, float py, float r, const SiBounds& b, float invW, float invH) {
-    SiWindow w;
-    const float dx = __fsub_rn(px, b.minX), dy = __fsub_rn(py, b.minY);
-    w.minX = max(0, (int)floorf(__fmul_rn(__fsub_rn(dx, r), invW)));
-    w.maxX = min(SI_GRID_COLS - 1, (int)ceilf(__fmul_rn(__fadd_rn(dx, r), invW)));
-    w.minY = max(0, (int)floorf(__fmul_rn(__fsub_rn(dy, r), invH)));
-    w.maxY = min(SI_GRID_ROWS - 1, (int)ceilf(__fmul_rn(__fadd_rn(dy, r), invH)));
-    w.empty = w.minX >= SI_GRID_COLS || w.maxX < 0 || w.minY >= SI_GRID_ROWS || w.maxY < 0;
-    return w;
-}
-__device__ __forceinline__ bool si_in_window(const SiCand& cd, const SiWindow& w, float px, float py, float r) {
-    const int gx = cd.cell >> 6, gy = cd.cell & 63;
-    if (gx < w.minX || gx > w.maxX || gy < w.minY || gy > w.maxY) return false;
-    const float distx = __fsub_rn(cd.x, px), disty = __fsub_rn(cd.y, py);
-    return fabsf(distx) < r && fabsf(disty) < r;
-}
-__device__ __forceinline__ bool si_in_window(const SiCandL& cd, const SiWindow& w, float px, float py, float r) {
-    const int gx = cd.cell >> 6, gy = cd.cell & 63;
-    if (gx < w.minX || gx > w.maxX || gy < w.minY || gy > w.maxY) return false;
-    const float distx = __fsub_rn(cd.x, px), disty = __fsub_rn(cd.y, py);
-    return fabsf(distx) < r && fabsf(disty) < r;
-}
-__device__ __forceinline__ uint32_t si_hamming(const uint4& da, const uint4& db, const uint4& ta, const uint4& tb) {
-    return __popc(da.x ^ ta.x) + __popc(da.y ^ ta.y) + __popc(da.z ^ ta.z) + __popc(da.w ^ ta.w) +
-           __popc(db.x ^ tb.x) + __popc(db.y ^ tb.y) + __popc(db.z ^ tb.z) + __popc(db.w ^ tb.w);
 }
 
 /* ------------------------------------------------------------------------------------------------
@@ -127,25 +79,21 @@ k_si_topm(InitJobs jobs, int cap, SiBounds bnd, int window, int max_c2, int M, u
     uint32_t* topm = (uint32_t*)(gqry + max_c2);
     const int q0 = blockIdx.x * SI_QPB;
 
-    /* Frame grid of frame 2 (frame.cpp:322-323, 746-756): (float)64 / (mnMaxX - mnMinX); {0, cols, 0, rows} without
-     * distortion, where (float)cols - 0.0f == (float)cols */
-    const float invW = __fdiv_rn((float)SI_GRID_COLS, __fsub_rn(bnd.maxX, bnd.minX));
-    const float invH = __fdiv_rn((float)SI_GRID_ROWS, __fsub_rn(bnd.maxY, bnd.minY));
+    const SiGridInv inv = si_grid_inv(bnd); /* Frame grid of frame 2 */
 
     int c2 = 0;
     for (int b = 0; b < n2; b += 256) {
         const int i = b + tid;
         bool take = false;
         vslam_kp k;
-        int gx = 0, gy = 0;
+        int cell = -1;
         if (i < n2) {
             k = jb.k2[i];
             if (k.octave == 0) {
-                /* PosInGrid: undistorted keypoints may lie left of / above the image or beyond it; they are rejected here,
-                 * before anything is packed into the u16 cell or the 12-bit key field */
-                gx = (int)roundf(__fmul_rn(__fsub_rn(k.x, bnd.minX), invW));
-                gy = (int)roundf(__fmul_rn(__fsub_rn(k.y, bnd.minY), invH));
-                take = !(gx < 0 || gx >= SI_GRID_COLS || gy < 0 || gy >= SI_GRID_ROWS);
+                /* keypoints outside the grid are rejected here, before anything is packed into the u16 cell or the
+                 * 12-bit key field */
+                cell = si_grid_cell(k.x, k.y, bnd, inv);
+                take = cell >= 0;
             }
         }
         const unsigned long long m = __ballot(take);
@@ -158,7 +106,7 @@ k_si_topm(InitJobs jobs, int cap, SiBounds bnd, int window, int max_c2, int M, u
             cd.x = k.x;
             cd.y = k.y;
             cd.angle = k.angle;
-            cd.cell = (uint16_t)(gx * 64 + gy);
+            cd.cell = (uint16_t)cell;
             cd.idx = (uint16_t)i;
             if (blockIdx.x == 0) gcand[pos] = cd;
             SiCandL cl;
@@ -168,7 +116,7 @@ k_si_topm(InitJobs jobs, int cap, SiBounds bnd, int window, int max_c2, int M, u
             cl.cell = cd.cell;
             cl.idx = cd.idx;
             tmpc[pos] = cl;
-            atomicAdd(&s_col[gx], 1);
+            atomicAdd(&s_col[cell >> 6], 1);
         }
         c2 += s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3];
         __syncthreads();
@@ -235,7 +183,7 @@ k_si_topm(InitJobs jobs, int cap, SiBounds bnd, int window, int max_c2, int M, u
     uint32_t* wk = wkeys + (size_t)wave * max_c2;
     for (int t = q0 + wave; t < min(c1, q0 + SI_QPB); t += 4) {
         const SiQuery qq = s_q[t - q0];
-        const SiWindow win = si_window_b(qq.px, qq.py, r, bnd, invW, invH);
+        const SiWindow win = si_window_b(qq.px, qq.py, r, bnd, inv);
         uint32_t mine = 0xFFFFFFFFu; /* lane j < M ends up with the j-th smallest key */
         if (!win.empty) {
             const uint4 da = ((const uint4*)jb.d1)[(size_t)qq.idx * 2];
@@ -252,7 +200,7 @@ k_si_topm(InitJobs jobs, int cap, SiBounds bnd, int window, int max_c2, int M, u
                         const uint4 ta = ((const uint4*)jb.d2)[(size_t)cd.idx * 2];
                         const uint4 tb = ((const uint4*)jb.d2)[(size_t)cd.idx * 2 + 1];
                         const uint32_t dist = si_hamming(da, db, ta, tb);
-                        key = (min(dist, 255u) << 24) | ((uint32_t)cd.cell << 12) | cd.c;
+                        key = si_key(dist, cd.cell, cd.c);
                         in = true;
                     }
                 }
@@ -293,9 +241,9 @@ __device__ __forceinline__ uint32_t sir_od_eff(const uint4 L, uint32_t q) {
 /* Full re-scan of one query's window (the reference loop body, fmatcher.cpp:1003-1035) by ONE wave: used when the query's
  * sorted prefix ran out.  Returns the best key; *second_out = bestDist2 (0x7FFFFFFF if none). */
 __device__ uint32_t si_full_scan(const InitJob& jb, const SiCand* gcand, const uint4* slotlog, int c2, int lane,
-                                 const SiQuery& qq, uint32_t qpos, float r, const SiBounds& bnd, float invW, float invH,
+                                 const SiQuery& qq, uint32_t qpos, float r, const SiBounds& bnd, const SiGridInv& inv,
                                  uint32_t* second_out) {
-    const SiWindow win = si_window_b(qq.px, qq.py, r, bnd, invW, invH);
+    const SiWindow win = si_window_b(qq.px, qq.py, r, bnd, inv);
     uint32_t bestKey = 0xFFFFFFFFu, second = 0x7FFFFFFFu; /* per lane: best key, smallest other distance */
     if (!win.empty) {
         const uint4 da = ((const uint4*)jb.d1)[(size_t)qq.idx * 2];
@@ -307,9 +255,9 @@ __device__ uint32_t si_full_scan(const InitJob& jb, const SiCand* gcand, const u
             const uint4 tb = ((const uint4*)jb.d2)[(size_t)cd.idx * 2 + 1];
             const uint32_t dist = min(si_hamming(da, db, ta, tb), 255u);
             if (sir_od_eff(slotlog[c], qpos) <= dist) continue; /* vMatchedDistance[i2] <= dist, fmatcher.cpp:1022 */
-            const uint32_t key = (dist << 24) | ((uint32_t)cd.cell << 12) | (uint32_t)c;
+            const uint32_t key = si_key(dist, cd.cell, (uint32_t)c);
             if (key < bestKey) {
-                if (bestKey != 0xFFFFFFFFu) second = min(second, bestKey >> 24);
+                if (bestKey != 0xFFFFFFFFu) second = min(second, si_key_dist(bestKey));
                 bestKey = key;
             } else {
                 second = min(second, dist);
@@ -319,7 +267,7 @@ __device__ uint32_t si_full_scan(const InitJob& jb, const SiCand* gcand, const u
     const uint32_t gBest = wave_min_u32(bestKey);
     /* second minimum over the multiset: lanes that do not hold the winner contribute their own best */
     uint32_t contrib = second;
-    if (bestKey != gBest && bestKey != 0xFFFFFFFFu) contrib = min(contrib, bestKey >> 24);
+    if (bestKey != gBest && bestKey != 0xFFFFFFFFu) contrib = min(contrib, si_key_dist(bestKey));
     *second_out = wave_min_u32(contrib);
     return gBest;
 }
@@ -402,13 +350,12 @@ k_si_replay(InitJobs jobs, int cap, SiBounds bnd, int window, float nnratio, int
     const uint32_t* keysrc = keys_in_lds ? keys_lds : topm;
     if (keys_in_lds)
         for (int i = tid; i < c1 * M; i += SIR_NT) keys_lds[i] = topm[i];
-    __shared__ int s_hist[SI_HISTO];
+    __shared__ int s_hist[VSLAM_HISTO_LENGTH];
     __shared__ int s_minpend[2], s_minwild[2], s_scanq, s_nlog, s_cnt;
 
     int32_t* mo = matches_out + (size_t)blockIdx.x * cap;
     float* po = prev_out + (size_t)blockIdx.x * cap * 2;
-    const float invW = __fdiv_rn((float)SI_GRID_COLS, __fsub_rn(bnd.maxX, bnd.minX));
-    const float invH = __fdiv_rn((float)SI_GRID_ROWS, __fsub_rn(bnd.maxY, bnd.minY));
+    const SiGridInv inv = si_grid_inv(bnd);
     const float r = (float)window;
 
     for (int c = tid; c < c2; c += SIR_NT) {
@@ -421,7 +368,7 @@ k_si_replay(InitJobs jobs, int cap, SiBounds bnd, int window, float nnratio, int
         m12[i] = -1;
         rotBin[i] = 255;
     }
-    if (tid < SI_HISTO) s_hist[tid] = 0;
+    if (tid < VSLAM_HISTO_LENGTH) s_hist[tid] = 0;
     if (tid == 0) {
         s_minpend[0] = s_minpend[1] = 0x7FFFFFFF;
         s_minwild[0] = s_minwild[1] = 0x7FFFFFFF;
@@ -448,7 +395,7 @@ k_si_replay(InitJobs jobs, int cap, SiBounds bnd, int window, float nnratio, int
                 if (j < M && key[j] != 0xFFFFFFFFu) {
                     nvalid++;
                     klast = key[j];
-                    const uint32_t slot = key[j] & 0xFFFu, d = key[j] >> 24;
+                    const uint32_t slot = si_key_index(key[j]), d = si_key_dist(key[j]);
                     if (!(sir_od_eff(slotlog[slot], (uint32_t)q) <= d)) { /* not skipped */
                         if (d <= SI_TH_LOW) atomicMin(&lister[slot], q); /* may still accept this slot */
                         if (gBest == 0xFFFFFFFFu) gBest = key[j];
@@ -457,19 +404,19 @@ k_si_replay(InitJobs jobs, int cap, SiBounds bnd, int window, float nnratio, int
                 }
             }
             const bool full = nvalid == M;
-            const uint32_t dlast = klast >> 24;
+            const uint32_t dlast = si_key_dist(klast);
             const bool wild = full && dlast <= SI_TH_LOW; /* could accept a slot beyond its list once the list is used up */
             bool accept = false, scan = false;
             if (gBest == 0xFFFFFFFFu) {
                 scan = wild; /* else: vIndices2 empty, everything skipped, or nothing within TH_LOW beyond the list */
-            } else if ((gBest >> 24) <= SI_TH_LOW) {
-                uint32_t bestDist2 = k2 == 0xFFFFFFFFu ? 0x7FFFFFFFu : (k2 >> 24);
+            } else if (si_key_dist(gBest) <= SI_TH_LOW) {
+                uint32_t bestDist2 = k2 == 0xFFFFFFFFu ? 0x7FFFFFFFu : si_key_dist(k2);
                 if (k2 == 0xFFFFFFFFu && full) {
                     /* the second survivor lies beyond the list: it is at least as far as the last entry */
-                    if ((float)(int)(gBest >> 24) < __fmul_rn((float)(int)dlast, nnratio)) bestDist2 = dlast; /* accepted whatever the true second is */
+                    if ((float)(int)si_key_dist(gBest) < __fmul_rn((float)(int)dlast, nnratio)) bestDist2 = dlast; /* accepted whatever the true second is */
                     else scan = true;
                 }
-                if (!scan) accept = (float)(int)(gBest >> 24) < __fmul_rn((float)(int)bestDist2, nnratio);
+                if (!scan) accept = (float)(int)si_key_dist(gBest) < __fmul_rn((float)(int)bestDist2, nnratio);
             }
             kfirst[q] = gBest;
             ksecond[q] = k2;
@@ -499,12 +446,12 @@ k_si_replay(InitJobs jobs, int cap, SiBounds bnd, int window, float nnratio, int
             }
             const uint32_t k1 = kfirst[q], k2 = ksecond[q];
             bool blocked = q > minw;
-            if (k1 != 0xFFFFFFFFu && lister[k1 & 0xFFFu] < q) blocked = true;
-            if (k2 != 0xFFFFFFFFu && lister[k2 & 0xFFFu] < q) blocked = true;
+            if (k1 != 0xFFFFFFFFu && lister[si_key_index(k1)] < q) blocked = true;
+            if (k2 != 0xFFFFFFFFu && lister[si_key_index(k2)] < q) blocked = true;
             if (blocked) continue;
             if (fl & SIR_ACC) {
-                if (!sir_slot_append(slotlog, k1 & 0xFFFu, (uint32_t)q, k1 >> 24, q == minp)) continue; /* slot full: wait to be first */
-                alog[atomicAdd(&s_nlog, 1)] = ((uint32_t)q << 12) | (k1 & 0xFFFu);
+                if (!sir_slot_append(slotlog, si_key_index(k1), (uint32_t)q, si_key_dist(k1), q == minp)) continue; /* slot full: wait to be first */
+                alog[atomicAdd(&s_nlog, 1)] = ((uint32_t)q << 12) | si_key_index(k1);
             }
             qstate[q] = 0;
         }
@@ -515,11 +462,11 @@ k_si_replay(InitJobs jobs, int cap, SiBounds bnd, int window, float nnratio, int
         if (sq >= 0) { /* block-uniform */
             if (tid < 64) {
                 uint32_t d2;
-                const uint32_t gb = si_full_scan(jb, gcand, slotlog, c2, lane, gqry[sq], (uint32_t)sq, r, bnd, invW, invH, &d2);
+                const uint32_t gb = si_full_scan(jb, gcand, slotlog, c2, lane, gqry[sq], (uint32_t)sq, r, bnd, inv, &d2);
                 if (tid == 0) {
-                    if (gb != 0xFFFFFFFFu && (gb >> 24) <= SI_TH_LOW && (float)(int)(gb >> 24) < __fmul_rn((float)(int)d2, nnratio)) {
-                        sir_slot_append(slotlog, gb & 0xFFFu, (uint32_t)sq, gb >> 24, true);
-                        alog[atomicAdd(&s_nlog, 1)] = ((uint32_t)sq << 12) | (gb & 0xFFFu);
+                    if (gb != 0xFFFFFFFFu && si_key_dist(gb) <= SI_TH_LOW && (float)(int)si_key_dist(gb) < __fmul_rn((float)(int)d2, nnratio)) {
+                        sir_slot_append(slotlog, si_key_index(gb), (uint32_t)sq, si_key_dist(gb), true);
+                        alog[atomicAdd(&s_nlog, 1)] = ((uint32_t)sq << 12) | si_key_index(gb);
                     }
                     qstate[sq] = 0;
                 }
@@ -542,17 +489,13 @@ k_si_replay(InitJobs jobs, int cap, SiBounds bnd, int window, float nnratio, int
     __syncthreads();
     for (int e = tid; e < nlog; e += SIR_NT) atomicMax(&ownerQ[alog[e] & 0xFFFu], (int)(alog[e] >> 12));
     __syncthreads();
-    const float factor = 1.0f / SI_HISTO;
     for (int e = tid; e < nlog; e += SIR_NT) {
         const uint32_t le = alog[e];
         const SiQuery q = gqry[le >> 12];
         const SiCand cd = gcand[le & 0xFFFu];
         if (ownerQ[le & 0xFFFu] == (int)(le >> 12)) m12[q.idx] = cd.idx;
         if (checkOri) {
-            float rot = __fsub_rn(q.angle, cd.angle);
-            if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-            int bin = (int)roundf(__fmul_rn(rot, factor));
-            if (bin == SI_HISTO) bin = 0;
+            const int bin = vslam_md::rot_bin(q.angle, cd.angle, VSLAM_HISTO_LENGTH);
             rotBin[q.idx] = (uint8_t)bin;
             atomicAdd(&s_hist[bin], 1); /* rotHist[bin].push_back(i1): never removed, even if stolen later */
         }
@@ -560,26 +503,10 @@ k_si_replay(InitJobs jobs, int cap, SiBounds bnd, int window, float nnratio, int
     __syncthreads();
     /* nmatches is counted from vnMatches12 at the end: the reference's running count equals it */
     if (checkOri) {
-        /* ComputeThreeMaxima (fmatcher.cpp:2813-2854) */
-        int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;
-        for (int i = 0; i < SI_HISTO; i++) {
-            const int s = s_hist[i];
-            if (s > max1) {
-                max3 = max2; max2 = max1; max1 = s;
-                ind3 = ind2; ind2 = ind1; ind1 = i;
-            } else if (s > max2) {
-                max3 = max2; max2 = s;
-                ind3 = ind2; ind2 = i;
-            } else if (s > max3) {
-                max3 = s;
-                ind3 = i;
-            }
-        }
-        if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
-        else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) { ind3 = -1; }
+        const vslam_md::ThreeMaxima mx = vslam_md::three_maxima(s_hist, VSLAM_HISTO_LENGTH);
         for (int i = tid; i < n1; i += SIR_NT) {
             const int b = rotBin[i];
-            if (b != 255 && b != ind1 && b != ind2 && b != ind3) m12[i] = -1;
+            if (b != 255 && !vslam_md::keeps_bin(mx, b)) m12[i] = -1;
         }
         __syncthreads();
     }
@@ -667,932 +594,3 @@ void vk_search_init(hipStream_t st, const InitJobs& jobs, int npairs, int cap, c
                            window, nnratio, checkOri, matches_out, prev_out, nmatch_out, max_c2, M, scratch, fallbacks, keys_lds);
 }
 
-/* ==================================================================================================
- * FMatcher::SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, th, bMono)
- * (fmatcher.cpp:2471-2687, pinhole frames: Nleft == -1) -- the per-frame tracking matcher of
- * TrackWithMotionModel (tracking.cpp:2728).  Same decomposition as SearchForInitialization above:
- *
- *   k_sbp_rank   (parallel, one wave per last-frame keypoint): project its MapPoint into the current frame
- *                (Rcw*x3Dw+tcw as ONE cv::gemm: products accumulated in double, rounded once; 1.0/z in
- *                double; Pinhole::project in float), query the window (Frame::GetFeaturesInArea with the
- *                forward / backward / +-1 octave rule), apply the order-free mvuRight gate, and write the M
- *                smallest keys = dist << 24 | gridcell << 12 | i2 in ascending order ("first wins" on equal
- *                distance is the key order).
- *   k_sbp_replay (one wave, last-frame keypoints in index order): the only sequential state is "current
- *                keypoint i2 already carries a MapPoint with observations" (the skip at fmatcher.cpp:2545-
- *                2547); the first list entry that is not occupied is bestIdx2.  An exhausted full list falls
- *                back to a full re-scan of that query.  Assignments go to a log; mvpMapPoints ("last writer
- *                wins"), the rotation histogram, ComputeThreeMaxima and nmatches are rebuilt from it.
- * ================================================================================================== */
-#define SBP_TH_HIGH 100
-#define SBP_QPB 16 /* queries per k_sbp_rank workgroup (4 waves x 4) */
-
-struct SbpCand { /* one keypoint of the current frame */
-    float x, y, uRight;
-    uint16_t cell;
-    uint16_t octave;
-};
-struct SbpProj { /* projection record of one last-frame keypoint (k_sbp_rank -> k_sbp_replay's re-scan) */
-    float u, v, radius, ur;
-    int32_t minLevel, maxLevel, valid, pad;
-};
-
-__device__ __forceinline__ float sbp_gemm_row(const float* r, float x0, float x1, float x2, float t, int flt) {
-    if (!flt) { /* GEMMSingleMul<float,double>: s += double(a)*double(b), then float(s + double(c)) */
-        double s = __dmul_rn((double)r[0], (double)x0);
-        s = __dadd_rn(s, __dmul_rn((double)r[1], (double)x1));
-        s = __dadd_rn(s, __dmul_rn((double)r[2], (double)x2));
-        return (float)__dadd_rn(s, (double)t);
-    }
-    float s = __fmul_rn(r[0], x0);
-    s = __fadd_rn(s, __fmul_rn(r[1], x1));
-    s = __fadd_rn(s, __fmul_rn(r[2], x2));
-    return __fadd_rn(s, t);
-}
-
-__device__ __forceinline__ bool sbp_level_ok(int octave, int minLevel, int maxLevel) { /* frame.cpp:712-728 */
-    const bool bCheckLevels = (minLevel > 0) || (maxLevel >= 0);
-    if (!bCheckLevels) return true;
-    if (octave < minLevel) return false;
-    if (maxLevel >= 0 && octave > maxLevel) return false;
-    return true;
-}
-
-/* the order-free part of the candidate loop body (fmatcher.cpp:2541-2556): window, level, mvuRight gate */
-__device__ __forceinline__ bool sbp_candidate_ok(const SbpCand& cd, const SiWindow& w, const SbpProj& pr) {
-    const int gx = cd.cell >> 6, gy = cd.cell & 63;
-    if (gx < w.minX || gx > w.maxX || gy < w.minY || gy > w.maxY) return false;
-    if (!sbp_level_ok(cd.octave, pr.minLevel, pr.maxLevel)) return false;
-    const float distx = __fsub_rn(cd.x, pr.u), disty = __fsub_rn(cd.y, pr.v);
-    if (!(fabsf(distx) < pr.radius && fabsf(disty) < pr.radius)) return false;
-    if (cd.uRight > 0.f) { /* CurrentFrame.mvuRight[i2] > 0 */
-        const float er = fabsf(__fsub_rn(pr.ur, cd.uRight));
-        if (er > pr.radius) return false;
-    }
-    return true;
-}
-
-__device__ __forceinline__ SbpCand sbp_make_cand(const vslam_kp& k, float uRight, const SiBounds& b, float invW, float invH,
-                                                 bool* in_grid) {
-    SbpCand c;
-    c.x = k.x;
-    c.y = k.y;
-    c.uRight = uRight;
-    const int gx = (int)roundf(__fmul_rn(__fsub_rn(k.x, b.minX), invW));
-    const int gy = (int)roundf(__fmul_rn(__fsub_rn(k.y, b.minY), invH));
-    *in_grid = !(gx < 0 || gx >= SI_GRID_COLS || gy < 0 || gy >= SI_GRID_ROWS); /* PosInGrid, frame.cpp:746-756 */
-    c.cell = (uint16_t)(*in_grid ? gx * 64 + gy : 0xFFFF);
-    c.octave = (uint16_t)k.octave;
-    return c;
-}
-
-__global__ void __launch_bounds__(256)
-k_sbp_rank(SbpJobs JS) {
-    extern __shared__ __align__(16) uint8_t sbsm[];
-    SbpCand* cand = (SbpCand*)sbsm; /* nCur */
-    const SbpJobDev& J = JS.job[blockIdx.y];
-    const int M = JS.M;
-    const int nLast = J.nLastPtr ? min(*J.nLastPtr, J.nLast) : J.nLast;
-    const int nCur = J.nCurPtr ? min(*J.nCurPtr, J.nCur) : J.nCur;
-    if ((int)blockIdx.x * SBP_QPB >= nLast) return; /* grid is sized for the capacity */
-    const vslam_kp* __restrict__ lastKps = J.lastKps;
-    const vslam_kp* __restrict__ curKps = J.curKps;
-    const uint8_t* __restrict__ curDesc = J.curDesc;
-    const uint8_t* __restrict__ mpDesc = J.mpDesc;
-    const float* __restrict__ uRight = J.uRight;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const SiBounds bnd = J.bnd; /* the frame's grid bounds mnMinX.. (frame.cpp:793-821) */
-    const SiBounds wbnd = J.mode == 3 ? si_kf_bounds(bnd) : bnd; /* window origin / in-image test: a KeyFrame's are integers */
-    const float invW = __fdiv_rn((float)SI_GRID_COLS, __fsub_rn(bnd.maxX, bnd.minX)); /* frame.cpp:322-323 */
-    const float invH = __fdiv_rn((float)SI_GRID_ROWS, __fsub_rn(bnd.maxY, bnd.minY));
-    for (int i = tid; i < nCur; i += 256) {
-        bool ing;
-        cand[i] = sbp_make_cand(curKps[i], uRight ? uRight[i] : -1.f, bnd, invW, invH, &ing);
-    }
-    __syncthreads();
-    for (int q = blockIdx.x * SBP_QPB + wave; q < min(nLast, (int)(blockIdx.x + 1) * SBP_QPB); q += 4) {
-        SbpProj pr;
-        pr.valid = 0;
-        pr.u = pr.v = pr.radius = pr.ur = 0.f;
-        pr.minLevel = pr.maxLevel = 0;
-        pr.pad = 0;
-        if (J.mode == 1) { /* pre-projected MapPoints (fmatcher.cpp:327-350) */
-            const MpTrack mp = J.mps[q];
-            if (mp.flags & 1) {
-                float r = (double)mp.viewCos > 0.998 ? 2.5f : 4.0f; /* RadiusByViewingCos, fmatcher.cpp:493-499 */
-                if (J.th != 1.0f) r = __fmul_rn(r, J.th);
-                pr.u = mp.projX;
-                pr.v = mp.projY;
-                pr.radius = __fmul_rn(r, JS.scale[min(max(mp.level, 0), JS.nlevels - 1)]);
-                pr.ur = mp.projXR;
-                pr.minLevel = mp.level - 1;
-                pr.maxLevel = mp.level;
-                pr.valid = 1;
-            }
-        } else if (J.mode == 2) { /* KeyFrame MapPoints into the current frame, fmatcher.cpp:2705-2743 */
-            if (J.flags[q] & 1) { /* pMP && !isBad() && !sAlreadyFound.count(pMP) */
-                const float X = J.x3Dw[3 * q], Y = J.x3Dw[3 * q + 1], Z = J.x3Dw[3 * q + 2];
-                const float xc = sbp_gemm_row(J.Tcw + 0, X, Y, Z, J.Tcw[3], J.gemmFloat);
-                const float yc = sbp_gemm_row(J.Tcw + 4, X, Y, Z, J.Tcw[7], J.gemmFloat);
-                const float zc = sbp_gemm_row(J.Tcw + 8, X, Y, Z, J.Tcw[11], J.gemmFloat);
-                const float u = __fadd_rn(__fdiv_rn(__fmul_rn(J.fx, xc), zc), J.cx); /* no depth test here */
-                const float v = __fadd_rn(__fdiv_rn(__fmul_rn(J.fy, yc), zc), J.cy);
-                if (!(u < bnd.minX || u > bnd.maxX) && !(v < bnd.minY || v > bnd.maxY)) {
-                    /* Ow = -Rcw^T tcw is cv::Mat algebra on the caller's side: it arrives in JS.kf.ow */
-                    const float p0 = __fsub_rn(X, JS.kf.ow[0]), p1 = __fsub_rn(Y, JS.kf.ow[1]), p2 = __fsub_rn(Z, JS.kf.ow[2]);
-                    double n2 = __dmul_rn((double)p0, (double)p0); /* cv::norm: double accumulation */
-                    n2 = __dadd_rn(n2, __dmul_rn((double)p1, (double)p1));
-                    n2 = __dadd_rn(n2, __dmul_rn((double)p2, (double)p2));
-                    const float dist3D = (float)__dsqrt_rn(n2);
-                    const float mn = JS.kf.minDist[q], mx = JS.kf.maxDist[q];
-                    if (!(dist3D < mn || dist3D > mx)) {
-                        const float lv = ceilf(__fdiv_rn(vslam_trig::glibc_logf(__fdiv_rn(mx, dist3D)), JS.kf.logScaleFactor));
-                        const int level = (lv != lv || lv >= 2147483648.0f || lv < 0.f) ? 0 : min((int)lv, JS.nlevels - 1);
-                        pr.u = u;
-                        pr.v = v;
-                        pr.radius = __fmul_rn(J.th, JS.scale[level]);
-                        pr.minLevel = level - 1;
-                        pr.maxLevel = level + 1;
-                        pr.valid = 1;
-                    }
-                }
-            }
-        } else if (J.mode == 3) { /* candidate MapPoints into a KeyFrame under Scw, fmatcher.cpp:773-825 / :890-941 */
-            if (J.flags[q] & 1) { /* !pMP->isBad() && !spAlreadyFound.count(pMP) */
-                const float X = J.x3Dw[3 * q], Y = J.x3Dw[3 * q + 1], Z = J.x3Dw[3 * q + 2];
-                const float xc = sbp_gemm_row(J.Tcw + 0, X, Y, Z, J.Tcw[3], J.gemmFloat);
-                const float yc = sbp_gemm_row(J.Tcw + 4, X, Y, Z, J.Tcw[7], J.gemmFloat);
-                const float zc = sbp_gemm_row(J.Tcw + 8, X, Y, Z, J.Tcw[11], J.gemmFloat);
-                if (!(zc < 0.0f)) {
-                    float u, v;
-                    if (JS.kf.projKind == 0) {
-                        u = __fadd_rn(__fdiv_rn(__fmul_rn(J.fx, xc), zc), J.cx);
-                        v = __fadd_rn(__fdiv_rn(__fmul_rn(J.fy, yc), zc), J.cy);
-                    } else {
-                        const float invz = __fdiv_rn(1.0f, zc);
-                        u = __fadd_rn(__fmul_rn(J.fx, __fmul_rn(xc, invz)), J.cx);
-                        v = __fadd_rn(__fmul_rn(J.fy, __fmul_rn(yc, invz)), J.cy);
-                    }
-                    if (u >= wbnd.minX && u < wbnd.maxX && v >= wbnd.minY && v < wbnd.maxY) { /* KeyFrame::IsInImage, keyframe.cpp:701-703 */
-                        const float p0 = __fsub_rn(X, JS.kf.ow[0]), p1 = __fsub_rn(Y, JS.kf.ow[1]), p2 = __fsub_rn(Z, JS.kf.ow[2]);
-                        double n2 = __dmul_rn((double)p0, (double)p0);
-                        n2 = __dadd_rn(n2, __dmul_rn((double)p1, (double)p1));
-                        n2 = __dadd_rn(n2, __dmul_rn((double)p2, (double)p2));
-                        const float dist3D = (float)__dsqrt_rn(n2);
-                        const float mn = JS.kf.minDist[q], mx = JS.kf.maxDist[q];
-                        bool ok = !(dist3D < mn || dist3D > mx);
-                        if (ok) { /* PO.dot(Pn) < 0.5*dist: cv::Mat::dot accumulates in double */
-                            const float* Pn = JS.kf.normals + 3 * q;
-                            double dot = __dmul_rn((double)p0, (double)Pn[0]);
-                            dot = __dadd_rn(dot, __dmul_rn((double)p1, (double)Pn[1]));
-                            dot = __dadd_rn(dot, __dmul_rn((double)p2, (double)Pn[2]));
-                            ok = !(dot < __dmul_rn(0.5, (double)dist3D));
-                        }
-                        if (ok) {
-                            const float lv = ceilf(__fdiv_rn(vslam_trig::glibc_logf(__fdiv_rn(mx, dist3D)), JS.kf.logScaleFactor));
-                            const int level = (lv != lv || lv >= 2147483648.0f || lv < 0.f) ? 0 : min((int)lv, JS.nlevels - 1);
-                            pr.u = u;
-                            pr.v = v;
-                            pr.radius = __fmul_rn(J.th, JS.scale[level]);
-                            pr.minLevel = level - 1;
-                            pr.maxLevel = level;
-                            pr.valid = 1;
-                        }
-                    }
-                }
-            }
-        } else if (J.flags[q] & 1) { /* pMP && !LastFrame.mvbOutlier[i] */
-            const float X = J.x3Dw[3 * q], Y = J.x3Dw[3 * q + 1], Z = J.x3Dw[3 * q + 2];
-            const float xc = sbp_gemm_row(J.Tcw + 0, X, Y, Z, J.Tcw[3], J.gemmFloat);
-            const float yc = sbp_gemm_row(J.Tcw + 4, X, Y, Z, J.Tcw[7], J.gemmFloat);
-            const float zc = sbp_gemm_row(J.Tcw + 8, X, Y, Z, J.Tcw[11], J.gemmFloat);
-            const float invzc = (float)__ddiv_rn(1.0, (double)zc);
-            if (!(invzc < 0.f)) {
-                const float u = __fadd_rn(__fdiv_rn(__fmul_rn(J.fx, xc), zc), J.cx); /* pinhole.cpp:13-16 */
-                const float v = __fadd_rn(__fdiv_rn(__fmul_rn(J.fy, yc), zc), J.cy);
-                if (!(u < bnd.minX || u > bnd.maxX) && !(v < bnd.minY || v > bnd.maxY)) {
-                    const int oct = lastKps[q].octave;
-                    pr.u = u;
-                    pr.v = v;
-                    pr.radius = __fmul_rn(J.th, JS.scale[min(max(oct, 0), JS.nlevels - 1)]);
-                    pr.ur = __fsub_rn(u, __fmul_rn(J.mbf, invzc));
-                    if (J.forward) { pr.minLevel = oct; pr.maxLevel = -1; }
-                    else if (J.backward) { pr.minLevel = 0; pr.maxLevel = oct; }
-                    else { pr.minLevel = oct - 1; pr.maxLevel = oct + 1; }
-                    pr.valid = 1;
-                }
-            }
-        }
-        /* per-lane sorted prefix (ascending), then an M-way merge across the wave */
-        uint32_t best[SI_MAX_M];
-#pragma unroll
-        for (int j = 0; j < SI_MAX_M; j++) best[j] = 0xFFFFFFFFu;
-        if (pr.valid) { /* wave-uniform */
-            const SiWindow win = si_window_b(pr.u, pr.v, pr.radius, wbnd, invW, invH);
-            if (!win.empty) {
-                const uint4 da = ((const uint4*)mpDesc)[(size_t)q * 2], db = ((const uint4*)mpDesc)[(size_t)q * 2 + 1];
-                for (int c = lane; c < nCur; c += 64) {
-                    const SbpCand cd = cand[c];
-                    if (cd.cell == 0xFFFF || !sbp_candidate_ok(cd, win, pr)) continue;
-                    const uint4 ta = ((const uint4*)curDesc)[(size_t)c * 2], tb = ((const uint4*)curDesc)[(size_t)c * 2 + 1];
-                    uint32_t key = (min(si_hamming(da, db, ta, tb), 255u) << 24) | ((uint32_t)cd.cell << 12) | (uint32_t)c;
-#pragma unroll
-                    for (int j = 0; j < SI_MAX_M; j++) { /* insertion: keeps best[] ascending, drops the largest */
-                        const uint32_t lo = min(key, best[j]);
-                        key = max(key, best[j]);
-                        best[j] = lo;
-                    }
-                }
-            }
-        }
-        uint32_t mine = 0xFFFFFFFFu;
-        for (int j = 0; j < M; j++) {
-            const uint32_t g = wave_min_u32(best[0]);
-            if (g == 0xFFFFFFFFu) break;
-            if (lane == j) mine = g;
-            if (best[0] == g) { /* pop (keys are unique: they contain i2) */
-#pragma unroll
-                for (int t = 0; t + 1 < SI_MAX_M; t++) best[t] = best[t + 1];
-                best[SI_MAX_M - 1] = 0xFFFFFFFFu;
-            }
-        }
-        if (lane < M) J.topm[(size_t)q * M + lane] = mine;
-        if (lane == 0) J.proj[q] = pr;
-    }
-}
-
-/* full re-scan of one query's window in candidate order (the reference loop body) -> best key or ~0 */
-__device__ uint32_t sbp_full_scan(const SbpProj& pr, const vslam_kp* curKps, const float* uRight, int nCur,
-                                  const uint8_t* mpDescQ, const uint8_t* curDesc, const uint32_t* occupied,
-                                  const SiBounds& bnd, const SiBounds& wbnd, float invW, float invH, int lane) {
-    uint32_t bestKey = 0xFFFFFFFFu;
-    const SiWindow win = si_window_b(pr.u, pr.v, pr.radius, wbnd, invW, invH);
-    if (!win.empty) {
-        const uint4 da = ((const uint4*)mpDescQ)[0], db = ((const uint4*)mpDescQ)[1];
-        for (int c = lane; c < nCur; c += 64) {
-            bool ing;
-            const SbpCand cd = sbp_make_cand(curKps[c], uRight ? uRight[c] : -1.f, bnd, invW, invH, &ing);
-            if (!ing || occupied[c] || !sbp_candidate_ok(cd, win, pr)) continue;
-            const uint4 ta = ((const uint4*)curDesc)[(size_t)c * 2], tb = ((const uint4*)curDesc)[(size_t)c * 2 + 1];
-            bestKey = min(bestKey, (min(si_hamming(da, db, ta, tb), 255u) << 24) | ((uint32_t)cd.cell << 12) | (uint32_t)c);
-        }
-    }
-    return wave_min_u32(bestKey);
-}
-
-/* ------------------------------------------------------------------------------------------------
- * The sequential rule "query q takes the first candidate of its sorted list that no earlier query with
- * observations has taken" is a serial dictatorship, and a serial dictatorship is the fixpoint of deferred
- * acceptance with one common priority order: every query points at a candidate; a candidate is held by the
- * lowest-index blocking query pointing at it; whoever sees a lower-index holder moves on to its next candidate.
- * Holders' indices only decrease, so a rejection is final and the fixpoint is the sequential result.  One
- * 1024-thread workgroup per job iterates this in parallel (a handful of rounds) instead of one wave walking
- * 2000 queries in order.  Only when some query runs off a FULL sorted prefix (it would need candidates that
- * k_sbp_rank did not keep) the job is handed to k_sbp_replay, which walks it sequentially with full re-scans.
- * ---------------------------------------------------------------------------------------------- */
-#define SBP_RT 1024
-#define SBP_QPT 4 /* queries per thread: capacity 4096 */
-__global__ void __launch_bounds__(SBP_RT)
-k_sbp_resolve(SbpJobs JS, int forceSeq) {
-    extern __shared__ __align__(16) uint8_t sbsm[];
-    const SbpJobDev& J = JS.job[blockIdx.x];
-    const uint32_t thHigh = JS.kf.thHigh ? (uint32_t)(JS.kf.thHigh - 1) : (uint32_t)SBP_TH_HIGH;
-    const int M = JS.M;
-    const int nLast = J.nLastPtr ? min(*J.nLastPtr, J.nLast) : J.nLast;
-    const int nCur = J.nCurPtr ? min(*J.nCurPtr, J.nCur) : J.nCur;
-    int32_t* holder = (int32_t*)sbsm; /* nCur: lowest-index blocking query pointing here; -1 = occupied from the start */
-    int32_t* owner = holder + nCur;   /* nCur: highest-index query assigned here (mvpMapPoints: last writer wins) */
-    __shared__ int s_changed, s_seq, s_nlog, s_removed;
-    __shared__ int s_hist[SI_HISTO];
-    const int tid = threadIdx.x;
-    if (tid == 0) {
-        s_seq = forceSeq;
-        s_nlog = 0;
-        s_removed = 0;
-    }
-    if (tid < SI_HISTO) s_hist[tid] = 0;
-    for (int c = tid; c < nCur; c += SBP_RT) {
-        holder[c] = (J.occupied0 && J.occupied0[c]) ? -1 : 0x7FFFFFFF;
-        owner[c] = -1;
-    }
-    uint32_t key[SBP_QPT];
-    int ptr[SBP_QPT];
-    bool blocking[SBP_QPT];
-#pragma unroll
-    for (int k = 0; k < SBP_QPT; k++) {
-        const int q = tid + k * SBP_RT;
-        ptr[k] = 0;
-        key[k] = q < nLast ? J.topm[(size_t)q * M] : 0xFFFFFFFFu;
-        blocking[k] = q < nLast && (J.flags[q] & 2);
-    }
-    __syncthreads();
-    for (int round = 0; round < 4096 && !s_seq; round++) { /* s_seq / s_changed are block-uniform at the barriers */
-        if (tid == 0) s_changed = 0;
-#pragma unroll
-        for (int k = 0; k < SBP_QPT; k++)
-            if (key[k] != 0xFFFFFFFFu && blocking[k] && (key[k] >> 24) <= thHigh)
-                atomicMin(&holder[key[k] & 0xFFF], tid + k * SBP_RT);
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < SBP_QPT; k++) {
-            const int q = tid + k * SBP_RT;
-            if (key[k] != 0xFFFFFFFFu && holder[key[k] & 0xFFF] < q) { /* taken by an earlier query: next candidate */
-                ptr[k]++;
-                if (ptr[k] >= M) {
-                    s_seq = 1; /* ran off a full prefix */
-                    key[k] = 0xFFFFFFFFu;
-                } else {
-                    key[k] = J.topm[(size_t)q * M + ptr[k]]; /* ~0: the list is complete and exhausted */
-                }
-                s_changed = 1;
-            }
-        }
-        __syncthreads();
-        if (!s_changed) break;
-        __syncthreads();
-    }
-    __syncthreads();
-    if (tid == 0) *J.needSeq = s_seq;
-    if (s_seq) return;
-    /* assignments */
-    uint32_t bin[SBP_QPT];
-    const float factor = 1.0f / SI_HISTO;
-#pragma unroll
-    for (int k = 0; k < SBP_QPT; k++) {
-        const int q = tid + k * SBP_RT;
-        bin[k] = 255;
-        if (key[k] != 0xFFFFFFFFu && (key[k] >> 24) <= thHigh) {
-            const int i2 = (int)(key[k] & 0xFFF);
-            atomicMax(&owner[i2], q);
-            atomicAdd(&s_nlog, 1);
-            bin[k] = 254;
-            if (J.checkOri) {
-                float rot = __fsub_rn(J.lastKps[q].angle, J.curKps[i2].angle);
-                if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-                int b = (int)roundf(__fmul_rn(rot, factor));
-                if (b == SI_HISTO) b = 0;
-                bin[k] = (uint32_t)b;
-                atomicAdd(&s_hist[b], 1);
-            }
-        }
-    }
-    __syncthreads();
-    for (int c = tid; c < nCur; c += SBP_RT) J.matchCur[c] = owner[c];
-    __syncthreads();
-    if (J.checkOri) {
-        int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0; /* ComputeThreeMaxima, fmatcher.cpp:2813-2854 */
-        for (int i = 0; i < SI_HISTO; i++) {
-            const int sv = s_hist[i];
-            if (sv > max1) {
-                max3 = max2; max2 = max1; max1 = sv;
-                ind3 = ind2; ind2 = ind1; ind1 = i;
-            } else if (sv > max2) {
-                max3 = max2; max2 = sv;
-                ind3 = ind2; ind2 = i;
-            } else if (sv > max3) {
-                max3 = sv;
-                ind3 = i;
-            }
-        }
-        if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
-        else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) { ind3 = -1; }
-#pragma unroll
-        for (int k = 0; k < SBP_QPT; k++) {
-            const int b = (int)bin[k];
-            if (b < SI_HISTO && b != ind1 && b != ind2 && b != ind3) { /* fmatcher.cpp:2668-2681 */
-                J.matchCur[key[k] & 0xFFF] = -1;
-                atomicAdd(&s_removed, 1);
-            }
-        }
-    }
-    __syncthreads();
-    if (tid == 0) J.nmatches[0] = s_nlog - s_removed;
-}
-
-__global__ void __launch_bounds__(64)
-k_sbp_replay(SbpJobs JS, int* fallbacks) {
-    extern __shared__ __align__(16) uint8_t sbsm[];
-    const SbpJobDev& J = JS.job[blockIdx.x];
-    const uint32_t thHigh = JS.kf.thHigh ? (uint32_t)(JS.kf.thHigh - 1) : (uint32_t)SBP_TH_HIGH;
-    const int M = JS.M;
-    const int nLast = J.nLastPtr ? min(*J.nLastPtr, J.nLast) : J.nLast;
-    const int nCur = J.nCurPtr ? min(*J.nCurPtr, J.nCur) : J.nCur;
-    const vslam_kp* __restrict__ lastKps = J.lastKps;
-    const vslam_kp* __restrict__ curKps = J.curKps;
-    const uint8_t* __restrict__ curDesc = J.curDesc;
-    const uint8_t* __restrict__ mpDesc = J.mpDesc;
-    const uint8_t* __restrict__ flags = J.flags;
-    const float* __restrict__ uRight = J.uRight;
-    const uint8_t* __restrict__ occupied0 = J.occupied0;
-    const SbpProj* __restrict__ proj = J.proj;
-    const uint32_t* __restrict__ topm = J.topm;
-    int32_t* __restrict__ matchCur = J.matchCur;
-    int32_t* __restrict__ nmatches_out = J.nmatches;
-    struct { int checkOri; SiBounds bnd; } A = {J.checkOri, J.bnd};
-    uint32_t* occupied = (uint32_t*)sbsm;              /* nCur: mvpMapPoints[i2] with Observations() > 0 */
-    int32_t* ownerEntry = (int32_t*)(occupied + nCur); /* nCur: last log entry that wrote mvpMapPoints[i2] */
-    uint32_t* alog = (uint32_t*)(ownerEntry + nCur);   /* nLast: (query << 12 | i2), in order */
-    uint8_t* logBin = (uint8_t*)(alog + nLast);        /* nLast: rotation bin of a log entry */
-    uint32_t* kbuf = (uint32_t*)(sbsm + (((size_t)nCur * 8 + (size_t)nLast * 5 + 15) & ~(size_t)15)); /* 64 x M */
-    __shared__ int s_hist[SI_HISTO];
-    const int lane = threadIdx.x;
-    if (*J.needSeq == 0) return; /* k_sbp_resolve finished this job */
-    const float invW = __fdiv_rn((float)SI_GRID_COLS, __fsub_rn(A.bnd.maxX, A.bnd.minX));
-    const float invH = __fdiv_rn((float)SI_GRID_ROWS, __fsub_rn(A.bnd.maxY, A.bnd.minY));
-    const SiBounds wbnd = J.mode == 3 ? si_kf_bounds(A.bnd) : A.bnd;
-    for (int c = lane; c < nCur; c += 64) {
-        occupied[c] = occupied0 ? occupied0[c] : 0u;
-        ownerEntry[c] = -1;
-        matchCur[c] = -1;
-    }
-    if (lane < SI_HISTO) s_hist[lane] = 0;
-    __syncthreads();
-
-    int nlog = 0, nfb = 0;
-    for (int qb = 0; qb < nLast; qb += 64) {
-        const int nq = min(64, nLast - qb);
-        __syncthreads();
-        for (int i = lane; i < nq * M; i += 64) kbuf[i] = topm[(size_t)qb * M + i];
-        const uint32_t myflags = lane < nq ? flags[qb + lane] : 0u; /* lane tq holds query qb+tq's flags */
-        __syncthreads();
-        uint32_t keyN = lane < M ? kbuf[lane] : 0xFFFFFFFFu;
-        uint32_t occN = keyN != 0xFFFFFFFFu ? occupied[keyN & 0xFFF] : 0u;
-        for (int tq = 0; tq < nq; tq++) {
-            const uint32_t key = keyN, occ = occN;
-            if (tq + 1 < nq) {
-                keyN = lane < M ? kbuf[(tq + 1) * M + lane] : 0xFFFFFFFFu;
-                occN = keyN != 0xFFFFFFFFu ? occupied[keyN & 0xFFF] : 0u;
-            }
-            const bool valid = key != 0xFFFFFFFFu;
-            const unsigned long long mv = __ballot(valid), mk = __ballot(valid && !occ);
-            if (mv == 0) continue; /* vIndices2 empty, or every candidate failed an order-free gate */
-            uint32_t gBest;
-            if (mk) {
-                const int first = __builtin_amdgcn_readfirstlane(__ffsll((long long)mk) - 1);
-                gBest = (uint32_t)__builtin_amdgcn_readlane((int)key, first);
-            } else if (__popcll(mv) < M) {
-                continue; /* the list is complete and every entry is occupied: bestDist stays 256 */
-            } else {
-                nfb++;
-                gBest = sbp_full_scan(proj[qb + tq], curKps, uRight, nCur, mpDesc + (size_t)(qb + tq) * 32, curDesc,
-                                      occupied, A.bnd, wbnd, invW, invH, lane);
-                if (gBest == 0xFFFFFFFFu) continue;
-            }
-            if ((gBest >> 24) > thHigh) continue; /* bestDist <= TH_HIGH (ORBdist in the KeyFrame overload) */
-            const uint32_t i2 = gBest & 0xFFF;
-            const uint32_t fl = (uint32_t)__builtin_amdgcn_readlane((int)myflags, tq);
-            if (lane == 0) {
-                alog[nlog] = ((uint32_t)(qb + tq) << 12) | i2;
-                if (fl & 2) occupied[i2] = 1u; /* pMP->Observations() > 0: later queries skip i2 */
-            }
-            nlog++;
-            if ((fl & 2) && keyN != 0xFFFFFFFFu && (keyN & 0xFFF) == i2) occN = 1u;
-        }
-    }
-    __syncthreads();
-    if (fallbacks && lane == 0 && nfb) atomicAdd(fallbacks, nfb);
-    /* mvpMapPoints[bestIdx2] = pMP: the last writer stays */
-    for (int e = lane; e < nlog; e += 64) atomicMax(&ownerEntry[alog[e] & 0xFFF], e);
-    __syncthreads();
-    const float factor = 1.0f / SI_HISTO;
-    for (int e = lane; e < nlog; e += 64) {
-        const uint32_t le = alog[e];
-        const int q = (int)(le >> 12), i2 = (int)(le & 0xFFF);
-        if (ownerEntry[i2] == e) matchCur[i2] = q;
-        if (A.checkOri) {
-            float rot = __fsub_rn(lastKps[q].angle, curKps[i2].angle);
-            if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-            int bin = (int)roundf(__fmul_rn(rot, factor));
-            if (bin == SI_HISTO) bin = 0;
-            logBin[e] = (uint8_t)bin;
-            atomicAdd(&s_hist[bin], 1);
-        }
-    }
-    __syncthreads();
-    int removed = 0;
-    if (A.checkOri) {
-        int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0; /* ComputeThreeMaxima, fmatcher.cpp:2813-2854 */
-        for (int i = 0; i < SI_HISTO; i++) {
-            const int s = s_hist[i];
-            if (s > max1) {
-                max3 = max2; max2 = max1; max1 = s;
-                ind3 = ind2; ind2 = ind1; ind1 = i;
-            } else if (s > max2) {
-                max3 = max2; max2 = s;
-                ind3 = ind2; ind2 = i;
-            } else if (s > max3) {
-                max3 = s;
-                ind3 = i;
-            }
-        }
-        if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
-        else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) { ind3 = -1; }
-        /* every entry of a rejected bin clears mvpMapPoints[idx] and decrements nmatches (fmatcher.cpp:2668-2681) */
-        for (int e = lane; e < nlog; e += 64) {
-            const int b = logBin[e];
-            if (b != ind1 && b != ind2 && b != ind3) {
-                matchCur[alog[e] & 0xFFF] = -1;
-                removed++;
-            }
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) removed += __shfl_xor(removed, o, 64);
-    if (lane == 0) nmatches_out[0] = nlog - removed;
-}
-
-size_t vk_sbp_rank_lds(int nCur) { return (size_t)nCur * sizeof(SbpCand); }
-size_t vk_sbp_replay_lds(int nCur, int nLast) {
-    return (((size_t)nCur * 8 + (size_t)nLast * 5 + 15) & ~(size_t)15) + 64 * SI_MAX_M * 4;
-}
-size_t vk_sbp_scratch_bytes(int nLast, int M) { return (size_t)nLast * (sizeof(SbpProj) + 4 * (size_t)M); }
-size_t vk_sbp_proj_bytes(int nLast) { return (size_t)nLast * sizeof(SbpProj); }
-__global__ void k_sbpm_resolve(SbpJobs JS, int forceSeq); /* defined below */
-__global__ void k_fuse_rank(FuseArgsDev A);
-int vk_sbp_set_max_lds(size_t bytes) {
-    int rc = (int)hipFuncSetAttribute((const void*)k_sbp_resolve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (rc) return rc;
-    rc = (int)hipFuncSetAttribute((const void*)k_sbpm_resolve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (rc) return rc;
-    rc = (int)hipFuncSetAttribute((const void*)k_sbp_rank, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (rc) return rc;
-    rc = (int)hipFuncSetAttribute((const void*)k_fuse_rank, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (rc) return rc;
-    return (int)hipFuncSetAttribute((const void*)k_sbp_replay, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-
-/* ------------------------------------------------------------------------------------------------
- * SearchByProjection(Frame& F, const vector<MapPoint*>&, th, ...) (fmatcher.cpp:321-411): same ranking, but a
- * query now looks at its first TWO free candidates (best / second with their octaves, ratio test only when both
- * lie on the same level).  A query's proposal can therefore appear or vanish while the occupancy around it
- * changes, so the resolution is a plain fixpoint: every round rebuilds "lowest-index blocking query that chose
- * this keypoint" from the current choices and lets every query choose again; by induction on the query index the
- * unique fixpoint is the sequential result.  Same hand-over to a sequential wave when a list prefix runs out.
- * ---------------------------------------------------------------------------------------------- */
-#define SBPM_M 8
-__global__ void __launch_bounds__(SBP_RT)
-k_sbpm_resolve(SbpJobs JS, int forceSeq) {
-    extern __shared__ __align__(16) uint8_t sbsm[];
-    const SbpJobDev& J = JS.job[blockIdx.x];
-    const int M = min(JS.M, SBPM_M);
-    const int nLast = J.nLastPtr ? min(*J.nLastPtr, J.nLast) : J.nLast;
-    const int nCur = J.nCurPtr ? min(*J.nCurPtr, J.nCur) : J.nCur;
-    int32_t* holder = (int32_t*)sbsm;
-    int32_t* owner = holder + nCur;
-    uint8_t* oct = (uint8_t*)(owner + nCur);
-    __shared__ int s_changed, s_seq, s_nlog;
-    const int tid = threadIdx.x;
-    if (tid == 0) {
-        s_seq = forceSeq;
-        s_nlog = 0;
-        s_changed = 0;
-    }
-    for (int c = tid; c < nCur; c += SBP_RT) {
-        oct[c] = (uint8_t)J.curKps[c].octave;
-        owner[c] = -1;
-    }
-    uint32_t keys[SBP_QPT][SBPM_M];
-    int choice[SBP_QPT];
-    bool blocking[SBP_QPT], full[SBP_QPT];
-#pragma unroll
-    for (int k = 0; k < SBP_QPT; k++) {
-        const int q = tid + k * SBP_RT;
-        choice[k] = -1;
-        blocking[k] = q < nLast && (J.flags[q] & 2);
-        full[k] = true;
-#pragma unroll
-        for (int j = 0; j < SBPM_M; j++) {
-            keys[k][j] = (q < nLast && j < M) ? J.topm[(size_t)q * JS.M + j] : 0xFFFFFFFFu;
-            if (j < M && keys[k][j] == 0xFFFFFFFFu) full[k] = false;
-        }
-    }
-    __syncthreads();
-    for (int round = 0; round < 1024 && !s_seq; round++) {
-        for (int c = tid; c < nCur; c += SBP_RT) holder[c] = (J.occupied0 && J.occupied0[c]) ? -1 : 0x7FFFFFFF;
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < SBP_QPT; k++)
-            if (choice[k] >= 0 && blocking[k]) atomicMin(&holder[choice[k]], tid + k * SBP_RT);
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < SBP_QPT; k++) {
-            const int q = tid + k * SBP_RT;
-            if (keys[k][0] == 0xFFFFFFFFu) continue; /* no candidates at all */
-            int found = 0, best = -1, bd = 256, bl = -1, sd = 256, sl = -1;
-#pragma unroll
-            for (int j = 0; j < SBPM_M; j++) {
-                const uint32_t key = keys[k][j];
-                if (key == 0xFFFFFFFFu || found == 2) continue;
-                const int c = (int)(key & 0xFFF);
-                if (holder[c] < q) continue; /* held by an earlier query (or occupied from the start) */
-                if (found == 0) {
-                    best = c;
-                    bd = (int)(key >> 24);
-                    bl = oct[c];
-                } else {
-                    sd = (int)(key >> 24);
-                    sl = oct[c];
-                }
-                found++;
-            }
-            int nc = -1;
-            if (found == 0) {
-                if (full[k]) s_seq = 1; /* free candidates may exist beyond the prefix */
-            } else if (bd <= SBP_TH_HIGH) {
-                if (found == 2) {
-                    if (!(bl == sl && (float)bd > __fmul_rn(J.nnratio, (float)sd))) nc = best;
-                } else if (!full[k]) {
-                    nc = best; /* bestLevel2 stays -1 */
-                } else {
-                    uint32_t klast = 0xFFFFFFFFu;
-#pragma unroll
-                    for (int j = 0; j < SBPM_M; j++)
-                        if (j == M - 1) klast = keys[k][j];
-                    const int dlast = (int)(klast >> 24);
-                    if ((float)bd <= __fmul_rn(J.nnratio, (float)dlast)) nc = best; /* whatever the second is */
-                    else s_seq = 1;
-                }
-            }
-            if (nc != choice[k]) {
-                choice[k] = nc;
-                s_changed = 1;
-            }
-        }
-        __syncthreads();
-        const int ch = s_changed;
-        __syncthreads();
-        if (tid == 0) s_changed = 0;
-        if (!ch) break;
-        if (round == 1023 && tid == 0) s_seq = 1;
-        __syncthreads();
-    }
-    __syncthreads();
-    if (tid == 0) *J.needSeq = s_seq;
-    if (s_seq) return;
-#pragma unroll
-    for (int k = 0; k < SBP_QPT; k++)
-        if (choice[k] >= 0) {
-            atomicMax(&owner[choice[k]], tid + k * SBP_RT); /* F.mvpMapPoints[bestIdx] = pMP: last writer */
-            atomicAdd(&s_nlog, 1);
-        }
-    __syncthreads();
-    for (int c = tid; c < nCur; c += SBP_RT) J.matchCur[c] = owner[c];
-    if (tid == 0) J.nmatches[0] = s_nlog;
-}
-
-/* sequential cross-check / fallback of the same function: one wave, MapPoints in index order, every window
- * scanned in full (two smallest free keys by two wave reductions) */
-__global__ void __launch_bounds__(64)
-k_sbpm_replay(SbpJobs JS, int* fallbacks) {
-    extern __shared__ __align__(16) uint8_t sbsm[];
-    const SbpJobDev& J = JS.job[blockIdx.x];
-    if (*J.needSeq == 0) return;
-    const int nLast = J.nLastPtr ? min(*J.nLastPtr, J.nLast) : J.nLast;
-    const int nCur = J.nCurPtr ? min(*J.nCurPtr, J.nCur) : J.nCur;
-    uint32_t* occupied = (uint32_t*)sbsm;
-    const int lane = threadIdx.x;
-    const SiBounds bnd = J.bnd;
-    const float invW = __fdiv_rn((float)SI_GRID_COLS, __fsub_rn(bnd.maxX, bnd.minX));
-    const float invH = __fdiv_rn((float)SI_GRID_ROWS, __fsub_rn(bnd.maxY, bnd.minY));
-    for (int c = lane; c < nCur; c += 64) {
-        occupied[c] = J.occupied0 ? J.occupied0[c] : 0u;
-        J.matchCur[c] = -1;
-    }
-    __syncthreads();
-    int nm = 0, nscan = 0;
-    for (int q = 0; q < nLast; q++) {
-        const SbpProj pr = J.proj[q];
-        if (!pr.valid) continue;
-        nscan++;
-        const SiWindow win = si_window_b(pr.u, pr.v, pr.radius, bnd, invW, invH);
-        if (win.empty) continue;
-        const uint4 da = ((const uint4*)J.mpDesc)[(size_t)q * 2], db = ((const uint4*)J.mpDesc)[(size_t)q * 2 + 1];
-        uint32_t k1 = 0xFFFFFFFFu, k2 = 0xFFFFFFFFu; /* this lane's two smallest free keys */
-        for (int c = lane; c < nCur; c += 64) {
-            bool ing;
-            const SbpCand cd = sbp_make_cand(J.curKps[c], J.uRight ? J.uRight[c] : -1.f, bnd, invW, invH, &ing);
-            if (!ing || occupied[c] || !sbp_candidate_ok(cd, win, pr)) continue;
-            const uint4 ta = ((const uint4*)J.curDesc)[(size_t)c * 2], tb = ((const uint4*)J.curDesc)[(size_t)c * 2 + 1];
-            const uint32_t key = (min(si_hamming(da, db, ta, tb), 255u) << 24) | ((uint32_t)cd.cell << 12) | (uint32_t)c;
-            if (key < k1) { k2 = k1; k1 = key; }
-            else if (key < k2) k2 = key;
-        }
-        const uint32_t g1 = wave_min_u32(k1);
-        if (g1 == 0xFFFFFFFFu) continue;
-        const uint32_t g2 = wave_min_u32(k1 == g1 ? k2 : k1);
-        const int bd = (int)(g1 >> 24), best = (int)(g1 & 0xFFF);
-        if (bd > SBP_TH_HIGH) continue;
-        const int bl = J.curKps[best].octave;
-        bool accept = true;
-        if (g2 != 0xFFFFFFFFu) {
-            const int sd = (int)(g2 >> 24), sl = J.curKps[g2 & 0xFFF].octave;
-            if (bl == sl && (float)bd > __fmul_rn(J.nnratio, (float)sd)) accept = false;
-        }
-        if (!accept) continue;
-        if (lane == 0) {
-            J.matchCur[best] = q;
-            if (J.flags[q] & 2) occupied[best] = 1u;
-        }
-        nm++;
-        __syncthreads();
-    }
-    __syncthreads();
-    if (lane == 0) {
-        J.nmatches[0] = nm;
-        if (fallbacks && nscan) atomicAdd(fallbacks, nscan);
-    }
-}
-
-size_t vk_sbpm_resolve_lds(int nCur) { return (size_t)nCur * 9 + 16; }
-
-size_t vk_sbp_resolve_lds(int nCur) { return (size_t)nCur * 8; }
-
-void vk_search_by_projection(hipStream_t st, const SbpJobs& JS, int njobs, int maxLast, int maxCur, int* fallbacks,
-                             int forceSeq) {
-    if (njobs <= 0) return;
-    if (maxLast > 0)
-        hipLaunchKernelGGL(k_sbp_rank, dim3((maxLast + SBP_QPB - 1) / SBP_QPB, njobs), dim3(256),
-                           vk_sbp_rank_lds(maxCur), st, JS);
-    if (JS.job[0].mode == 1) {
-        hipLaunchKernelGGL(k_sbpm_resolve, dim3(njobs), dim3(SBP_RT), vk_sbpm_resolve_lds(maxCur), st, JS, forceSeq);
-        hipLaunchKernelGGL(k_sbpm_replay, dim3(njobs), dim3(64), (size_t)maxCur * 4, st, JS, fallbacks);
-        return;
-    }
-    hipLaunchKernelGGL(k_sbp_resolve, dim3(njobs), dim3(SBP_RT), vk_sbp_resolve_lds(maxCur), st, JS, forceSeq);
-    hipLaunchKernelGGL(k_sbp_replay, dim3(njobs), dim3(64), vk_sbp_replay_lds(maxCur, maxLast), st, JS, fallbacks);
-}
-
-/* ------------------------------------------------------------------------------------------------
- * Frame::UnprojectStereo (frame.cpp:1023-1037) for every left keypoint of up to VSLAM_MAX_SBP_JOBS stereo
- * pairs: z = mvDepth[i] > 0  ->  x3Dc = ((u-cx)*z*invfx, (v-cy)*z*invfy, z), x3Dw = mRwc*x3Dc + mOw (one
- * cv::gemm, see sbp_gemm_row).  These are the points UpdateLastFrame turns into (temporal) MapPoints for
- * TrackWithMotionModel, i.e. the last-frame side of SearchByProjection; flags = has-a-point | observations.
- * ---------------------------------------------------------------------------------------------- */
-__global__ void __launch_bounds__(256)
-k_unproject_stereo(UnprojJobs U) {
-    const UnprojJob& J = U.job[blockIdx.y];
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    const int n = min(*J.nPtr, U.cap);
-    if (i >= U.cap) return;
-    float X = 0.f, Y = 0.f, Z = 0.f;
-    uint8_t fl = 0;
-    if (i < n) {
-        const float z = J.depth[i];
-        if (z > 0.f) {
-            const vslam_kp k = J.kps[i];
-            const float x = __fmul_rn(__fmul_rn(__fsub_rn(k.x, U.cx), z), U.invfx);
-            const float y = __fmul_rn(__fmul_rn(__fsub_rn(k.y, U.cy), z), U.invfy);
-            X = sbp_gemm_row(J.Twc + 0, x, y, z, J.Twc[3], U.gemmFloat);
-            Y = sbp_gemm_row(J.Twc + 4, x, y, z, J.Twc[7], U.gemmFloat);
-            Z = sbp_gemm_row(J.Twc + 8, x, y, z, J.Twc[11], U.gemmFloat);
-            fl = (uint8_t)(1 | (U.observations ? 2 : 0));
-        }
-    }
-    J.x3Dw[3 * i] = X;
-    J.x3Dw[3 * i + 1] = Y;
-    J.x3Dw[3 * i + 2] = Z;
-    J.flags[i] = fl;
-}
-
-void vk_unproject_stereo(hipStream_t st, const UnprojJobs& U, int njobs) {
-    if (njobs <= 0) return;
-    hipLaunchKernelGGL(k_unproject_stereo, dim3((U.cap + 255) / 256, njobs), dim3(256), 0, st, U);
-}
-
-/* ------------------------------------------------------------------------------------------------
- * The search half of FMatcher::Fuse (fmatcher.cpp:1918-2119 with bRight = false; Sim3 overload :2121-2243):
- * per MapPoint  Rcw*p + tcw (one cv::gemm, sbp_gemm_row), depth >= 0, Pinhole::project, KeyFrame::IsInImage,
- * cv::norm(p - Ow) inside the scale-invariance range, viewing angle (cv::Mat::dot, both accumulate in double),
- * MapPoint::PredictScale (mappoint.cpp:506-521: ceil(logf(max/dist) / mfLogScaleFactor), glibc logf), radius =
- * th * scale[level], KeyFrame::GetFeaturesInArea (keyframe.cpp:656-699), level gate, chi2 gate (7.8 with a right
- * coordinate, 5.99 without; not in the Sim3 overload), then the least Hamming distance, first of the window order
- * wins: key = dist << 24 | cell << 12 | index -> wave min.  Nothing here depends on other MapPoints; the map
- * mutation that follows in the reference (Replace / AddObservation / vpReplacePoint) stays with the caller.
- * One wave per MapPoint, the KeyFrame's keypoints in LDS as for SearchByProjection.
- * ---------------------------------------------------------------------------------------------- */
-#define FUSE_QPB 16
-__global__ void __launch_bounds__(256)
-k_fuse_rank(FuseArgsDev A) {
-    extern __shared__ __align__(16) uint8_t sbsm[];
-    SbpCand* cand = (SbpCand*)sbsm;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const SiBounds bnd = A.bnd;               /* Frame::mnMinX..: the cells of the grid the KeyFrame copied */
-    const SiBounds kbnd = si_kf_bounds(bnd);  /* the KeyFrame's integer copy (keyframe.cpp:44): window origin, IsInImage */
-    const float invW = __fdiv_rn((float)SI_GRID_COLS, __fsub_rn(bnd.maxX, bnd.minX));
-    const float invH = __fdiv_rn((float)SI_GRID_ROWS, __fsub_rn(bnd.maxY, bnd.minY));
-    for (int i = tid; i < A.nKF; i += 256) {
-        bool ing;
-        cand[i] = sbp_make_cand(A.kfKps[i], A.kfURight[i], bnd, invW, invH, &ing);
-    }
-    __syncthreads();
-    for (int q = blockIdx.x * FUSE_QPB + wave; q < min(A.nPoints, (int)(blockIdx.x + 1) * FUSE_QPB); q += 4) {
-        const FusePoint mp = A.pts[q];
-        uint32_t best = 0xFFFFFFFFu;
-        bool go = mp.valid != 0;
-        float u = 0.f, v = 0.f, ur = 0.f, radius = 0.f;
-        int level = 0;
-        if (go && A.sim3 == 2) { /* SearchBySim3, one direction (fmatcher.cpp:2301-2332 / :2381-2412) */
-            const float x1 = sbp_gemm_row(A.Rcw + 0, mp.pos[0], mp.pos[1], mp.pos[2], A.tcw[0], A.gemmFloat);
-            const float y1 = sbp_gemm_row(A.Rcw + 3, mp.pos[0], mp.pos[1], mp.pos[2], A.tcw[1], A.gemmFloat);
-            const float z1 = sbp_gemm_row(A.Rcw + 6, mp.pos[0], mp.pos[1], mp.pos[2], A.tcw[2], A.gemmFloat);
-            const float xc = sbp_gemm_row(A.Rb + 0, x1, y1, z1, A.tb[0], A.gemmFloat);
-            const float yc = sbp_gemm_row(A.Rb + 3, x1, y1, z1, A.tb[1], A.gemmFloat);
-            const float zc = sbp_gemm_row(A.Rb + 6, x1, y1, z1, A.tb[2], A.gemmFloat);
-            go = !(zc < 0.0f);
-            if (go) {
-                const float invz = (float)__ddiv_rn(1.0, (double)zc); /* const float invz = 1.0/z */
-                u = __fadd_rn(__fmul_rn(A.fx, __fmul_rn(xc, invz)), A.cx);
-                v = __fadd_rn(__fmul_rn(A.fy, __fmul_rn(yc, invz)), A.cy);
-                go = u >= kbnd.minX && u < kbnd.maxX && v >= kbnd.minY && v < kbnd.maxY; /* KeyFrame::IsInImage */
-            }
-            if (go) {
-                double n2 = __dmul_rn((double)xc, (double)xc); /* cv::norm(p3Dc2) */
-                n2 = __dadd_rn(n2, __dmul_rn((double)yc, (double)yc));
-                n2 = __dadd_rn(n2, __dmul_rn((double)zc, (double)zc));
-                const float dist3D = (float)__dsqrt_rn(n2);
-                go = !(dist3D < mp.minDistance || dist3D > mp.maxDistance);
-                if (go) {
-                    const float lv = ceilf(__fdiv_rn(vslam_trig::glibc_logf(__fdiv_rn(mp.maxDistance, dist3D)), A.logScaleFactor));
-                    level = (lv != lv || lv >= 2147483648.0f || lv < 0.f) ? 0 : min((int)lv, A.nlevels - 1);
-                    radius = __fmul_rn(A.th, A.scale[level]);
-                }
-            }
-        } else if (go) { /* wave-uniform */
-            const float xc = sbp_gemm_row(A.Rcw + 0, mp.pos[0], mp.pos[1], mp.pos[2], A.tcw[0], A.gemmFloat);
-            const float yc = sbp_gemm_row(A.Rcw + 3, mp.pos[0], mp.pos[1], mp.pos[2], A.tcw[1], A.gemmFloat);
-            const float zc = sbp_gemm_row(A.Rcw + 6, mp.pos[0], mp.pos[1], mp.pos[2], A.tcw[2], A.gemmFloat);
-            go = !(zc < 0.0f);
-            if (go) {
-                const float invz = __fdiv_rn(1.0f, zc);
-                u = __fadd_rn(__fdiv_rn(__fmul_rn(A.fx, xc), zc), A.cx);
-                v = __fadd_rn(__fdiv_rn(__fmul_rn(A.fy, yc), zc), A.cy);
-                go = u >= kbnd.minX && u < kbnd.maxX && v >= kbnd.minY && v < kbnd.maxY; /* KeyFrame::IsInImage */
-                ur = __fsub_rn(u, __fmul_rn(A.bf, invz));
-            }
-            if (go) {
-                const float p0 = __fsub_rn(mp.pos[0], A.Ow[0]), p1 = __fsub_rn(mp.pos[1], A.Ow[1]),
-                            p2 = __fsub_rn(mp.pos[2], A.Ow[2]);
-                double n2 = __dmul_rn((double)p0, (double)p0);
-                n2 = __dadd_rn(n2, __dmul_rn((double)p1, (double)p1));
-                n2 = __dadd_rn(n2, __dmul_rn((double)p2, (double)p2));
-                const float dist3D = (float)__dsqrt_rn(n2);
-                go = !(dist3D < mp.minDistance || dist3D > mp.maxDistance);
-                if (go) {
-                    double dot = __dmul_rn((double)p0, (double)mp.normal[0]);
-                    dot = __dadd_rn(dot, __dmul_rn((double)p1, (double)mp.normal[1]));
-                    dot = __dadd_rn(dot, __dmul_rn((double)p2, (double)mp.normal[2]));
-                    go = !(dot < __dmul_rn(0.5, (double)dist3D));
-                }
-                if (go) {
-                    const float ratio = __fdiv_rn(mp.maxDistance, dist3D);
-                    /* NaN and out-of-range quotients convert to INT_MIN on the reference's x86-64 build
-                     * (cvttss2si) and so clamp to level 0 */
-                    const float lv = ceilf(__fdiv_rn(vslam_trig::glibc_logf(ratio), A.logScaleFactor));
-                    level = (lv != lv || lv >= 2147483648.0f || lv < 0.f) ? 0 : min((int)lv, A.nlevels - 1);
-                    radius = __fmul_rn(A.th, A.scale[level]);
-                }
-            }
-        }
-        if (go) {
-            const SiWindow win = si_window_b(u, v, radius, kbnd, invW, invH);
-            if (!win.empty) {
-                const uint4 da = ((const uint4*)A.mpDesc)[(size_t)q * 2], db = ((const uint4*)A.mpDesc)[(size_t)q * 2 + 1];
-                for (int c = lane; c < A.nKF; c += 64) {
-                    const SbpCand cd = cand[c];
-                    if (cd.cell == 0xFFFF) continue;
-                    const int gx = cd.cell >> 6, gy = cd.cell & 63;
-                    if (gx < win.minX || gx > win.maxX || gy < win.minY || gy > win.maxY) continue;
-                    const float ex = __fsub_rn(cd.x, u), ey = __fsub_rn(cd.y, v);
-                    if (!(fabsf(ex) < radius && fabsf(ey) < radius)) continue;
-                    const int kpLevel = cd.octave;
-                    if (kpLevel < level - 1 || kpLevel > level) continue;
-                    if (!A.sim3) {
-                        /* ex = uv.x - kpx in the reference; only its square is used */
-                        const float is2 = A.invSigma2[min(kpLevel, A.nlevels - 1)];
-                        const float exx = __fsub_rn(u, cd.x), eyy = __fsub_rn(v, cd.y);
-                        if (cd.uRight >= 0.f) {
-                            const float er = __fsub_rn(ur, cd.uRight);
-                            const float e2 = __fadd_rn(__fadd_rn(__fmul_rn(exx, exx), __fmul_rn(eyy, eyy)), __fmul_rn(er, er));
-                            if ((double)__fmul_rn(e2, is2) > 7.8) continue;
-                        } else {
-                            const float e2 = __fadd_rn(__fmul_rn(exx, exx), __fmul_rn(eyy, eyy));
-                            if ((double)__fmul_rn(e2, is2) > 5.99) continue;
-                        }
-                    }
-                    const uint4 ta = ((const uint4*)A.kfDesc)[(size_t)c * 2], tb = ((const uint4*)A.kfDesc)[(size_t)c * 2 + 1];
-                    best = min(best, (min(si_hamming(da, db, ta, tb), 255u) << 24) | ((uint32_t)cd.cell << 12) | (uint32_t)c);
-                }
-            }
-        }
-        const uint32_t g = wave_min_u32(best);
-        if (lane == 0) {
-            A.bestIdx[q] = g == 0xFFFFFFFFu ? -1 : (int32_t)(g & 0xFFFu);
-            A.bestDist[q] = g == 0xFFFFFFFFu ? 256 : (int32_t)(g >> 24);
-        }
-    }
-}
-
-void vk_fuse_search(hipStream_t st, const FuseArgsDev& A) {
-    if (A.nPoints <= 0) return;
-    hipLaunchKernelGGL(k_fuse_rank, dim3((A.nPoints + FUSE_QPB - 1) / FUSE_QPB), dim3(256), vk_sbp_rank_lds(A.nKF), st, A);
-}

@@ -1,5 +1,5 @@
 /* vslam_kernels.h -- launch wrappers implemented in the kernel files (vslam_image_kernels.hip, vslam_kernels.hip,
- * vslam_octree_kernel.hip, vslam_match_kernels.hip, vslam_init_kernel.hip).  T: the context's resolved switches
+ * vslam_octree_kernel.hip, vslam_match_kernels.hip, vslam_init_kernel.hip, vslam_projection_kernels.hip).  T: the context's resolved switches
  * (vslam_tuning.h); the launchers read their A/B knobs from it, never from the environment. */
 #ifndef VSLAM_KERNELS_H
 #define VSLAM_KERNELS_H

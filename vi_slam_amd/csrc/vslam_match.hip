@@ -1,6 +1,7 @@
 /* vslam_match.hip -- FMatcher::SearchForInitialization: the whole matcher on the device (k_si_*), or the distances from
  * the device and the order-dependent part replayed on the host; the grid-bounds setters of the projection matchers;
- * the dbg_* entry points of the tests. */
+ * the dbg_* entry points of the tests; the brute-force descriptor matchers (vslam_hamming_*, the fisheye stereo
+ * candidates). */
 #include "vslam_ctx.h"
 
 /* ------------------------------------------------------------------ SearchForInitialization on the device */
@@ -440,5 +441,167 @@ extern "C" int vslam_dbg_search_init_replay_stats(vslam_fe* fe, int* rounds, int
     if (rounds) *rounds = v[1];
     if (queries) *queries = v[2];
     if (pairs) *pairs = v[3];
+    return VSLAM_OK;
+}
+
+/* ------------------------------------------------------------------ brute-force descriptor matching (k_hamming_*) */
+extern "C" int vslam_hamming_top2_batch(vslam_fe* fe, int nprob, const uint8_t* const* dev_q, const int32_t* nq,
+                                        const uint8_t* const* dev_t, const int32_t* nt, int32_t* const* idx2,
+                                        int32_t* const* dist2) {
+    if (!fe || nprob < 0 || nprob > VSLAM_MAX_TOP2_JOBS || (nprob && (!dev_q || !nq || !dev_t || !nt || !idx2 || !dist2))) {
+        g_err = "invalid arguments";
+        return VSLAM_ERR_INVALID;
+    }
+    Top2Jobs J;
+    memset(&J, 0, sizeof(J));
+    size_t rows = 0;
+    int max_nq = 0, max_nt = 0;
+    for (int p = 0; p < nprob; p++) {
+        if (nq[p] < 0 || nt[p] < 0 || nt[p] > 65535 || (nq[p] && (!dev_q[p] || !idx2[p] || !dist2[p])) || (nt[p] && !dev_t[p])) {
+            g_err = "invalid arguments";
+            return VSLAM_ERR_INVALID;
+        }
+        J.job[p].q = (const uint32_t*)dev_q[p];
+        J.job[p].t = (const uint32_t*)dev_t[p];
+        J.job[p].nq = nq[p];
+        J.job[p].nt = nt[p];
+        J.job[p].row0 = (uint32_t)rows;
+        rows += (size_t)nq[p];
+        max_nq = std::max(max_nq, nq[p]);
+        max_nt = std::max(max_nt, nt[p]);
+    }
+    if (rows == 0) return VSLAM_OK;
+    HIPCHK(hipSetDevice(fe->p.device));
+    const int nsplit = vk_hamming_top2_batch_split(nprob, max_nq, max_nt);
+    int rc;
+    if ((rc = vslam_ensure((void**)&fe->d_part, &fe->part_bytes, rows * nsplit * 8))) return rc;
+    if (fe->top2_cap < rows) {
+        hipFree(fe->d_idx2);
+        hipFree(fe->d_dist2);
+        fe->d_idx2 = fe->d_dist2 = nullptr;
+        fe->top2_cap = 0;
+        HIPCHK(hipMalloc((void**)&fe->d_idx2, rows * 8));
+        HIPCHK(hipMalloc((void**)&fe->d_dist2, rows * 8));
+        fe->top2_cap = rows;
+    }
+    if ((rc = vslam_ensure_pinned(&fe->h_top2, &fe->h_top2_bytes, rows * 16))) return rc;
+    /* a split that lies past a problem's last tile, or a problem without train descriptors, writes nothing: "missing" */
+    HIPCHK(hipMemsetAsync(fe->d_part, 0xFF, rows * nsplit * 8, fe->stream));
+    vk_hamming_top2_batch(fe->stream, J, nprob, max_nq, (int)rows, nsplit, fe->d_part, fe->d_idx2, fe->d_dist2);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(fe->h_top2, fe->d_idx2, rows * 8, hipMemcpyDeviceToHost, fe->stream));
+    HIPCHK(hipMemcpyAsync(fe->h_top2 + rows * 8, fe->d_dist2, rows * 8, hipMemcpyDeviceToHost, fe->stream));
+    HIPCHK(vslam_stream_wait(fe->stream));
+    for (int p = 0; p < nprob; p++) {
+        if (!nq[p]) continue;
+        memcpy(idx2[p], fe->h_top2 + (size_t)J.job[p].row0 * 8, (size_t)nq[p] * 8);
+        memcpy(dist2[p], fe->h_top2 + rows * 8 + (size_t)J.job[p].row0 * 8, (size_t)nq[p] * 8);
+    }
+    return VSLAM_OK;
+}
+
+/* one problem = a batch of one (k_hamming_top2_batch splits the train set over as many workgroups as fill the GPU) */
+extern "C" int vslam_hamming_top2(vslam_fe* fe, const uint8_t* dev_q, int nq, const uint8_t* dev_t, int nt,
+                                  int32_t* idx2, int32_t* dist2) {
+    if (!fe || nq < 0 || nt < 0 || nt > 65535 || (nq && (!dev_q || !idx2 || !dist2)) || (nt && !dev_t)) {
+        g_err = "invalid arguments";
+        return VSLAM_ERR_INVALID;
+    }
+    if (nq == 0) return VSLAM_OK;
+    const int32_t nq1 = nq, nt1 = nt;
+    return vslam_hamming_top2_batch(fe, 1, &dev_q, &nq1, &dev_t, &nt1, &idx2, &dist2);
+}
+
+/* enqueue-only form for profilers and pipelines: results stay in the context's device arrays (rows back to back) */
+extern "C" int vslam_hamming_top2_batch_dev_async(vslam_fe* fe, int nprob, const uint8_t* const* dev_q, const int32_t* nq,
+                                                  const uint8_t* const* dev_t, const int32_t* nt) {
+    if (!fe || nprob <= 0 || nprob > VSLAM_MAX_TOP2_JOBS || !dev_q || !nq || !dev_t || !nt) {
+        g_err = "invalid arguments";
+        return VSLAM_ERR_INVALID;
+    }
+    Top2Jobs J;
+    memset(&J, 0, sizeof(J));
+    size_t rows = 0;
+    int max_nq = 0, max_nt = 0;
+    for (int p = 0; p < nprob; p++) {
+        if (nq[p] < 0 || nt[p] < 0 || nt[p] > 65535 || (nq[p] && !dev_q[p]) || (nt[p] && !dev_t[p])) {
+            g_err = "invalid arguments";
+            return VSLAM_ERR_INVALID;
+        }
+        J.job[p].q = (const uint32_t*)dev_q[p];
+        J.job[p].t = (const uint32_t*)dev_t[p];
+        J.job[p].nq = nq[p];
+        J.job[p].nt = nt[p];
+        J.job[p].row0 = (uint32_t)rows;
+        rows += (size_t)nq[p];
+        max_nq = std::max(max_nq, nq[p]);
+        max_nt = std::max(max_nt, nt[p]);
+    }
+    if (rows == 0) return VSLAM_OK;
+    HIPCHK(hipSetDevice(fe->p.device));
+    const int nsplit = vk_hamming_top2_batch_split(nprob, max_nq, max_nt);
+    if (fe->part_bytes < rows * nsplit * 8 || fe->top2_cap < rows) { /* sized by a previous vslam_hamming_top2_batch */
+        g_err = "vslam_hamming_top2_batch_dev_async: call vslam_hamming_top2_batch with these sizes first (it allocates)";
+        return VSLAM_ERR_INVALID;
+    }
+    HIPCHK(hipMemsetAsync(fe->d_part, 0xFF, rows * nsplit * 8, fe->stream));
+    vk_hamming_top2_batch(fe->stream, J, nprob, max_nq, (int)rows, nsplit, fe->d_part, fe->d_idx2, fe->d_dist2);
+    HIPCHK(hipGetLastError());
+    return VSLAM_OK;
+}
+
+/* Frame::ComputeStereoFishEyeMatches (frame.cpp:1149-1174), the descriptor half: BFmatcher.knnMatch(left rows
+ * [mono_left, n_left), right rows [mono_right, n_right), k = 2) + Lowe's ratio test.  What follows in the reference --
+ * KannalaBrandt8::TriangulateMatches per surviving pair (:1176-1188) -- is the camera model's and stays with the caller. */
+extern "C" int vslam_stereo_fisheye_candidates(vslam_fe* fe, const uint8_t* dev_desc_left, int n_left, int mono_left,
+                                               const uint8_t* dev_desc_right, int n_right, int mono_right,
+                                               int32_t* left_to_right, int32_t* best_dist, int32_t* second_dist,
+                                               int* n_candidates) {
+    if (!fe || !left_to_right || n_left < 0 || n_right < 0 || mono_left < 0 || mono_right < 0 || mono_left > n_left ||
+        mono_right > n_right || (n_left && !dev_desc_left) || (n_right && !dev_desc_right)) {
+        g_err = "invalid arguments";
+        return VSLAM_ERR_INVALID;
+    }
+    for (int i = 0; i < n_left; i++) {
+        left_to_right[i] = -1;
+        if (best_dist) best_dist[i] = -1;
+        if (second_dist) second_dist[i] = -1;
+    }
+    if (n_candidates) *n_candidates = 0;
+    const int nq = n_left - mono_left, nt = n_right - mono_right;
+    if (nq == 0) return VSLAM_OK;
+    std::vector<int32_t> idx2((size_t)nq * 2), dist2((size_t)nq * 2);
+    int rc = vslam_hamming_top2(fe, dev_desc_left + (size_t)mono_left * 32, nq, dev_desc_right + (size_t)mono_right * 32, nt,
+                                idx2.data(), dist2.data());
+    if (rc != VSLAM_OK) return rc;
+    int nc = 0;
+    for (int q = 0; q < nq; q++) {
+        if (idx2[2 * q] < 0 || idx2[2 * q + 1] < 0) continue; /* (*it).size() >= 2 */
+        /* DMatch::distance is a float; `distance * 0.7` is float x double: the comparison happens in double */
+        const float d0 = (float)dist2[2 * q], d1 = (float)dist2[2 * q + 1];
+        if (!((double)d0 < (double)d1 * 0.7)) continue;
+        left_to_right[q + mono_left] = idx2[2 * q] + mono_right;
+        if (best_dist) best_dist[q + mono_left] = dist2[2 * q];
+        if (second_dist) second_dist[q + mono_left] = dist2[2 * q + 1];
+        nc++;
+    }
+    if (n_candidates) *n_candidates = nc; /* the reference's descMatches */
+    return VSLAM_OK;
+}
+
+extern "C" int vslam_hamming_matrix(vslam_fe* fe, const uint8_t* dev_q, int nq, const uint8_t* dev_t, int nt,
+                                    uint8_t* out) {
+    if (!fe || nq < 0 || nt < 0 || (nq && nt && (!dev_q || !dev_t || !out))) {
+        g_err = "invalid arguments";
+        return VSLAM_ERR_INVALID;
+    }
+    if (nq == 0 || nt == 0) return VSLAM_OK;
+    HIPCHK(hipSetDevice(fe->p.device));
+    int rc;
+    if ((rc = vslam_ensure((void**)&fe->d_dmat, &fe->dmat_bytes, (size_t)nq * nt))) return rc;
+    vk_hamming_matrix(fe->stream, dev_q, nq, dev_t, nt, fe->d_dmat);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, fe->d_dmat, (size_t)nq * nt, hipMemcpyDeviceToHost, fe->stream));
+    HIPCHK(vslam_stream_wait(fe->stream));
     return VSLAM_OK;
 }

@@ -1,0 +1,255 @@
+/* vslam_matchdev.h -- the reference arithmetic that the matchers share, each thing once.
+ *
+ * The first part is host/device text (VSLAM_HD): the rotation histogram of every FMatcher search, cv::norm / cv::Mat::dot
+ * of a 3-vector and MapPoint::PredictScale.  The kernels, vslam_frustum.h and the host replay of vslam_host.cpp (CPU
+ * tests) run the same lines.  The second part is device only: the Frame grid window, the match key, and the pieces of
+ * the SearchByProjection family that more than one kernel file or kernel needs.
+ *
+ * Contraction: on the device every operation goes through the _rn intrinsics; host builds rely on -ffp-contract=off
+ * (vi_slam_amd/csrc/Makefile), so plain `*` there equals __fmul_rn here.
+ *
+ * Results come back by value throughout: a helper that hands three indices back through int& parameters puts them into
+ * scratch memory on gfx950 (16 bytes per lane in k_si_replay, k_sbp_resolve, k_sbp_replay), __forceinline__ or not.
+ */
+#ifndef VSLAM_MATCHDEV_H
+#define VSLAM_MATCHDEV_H
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#endif
+#include <math.h>
+#include <stdint.h>
+
+#include "vslam_trig.h"
+
+#define VSLAM_HISTO_LENGTH 30 /* FMatcher::HISTO_LENGTH */
+
+namespace vslam_md {
+
+VSLAM_HD float fmul(float a, float b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __fmul_rn(a, b);
+#else
+    return a * b;
+#endif
+}
+VSLAM_HD float fadd(float a, float b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __fadd_rn(a, b);
+#else
+    return a + b;
+#endif
+}
+VSLAM_HD float fsub(float a, float b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __fsub_rn(a, b);
+#else
+    return a - b;
+#endif
+}
+VSLAM_HD float fdvd(float a, float b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __fdiv_rn(a, b);
+#else
+    return a / b;
+#endif
+}
+VSLAM_HD double dmul(double a, double b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __dmul_rn(a, b);
+#else
+    return a * b;
+#endif
+}
+VSLAM_HD double dadd(double a, double b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __dadd_rn(a, b);
+#else
+    return a + b;
+#endif
+}
+/* a0*b0 + a1*b1 + a2*b2 accumulated in double, in index order */
+VSLAM_HD double dot3_f64(float a0, float a1, float a2, float b0, float b1, float b2) {
+    double s = dmul((double)a0, (double)b0);
+    s = dadd(s, dmul((double)a1, (double)b1));
+    return dadd(s, dmul((double)a2, (double)b2));
+}
+/* cv::norm of a 3-vector (Matx31f or a 3x1 cv::Mat): squares accumulated in double, double sqrt, rounded to float */
+VSLAM_HD float norm3(float a, float b, float c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (float)__dsqrt_rn(dot3_f64(a, b, c, a, b, c));
+#else
+    return (float)sqrt(dot3_f64(a, b, c, a, b, c));
+#endif
+}
+/* cv::Mat::dot of two 3x1 float matrices: accumulated in double (the KeyFrame / Sim3 / Fuse viewing-angle gates) */
+VSLAM_HD double dot3_mat(float p0, float p1, float p2, const float* n) { return dot3_f64(p0, p1, p2, n[0], n[1], n[2]); }
+/* one row of a Matx product, or Matx::dot: FLOAT accumulation from zero (Frame::isInFrustum) */
+VSLAM_HD float dot3_matx(const float* r, float x0, float x1, float x2) {
+    float s = 0.0f;
+    s = fadd(s, fmul(r[0], x0));
+    s = fadd(s, fmul(r[1], x1));
+    s = fadd(s, fmul(r[2], x2));
+    return s;
+}
+
+/* MapPoint::PredictScale (mappoint.cpp:506-538): ceil(logf(max / dist) / mfLogScaleFactor) with glibc's logf.  NaN and
+ * out-of-range quotients convert to INT_MIN on the reference's x86-64 build (cvttss2si) and so clamp to level 0. */
+VSLAM_HD int predict_level(float maxDist, float dist, float logScaleFactor, int nlevels) {
+    const float lv = ceilf(fdvd(vslam_trig::glibc_logf(fdvd(maxDist, dist)), logScaleFactor));
+    if (lv != lv || lv >= 2147483648.0f || lv < 0.f) return 0;
+    const int level = (int)lv;
+    return level > nlevels - 1 ? nlevels - 1 : level;
+}
+
+/* the rotation-histogram bin of a match (fmatcher.cpp:1068-1075 and its copies in every search): angles in degrees */
+VSLAM_HD int rot_bin(float angle1, float angle2, int L) {
+    float rot = fsub(angle1, angle2);
+    if (rot < 0.0f) rot = fadd(rot, 360.0f);
+    int bin = (int)roundf(fmul(rot, fdvd(1.0f, (float)L)));
+    if (bin == L) bin = 0;
+    return bin;
+}
+
+/* ComputeThreeMaxima (fmatcher.cpp:2813-2854): the three fullest bins, -1 where a bin holds under a tenth of the fullest */
+struct ThreeMaxima {
+    int ind1, ind2, ind3;
+};
+VSLAM_HD ThreeMaxima three_maxima(const int* histo, int L) {
+    int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;
+    for (int i = 0; i < L; i++) {
+        const int s = histo[i];
+        if (s > max1) {
+            max3 = max2; max2 = max1; max1 = s;
+            ind3 = ind2; ind2 = ind1; ind1 = i;
+        } else if (s > max2) {
+            max3 = max2; max2 = s;
+            ind3 = ind2; ind2 = i;
+        } else if (s > max3) {
+            max3 = s;
+            ind3 = i;
+        }
+    }
+    if ((float)max2 < fmul(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
+    else if ((float)max3 < fmul(0.1f, (float)max1)) { ind3 = -1; }
+    return ThreeMaxima{ind1, ind2, ind3};
+}
+VSLAM_HD bool keeps_bin(const ThreeMaxima& m, int bin) { return bin == m.ind1 || bin == m.ind2 || bin == m.ind3; }
+
+} // namespace vslam_md
+
+#if defined(__HIPCC__)
+#include "vslam_device.h"
+
+#define SI_GRID_COLS 64 /* FRAME_GRID_COLS, frame.h:42 */
+#define SI_GRID_ROWS 48 /* FRAME_GRID_ROWS, frame.h:43 */
+#define SI_MAX_M 16     /* longest sorted prefix a ranking kernel keeps per query */
+
+/* Frame grid (frame.cpp:322-323, 746-756): mfGridElementWidthInv = (float)64 / (mnMaxX - mnMinX); {0, cols, 0, rows}
+ * without distortion, where (float)cols - 0.0f == (float)cols */
+struct SiGridInv {
+    float w, h;
+};
+__device__ __forceinline__ SiGridInv si_grid_inv(const SiBounds& b) {
+    return SiGridInv{__fdiv_rn((float)SI_GRID_COLS, __fsub_rn(b.maxX, b.minX)),
+                     __fdiv_rn((float)SI_GRID_ROWS, __fsub_rn(b.maxY, b.minY))};
+}
+
+struct SiWindow {
+    int minX, maxX, minY, maxY;
+    bool empty;
+};
+/* GetFeaturesInArea(x, y, r, ..): cell range over the grid bounds (frame.cpp:686-708 with mnMinX / mnMinY; KeyFrame's
+ * copy, keyframe.cpp:655-699, is the same expression over its integer bounds: pass si_kf_bounds): floor((x - minX - r) *
+ * inv), left to right.  With
+ * minX = minY = 0 (the integer image, int_bounds() on the host) x - 0.0f == x, so every value equals the plain
+ * floor((x - r) * inv) bit for bit. */
+/* A KeyFrame keeps the bounds as `const int mnMinX, mnMinY, mnMaxX, mnMaxY` (keyframe.h:255-258), initialised from the
+ * Frame's floats (keyframe.cpp:44): truncated toward zero.  Its grid cells are the Frame's (binned with the float bounds,
+ * keyframe.cpp:58-67) and its mfGridElement*Inv the Frame's floats (:36), but the window origin of
+ * KeyFrame::GetFeaturesInArea (:663-675) and KeyFrame::IsInImage (:701-703) read the integers, converted back to float by
+ * the comparison / subtraction.  {0, w, 0, h} is its own truncation. */
+__device__ __forceinline__ SiBounds si_kf_bounds(const SiBounds& b) {
+    return SiBounds{(float)(int)b.minX, (float)(int)b.maxX, (float)(int)b.minY, (float)(int)b.maxY};
+}
+__device__ __forceinline__ SiWindow si_window_b(float px, float py, float r, const SiBounds& b, const SiGridInv& inv) {
+    SiWindow w;
+    const float dx = __fsub_rn(px, b.minX), dy = __fsub_rn(py, b.minY);
+    w.minX = max(0, (int)floorf(__fmul_rn(__fsub_rn(dx, r), inv.w)));
+    w.maxX = min(SI_GRID_COLS - 1, (int)ceilf(__fmul_rn(__fadd_rn(dx, r), inv.w)));
+    w.minY = max(0, (int)floorf(__fmul_rn(__fsub_rn(dy, r), inv.h)));
+    w.maxY = min(SI_GRID_ROWS - 1, (int)ceilf(__fmul_rn(__fadd_rn(dy, r), inv.h)));
+    w.empty = w.minX >= SI_GRID_COLS || w.maxX < 0 || w.minY >= SI_GRID_ROWS || w.maxY < 0;
+    return w;
+}
+/* PosInGrid (frame.cpp:746-756): the cell gridX * 64 + gridY (gridY < 48) of a keypoint, or -1 outside the grid --
+ * undistorted keypoints may lie left of / above the image or beyond it */
+__device__ __forceinline__ int si_grid_cell(float x, float y, const SiBounds& b, const SiGridInv& inv) {
+    const int gx = (int)roundf(__fmul_rn(__fsub_rn(x, b.minX), inv.w));
+    const int gy = (int)roundf(__fmul_rn(__fsub_rn(y, b.minY), inv.h));
+    return (gx < 0 || gx >= SI_GRID_COLS || gy < 0 || gy >= SI_GRID_ROWS) ? -1 : gx * 64 + gy;
+}
+/* the cell gridX * 64 + gridY lies in the window's cell range */
+__device__ __forceinline__ bool si_cell_in_window(int cell, const SiWindow& w) {
+    const int gx = cell >> 6, gy = cell & 63;
+    return !(gx < w.minX || gx > w.maxX || gy < w.minY || gy > w.maxY);
+}
+/* the body of GetFeaturesInArea for one keypoint record with .cell, .x, .y: its cell lies in the window's cell range and
+ * |kp.x - x| < r && |kp.y - y| < r */
+template <typename Cand>
+__device__ __forceinline__ bool si_in_window(const Cand& cd, const SiWindow& w, float px, float py, float r) {
+    if (!si_cell_in_window(cd.cell, w)) return false;
+    const float distx = __fsub_rn(cd.x, px), disty = __fsub_rn(cd.y, py);
+    return fabsf(distx) < r && fabsf(disty) < r;
+}
+__device__ __forceinline__ uint32_t si_hamming(const uint4& da, const uint4& db, const uint4& ta, const uint4& tb) {
+    return __popc(da.x ^ ta.x) + __popc(da.y ^ ta.y) + __popc(da.z ^ ta.z) + __popc(da.w ^ ta.w) +
+           __popc(db.x ^ tb.x) + __popc(db.y ^ tb.y) + __popc(db.z ^ tb.z) + __popc(db.w ^ tb.w);
+}
+
+/* The match key: min(distance, 255) << 24 | gridcell << 12 | index, i.e. (distance, position in GetFeaturesInArea's
+ * output: grid cell column-major, ascending index inside a cell, frame.cpp:712-741); 0xFFFFFFFF = none.  "First wins" on
+ * equal distance is the key order.  About the clamp see vslam_init_kernel.hip. */
+__device__ __forceinline__ uint32_t si_key(uint32_t hamming, uint32_t cell, uint32_t index) {
+    return (min(hamming, 255u) << 24) | (cell << 12) | index;
+}
+__device__ __forceinline__ uint32_t si_key_dist(uint32_t key) { return key >> 24; }
+__device__ __forceinline__ uint32_t si_key_index(uint32_t key) { return key & 0xFFFu; }
+
+/* the counts of a job: capacities clamped by the real counts in HBM where the job names them */
+struct SbpCounts {
+    int nLast, nCur;
+};
+__device__ __forceinline__ SbpCounts sbp_counts(const SbpJobDev& J) {
+    return SbpCounts{J.nLastPtr ? min(*J.nLastPtr, J.nLast) : J.nLast, J.nCurPtr ? min(*J.nCurPtr, J.nCur) : J.nCur};
+}
+
+/* one row of R*x + t as ONE cv::gemm: products accumulated in double, rounded once (flt: a build whose gemm stays in float) */
+__device__ __forceinline__ float sbp_gemm_row(const float* r, float x0, float x1, float x2, float t, int flt) {
+    if (!flt) { /* GEMMSingleMul<float,double>: s += double(a)*double(b), then float(s + double(c)) */
+        double s = __dmul_rn((double)r[0], (double)x0);
+        s = __dadd_rn(s, __dmul_rn((double)r[1], (double)x1));
+        s = __dadd_rn(s, __dmul_rn((double)r[2], (double)x2));
+        return (float)__dadd_rn(s, (double)t);
+    }
+    float s = __fmul_rn(r[0], x0);
+    s = __fadd_rn(s, __fmul_rn(r[1], x1));
+    s = __fadd_rn(s, __fmul_rn(r[2], x2));
+    return __fadd_rn(s, t);
+}
+struct SbpPoint {
+    float x, y, z;
+};
+/* R * p + t; T: the rows [R | t] of a 3x4 pose */
+__device__ __forceinline__ SbpPoint sbp_transform(const float* T, float x, float y, float z, int flt) {
+    return SbpPoint{sbp_gemm_row(T + 0, x, y, z, T[3], flt), sbp_gemm_row(T + 4, x, y, z, T[7], flt),
+                    sbp_gemm_row(T + 8, x, y, z, T[11], flt)};
+}
+/* the same with R (3x3, row-major) and t apart */
+__device__ __forceinline__ SbpPoint sbp_transform(const float* R, const float* t, float x, float y, float z, int flt) {
+    return SbpPoint{sbp_gemm_row(R + 0, x, y, z, t[0], flt), sbp_gemm_row(R + 3, x, y, z, t[1], flt),
+                    sbp_gemm_row(R + 6, x, y, z, t[2], flt)};
+}
+#endif /* __HIPCC__ */
+
+#endif
