@@ -948,6 +948,12 @@ int vslam_dbg_search_init_fallbacks(vslam_fe* fe, int* count);
 /* Rounds of the replay wave, queries and pairs it decided since the last call (read-and-reset, synchronises): the
  * sequential half of SearchForInitialization commits `queries / rounds` queries per round on average. */
 int vslam_dbg_search_init_replay_stats(vslam_fe* fe, int* rounds, int* queries, int* pairs);
+/* What this library holds right now, process-wide: bytes and blocks of device memory and of pinned host memory that its
+ * objects (contexts, detectors, trackers, vocabularies, keyframe databases) own.  Any pointer may be NULL.  A create /
+ * use / destroy sequence leaves all four where they were; the device's own free-memory figure cannot show that on a
+ * GPU that other processes use too.  Memory handed out by vslam_host_alloc belongs to the caller and is not counted. */
+int vslam_dbg_live_memory(unsigned long long* device_bytes, unsigned long long* device_blocks,
+                          unsigned long long* pinned_bytes, unsigned long long* pinned_blocks);
 
 #ifdef __cplusplus
 }

@@ -292,6 +292,19 @@ def test_worker_pool_stress_under_thread_sanitizer(tmp_path):
     assert "pool_stress ok" in r.stdout and "WARNING: ThreadSanitizer" not in r.stderr
 
 
+def test_owning_buffer_over_a_counting_space(tmp_path):
+    """The owning buffer of vslam_mem.h (generic part, no HIP) over a space that records every live block, fails on
+    demand and aborts on a free of a block that is not live: grow-only ensure, the failed allocation, move, swap,
+    release twice, the zero-length upload, a vector of buffer-holding structs; nothing is live at exit."""
+    import subprocess
+    exe = str(tmp_path / "mem_owner")
+    src = os.path.join(ROOT, "tests", "cpp", "mem_owner.cpp")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-o", exe, src])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "mem_owner ok" in r.stdout and "0 live" in r.stdout
+
+
 @pytest.mark.parametrize("size,nlevels,scale", [((1241, 376), 8, 1.2), ((1920, 1080), 8, 1.2), ((752, 480), 8, 1.2),
                                                 ((321, 203), 6, 1.2), ((640, 480), 5, 1.1), ((1241, 376), 12, 1.1),
                                                 ((128, 128), 2, 1.2), ((500, 400), 4, 1.5)])

@@ -63,6 +63,7 @@ ABI_SYMBOLS = [
     "vslam_kfdb_create", "vslam_kfdb_create_ex", "vslam_kfdb_destroy", "vslam_kfdb_add", "vslam_kfdb_erase",
     "vslam_kfdb_clear", "vslam_kfdb_clear_map", "vslam_kfdb_size", "vslam_kfdb_stats", "vslam_kfdb_query_async",
     "vslam_kfdb_query_wait", "vslam_kfdb_select_relocalization", "vslam_kfdb_select_nbest",
+    "vslam_dbg_live_memory",
 ]
 
 
@@ -366,6 +367,7 @@ def lib():
         L.vslam_search_for_triangulation.argtypes = [vp, vp] + [vp, vp, vp, vp, i, vp, vp, vp, i] * 2 + [vp, vp]
         L.vslam_fuse_search.argtypes = [vp, vp, vp, vp, i, vp, vp, i, vp, vp, vp]
         L.vslam_dbg_logf.argtypes = [vp, vp, i, vp]
+        L.vslam_dbg_live_memory.argtypes = [vp, vp, vp, vp]
         L.vslam_search_by_projection_sim3.argtypes = [vp, vp, vp, C.c_float, C.c_float, i, vp, vp, vp, vp, vp, vp, i, vp, vp, i,
                                                       vp, vp, vp]
         L.vslam_search_by_projection_keyframe.argtypes = [vp, vp, vp, C.c_float, i, vp, i, vp, vp, vp, vp, vp, vp, vp, i, vp,

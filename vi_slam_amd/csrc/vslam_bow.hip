@@ -13,9 +13,9 @@
 struct vslam_voc {
     int device = 0;
     int nNodes = 0, L = 0, weighting = 0, norm = 1;
-    int32_t *d_childStart = nullptr, *d_childCount = nullptr, *d_childIds = nullptr, *d_word = nullptr;
-    uint8_t* d_desc = nullptr;
-    double* d_weight = nullptr;
+    vslam_dbuf<int32_t> d_childStart, d_childCount, d_childIds, d_word;
+    vslam_dbuf<uint8_t> d_desc;
+    vslam_dbuf<double> d_weight;
 };
 
 struct BowJobsDev {
@@ -61,13 +61,6 @@ k_bow_descend(BowJobsDev J, const int32_t* __restrict__ childStart, const int32_
     }
 }
 
-template <typename T>
-static int up(T** dst, const void* src, size_t bytes) {
-    HIPCHK(hipMalloc((void**)dst, bytes ? bytes : 8));
-    if (bytes) HIPCHK(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-    return VSLAM_OK;
-}
-
 /* DBoW3::Vocabulary::load(filename) (Vocabulary.cpp:1084-1112; called by core::System, system.cpp:76): parse the file on
  * the host (vslam_voc_file.cpp) and upload the node table. */
 extern "C" int vslam_voc_load(int device, const char* path, vslam_voc** out) {
@@ -96,12 +89,6 @@ extern "C" int vslam_voc_load(int device, const char* path, vslam_voc** out) {
 extern "C" void vslam_voc_destroy(vslam_voc* v) {
     if (!v) return;
     hipSetDevice(v->device);
-    hipFree(v->d_childStart);
-    hipFree(v->d_childCount);
-    hipFree(v->d_childIds);
-    hipFree(v->d_word);
-    hipFree(v->d_desc);
-    hipFree(v->d_weight);
     delete v;
 }
 
@@ -147,9 +134,9 @@ extern "C" int vslam_voc_create(int device, int depth_levels, int weighting, int
     v->weighting = weighting;
     v->norm = norm;
     int rc;
-    if ((rc = up(&v->d_childStart, child_start, (size_t)n_nodes * 4)) || (rc = up(&v->d_childCount, child_count, (size_t)n_nodes * 4)) ||
-        (rc = up(&v->d_childIds, child_ids, (size_t)n_child_ids * 4)) || (rc = up(&v->d_word, node_word_id, (size_t)n_nodes * 4)) ||
-        (rc = up(&v->d_desc, node_desc, (size_t)n_nodes * 32)) || (rc = up(&v->d_weight, node_weight, (size_t)n_nodes * 8))) {
+    if ((rc = vslam_upload(v->d_childStart, child_start, (size_t)n_nodes * 4)) || (rc = vslam_upload(v->d_childCount, child_count, (size_t)n_nodes * 4)) ||
+        (rc = vslam_upload(v->d_childIds, child_ids, (size_t)n_child_ids * 4)) || (rc = vslam_upload(v->d_word, node_word_id, (size_t)n_nodes * 4)) ||
+        (rc = vslam_upload(v->d_desc, node_desc, (size_t)n_nodes * 32)) || (rc = vslam_upload(v->d_weight, node_weight, (size_t)n_nodes * 8))) {
         vslam_voc_destroy(v);
         return rc;
     }

@@ -1,7 +1,7 @@
 /* vslam_ctx.h -- private: the vslam_fe context (HBM layout, scratch, worker pool) shared by
- * vslam_fe.hip (extractor ABI) and by the matcher ABI: vslam_stereo.hip (stereo, RGB-D), vslam_match.hip
- * (SearchForInitialization), vslam_projection.hip (SearchByProjection family, Fuse, SearchLocalPoints), vslam_bow.hip
- * and vslam_kfdb.hip. */
+ * vslam_context.hip (its life and accessors), vslam_upload.hip (host images into level 0), vslam_fe.hip (the extraction
+ * pipeline) and by the matcher ABI: vslam_stereo.hip (stereo, RGB-D), vslam_match.hip (SearchForInitialization),
+ * vslam_projection.hip (SearchByProjection family, Fuse, SearchLocalPoints), vslam_bow.hip and vslam_kfdb.hip. */
 #ifndef VSLAM_CTX_H
 #define VSLAM_CTX_H
 #include <hip/hip_runtime.h>
@@ -23,22 +23,13 @@
 #include "vslam_pool.h"
 #include "vslam_kernels.h"
 #include "vslam_tuning.h"
+#include "vslam_mem.h" /* g_err, HIPCHK, the owning buffers and events */
 #include "vslam_staging.h"
-
-std::string& vslam_err();
-#define g_err (vslam_err())
-
-#define HIPCHK(call)                                                                             \
-    do {                                                                                         \
-        hipError_t e_ = (call);                                                                  \
-        if (e_ != hipSuccess) {                                                                  \
-            g_err = std::string(#call) + ": " + hipGetErrorString(e_);                           \
-            return VSLAM_ERR_HIP;                                                                \
-        }                                                                                        \
-    } while (0)
 
 /* ------------------------------------------------------------------ context */
 enum { VSLAM_REGION_NONE = 0, VSLAM_REGION_INIT = 1, VSLAM_REGION_STEREO = 2 };
+/* Every vslam_dbuf / vslam_hbuf / vslam_event member is owned and goes with the context (vslam_mem.h); a raw d_* / h_*
+ * pointer is a view into one of them and is commented as such. */
 struct vslam_fe {
     vslam_fe_params p;
     vslam_tuning tune; /* the context's behaviour switches, resolved once by vslam_fe_create (vslam_tuning.h) */
@@ -48,30 +39,30 @@ struct vslam_fe {
     int B = 1, cap = 0;
 
     hipStream_t stream = nullptr;
-    hipEvent_t ev_cand = nullptr;
-    hipEvent_t ev_x = nullptr; /* cross-context ordering (vslam_fe_wait_for) */
-    hipEvent_t ev_user[4] = {};  /* vslam_fe_event_record / _wait */
+    vslam_event ev_cand;
+    vslam_event ev_x; /* cross-context ordering (vslam_fe_wait_for) */
+    vslam_event ev_user[4];      /* vslam_fe_event_record / _wait */
     int desc_kpw_hint = -1;           /* keypoints per wave of the descriptor kernel for the pass being enqueued (-1: by batch size) */
-    hipEvent_t ev_fast = nullptr;     /* recorded behind the FAST launch of every pass once a gate refers to this context */
+    vslam_event ev_fast;              /* recorded behind the FAST launch of every pass once a gate refers to this context */
     vslam_fe* fast_gate = nullptr;    /* vslam_fe_set_fast_gate: this context's FAST waits for that context's last FAST */
     bool fast_gated_by_someone = false;
     std::vector<vslam_fe*> gate_waiters; /* contexts whose fast_gate is this one: un-gated when this context is destroyed */
 
-    uint8_t* d_pyr = nullptr;
-    uint8_t* d_blur = nullptr;
+    vslam_dbuf<uint8_t> d_pyr;
+    vslam_dbuf<uint8_t> d_blur;
     /* resize tables, one set per destination level >= 1 */
-    uint16_t* d_xtab[VSLAM_MAX_LEVELS] = {};
-    int16_t* d_xa[VSLAM_MAX_LEVELS] = {};
-    uint16_t* d_ytab[VSLAM_MAX_LEVELS] = {};
-    int16_t* d_yb[VSLAM_MAX_LEVELS] = {};
-    uint16_t* d_qbase[VSLAM_MAX_LEVELS] = {};    /* k_resize_level_v2 quad tables (nullptr: generic k_resize_level) */
-    ResizeQuad* d_quads[VSLAM_MAX_LEVELS] = {};
+    vslam_dbuf<uint16_t> d_xtab[VSLAM_MAX_LEVELS];
+    vslam_dbuf<int16_t> d_xa[VSLAM_MAX_LEVELS];
+    vslam_dbuf<uint16_t> d_ytab[VSLAM_MAX_LEVELS];
+    vslam_dbuf<int16_t> d_yb[VSLAM_MAX_LEVELS];
+    vslam_dbuf<uint16_t> d_qbase[VSLAM_MAX_LEVELS];    /* k_resize_level_v2 quad tables (nullptr: generic k_resize_level) */
+    vslam_dbuf<ResizeQuad> d_quads[VSLAM_MAX_LEVELS];
     /* fused pyramid: groups of levels per launch (k_pyramid_group); empty -> one launch per level */
-    struct PyrGroupCtx {
+    struct PyrGroupCtx { /* move-only: owns its tile table */
         PyrGroupDev dev;
         size_t lds_bytes;
         bool fit; /* ping-pong plan: k_pyramid_group<.., true> */
-        PyrTileDev* d_tiles;
+        vslam_dbuf<PyrTileDev> d_tiles;
     };
     std::vector<PyrGroupCtx> pyr_groups;
     /* the resident plan beside a default ping-pong one, for the passes of the stereo-frame entry (empty: pyr_groups serves every
@@ -81,29 +72,29 @@ struct vslam_fe {
     /* FAST cells */
     std::vector<vslam::HostCell> cells;
     int level_cell_first[VSLAM_MAX_LEVELS + 1] = {};
-    CellDesc* d_cells = nullptr;
+    vslam_dbuf<CellDesc> d_cells;
     int tile_pitch = 0, tile_rows = 0, max_px = 0;
     /* FAST bands (k_fast_bands): up to four cells of a cell row per workgroup; nbands == 0: not available for this geometry */
-    BandDesc* d_bands = nullptr;
-    uint8_t* d_band_classes = nullptr; /* 272-byte column tables, BandDesc::lnw >> 16 indexes them */
+    vslam_dbuf<BandDesc> d_bands;
+    vslam_dbuf<uint8_t> d_band_classes; /* 272-byte column tables, BandDesc::lnw >> 16 indexes them */
     int nbands = 0, band_max_wh = 0, band_max_iw = 0;
     /* candidates: per slot [total, overflow, CellOut[ncells], cand[cand_cap]] */
-    uint8_t* d_cand = nullptr;
-    uint8_t* h_cand = nullptr; /* pinned */
+    vslam_dbuf<uint8_t> d_cand;
+    vslam_hbuf<uint8_t> h_cand;
     size_t cand_stride = 0;
     int cand_cap = 0;
     int32_t taps[7];
-    uint32_t* d_blur_tasks = nullptr;
+    vslam_dbuf<uint32_t> d_blur_tasks;
     int n_blur_tasks = 0;
     int oct_threads = 1024; /* threads per quadtree problem (k_octree_v4), chosen at creation */
     int blur_rows = 32; /* output rows per wave task of k_blur7_v2 (VSLAM_BLUR_ROWS) */
     /* selection + outputs */
-    SelKp* d_sel = nullptr;
-    SelKp* h_sel = nullptr; /* pinned, B*cap */
-    uint8_t* d_res = nullptr;  /* the context's result block: counts (res_counts_bytes) | kps B*cap | desc B*cap*32 */
-    uint8_t* h_res = nullptr;  /* pinned mirror, same layout */
+    vslam_dbuf<SelKp> d_sel;
+    vslam_hbuf<SelKp> h_sel; /* B*cap */
+    vslam_dbuf<uint8_t> d_res; /* the context's result block: counts (res_counts_bytes) | kps B*cap | desc B*cap*32 */
+    vslam_hbuf<uint8_t> h_res; /* pinned mirror, same layout */
     size_t res_bytes = 0, res_counts_bytes = 0, res_feat_bytes = 0, res_init_bytes = 0;
-    bool init_in_block = false;    /* d_init / h_init are the block's own matcher region (not allocations of their own) */
+    bool init_in_block = false;    /* d_init / h_init are the block's own matcher region (not d_init_own / h_init_own) */
     /* result deliveries of the extraction / SearchForInitialization paths so far (vslam_fe_delivery_stats) */
     unsigned long long n_deliveries = 0, n_delivery_bytes = 0, graph_deliveries = 0, graph_delivery_bytes = 0;
     bool deliver_deferred = false; /* an extraction with want_host = 2 is waiting for the matcher call that delivers both */
@@ -111,7 +102,7 @@ struct vslam_fe {
     uint8_t* d_desc = nullptr;
     vslam_kp* h_kps = nullptr;
     uint8_t* h_desc = nullptr;
-    int8_t* d_pattern = nullptr;
+    vslam_dbuf<int8_t> d_pattern;
     BatchSrc src;
     int n_out[VSLAM_MAX_BATCH] = {};
     int mono_out[VSLAM_MAX_BATCH] = {};
@@ -123,34 +114,31 @@ struct vslam_fe {
     std::vector<std::vector<vslam::Cand>> sel_level; /* [slot*nlevels + level] */
     std::vector<std::vector<vslam::Cand>> cand_level;
     /* matcher scratch (grown on demand) */
-    uint8_t* h_top2 = nullptr; /* pinned: idx2 | dist2 of the batched brute-force matcher */
-    size_t h_top2_bytes = 0;
-    uint32_t* d_part = nullptr;
-    size_t part_bytes = 0;
-    int32_t* d_idx2 = nullptr;
-    int32_t* d_dist2 = nullptr;
-    size_t top2_cap = 0;
-    uint8_t* d_dmat = nullptr;
-    size_t dmat_bytes = 0;
-    uint8_t* d_tmp_desc[2] = {nullptr, nullptr};
-    size_t tmp_desc_bytes[2] = {0, 0};
-    /* device SearchForInitialization: matches12 | prevMatched | nmatches of every pair */
+    vslam_hbuf<uint8_t> h_top2; /* idx2 | dist2 of the batched brute-force matcher */
+    vslam_dbuf<uint32_t> d_part;
+    vslam_dbuf<int32_t> d_idx2; /* rows x 2, as d_dist2 */
+    vslam_dbuf<int32_t> d_dist2;
+    vslam_dbuf<uint8_t> d_dmat;
+    vslam_dbuf<uint8_t> d_tmp_desc[2];
+    /* device SearchForInitialization: matches12 | prevMatched | nmatches of every pair.  d_init / h_init are views: of the
+     * result block's matcher region (init_in_block), or of the pair below once there are more pairs than image slots or
+     * the stereo matcher's outputs live in the region (init_scratch in vslam_match.hip decides) */
     uint8_t* d_init = nullptr;
-    size_t init_bytes = 0;
-    uint8_t* h_init = nullptr; /* pinned */
-    size_t h_init_bytes = 0;
+    uint8_t* h_init = nullptr;
+    size_t init_bytes = 0; /* bytes behind either view */
+    vslam_dbuf<uint8_t> d_init_own;
+    vslam_hbuf<uint8_t> h_init_own;
     int init_pairs = 0;
     bool init_lds_set = false;
     /* vslam_fe_set_camera: Frame::UndistortKeyPoints behind every pass when has_cam && ud.dist[0] != 0 */
     bool has_cam = false;
     UdCam ud;
-    vslam_kp* d_ukps = nullptr; /* B x cap, allocated by the first camera with k1 != 0 */
+    vslam_dbuf<vslam_kp> d_ukps; /* B x cap, allocated by the first camera with k1 != 0 */
     /* vslam_fe_set_grid_bounds: Frame::mnMinX.. for the SearchByProjection / Fuse / SearchBySim3 matchers */
     bool has_grid_bounds = false;
     SiBounds grid_bounds = {0.0f, 0.0f, 0.0f, 0.0f};
-    uint8_t* d_init_scratch = nullptr; /* k_si_topm -> k_si_replay: compacted octave-0 lists + sorted prefixes */
-    size_t init_scratch_bytes = 0;
-    int* d_init_fb = nullptr; /* number of full re-scans in k_si_replay / k_sbp_replay (diagnostics) */
+    vslam_dbuf<uint8_t> d_init_scratch; /* k_si_topm -> k_si_replay: compacted octave-0 lists + sorted prefixes */
+    vslam_dbuf<int> d_init_fb; /* 4 words, by vslam_init_fb_ensure: number of full re-scans in k_si_replay / k_sbp_replay (diagnostics) */
     /* one staging block for the single-call matchers (SearchByProjection, Fuse, ComputeDistinctiveDescriptors, SearchByBoW,
      * SearchForTriangulation): inputs | scratch | results, carved anew by every call */
     vslam_staging proj;
@@ -168,37 +156,32 @@ struct vslam_fe {
     size_t graph_pitch = 0;                          /* pinned-image passes: the captured pull reads these */
     const uint8_t* graph_imgs[VSLAM_MAX_BATCH] = {};
     int graph_lap0 = 0, graph_lap1 = 0;
-    uint8_t* h_img = nullptr;   /* pinned staging for host images: B x height x level-0 pitch */
+    vslam_hbuf<uint8_t> h_img;  /* staging for host images: B x height x level-0 pitch (sized for the pixel format in force) */
     size_t h_img_pitch = 0;     /* row pitch of the images staged last: the level-0 pitch, or the width for dense sources */
-    uint8_t* d_stage = nullptr; /* device staging of pinned caller images copied by the DMA engines (VSLAM_H2D=sdma) */
-    size_t d_stage_bytes = 0;
+    vslam_dbuf<uint8_t> d_stage; /* device staging of pinned caller images copied by the DMA engines (VSLAM_H2D=sdma) */
     vslam_staging sbp;          /* batched device-resident SearchByProjection: scratch of every job | results of all jobs */
     int sbp_jobs = 0, sbp_M = 8;
     size_t sbp_o_res = 0;       /* where the results (match tables | counts) start */
-    float* d_x3dw = nullptr;    /* stereo points per pair: B x cap x 3 */
-    uint8_t* d_mpflags = nullptr; /* B x cap */
+    vslam_dbuf<float> d_x3dw;    /* stereo points per pair: B x cap x 3 */
+    vslam_dbuf<uint8_t> d_mpflags; /* B x cap */
     /* stereo scratch */
-    void* d_stereo = nullptr;
-    size_t stereo_bytes = 0;
-    float* h_stereo = nullptr; /* pinned: [uRight | depth] x pairs x cap */
-    float *d_stereo_u = nullptr, *d_stereo_depth = nullptr; /* mvuRight / mvDepth of the last stereo pass on the device */
-    float* h_stereo_cur = nullptr; /* where the last stereo pass delivered: h_stereo, or the result block's matcher region */
+    vslam_dbuf<void> d_stereo;
+    vslam_hbuf<float> h_stereo; /* [uRight | depth] x pairs x cap */
+    float *d_stereo_u = nullptr, *d_stereo_depth = nullptr; /* views: mvuRight / mvDepth of the last stereo pass on the device */
+    float* h_stereo_cur = nullptr; /* view: where the last stereo pass delivered: h_stereo, or the result block's matcher region */
     int block_region_owner = 0;    /* VSLAM_REGION_*: which matcher's outputs live in the result block's extra region */
-    size_t h_stereo_bytes = 0;
     int stereo_pairs = 0;
     int stereo_capR = 0; /* slot capacity of the right context of the last stereo enqueue (scratch carving) */
     int stereo_slotL[VSLAM_MAX_BATCH] = {}; /* an RGB-D pass has one "pair" per image slot */
     /* vslam_fe_set_pixel_format: interleaved colour input, converted to gray into level 0 by k_gray_images */
     int pix_fmt = VSLAM_PIX_GRAY8, gray_shift = 15;
-    size_t h_img_bytes = 0;     /* bytes of h_img (sized for the pixel format in force) */
-    uint8_t* h_depth = nullptr; /* pinned staging of pageable depth images (vslam_frame_rgbd_batch_async, VSLAM_IMGS_HOST) */
-    size_t h_depth_bytes = 0;
+    vslam_hbuf<uint8_t> h_depth; /* staging of pageable depth images (vslam_frame_rgbd_batch_async, VSLAM_IMGS_HOST) */
     bool last_rgbd = false;     /* the last pass enqueued was an RGB-D pass: vslam_frame_rgbd_wait may deliver it */
-    hipEvent_t ev_rgbd[2] = {}; /* profiling: around k_rgbd_depth */
+    vslam_event ev_rgbd[2];     /* profiling: around k_rgbd_depth */
     bool rgbd_timed = false;
     double rgbd_ms = 0;
     long rgbd_passes = 0;
-    hipEvent_t ev_lp[3] = {};   /* profiling: before k_frustum | between | behind k_frustum_compact */
+    vslam_event ev_lp[3];       /* profiling: before k_frustum | between | behind k_frustum_compact */
     bool lp_timed = false;
     double lp_ms[2] = {0, 0};
     long lp_passes = 0;
@@ -206,21 +189,22 @@ struct vslam_fe {
     /* GPU quadtree distribution */
     bool dev_octree = false;
     OctParams oct;
-    uint32_t* d_pts = nullptr;                /* k_octree_v4: every level's keys in key order, B x cand_cap */
-    uint8_t* d_oct_sorted = nullptr;          /* k_octree_v4: {key, position} sorted by fine cell, B x cand_cap x 8 bytes (written only by problems that split below the grid) */
-    uint32_t* d_oct_lut = nullptr;            /* k_octree_v4: per level the x and y path tables (vslam::build_oct_lut) */
-    int32_t* d_oct_redo = nullptr;            /* k_octree_v4: (slot, level) split nodes finer than the grid, B x VSLAM_MAX_LEVELS */
-    uint32_t* d_sel_xyr = nullptr;            /* per slot / level result lists */
-    int32_t* d_sel_cnt = nullptr;
-    int32_t* d_counts = nullptr;              /* [slot][4] = n, monoIndex, -, - ; then [B*4] = error flags */
-    int32_t* h_counts = nullptr;              /* pinned mirror */
+    vslam_dbuf<unsigned long long> d_oct_dbg;  /* vslam_tuning.oct_debug: the 64 stamps oct.dbg points at */
+    vslam_dbuf<uint32_t> d_pts;               /* k_octree_v4: every level's keys in key order, B x cand_cap */
+    vslam_dbuf<uint8_t> d_oct_sorted;         /* k_octree_v4: {key, position} sorted by fine cell, B x cand_cap x 8 bytes (written only by problems that split below the grid) */
+    vslam_dbuf<uint32_t> d_oct_lut;           /* k_octree_v4: per level the x and y path tables (vslam::build_oct_lut) */
+    vslam_dbuf<int32_t> d_oct_redo;           /* k_octree_v4: (slot, level) split nodes finer than the grid, B x VSLAM_MAX_LEVELS */
+    vslam_dbuf<uint32_t> d_sel_xyr;           /* per slot / level result lists */
+    vslam_dbuf<int32_t> d_sel_cnt;
+    int32_t* d_counts = nullptr;              /* view into d_res: [slot][4] = n, monoIndex, -, - ; then [B*4] = error flags */
+    int32_t* h_counts = nullptr;              /* view into h_res */
     bool cand_on_host = false;                /* h_cand holds the last batch's candidates */
     int last_nimg = 0;
 
     /* optional HIP-event timing of the kernel stages (bench.py roofline): resize x7, fast, blur, describe,
      * quadtree (+ output order) */
     bool profiling = false;
-    hipEvent_t ev_prof[10] = {};
+    vslam_event ev_prof[10];
     double prof_ms[5] = {0, 0, 0, 0, 0};
     long prof_batches = 0, prof_images = 0;
 
@@ -232,7 +216,12 @@ struct vslam_fe {
 static inline int vslam_pix_bpp(int fmt) { return fmt == VSLAM_PIX_GRAY8 ? 1 : fmt <= VSLAM_PIX_BGR8 ? 3 : 4; }
 static inline size_t vslam_row_bytes(const vslam_fe* fe) { return (size_t)fe->p.width * vslam_pix_bpp(fe->pix_fmt); }
 
-int vslam_pinned_alloc(void** p, size_t bytes);                  /* hipHostMalloc on the device's NUMA node; returns a hipError_t */
+/* vslam_upload.hip, for the extraction pipeline: pageable rows into the pinned staging, the widest pitch that leaves
+ * there, the DMA route's device buffer (grown outside any capture), and the upload itself on fe's stream */
+int vslam_stage_host_images(vslam_fe* fe, int nimg, const uint8_t* const* imgs, size_t pitch);
+size_t vslam_host_stage_pitch(const vslam_fe* fe);
+int vslam_stage_ensure(vslam_fe* fe, size_t spitch, int nimg);
+int vslam_upload_host_rows(vslam_fe* fe, int nimg, const uint8_t* const* imgs, size_t pitch, int where);
 int vslam_enqueue_extract(vslam_fe* fe, int nimg, const uint8_t* const* imgs, size_t pitch, int on_device,
                           int lap0, int lap1, int want_host);
 int vslam_finish_extract(vslam_fe* fe, int nimg);
@@ -272,6 +261,14 @@ static inline int vslam_deliver_block(vslam_fe* fe, size_t extra) {
     const size_t bytes = fe->res_feat_bytes + extra;
     vslam_count_delivery(fe, vslam_copy_range(fe->stream, fe->h_res, fe->d_res, bytes, fe->tune), bytes);
     HIPCHK(hipGetLastError());
+    return VSLAM_OK;
+}
+
+/* the diagnostics words of k_si_replay / k_sbp_replay (d_init_fb), zeroed when they are first allocated */
+static inline int vslam_init_fb_ensure(vslam_fe* fe) {
+    if (fe->d_init_fb) return VSLAM_OK;
+    if (int rc = fe->d_init_fb.alloc(4)) return rc;
+    HIPCHK(hipMemset(fe->d_init_fb, 0, 16));
     return VSLAM_OK;
 }
 

@@ -360,16 +360,18 @@ struct vslam_ft {
     size_t pyr_bytes = 0;
     /* stage, packed anew in every call so that it goes up as one range: float2 newpx[n_upd] (per entry of ucand) |
      * uint32 cand[n] (the next call's k_ft_track; cand_off bytes in) | uint32 ucand[n_upd] (k_ft_update); n, n_upd <= cap */
-    uint8_t *d_pyr = nullptr, *d_stage = nullptr, *h_stage = nullptr;
+    vslam_dbuf<uint8_t> d_pyr, d_stage;
+    vslam_hbuf<uint8_t> h_stage;
     size_t cand_off = 0;
-    float *d_meta = nullptr, *d_invh = nullptr, *h_res = nullptr;
-    float4* d_res = nullptr;
-    int32_t* d_patch = nullptr;
+    vslam_dbuf<float> d_meta, d_invh;
+    vslam_hbuf<float> h_res;
+    vslam_dbuf<float4> d_res;
+    vslam_dbuf<int32_t> d_patch;
     std::vector<float> pos, score; /* the detector's grids of slots 0 .. n_cam - 1 */
     std::vector<int32_t> level;
     std::vector<vslam_ft_track_info> info;
     std::vector<int32_t> n_live, tracked, detected; /* per camera, within a call */
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr}; /* vslam_ft_profile: around k_ft_track, around k_ft_update */
+    vslam_event ev[4]; /* vslam_ft_profile: around k_ft_track, around k_ft_update */
     bool profile = false, ran_track = false, ran_update = false;
 };
 
@@ -387,16 +389,6 @@ extern "C" void vslam_ft_destroy(vslam_ft* ft) {
         (void)hipSetDevice(ft->det->device);
         if (ft->det->stream) (void)hipStreamSynchronize(ft->det->stream);
     }
-    for (hipEvent_t e : ft->ev)
-        if (e) (void)hipEventDestroy(e);
-    if (ft->d_pyr) (void)hipFree(ft->d_pyr);
-    if (ft->d_stage) (void)hipFree(ft->d_stage);
-    if (ft->h_stage) (void)hipHostFree(ft->h_stage);
-    if (ft->d_meta) (void)hipFree(ft->d_meta);
-    if (ft->d_invh) (void)hipFree(ft->d_invh);
-    if (ft->h_res) (void)hipHostFree(ft->h_res);
-    if (ft->d_res) (void)hipFree(ft->d_res);
-    if (ft->d_patch) (void)hipFree(ft->d_patch);
     for (vslam_ftbook* b : ft->book) vslam_ftbook_destroy(b);
     delete ft;
 }
@@ -404,19 +396,19 @@ extern "C" void vslam_ft_destroy(vslam_ft* ft) {
 static int ft_alloc(vslam_ft* ft) {
     const size_t n = ft->cap;
     HIPCHK(hipSetDevice(ft->det->device));
-    HIPCHK(hipMalloc((void**)&ft->d_pyr, ft->pyr_bytes));
+    if (int rc = ft->d_pyr.alloc(ft->pyr_bytes)) return rc;
     HIPCHK(hipMemset(ft->d_pyr, 0, ft->pyr_bytes));
-    HIPCHK(hipMalloc((void**)&ft->d_stage, n * 16));
-    HIPCHK((hipError_t)vslam_pinned_alloc((void**)&ft->h_stage, n * 16));
+    if (int rc = ft->d_stage.alloc(n * 16)) return rc;
+    if (int rc = ft->h_stage.alloc(n * 16)) return rc;
     memset(ft->h_stage, 0, n * 16);
-    HIPCHK(hipMalloc((void**)&ft->d_meta, n * FT_META * 4));
+    if (int rc = ft->d_meta.alloc(n * FT_META)) return rc;
     HIPCHK(hipMemset(ft->d_meta, 0, n * FT_META * 4));
-    HIPCHK(hipMalloc((void**)&ft->d_patch, n * ft->G.nlev * ft->G.max_area * 4));
+    if (int rc = ft->d_patch.alloc(n * ft->G.nlev * ft->G.max_area)) return rc;
     HIPCHK(hipMemset(ft->d_patch, 0, n * ft->G.nlev * ft->G.max_area * 4));
-    HIPCHK(hipMalloc((void**)&ft->d_invh, n * ft->G.nlev * 40));
+    if (int rc = ft->d_invh.alloc(n * ft->G.nlev * 10)) return rc;
     HIPCHK(hipMemset(ft->d_invh, 0, n * ft->G.nlev * 40));
-    HIPCHK(hipMalloc((void**)&ft->d_res, n * 16));
-    HIPCHK((hipError_t)vslam_pinned_alloc((void**)&ft->h_res, n * 16));
+    if (int rc = ft->d_res.alloc(n)) return rc;
+    if (int rc = ft->h_res.alloc(n * 4)) return rc;
     HIPCHK(hipDeviceSynchronize());
     return VSLAM_OK;
 }
@@ -517,8 +509,6 @@ extern "C" int vslam_ft_track_bundle(vslam_ft* ft, const uint8_t* const* imgs, s
     GdHost* det = ft->det;
     HIPCHK(hipSetDevice(det->device));
     hipStream_t st = det->stream;
-    CopyRanges R;
-    memset(&R, 0, sizeof(R));
     /* 00) the bundle's pyramids, once for the tracker and the detector: camera c is image slot c of every level */
     gd_stage_images(det, C, imgs, pitch, on_device, ft->d_pyr);
     fg_pyramid_halfsample(st, ft->d_pyr, ft->G.lv, ft->p.pyramid_levels, C);
@@ -536,11 +526,7 @@ extern "C" int vslam_ft_track_bundle(vslam_ft* ft, const uint8_t* const* imgs, s
                            dim3((n + 1) / 2), dim3(64), 0, st, n, (const uint32_t*)(ft->d_stage + ft->cand_off), ft->d_pyr, ft->G, ft->d_meta, ft->d_patch,
                            ft->d_invh, ft->d_res);
         if (ft->profile) HIPCHK(hipEventRecord(ft->ev[1], st));
-        R.n = 1;
-        R.dst[0] = ft->h_res;
-        R.src[0] = ft->d_res;
-        R.bytes[0] = (size_t)n * 16;
-        vk_copy_ranges(st, R);
+        vslam_copy_range(st, ft->h_res, ft->d_res, (size_t)n * 16);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(st));
     }
@@ -597,13 +583,7 @@ extern "C" int vslam_ft_track_bundle(vslam_ft* ft, const uint8_t* const* imgs, s
             u++;
         }
     }
-    if (n > 0) {
-        R.n = 1;
-        R.dst[0] = ft->d_stage;
-        R.src[0] = ft->h_stage;
-        R.bytes[0] = ((size_t)n + 3 * (size_t)n_upd) * 4;
-        vk_copy_ranges(st, R);
-    }
+    if (n > 0) vslam_copy_range(st, ft->d_stage, ft->h_stage, ((size_t)n + 3 * (size_t)n_upd) * 4);
     ft->ran_update = n_upd > 0;
     if (n_upd > 0) {
         if (ft->profile) HIPCHK(hipEventRecord(ft->ev[2], st));
@@ -636,8 +616,9 @@ extern "C" int vslam_ft_profile(vslam_ft* ft, int enable) {
         return VSLAM_ERR_INVALID;
     }
     HIPCHK(hipSetDevice(ft->det->device));
-    for (hipEvent_t& e : ft->ev)
-        if (enable && !e) HIPCHK(hipEventCreate(&e));
+    for (vslam_event& e : ft->ev)
+        if (enable)
+            if (int rc = e.ensure()) return rc;
     ft->profile = enable != 0;
     ft->ran_track = ft->ran_update = false;
     return VSLAM_OK;

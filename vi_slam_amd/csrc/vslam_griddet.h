@@ -199,8 +199,10 @@ struct GdHost { /* vslam_fg and vslam_hg derive from this */
     int device = 0, max_batch = 0, cells = 0, last_n = 0;
     size_t pyr_bytes = 0;
     hipStream_t stream = nullptr;
-    uint8_t *d_pyr = nullptr, *h_img = nullptr, *d_grid = nullptr, *h_grid = nullptr;
-    float* d_resp = nullptr;
+    vslam_dbuf<uint8_t> d_pyr, d_grid;
+    vslam_hbuf<uint8_t> h_img, h_grid;
+    vslam_dbuf<float> d_resp;
+    const uint8_t* search_pyr = nullptr; /* view: the pyramid the launch searches -- d_pyr, or a caller's in this layout (gd_detect_pyramid) */
     void (*launch)(const GdHost*, int n, float* resp_out, int resp_level, int resp_slot) = nullptr; /* the detect kernel */
 };
 
@@ -242,7 +244,7 @@ void gd_fill(GdHost& h, const P& p, int min_border) {
     h.pyr_bytes = fg_pyramid_layout(G.lv, p.image_width, p.image_height, G.max_level, p.max_batch);
 }
 int gd_alloc(GdHost& h); /* stream and buffers; on failure the caller destroys the object */
-void gd_free(GdHost& h);
+void gd_free(GdHost& h); /* waits for the stream and destroys it; the buffers go with the object */
 int gd_grid(const GdHost* h, int* n_cols, int* n_rows);
 /* upload or gather, halfsample, launch, grid copy, unpack into pos / score / level */
 int gd_detect_batch(GdHost* h, int n, const uint8_t* const* imgs, size_t pitch, int on_device, float* pos, float* score,
@@ -262,7 +264,7 @@ void gd_launch(const GdHost& h, K* k64, K* k128, K* k256, const typename Pol::Pa
                int resp_slot) {
     const int nt = gd_nt();
     hipLaunchKernelGGL(nt == 64 ? k64 : nt == 128 ? k128 : k256, dim3(((h.cells + 7) / 8) * 8, n), dim3(nt), gd_lds_bytes<Pol>(h.G),
-                       h.stream, h.d_pyr, h.G, D, h.d_grid, resp_out, resp_level, resp_slot);
+                       h.stream, h.search_pyr, h.G, D, h.d_grid, resp_out, resp_level, resp_slot);
 }
 
 #endif

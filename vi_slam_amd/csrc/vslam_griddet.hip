@@ -70,13 +70,14 @@ int gd_alloc(GdHost& h) {
     const FgLevel& L0 = h.G.lv[0];
     HIPCHK(hipSetDevice(h.device));
     HIPCHK(hipStreamCreateWithFlags(&h.stream, hipStreamNonBlocking));
-    HIPCHK(hipMalloc((void**)&h.d_pyr, h.pyr_bytes));
+    if (int rc = h.d_pyr.alloc(h.pyr_bytes)) return rc;
+    h.search_pyr = h.d_pyr;
     HIPCHK(hipMemset(h.d_pyr, 0, h.pyr_bytes));
-    HIPCHK((hipError_t)vslam_pinned_alloc((void**)&h.h_img, L0.bytes * h.max_batch));
+    if (int rc = h.h_img.alloc(L0.bytes * h.max_batch)) return rc;
     memset(h.h_img, 0, L0.bytes * h.max_batch);
-    HIPCHK(hipMalloc((void**)&h.d_grid, (size_t)h.cells * 16 * h.max_batch));
-    HIPCHK((hipError_t)vslam_pinned_alloc((void**)&h.h_grid, (size_t)h.cells * 16 * h.max_batch));
-    HIPCHK(hipMalloc((void**)&h.d_resp, (size_t)L0.w * L0.h * 4));
+    if (int rc = h.d_grid.alloc((size_t)h.cells * 16 * h.max_batch)) return rc;
+    if (int rc = h.h_grid.alloc((size_t)h.cells * 16 * h.max_batch)) return rc;
+    if (int rc = h.d_resp.alloc((size_t)L0.w * L0.h)) return rc;
     HIPCHK(hipDeviceSynchronize());
     return VSLAM_OK;
 }
@@ -84,11 +85,6 @@ int gd_alloc(GdHost& h) {
 void gd_free(GdHost& h) {
     (void)hipSetDevice(h.device);
     if (h.stream) (void)hipStreamSynchronize(h.stream);
-    if (h.d_pyr) (void)hipFree(h.d_pyr);
-    if (h.h_img) (void)hipHostFree(h.h_img);
-    if (h.d_grid) (void)hipFree(h.d_grid);
-    if (h.h_grid) (void)hipHostFree(h.h_grid);
-    if (h.d_resp) (void)hipFree(h.d_resp);
     if (h.stream) (void)hipStreamDestroy(h.stream);
 }
 
@@ -111,28 +107,15 @@ void gd_stage_images(GdHost* h, int n, const uint8_t* const* imgs, size_t pitch,
     } else { /* pageable rows -> pinned staging in the device layout -> one copy kernel (see vslam_fe.hip) */
         for (int s = 0; s < n; s++)
             for (int y = 0; y < L0.h; y++) memcpy(h->h_img + (size_t)s * L0.bytes + (size_t)y * L0.pitch, imgs[s] + (size_t)y * pitch, L0.w);
-        CopyRanges R;
-        memset(&R, 0, sizeof(R));
-        R.n = 1;
-        R.dst[0] = pyr + L0.base;
-        R.src[0] = h->h_img;
-        R.bytes[0] = L0.bytes * n;
-        vk_copy_ranges(h->stream, R);
+        vslam_copy_range(h->stream, pyr + L0.base, h->h_img, L0.bytes * n);
     }
 }
 
 int gd_detect_pyramid(GdHost* h, int n, uint8_t* pyr, float* pos, float* score, int32_t* level) {
-    uint8_t* const own = h->d_pyr; /* the launch reads the object's pyramid pointer */
-    h->d_pyr = pyr;
+    h->search_pyr = pyr; /* the launch reads it */
     h->launch(h, n, nullptr, -1, -1);
-    h->d_pyr = own;
-    CopyRanges R;
-    memset(&R, 0, sizeof(R));
-    R.n = 1;
-    R.dst[0] = h->h_grid;
-    R.src[0] = h->d_grid;
-    R.bytes[0] = (size_t)h->cells * 16 * n;
-    vk_copy_ranges(h->stream, R);
+    h->search_pyr = h->d_pyr;
+    vslam_copy_range(h->stream, h->h_grid, h->d_grid, (size_t)h->cells * 16 * n);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
     const int C = h->cells;

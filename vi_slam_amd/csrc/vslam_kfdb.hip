@@ -97,18 +97,17 @@ __global__ void __launch_bounds__(64 * KFDB_WAVES) k_kfdb_query(KfdbQueryArgs A)
 struct vslam_kfdb {
     int device = 0, nWords = 0;
     std::mutex mu;
-    int32_t* d_ids = nullptr;
-    double* d_vals = nullptr;
+    vslam_dbuf<int32_t> d_ids; /* the pool: cap entries each */
+    vslam_dbuf<double> d_vals;
     size_t cap = 0, used = 0, dead = 0; /* pool entries: allocated, handed out, belonging to erased keyframes */
     std::vector<KfdbSlot> slots;
     std::vector<int64_t> kf; /* keyframe id of every slot */
     std::unordered_map<int64_t, int> live; /* keyframe id -> slot */
-    KfdbSlot* d_slots = nullptr;
-    size_t d_slots_cap = 0;
+    vslam_dbuf<KfdbSlot> d_slots;
     bool table_dirty = true;
     unsigned long long n_grow = 0, n_compact = 0;
     /* the query in flight / delivered last: results lie in q_fe's pinned staging, the slot table as it was */
-    hipEvent_t ev = nullptr;
+    vslam_event ev;
     vslam_fe* q_fe = nullptr;
     int q_n = 0;
     std::vector<KfdbSlot> q_slots;
@@ -119,19 +118,6 @@ struct vslam_kfdb {
 /* nothing of the pool or the slot table changes under a query kernel that may still read it */
 static int kfdb_settle(vslam_kfdb* db) {
     if (db->q_fe) HIPCHK(hipEventSynchronize(db->ev));
-    return VSLAM_OK;
-}
-
-static int kfdb_alloc_pool(size_t cap, int32_t** ids, double** vals) {
-    *ids = nullptr;
-    *vals = nullptr;
-    HIPCHK(hipMalloc((void**)ids, cap * 4));
-    if (hipMalloc((void**)vals, cap * 8) != hipSuccess) {
-        hipFree(*ids);
-        *ids = nullptr;
-        g_err = "hipMalloc: KeyFrameDatabase pool";
-        return VSLAM_ERR_HIP;
-    }
     return VSLAM_OK;
 }
 
@@ -150,19 +136,14 @@ static int kfdb_grow(vslam_kfdb* db, size_t need) {
         g_err = "KeyFrameDatabase: more than 2^31 pool entries";
         return VSLAM_ERR_CAPACITY;
     }
-    int32_t* ids;
-    double* vals;
-    int rc = kfdb_alloc_pool(cap, &ids, &vals);
+    vslam_dbuf<int32_t> ids; /* built aside and swapped in on success; the old pair goes with these */
+    vslam_dbuf<double> vals;
+    int rc = ids.alloc(cap);
+    if (!rc) rc = vals.alloc(cap);
+    if (!rc) rc = kfdb_move(db, ids, vals, 0, 0, db->used);
     if (rc) return rc;
-    if ((rc = kfdb_move(db, ids, vals, 0, 0, db->used))) {
-        hipFree(ids);
-        hipFree(vals);
-        return rc;
-    }
-    hipFree(db->d_ids);
-    hipFree(db->d_vals);
-    db->d_ids = ids;
-    db->d_vals = vals;
+    db->d_ids.swap(ids);
+    db->d_vals.swap(vals);
     db->cap = cap;
     db->n_grow++;
     return VSLAM_OK;
@@ -172,9 +153,10 @@ static int kfdb_grow(vslam_kfdb* db, size_t need) {
  * neighbours in the pool too and move as one copy. */
 static int kfdb_compact(vslam_kfdb* db) {
     if (db->dead * 2 <= db->used) return VSLAM_OK;
-    int32_t* ids;
-    double* vals;
-    int rc = kfdb_alloc_pool(db->cap, &ids, &vals);
+    vslam_dbuf<int32_t> ids; /* as in kfdb_grow */
+    vslam_dbuf<double> vals;
+    int rc = ids.alloc(db->cap);
+    if (!rc) rc = vals.alloc(db->cap);
     if (rc) return rc;
     std::vector<KfdbSlot> slots;
     std::vector<int64_t> kf;
@@ -195,15 +177,9 @@ static int kfdb_compact(vslam_kfdb* db) {
         kf.push_back(db->kf[s]);
     }
     if (!rc) rc = kfdb_move(db, ids, vals, to, run_from, run_n);
-    if (rc) {
-        hipFree(ids);
-        hipFree(vals);
-        return rc;
-    }
-    hipFree(db->d_ids);
-    hipFree(db->d_vals);
-    db->d_ids = ids;
-    db->d_vals = vals;
+    if (rc) return rc;
+    db->d_ids.swap(ids);
+    db->d_vals.swap(vals);
     db->slots.swap(slots);
     db->kf.swap(kf);
     db->live.clear();
@@ -235,14 +211,10 @@ extern "C" int vslam_kfdb_create_ex(int device, int n_words, int scoring, int in
     db->device = device;
     db->nWords = n_words;
     db->cap = initial_entries ? (size_t)initial_entries : KFDB_DEFAULT_ENTRIES;
-    int rc = kfdb_alloc_pool(db->cap, &db->d_ids, &db->d_vals);
-    if (!rc && hipEventCreateWithFlags(&db->ev, hipEventDisableTiming) != hipSuccess) {
-        g_err = "hipEventCreateWithFlags failed";
-        rc = VSLAM_ERR_HIP;
-    }
+    int rc = db->d_ids.alloc(db->cap);
+    if (!rc) rc = db->d_vals.alloc(db->cap);
+    if (!rc) rc = db->ev.ensure(hipEventDisableTiming);
     if (rc) {
-        hipFree(db->d_ids);
-        hipFree(db->d_vals);
         delete db;
         return rc;
     }
@@ -258,10 +230,6 @@ extern "C" void vslam_kfdb_destroy(vslam_kfdb* db) {
     if (!db) return;
     hipSetDevice(db->device);
     if (db->q_fe) hipEventSynchronize(db->ev);
-    hipEventDestroy(db->ev);
-    hipFree(db->d_ids);
-    hipFree(db->d_vals);
-    hipFree(db->d_slots);
     delete db;
 }
 
@@ -418,14 +386,7 @@ extern "C" int vslam_kfdb_query_async(vslam_kfdb* db, vslam_fe* fe, int nq, cons
     }
     off[nq] = (int32_t)at;
     if (S && db->table_dirty) {
-        if (db->d_slots_cap < S) {
-            hipFree(db->d_slots);
-            db->d_slots = nullptr;
-            db->d_slots_cap = 0;
-            const size_t want = std::max(S * 2, (size_t)256);
-            HIPCHK(hipMalloc((void**)&db->d_slots, want * sizeof(KfdbSlot)));
-            db->d_slots_cap = want;
-        }
+        if (db->d_slots.count() < S && (rc = db->d_slots.alloc(std::max(S * 2, (size_t)256)))) return rc;
         HIPCHK(hipMemcpy(db->d_slots, db->slots.data(), S * sizeof(KfdbSlot), hipMemcpyHostToDevice));
         db->table_dirty = false;
     }

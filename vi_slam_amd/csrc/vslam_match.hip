@@ -12,14 +12,17 @@ static int init_scratch(vslam_fe* fe, int npairs) {
         if (fe->init_in_block) fe->block_region_owner = VSLAM_REGION_INIT;
         return VSLAM_OK;
     }
-    if (fe->init_in_block) { /* more pairs than image slots, or the stereo matcher's outputs live there: buffers of their own from now on */
-        fe->init_in_block = false;
-        fe->d_init = nullptr;
-        fe->h_init = nullptr;
-        fe->init_bytes = fe->h_init_bytes = 0;
-    }
-    int rc = vslam_ensure((void**)&fe->d_init, &fe->init_bytes, per * npairs);
-    return rc ? rc : vslam_ensure_pinned(&fe->h_init, &fe->h_init_bytes, per * npairs);
+    /* more pairs than image slots, or the stereo matcher's outputs live there: the context's own pair from now on */
+    fe->init_in_block = false;
+    fe->d_init = fe->h_init = nullptr;
+    fe->init_bytes = 0;
+    int rc = fe->d_init_own.ensure(per * npairs);
+    if (!rc) rc = fe->h_init_own.ensure(per * npairs);
+    if (rc) return rc;
+    fe->d_init = fe->d_init_own;
+    fe->h_init = fe->h_init_own;
+    fe->init_bytes = fe->d_init_own.bytes();
+    return VSLAM_OK;
 }
 
 extern "C" int vslam_fe_set_grid_bounds(vslam_fe* fe, const vslam_bounds* b) {
@@ -101,13 +104,9 @@ static int search_init_dev_async_b(vslam_fe* fe, int npairs, const vslam_init_jo
     }
     /* sorted candidate prefix per query; VSLAM_INIT_TOPM=<1..16> (tests force the re-scan path with 2) */
     const int M = std::min(16, std::max(1, tune_or(fe->tune.init_topm, 8)));
-    rc = vslam_ensure((void**)&fe->d_init_scratch, &fe->init_scratch_bytes,
-                      vk_search_init_scratch_bytes(npairs, max_c2, M) + 16);
+    rc = fe->d_init_scratch.ensure(vk_search_init_scratch_bytes(npairs, max_c2, M) + 16);
+    if (!rc) rc = vslam_init_fb_ensure(fe);
     if (rc) return rc;
-    if (!fe->d_init_fb) {
-        HIPCHK(hipMalloc((void**)&fe->d_init_fb, 16));
-        HIPCHK(hipMemset(fe->d_init_fb, 0, 16));
-    }
     const size_t nm = (size_t)npairs * fe->cap;
     int32_t* d_m = (int32_t*)fe->d_init;
     float* d_p = (float*)(d_m + nm);
@@ -210,7 +209,7 @@ static int search_init_batch_b(vslam_fe* fe, int npairs, const vslam_kp* const* 
             /* upload keypoints, counts and vbPrevMatched of every pair, run, download */
             size_t bytes = 0;
             for (int j = 0; j < npairs; j++) bytes += ((size_t)(n1[j] + n2[j]) * sizeof(vslam_kp) + (size_t)n1[j] * 8 + 16 + 63) & ~(size_t)63;
-            int rc = vslam_ensure((void**)&fe->d_tmp_desc[1], &fe->tmp_desc_bytes[1], bytes + 64);
+            int rc = fe->d_tmp_desc[1].ensure(bytes + 64);
             if (rc) return rc;
             std::vector<uint8_t> stage(bytes + 64);
             std::vector<vslam_init_job> jobs(npairs);
@@ -275,8 +274,8 @@ static int search_init_batch_b(vslam_fe* fe, int npairs, const vslam_kp* const* 
     if (maxr && maxc) {
         int rc;
         const size_t ib = (idx.size() * 4 + 255) & ~(size_t)255;
-        if ((rc = vslam_ensure((void**)&fe->d_tmp_desc[0], &fe->tmp_desc_bytes[0], ib + rows_total * 32))) return rc;
-        if ((rc = vslam_ensure((void**)&fe->d_dmat, &fe->dmat_bytes, out_total))) return rc;
+        if ((rc = fe->d_tmp_desc[0].ensure(ib + rows_total * 32))) return rc;
+        if ((rc = fe->d_dmat.ensure(out_total))) return rc;
         int32_t* d_idx = (int32_t*)fe->d_tmp_desc[0];
         uint8_t* d_rows = fe->d_tmp_desc[0] + ib;
         hipStream_t st = fe->stream;
@@ -365,7 +364,7 @@ extern "C" int vslam_search_for_initialization_ex(vslam_fe* fe, const vslam_kp* 
 
 /* ------------------------------------------------------------------ diagnostics */
 static int dbg_buffers(vslam_fe* fe, int n, float** a, float** b, float** c) {
-    int rc = vslam_ensure((void**)&fe->d_tmp_desc[1], &fe->tmp_desc_bytes[1], (size_t)n * 12);
+    int rc = fe->d_tmp_desc[1].ensure((size_t)n * 12);
     if (rc) return rc;
     *a = (float*)fe->d_tmp_desc[1];
     *b = *a + n;
@@ -474,17 +473,10 @@ extern "C" int vslam_hamming_top2_batch(vslam_fe* fe, int nprob, const uint8_t* 
     HIPCHK(hipSetDevice(fe->p.device));
     const int nsplit = vk_hamming_top2_batch_split(nprob, max_nq, max_nt);
     int rc;
-    if ((rc = vslam_ensure((void**)&fe->d_part, &fe->part_bytes, rows * nsplit * 8))) return rc;
-    if (fe->top2_cap < rows) {
-        hipFree(fe->d_idx2);
-        hipFree(fe->d_dist2);
-        fe->d_idx2 = fe->d_dist2 = nullptr;
-        fe->top2_cap = 0;
-        HIPCHK(hipMalloc((void**)&fe->d_idx2, rows * 8));
-        HIPCHK(hipMalloc((void**)&fe->d_dist2, rows * 8));
-        fe->top2_cap = rows;
-    }
-    if ((rc = vslam_ensure_pinned(&fe->h_top2, &fe->h_top2_bytes, rows * 16))) return rc;
+    if ((rc = fe->d_part.ensure(rows * nsplit * 2))) return rc;
+    if ((rc = fe->d_idx2.ensure(rows * 2))) return rc;
+    if ((rc = fe->d_dist2.ensure(rows * 2))) return rc;
+    if ((rc = fe->h_top2.ensure(rows * 16))) return rc;
     /* a split that lies past a problem's last tile, or a problem without train descriptors, writes nothing: "missing" */
     HIPCHK(hipMemsetAsync(fe->d_part, 0xFF, rows * nsplit * 8, fe->stream));
     vk_hamming_top2_batch(fe->stream, J, nprob, max_nq, (int)rows, nsplit, fe->d_part, fe->d_idx2, fe->d_dist2);
@@ -540,7 +532,7 @@ extern "C" int vslam_hamming_top2_batch_dev_async(vslam_fe* fe, int nprob, const
     if (rows == 0) return VSLAM_OK;
     HIPCHK(hipSetDevice(fe->p.device));
     const int nsplit = vk_hamming_top2_batch_split(nprob, max_nq, max_nt);
-    if (fe->part_bytes < rows * nsplit * 8 || fe->top2_cap < rows) { /* sized by a previous vslam_hamming_top2_batch */
+    if (fe->d_part.count() < rows * nsplit * 2 || fe->d_idx2.count() < rows * 2 || fe->d_dist2.count() < rows * 2) { /* sized by a previous vslam_hamming_top2_batch */
         g_err = "vslam_hamming_top2_batch_dev_async: call vslam_hamming_top2_batch with these sizes first (it allocates)";
         return VSLAM_ERR_INVALID;
     }
@@ -598,7 +590,7 @@ extern "C" int vslam_hamming_matrix(vslam_fe* fe, const uint8_t* dev_q, int nq, 
     if (nq == 0 || nt == 0) return VSLAM_OK;
     HIPCHK(hipSetDevice(fe->p.device));
     int rc;
-    if ((rc = vslam_ensure((void**)&fe->d_dmat, &fe->dmat_bytes, (size_t)nq * nt))) return rc;
+    if ((rc = fe->d_dmat.ensure((size_t)nq * nt))) return rc;
     vk_hamming_matrix(fe->stream, dev_q, nq, dev_t, nt, fe->d_dmat);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, fe->d_dmat, (size_t)nq * nt, hipMemcpyDeviceToHost, fe->stream));

@@ -46,11 +46,7 @@ static int sbp_prepare(vslam_fe* fe, int* M_out) {
         }
         fe->proj_lds_set = true;
     }
-    if (!fe->d_init_fb) {
-        HIPCHK(hipMalloc((void**)&fe->d_init_fb, 16));
-        HIPCHK(hipMemset(fe->d_init_fb, 0, 16));
-    }
-    return VSLAM_OK;
+    return vslam_init_fb_ensure(fe);
 }
 
 /* the header of a job list: the pyramid's scale factors and M; every job zeroed */
@@ -636,8 +632,8 @@ extern "C" int vslam_search_local_points_async(vslam_fe* fe, const vslam_frustum
     const size_t up0 = cur_u_right_host ? o_u : cur_occupied_host ? o_o : o_pts;
     fe->lp.up(st, up0, o_track - up0);
     const bool prof = fe->profiling; /* vslam_fe_set_profiling: the two kernels' own spans (vslam_fe_get_local_points_profile) */
-    if (prof && !fe->ev_lp[0])
-        for (int i = 0; i < 3; i++) HIPCHK(hipEventCreate(&fe->ev_lp[i]));
+    for (int i = 0; i < 3 && prof; i++)
+        if (int rc = fe->ev_lp[i].ensure()) return rc;
     FrustumArgsDev A;
     A.F = frustum_frame(fe, p);
     A.n = n_mp;

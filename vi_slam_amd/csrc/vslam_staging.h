@@ -9,9 +9,7 @@
 
 #include "vslam_host.h"
 #include "vslam_kernels.h"
-
-int vslam_ensure(void** p, size_t* have, size_t want);
-int vslam_ensure_pinned(uint8_t** p, size_t* have, size_t want); /* grow-only pinned host buffer */
+#include "vslam_mem.h"
 
 /* `bytes` from src to dst on st by vk_copy_ranges (a copy kernel, or the runtime for large ranges); returns the number
  * of copy operations, which the sites that keep delivery statistics hand to vslam_count_delivery */
@@ -27,20 +25,16 @@ static inline int vslam_copy_range(hipStream_t st, void* dst, const void* src, s
 }
 
 struct vslam_staging {
-    uint8_t* d = nullptr; /* HBM */
-    size_t d_bytes = 0;
-    uint8_t* h = nullptr; /* pinned mirror */
-    size_t h_bytes = 0;
+    vslam_dbuf<uint8_t> d; /* HBM */
+    vslam_hbuf<uint8_t> h; /* pinned mirror */
     /* grow-only: a smaller block reuses the buffers of a larger one before it */
     int ensure(size_t total) {
-        const int rc = vslam_ensure((void**)&d, &d_bytes, total);
-        return rc ? rc : vslam_ensure_pinned(&h, &h_bytes, total);
+        const int rc = d.ensure(total);
+        return rc ? rc : h.ensure(total);
     }
     void release() {
-        hipFree(d);
-        if (h) hipHostFree(h);
-        d = h = nullptr;
-        d_bytes = h_bytes = 0;
+        d.release();
+        h.release();
     }
     /* [off, off + bytes) of the block: mirror -> HBM, HBM -> mirror */
     int up(hipStream_t st, size_t off, size_t bytes) const { return vslam_copy_range(st, d + off, h + off, bytes); }

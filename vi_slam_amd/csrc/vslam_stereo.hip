@@ -18,14 +18,14 @@ static int stereo_scratch(vslam_fe* fe, int njobs, int capR, StereoScratch* s) {
     /* rows of a right keypoint's band: floor(y - 2s) .. ceil(y + 2s), s <= the coarsest level's scale factor */
     s->max_band = 2 * (int)std::ceil(2.0f * fe->tab.scale[fe->p.nlevels - 1]) + 3;
     const size_t rows_bytes = vk_stereo_rows_bytes(njobs, fe->p.height, s->max_band, capR);
-    int rc = vslam_ensure(&fe->d_stereo, &fe->stereo_bytes, n * 16 + rows_bytes + 16);
+    int rc = fe->d_stereo.ensure(n * 16 + rows_bytes + 16);
     if (rc) return rc;
     s->best = (uint32_t*)fe->d_stereo;
     s->uRight = (float*)(s->best + n);
     s->depth = s->uRight + n;
     s->sad = (int32_t*)(s->depth + n);
     s->rows = (uint8_t*)(s->sad + n);
-    return vslam_ensure_pinned((uint8_t**)&fe->h_stereo, &fe->h_stereo_bytes, n * 8);
+    return fe->h_stereo.ensure(n * 2);
 }
 
 /* mvuRight | mvDepth of npairs pairs (uRight, then depth, npairs x cap floats each) to the host, enqueued on fe's stream */
@@ -218,7 +218,7 @@ extern "C" int vslam_frame_rgbd_batch_async(vslam_fe* fe, int nframes, const uin
     if (depth_where == VSLAM_IMGS_HOST) { /* pageable: dense rows into pinned staging, which the kernel reads in place */
         const size_t rowb = (size_t)fe->p.width * esize, one = (rowb * fe->p.height + 255) & ~(size_t)255;
         HIPCHK(vslam_stream_wait(fe->stream)); /* the previous pass's gather may still read the staging */
-        int rc = vslam_ensure_pinned(&fe->h_depth, &fe->h_depth_bytes, one * fe->B);
+        int rc = fe->h_depth.ensure(one * fe->B);
         if (rc) return rc;
         fe->pool->parallel_for(nframes, [&](int j) {
             uint8_t* hd = fe->h_depth + one * j;
@@ -243,9 +243,7 @@ extern "C" int vslam_frame_rgbd_batch_async(vslam_fe* fe, int nframes, const uin
     fe->stereo_capR = fe->cap;
     rc = vslam_enqueue_extract(fe, nframes, imgs, pitch, imgs_where, 0, 0, blk ? 2 : (want_host != 0));
     const bool prof = rc == VSLAM_OK && fe->profiling;
-    if (prof && !fe->ev_rgbd[0])
-        for (int i = 0; i < 2 && rc == VSLAM_OK; i++)
-            if (hipEventCreate(&fe->ev_rgbd[i]) != hipSuccess) rc = VSLAM_ERR_HIP;
+    for (int i = 0; i < 2 && prof && rc == VSLAM_OK; i++) rc = fe->ev_rgbd[i].ensure();
     if (rc == VSLAM_OK) {
         if (blk) {
             sc.uRight = (float*)(fe->d_res + fe->res_feat_bytes);
@@ -304,10 +302,8 @@ extern "C" int vslam_fe_get_rgbd_profile(vslam_fe* fe, double* depth_ms, long* p
 /* ------------------------------------------------------------------ stereo points on the device */
 /* the stereo points of every pair, allocated by the first call that hands them out or fills them */
 static int stereo_points_alloc(vslam_fe* fe) {
-    if (fe->d_x3dw) return VSLAM_OK;
-    HIPCHK(hipMalloc((void**)&fe->d_x3dw, (size_t)fe->B * fe->cap * 12));
-    HIPCHK(hipMalloc((void**)&fe->d_mpflags, (size_t)fe->B * fe->cap));
-    return VSLAM_OK;
+    const int rc = fe->d_x3dw.ensure((size_t)fe->B * fe->cap * 3);
+    return rc ? rc : fe->d_mpflags.ensure((size_t)fe->B * fe->cap);
 }
 
 extern "C" int vslam_stereo_points_dev_async(vslam_fe* fe, int npairs, const float* Twc, float cx, float cy,

@@ -82,8 +82,8 @@ extern "C" int vslam_fe_set_camera(vslam_fe* fe, const vslam_camera* cam) {
     u.cam[2] = cam->cx;
     u.cam[3] = cam->cy;
     for (int i = 0; i < 5; i++) u.dist[i] = i < cam->ndist ? cam->dist[i] : 0.0f;
-    if (u.dist[0] != 0.0f && !fe->d_ukps) /* lazily: contexts without such a camera keep their footprint */
-        HIPCHK(hipMalloc((void**)&fe->d_ukps, (size_t)fe->B * fe->cap * sizeof(vslam_kp)));
+    if (u.dist[0] != 0.0f) /* lazily: contexts without such a camera keep their footprint */
+        if (int rc = fe->d_ukps.ensure((size_t)fe->B * fe->cap)) return rc;
     fe->ud = u;
     fe->has_cam = true;
     return VSLAM_OK;
@@ -125,7 +125,7 @@ extern "C" int vslam_undistort_points(vslam_fe* fe, const float* xy, int n, floa
     }
     if (!n) return VSLAM_OK;
     HIPCHK(hipSetDevice(fe->p.device));
-    int rc = vslam_ensure((void**)&fe->d_tmp_desc[1], &fe->tmp_desc_bytes[1], (size_t)n * 16);
+    int rc = fe->d_tmp_desc[1].ensure((size_t)n * 16);
     if (rc) return rc;
     float* d_in = (float*)fe->d_tmp_desc[1];
     float* d_out = d_in + 2 * (size_t)n;
