@@ -425,6 +425,62 @@ int vslam_search_init_dev_wait(vslam_fe* fe, const int* n1, int32_t* const* matc
 /* device address of a slot's keypoint count (int32), valid for the life of the context */
 int vslam_fe_slot_count_ptr(vslam_fe* fe, int slot, const int32_t** dev_n);
 
+/* ---------------------------------------------------------------- two-view consensus (MotionEstimator::Reconstruct)
+ *
+ * The monocular initialiser calls mpCamera->ReconstructWithTwoViews right behind SearchForInitialization
+ * (tracking.cpp:2324 -> :2339; pinhole.cpp:98-106; motion_estimation.cpp:2006-2094).  Its two RANSAC loops, FindHomography
+ * and FindFundamental (:2096-2195), have no early exit: mMaxIterations hypotheses each, every one scored over every match by
+ * CheckHomography (:2277-2360) or CheckFundamental (:2362-2440), plain float arithmetic without an OpenCV call.  This
+ * section is that scoring and the selection of the loops (:2137-2142, :2188-2193) for all hypotheses of both models and
+ * for a batch of frame pairs, in one enqueue.  HYPOTHESIS GENERATION STAYS WITH THE CALLER: the 8-point sets
+ * (DUtils::Random on the process-global rand() state), Normalize, ComputeH21 / ComputeF21 (cv::SVDecomp, whose arithmetic
+ * depends on how OpenCV was built), T2inv*Hn*T1, H21i.inv() and T2t*Fn*T1 -- the caller runs loop one to fill H21 / H12 /
+ * F21, calls this once, and goes on with RH = SH / (SH + SF) and ReconstructH / ReconstructF.
+ *
+ * The pair list (:2017-2029) is (i, matches12[i]) for ascending i with matches12[i] >= 0; every result is in that order.
+ * Arithmetic: vi_slam_amd/csrc/vslam_two_view.h -- each operation rounded on its own, associated as the C source reads,
+ * subnormals kept, the score a serial float chain over the pairs (image 1 term, then image 2 term) from zero.  A NaN chi
+ * (a projective w of exactly zero, 0/0 in the epipolar distance) is not `> th`: the pair counts as an inlier and the score
+ * becomes NaN, which never wins (`currentScore > score` is false).  The winner is the lowest index with the maximal score,
+ * if that score is > 0; otherwise best = -1, the score is 0 and the mask all zero.
+ * Deviations: without a winner the reference's FindFundamental leaves a mask of length 0 (:2150 reads the size of an empty
+ * vector), here it has n_pairs zeros; a NaN score is reported as the quiet NaN 0x7fc00000 whatever sign and payload the
+ * host's arithmetic would leave (nothing in the reference observes them).
+ * Limits: njobs <= VSLAM_TWO_VIEW_MAX_JOBS, nH / nF <= VSLAM_TWO_VIEW_MAX_HYP, n1 <= 65536.  A job with more than
+ * VSLAM_TWO_VIEW_MAX_PAIRS pairs makes _wait return VSLAM_ERR_UNSUPPORTED, a matches12 entry >= n2 (the reference would
+ * read out of bounds) VSLAM_ERR_INVALID; n_pairs of every job is delivered all the same, the failing job has no winner.
+ * sigma must be finite and not zero.  n_pairs == 0 is valid: no winner, both scores 0. */
+#define VSLAM_TWO_VIEW_MAX_JOBS 32
+#define VSLAM_TWO_VIEW_MAX_HYP 1024
+#define VSLAM_TWO_VIEW_MAX_PAIRS 8192
+typedef struct vslam_two_view_job {
+    const vslam_kp* kps1; const vslam_kp* kps2;   /* ukeypoints_ of frame 1 / 2 */
+    int32_t n1, n2;
+    const int32_t* matches12;                     /* n1 entries, -1 = unmatched */
+    int32_t kps_on_device, matches_on_device;     /* 0 host (uploaded with the block), 1 HBM */
+    const float* H21; const float* H12; int32_t nH; /* host, nH x 9 row-major each; nH may be 0 */
+    const float* F21; int32_t nF;                   /* host, nF x 9; nF may be 0 */
+    float sigma;                                    /* MotionEstimator's mSigma (1.0) */
+} vslam_two_view_job;
+
+typedef struct vslam_two_view_result {            /* caller storage; any pointer may be NULL */
+    int32_t n_pairs, best_h, best_f;  float score_h, score_f;   /* SH, SF of Reconstruct */
+    int32_t* pairs;                   /* 2 * n_pairs: (i, matches12[i]) */
+    float* scores_h; float* scores_f; /* nH / nF: every hypothesis' currentScore */
+    uint8_t* inliers_h; uint8_t* inliers_f;       /* n_pairs each, the winner's */
+} vslam_two_view_result;
+
+/* upload (job table | hypotheses | host keypoints and matches, one range) -> k_tv_pairs -> k_tv_score -> k_tv_select ->
+ * one result copy, all on fe's stream without a host wait.  One enqueue per context may be in flight; device arrays must
+ * stay valid and unchanged until _wait.  `results`: njobs entries; the arrays a job's result points to hold n1 pairs at
+ * most (min(n1, VSLAM_TWO_VIEW_MAX_PAIRS)). */
+int vslam_two_view_score_async(vslam_fe* fe, int njobs, const vslam_two_view_job* jobs);
+int vslam_two_view_score_wait(vslam_fe* fe, vslam_two_view_result* results);
+int vslam_two_view_score(vslam_fe* fe, const vslam_two_view_job* job, vslam_two_view_result* result);
+/* With vslam_fe_set_profiling on: HIP-event time of k_tv_pairs, k_tv_score and k_tv_select alone, summed over the calls
+ * waited for since.  Any pointer may be NULL. */
+int vslam_fe_get_two_view_profile(vslam_fe* fe, double* pairs_ms, double* score_ms, double* select_ms, long* passes);
+
 /* ---------------------------------------------------------------- distorted pinhole cameras (Frame::ukeypoints_)
  *
  * Frame::UndistortKeyPoints (frame.cpp:758-790) runs cv::undistortPoints(mat, mat, mK, mDistCoef, cv::Mat(), mK) on

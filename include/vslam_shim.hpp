@@ -578,6 +578,125 @@ inline void ComputeStereoMatches(const FExtractor& left, const FExtractor& right
 }
 
 /* ---------------------------------------------------------------------------------------------------
+ * The scoring half of MotionEstimator::Reconstruct (motion_estimation.cpp:2006-2094).  FindHomography and FindFundamental
+ * (:2096-2195) split in two: loop one stays in the caller and computes every H21i = T2inv*Hn*T1, H12i = H21i.inv() and
+ * F21i = T2t*Fn*T1 (ComputeH21 / ComputeF21 run cv::SVDecomp, which this library does not restate); then ONE call scores
+ * all of them over all matches and selects, as loop two and the two threads of the reference do:
+ *
+ *     MotionEstimator me(extractor, mSigma);
+ *     me.Check(vKeys1, vKeys2, vMatches12, vH21, vH12, vF21, out);       // CheckHomographies + CheckFundamentals
+ *     if (out.SH + out.SF == 0.f) return false;
+ *     float RH = out.SH / (out.SH + out.SF);                             // :2078-2093 as before, with
+ *     ... ReconstructH(out.vbMatchesInliersH, vH21[out.bestH], ...)  or  ReconstructF(out.vbMatchesInliersF, vF21[out.bestF], ...)
+ *
+ * A model is 9 floats row-major (Mat3f); with VSLAM_SHIM_WITH_OPENCV the overloads take std::vector<cv::Mat> of 3 x 3
+ * CV_32F.  The extractor only lends its device context and stream; it must have processed an image.
+ * ------------------------------------------------------------------------------------------------- */
+struct Mat3f {
+    float v[9];
+};
+static_assert(sizeof(Mat3f) == 36, "a vector of Mat3f is n x 9 packed floats");
+
+class MotionEstimator {
+public:
+    struct Consensus {
+        float SH = 0.0f, SF = 0.0f;                                /* score of FindHomography / FindFundamental */
+        int bestH = -1, bestF = -1;                                /* index of H21 / F21 among the hypotheses, -1: none */
+        std::vector<std::pair<int, int>> mvMatches12;              /* (index in frame 1, index in frame 2) */
+        std::vector<bool> vbMatchesInliersH, vbMatchesInliersF;    /* over mvMatches12; all false without a winner */
+        std::vector<float> vScoresH, vScoresF;                     /* currentScore of every iteration */
+    };
+
+    explicit MotionEstimator(const FExtractor& extractor, float sigma = 1.0f) : extractor_(&extractor), mSigma(sigma) {}
+
+    void Check(const std::vector<KeyPoint>& vKeys1, const std::vector<KeyPoint>& vKeys2, const std::vector<int>& vMatches12,
+               const std::vector<Mat3f>& vH21, const std::vector<Mat3f>& vH12, const std::vector<Mat3f>& vF21,
+               Consensus& out) const {
+        if (!extractor_->context()) throw std::runtime_error("MotionEstimator: the extractor has not processed an image yet");
+        if (vH21.size() != vH12.size() || vMatches12.size() != vKeys1.size())
+            throw std::runtime_error("MotionEstimator: vH21 / vH12 or vMatches12 / vKeys1 differ in length");
+        vslam_two_view_job job;
+        std::memset(&job, 0, sizeof(job));
+        job.kps1 = reinterpret_cast<const vslam_kp*>(vKeys1.data());
+        job.kps2 = reinterpret_cast<const vslam_kp*>(vKeys2.data());
+        job.n1 = (int32_t)vKeys1.size();
+        job.n2 = (int32_t)vKeys2.size();
+        job.matches12 = vMatches12.data();
+        job.H21 = vH21.empty() ? nullptr : vH21[0].v;
+        job.H12 = vH12.empty() ? nullptr : vH12[0].v;
+        job.nH = (int32_t)vH21.size();
+        job.F21 = vF21.empty() ? nullptr : vF21[0].v;
+        job.nF = (int32_t)vF21.size();
+        job.sigma = mSigma;
+        const size_t cap = vKeys1.size() < (size_t)VSLAM_TWO_VIEW_MAX_PAIRS ? vKeys1.size() : (size_t)VSLAM_TWO_VIEW_MAX_PAIRS;
+        std::vector<int32_t> pairs(2 * cap + 2);
+        std::vector<uint8_t> inH(cap + 1), inF(cap + 1);
+        out.vScoresH.assign(vH21.size(), 0.0f);
+        out.vScoresF.assign(vF21.size(), 0.0f);
+        vslam_two_view_result res;
+        std::memset(&res, 0, sizeof(res));
+        res.pairs = pairs.data();
+        res.scores_h = out.vScoresH.empty() ? nullptr : out.vScoresH.data();
+        res.scores_f = out.vScoresF.empty() ? nullptr : out.vScoresF.data();
+        res.inliers_h = inH.data();
+        res.inliers_f = inF.data();
+        check(vslam_two_view_score(extractor_->context(), &job, &res));
+        out.SH = res.score_h;
+        out.SF = res.score_f;
+        out.bestH = res.best_h;
+        out.bestF = res.best_f;
+        out.mvMatches12.resize((size_t)res.n_pairs);
+        out.vbMatchesInliersH.assign((size_t)res.n_pairs, false);
+        out.vbMatchesInliersF.assign((size_t)res.n_pairs, false);
+        for (int i = 0; i < res.n_pairs; i++) {
+            out.mvMatches12[i] = std::make_pair((int)pairs[2 * i], (int)pairs[2 * i + 1]);
+            out.vbMatchesInliersH[i] = inH[i] != 0;
+            out.vbMatchesInliersF[i] = inF[i] != 0;
+        }
+    }
+
+    /* one model only: the loop of FindHomography, or of FindFundamental */
+    void CheckHomographies(const std::vector<KeyPoint>& vKeys1, const std::vector<KeyPoint>& vKeys2,
+                           const std::vector<int>& vMatches12, const std::vector<Mat3f>& vH21, const std::vector<Mat3f>& vH12,
+                           Consensus& out) const {
+        Check(vKeys1, vKeys2, vMatches12, vH21, vH12, std::vector<Mat3f>(), out);
+    }
+    void CheckFundamentals(const std::vector<KeyPoint>& vKeys1, const std::vector<KeyPoint>& vKeys2,
+                           const std::vector<int>& vMatches12, const std::vector<Mat3f>& vF21, Consensus& out) const {
+        Check(vKeys1, vKeys2, vMatches12, std::vector<Mat3f>(), std::vector<Mat3f>(), vF21, out);
+    }
+
+#ifdef VSLAM_SHIM_WITH_OPENCV
+    static std::vector<Mat3f> pack(const std::vector<cv::Mat>& v) {
+        std::vector<Mat3f> out(v.size());
+        for (size_t k = 0; k < v.size(); k++) {
+            CV_Assert(v[k].rows == 3 && v[k].cols == 3 && v[k].type() == CV_32F);
+            for (int i = 0; i < 9; i++) out[k].v[i] = v[k].at<float>(i / 3, i % 3);
+        }
+        return out;
+    }
+    void CheckHomographies(const std::vector<KeyPoint>& vKeys1, const std::vector<KeyPoint>& vKeys2,
+                           const std::vector<int>& vMatches12, const std::vector<cv::Mat>& vH21,
+                           const std::vector<cv::Mat>& vH12, Consensus& out) const {
+        CheckHomographies(vKeys1, vKeys2, vMatches12, pack(vH21), pack(vH12), out);
+    }
+    void CheckFundamentals(const std::vector<KeyPoint>& vKeys1, const std::vector<KeyPoint>& vKeys2,
+                           const std::vector<int>& vMatches12, const std::vector<cv::Mat>& vF21, Consensus& out) const {
+        CheckFundamentals(vKeys1, vKeys2, vMatches12, pack(vF21), out);
+    }
+    void Check(const std::vector<KeyPoint>& vKeys1, const std::vector<KeyPoint>& vKeys2, const std::vector<int>& vMatches12,
+               const std::vector<cv::Mat>& vH21, const std::vector<cv::Mat>& vH12, const std::vector<cv::Mat>& vF21,
+               Consensus& out) const {
+        Check(vKeys1, vKeys2, vMatches12, pack(vH21), pack(vH12), pack(vF21), out);
+    }
+#endif
+
+private:
+    const FExtractor* extractor_;
+    float mSigma;
+};
+
+/* ---------------------------------------------------------------------------------------------------
  * The grid FAST detector of fast_cuda.h:19-25 / fast_cuda.cpp:70-132.  FASTGPU carries vilib::FASTGPU's
  * constructor (fast_gpu.h:46-56) and DetectorBase's read side (detector_base.h:48-57,75-80): detect() on an
  * 8-bit image replaces `Frame(image, 0, levels)` + `detect(frame->pyramid_)`; getPoints() holds one FeaturePoint

@@ -60,6 +60,7 @@ ABI_SYMBOLS = [
     "vslam_fe_get_rgbd_profile",
     "vslam_frame_in_frustum", "vslam_search_local_points_async", "vslam_search_local_points_wait",
     "vslam_search_local_points", "vslam_fe_get_local_points_profile",
+    "vslam_two_view_score_async", "vslam_two_view_score_wait", "vslam_two_view_score", "vslam_fe_get_two_view_profile",
     "vslam_kfdb_create", "vslam_kfdb_create_ex", "vslam_kfdb_destroy", "vslam_kfdb_add", "vslam_kfdb_erase",
     "vslam_kfdb_clear", "vslam_kfdb_clear_map", "vslam_kfdb_size", "vslam_kfdb_stats", "vslam_kfdb_query_async",
     "vslam_kfdb_query_wait", "vslam_kfdb_select_relocalization", "vslam_kfdb_select_nbest",
@@ -126,6 +127,90 @@ def frustum_params(Tcw, Ow, cam, log_scale_factor, img_size, viewing_cos_limit=0
     P.far_points = int(bool(far_points))
     P.th_far_points = float(np.float32(th_far_points))
     return P
+
+
+#: limits of two_view_score (VSLAM_TWO_VIEW_MAX_*)
+TWO_VIEW_MAX_JOBS, TWO_VIEW_MAX_HYP, TWO_VIEW_MAX_PAIRS = 32, 1024, 8192
+
+
+class _TwoViewJob(C.Structure):  # vslam_two_view_job
+    _fields_ = [("kps1", C.c_void_p), ("kps2", C.c_void_p), ("n1", C.c_int32), ("n2", C.c_int32),
+                ("matches12", C.c_void_p), ("kps_on_device", C.c_int32), ("matches_on_device", C.c_int32),
+                ("H21", C.c_void_p), ("H12", C.c_void_p), ("nH", C.c_int32), ("F21", C.c_void_p), ("nF", C.c_int32),
+                ("sigma", C.c_float)]
+
+
+class _TwoViewResult(C.Structure):  # vslam_two_view_result
+    _fields_ = [("n_pairs", C.c_int32), ("best_h", C.c_int32), ("best_f", C.c_int32), ("score_h", C.c_float),
+                ("score_f", C.c_float), ("pairs", C.c_void_p), ("scores_h", C.c_void_p), ("scores_f", C.c_void_p),
+                ("inliers_h", C.c_void_p), ("inliers_f", C.c_void_p)]
+
+
+class _TwoViewCall:
+    """the C arrays of one two-view call: jobs from dicts(kps1, kps2, matches12, H21, H12, F21[, sigma, n1, n2]) and the
+    caller storage of their results.  kps1 / kps2: KP_DTYPE arrays, or two device addresses (ints) with n1 / n2;
+    matches12: an int32 array, or a device address."""
+
+    def __init__(self, jobs):
+        self.n = len(jobs)
+        self.jobs = (_TwoViewJob * max(self.n, 1))()
+        self.res = (_TwoViewResult * max(self.n, 1))()
+        self.keep, self.out = [], []
+        for j, q in enumerate(jobs):
+            J, R = self.jobs[j], self.res[j]
+            kdev, mdev = isinstance(q["kps1"], int), isinstance(q["matches12"], int)
+            if kdev:
+                J.kps1, J.kps2, J.n1, J.n2 = q["kps1"], int(q["kps2"]), int(q["n1"]), int(q["n2"])
+            else:
+                k1, k2 = np.ascontiguousarray(q["kps1"], KP_DTYPE), np.ascontiguousarray(q["kps2"], KP_DTYPE)
+                self.keep += [k1, k2]
+                J.kps1, J.kps2, J.n1, J.n2 = k1.ctypes.data, k2.ctypes.data, len(k1), len(k2)
+            if mdev:
+                J.matches12 = q["matches12"]
+            else:
+                m = np.ascontiguousarray(q["matches12"], np.int32)
+                if len(m) != J.n1:
+                    raise ValueError("matches12 has %d entries for %d keypoints" % (len(m), J.n1))
+                self.keep.append(m)
+                J.matches12 = m.ctypes.data
+            J.kps_on_device, J.matches_on_device = int(kdev), int(mdev)
+            H21, H12, F21 = (np.ascontiguousarray(q[k], np.float32).reshape(-1, 9) for k in ("H21", "H12", "F21"))
+            if len(H21) != len(H12):
+                raise ValueError("H21 and H12 differ in length")
+            self.keep += [H21, H12, F21]
+            J.H21, J.H12, J.nH, J.F21, J.nF = H21.ctypes.data, H12.ctypes.data, len(H21), F21.ctypes.data, len(F21)
+            J.sigma = float(np.float32(q.get("sigma", 1.0)))
+            cap = max(min(J.n1, TWO_VIEW_MAX_PAIRS), 1)
+            o = dict(pairs=np.zeros((cap, 2), np.int32), scores_h=np.zeros(max(J.nH, 1), np.float32),
+                     scores_f=np.zeros(max(J.nF, 1), np.float32), inliers_h=np.zeros(cap, np.uint8),
+                     inliers_f=np.zeros(cap, np.uint8))
+            for k, a in o.items():
+                setattr(R, k, a.ctypes.data)
+            self.out.append(o)
+
+    def results(self):
+        """-> one dict per job with the fields of vslam_two_view_result; a job over the pair cap or with a bad entry has
+        n_pairs, no winner and empty masks"""
+        out = []
+        for j in range(self.n):
+            J, R, o = self.jobs[j], self.res[j], self.out[j]
+            n = R.n_pairs
+            scored = n if n <= TWO_VIEW_MAX_PAIRS else 0
+            out.append(dict(n_pairs=n, best_h=R.best_h, best_f=R.best_f, score_h=np.float32(R.score_h),
+                            score_f=np.float32(R.score_f), pairs=o["pairs"][:min(n, len(o["pairs"]))],
+                            scores_h=o["scores_h"][:J.nH], scores_f=o["scores_f"][:J.nF],
+                            inliers_h=o["inliers_h"][:scored], inliers_f=o["inliers_f"][:scored]))
+        return out
+
+
+def two_view_score_host(job, library=None):
+    """vslamh_two_view_score (libvslam_host.so; CPU tests and measurements, not a fallback): one job dict as for
+    FExtractor.two_view_score, host arrays only -> (rc, result dict)"""
+    L = library if library is not None else host_lib()
+    call = _TwoViewCall([job])
+    L.vslamh_two_view_score.argtypes = [C.POINTER(_TwoViewJob), C.POINTER(_TwoViewResult)]
+    rc = L.vslamh_two_view_score(call.jobs, call.res)
+    return rc, call.results()[0]
 
 
 class _SbpJob(C.Structure):  # vslam_sbp_job
@@ -438,6 +523,11 @@ def lib():
         L.vslam_fe_get_local_points_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_long)]
         L.vslam_search_local_points.argtypes = [vp, fp, vp, vp, i, i, vp, vp, i, vp, vp, f, f, vp, C.POINTER(i),
                                                 C.POINTER(i), C.POINTER(i), vp]
+        L.vslam_two_view_score_async.argtypes = [vp, i, C.POINTER(_TwoViewJob)]
+        L.vslam_two_view_score_wait.argtypes = [vp, C.POINTER(_TwoViewResult)]
+        L.vslam_two_view_score.argtypes = [vp, C.POINTER(_TwoViewJob), C.POINTER(_TwoViewResult)]
+        L.vslam_fe_get_two_view_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                    C.POINTER(C.c_long)]
         L.vslam_kfdb_create.argtypes = [i, i, i, C.POINTER(vp)]
         L.vslam_kfdb_create_ex.argtypes = [i, i, i, i, C.POINTER(vp)]
         L.vslam_kfdb_destroy.argtypes = [vp]
@@ -540,6 +630,7 @@ class FExtractor:
         h = C.c_void_p()
         _check(L.vslam_fe_create(C.byref(p), C.byref(h)))
         self._h = h
+        self._tv_call = None  # the C arrays of a two_view_score_async until its wait
         self.nfeatures, self.nlevels, self.width, self.height = nfeatures, nlevels, width, height
         self.scaleFactor = scaleFactor
         self.max_batch = max_batch
@@ -927,6 +1018,42 @@ class FExtractor:
         self.search_local_points_async(params, points, mp_desc, dev_cur_kps, dev_cur_desc, n_cur, cur_u_right, occupied, th,
                                        nnratio, n_mp)
         return self.search_local_points_wait(want_track)
+
+    def two_view_score_async(self, jobs):
+        """Enqueue MotionEstimator::CheckHomography / CheckFundamental of every hypothesis and the selection of
+        FindHomography / FindFundamental (motion_estimation.cpp:2096-2195, 2277-2440) for up to 32 frame pairs and return.
+        jobs: dicts(kps1, kps2, matches12, H21 (nH, 9), H12, F21 (nF, 9)[, sigma = 1.0]); kps1 / kps2 are KP_DTYPE arrays
+        (ukeypoints_) or two device addresses with n1 / n2 (slot_ukps_ptr, slot_dev_ptrs), matches12 an int32 array or a
+        device address.  The hypotheses are the caller's (ComputeH21 / ComputeF21)."""
+        call = _TwoViewCall(jobs)
+        _check(lib().vslam_two_view_score_async(self._h, call.n, call.jobs))
+        self._tv_call = call
+
+    def two_view_score_wait(self):
+        """-> one dict per job: n_pairs, pairs (n_pairs, 2), best_h, best_f (-1: no winner), score_h, score_f (SH, SF),
+        scores_h, scores_f (every hypothesis' score), inliers_h, inliers_f (the winner's, one byte per pair).  Raises
+        VslamError(ERR_UNSUPPORTED) when a job has more than 8192 pairs, ERR_INVALID on a matches12 entry >= n2; the
+        error carries .results."""
+        call, self._tv_call = self._tv_call, None
+        if call is None:
+            raise VslamError(ERR_INVALID, "nothing enqueued")
+        rc = lib().vslam_two_view_score_wait(self._h, call.res)
+        if rc != VSLAM_OK:
+            e = VslamError(rc, lib().vslam_last_error().decode())
+            e.results = call.results()
+            raise e
+        return call.results()
+
+    def two_view_score(self, jobs):
+        """two_view_score_async + two_view_score_wait"""
+        self.two_view_score_async(jobs)
+        return self.two_view_score_wait()
+
+    def get_two_view_profile(self):
+        """with set_profiling(True): (k_tv_pairs ms, k_tv_score ms, k_tv_select ms, calls) by HIP events, summed since"""
+        a, b, c, n = C.c_double(), C.c_double(), C.c_double(), C.c_long()
+        _check(lib().vslam_fe_get_two_view_profile(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(n)))
+        return a.value, b.value, c.value, n.value
 
     def grid_bounds(self):
         """-> (bounds as float32[4] in image_bounds() order, is_set); (0, width, 0, height) while none are set"""

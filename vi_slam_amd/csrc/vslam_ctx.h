@@ -1,7 +1,8 @@
 /* vslam_ctx.h -- private: the vslam_fe context (HBM layout, scratch, worker pool) shared by
  * vslam_context.hip (its life and accessors), vslam_upload.hip (host images into level 0), vslam_fe.hip (the extraction
  * pipeline) and by the matcher ABI: vslam_stereo.hip (stereo, RGB-D), vslam_match.hip (SearchForInitialization),
- * vslam_projection.hip (SearchByProjection family, Fuse, SearchLocalPoints), vslam_bow.hip and vslam_kfdb.hip. */
+ * vslam_projection.hip (SearchByProjection family, Fuse, SearchLocalPoints), vslam_two_view.hip (CheckHomography /
+ * CheckFundamental), vslam_bow.hip and vslam_kfdb.hip. */
 #ifndef VSLAM_CTX_H
 #define VSLAM_CTX_H
 #include <hip/hip_runtime.h>
@@ -181,6 +182,19 @@ struct vslam_fe {
     bool rgbd_timed = false;
     double rgbd_ms = 0;
     long rgbd_passes = 0;
+    /* two-view scoring (vslam_two_view.hip): job table | hypotheses | host inputs | results of every job; the gathered pairs
+     * and the flag bytes of every hypothesis stay in HBM */
+    vslam_staging tv;
+    vslam_dbuf<uint8_t> d_tv_scratch;
+    int tv_state = 0, tv_njobs = 0; /* 1: a scoring is in flight */
+    struct TvJobHost {              /* where a job's results start in the block, and the counts _wait copies by */
+        size_t o_hdr, o_pairs, o_sh, o_sf, o_ih, o_if;
+        int cap, nH, nF;
+    } tv_jobs[VSLAM_TWO_VIEW_MAX_JOBS] = {};
+    vslam_event ev_tv[4];       /* profiling: before k_tv_pairs | k_tv_score | k_tv_select | behind it */
+    bool tv_timed = false;
+    double tv_ms[3] = {0, 0, 0};
+    long tv_passes = 0;
     vslam_event ev_lp[3];       /* profiling: before k_frustum | between | behind k_frustum_compact */
     bool lp_timed = false;
     double lp_ms[2] = {0, 0};

@@ -2,6 +2,7 @@
 #include "vslam_host.h"
 #include "vslam_undistort.h"
 #include "vslam_frustum.h"
+#include "vslam_two_view.h"
 #include "vslam_matchdev.h"
 
 #include <algorithm>
@@ -1113,6 +1114,68 @@ int vslamh_local_points_finish(const int32_t* match_compact, int n_cur, const in
         match_cur[i] = (k >= 0 && k < n_kept) ? orig_index[k] : -1;
     }
     return VSLAM_OK;
+}
+
+/* vslam_two_view_score on the host, every pointer of the job a HOST pointer (the placement fields are not read): the pair
+ * list, CheckHomography / CheckFundamental for every hypothesis by the shared vslam_two_view.h code, the selection.  Same
+ * limits, error codes and results as the device entry (include/vslam_fe.h).  CPU tests and the stand-alone demo; the
+ * product runs k_tv_pairs / k_tv_score / k_tv_select. */
+int vslamh_two_view_score(const vslam_two_view_job* job, vslam_two_view_result* result) {
+    if (!job || !result) return VSLAM_ERR_INVALID;
+    const vslam_two_view_job& q = *job;
+    if (q.n1 < 0 || q.n1 > 65536 || q.n2 < 0 || q.nH < 0 || q.nH > VSLAM_TWO_VIEW_MAX_HYP || q.nF < 0 ||
+        q.nF > VSLAM_TWO_VIEW_MAX_HYP || (q.n1 && (!q.kps1 || !q.matches12)) || (q.n1 && q.n2 && !q.kps2) ||
+        (q.nH && (!q.H21 || !q.H12)) || (q.nF && !q.F21) || !std::isfinite(q.sigma) || q.sigma == 0.0f)
+        return VSLAM_ERR_INVALID;
+    vslam_two_view_result& R = *result;
+    const int cap = std::min(q.n1, VSLAM_TWO_VIEW_MAX_PAIRS);
+    std::vector<float> pts;
+    std::vector<int32_t> pairs;
+    int n = 0;
+    bool err = false;
+    for (int i = 0; i < q.n1; i++) { /* motion_estimation.cpp:2020-2029 */
+        const int32_t m = q.matches12[i];
+        if (m >= q.n2) err = true;
+        if (m < 0 || m >= q.n2) continue;
+        if (n < cap) {
+            pairs.insert(pairs.end(), {i, m});
+            pts.insert(pts.end(), {q.kps1[i].x, q.kps1[i].y, q.kps2[m].x, q.kps2[m].y});
+        }
+        n++;
+    }
+    const int used = (err || n > cap) ? 0 : n;
+    const float inv = vslam_tv::inv_sigma_square(q.sigma);
+    R.n_pairs = n;
+    if (R.pairs && !pairs.empty()) memcpy(R.pairs, pairs.data(), pairs.size() * 4);
+    std::vector<uint8_t> cur((size_t)used);
+    for (int model = 0; model < 2; model++) {
+        const int nhyp = model ? q.nF : q.nH;
+        float* scores = model ? R.scores_f : R.scores_h;
+        uint8_t* mask = model ? R.inliers_f : R.inliers_h;
+        vslam_tv::Best best = vslam_tv::best_none();
+        if (mask && used) memset(mask, 0, (size_t)used);
+        for (int it = 0; it < nhyp; it++) {
+            const vslam_tv::Mat3 A = vslam_tv::load_mat3((model ? q.F21 : q.H21) + (size_t)it * 9);
+            const vslam_tv::Mat3 B = model ? A : vslam_tv::load_mat3(q.H12 + (size_t)it * 9);
+            float score = 0.0f;
+            for (int p = 0; p < used; p++) {
+                const float* x = &pts[4 * (size_t)p];
+                const vslam_tv::Terms t = model ? vslam_tv::check_f(A, x[0], x[1], x[2], x[3], inv)
+                                                : vslam_tv::check_h(A, B, x[0], x[1], x[2], x[3], inv);
+                score = vslam_tv::fadd(score, t.t1);
+                score = vslam_tv::fadd(score, t.t2);
+                cur[p] = t.in ? 1 : 0;
+            }
+            score = vslam_tv::report_score(score);
+            if (scores) scores[it] = score;
+            const vslam_tv::Best was = best;
+            best = vslam_tv::best_take(best, score, it);
+            if (best.index != was.index && mask && used) memcpy(mask, cur.data(), (size_t)used);
+        }
+        (model ? R.best_f : R.best_h) = best.index;
+        (model ? R.score_f : R.score_h) = best.index >= 0 ? best.score : 0.0f;
+    }
+    return err ? VSLAM_ERR_INVALID : n > cap ? VSLAM_ERR_UNSUPPORTED : VSLAM_OK;
 }
 
 uint64_t vslamh_layout(uint64_t align, const uint64_t* sizes, int n, uint64_t* off) {

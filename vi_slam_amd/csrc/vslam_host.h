@@ -219,4 +219,6 @@ extern "C" uint64_t vslamh_layout(uint64_t align, const uint64_t* sizes, int n, 
 /* vslam_host.cpp: index map-back and over-capacity decision of vslam_search_local_points_wait */
 extern "C" int vslamh_local_points_finish(const int32_t* match_compact, int n_cur, const int32_t* orig_index, int n_kept,
                                           int capacity, int32_t* match_cur);
+/* vslam_host.cpp: vslam_two_view_score over host arrays by the shared vslam_two_view.h code (CPU tests, the demo) */
+extern "C" int vslamh_two_view_score(const vslam_two_view_job* job, vslam_two_view_result* result);
 #endif

@@ -109,6 +109,10 @@ struct FrustumArgsDev;
 struct FrustumCompactDev;
 void vk_frustum(hipStream_t st, const FrustumArgsDev& A);
 void vk_frustum_compact(hipStream_t st, const FrustumCompactDev& A);
+/* the pair list, every hypothesis' score and flags, the selection (vslam_two_view.hip): njobs TvJobDev in HBM, max_groups =
+ * the most 64-hypothesis groups (H and F together) of any job, ev = four events around the three launches or NULL */
+struct TvJobDev;
+void vk_two_view(hipStream_t st, const TvJobDev* jobs, int njobs, int max_groups, hipEvent_t* ev);
 void vk_pack_slots(hipStream_t st, const vslam_kp* kps, const uint8_t* desc, const int32_t* counts, int cap, int first,
                    int nslots, uint8_t* dst, size_t slot_bytes);
 void vk_gather_rows32(hipStream_t st, const uint8_t* src, const int32_t* idx, int n, uint8_t* dst);
