@@ -1187,7 +1187,12 @@ k_fast_bands(const uint8_t* __restrict__ pyr, size_t slot_stride, BatchSrc src, 
             }
             if (nD + nB > lcap) { /* block-uniform: the two lists ran into each other -- these rows again, half as many */
                 CR = max(2, lcap >> (LOGW + 1));
-                par ^= 1; /* the other counter is zero; this one is zeroed one chunk later, like every used one */
+                /* ... counted from zero in the same counter.  (The other counter is zero only before the first chunk of the
+                 * first stage: behind any other chunk it still holds that chunk's totals, and a sweep that started from them
+                 * put its entries behind stale ones or, past lcap again, below and above the list.) */
+                __syncthreads(); /* every thread has read the totals */
+                if (tid == 0) s_cnt[par] = 0u;
+                __syncthreads();
                 continue;
             }
             if (tid == 0) s_cnt[par ^ 1] = 0u; /* the next chunk's / stage's counter: its last readers passed a barrier ago */
