@@ -818,6 +818,91 @@ int vslam_bow_assemble(int weighting, int norm, const int32_t* word_id, const do
                        int n, int32_t* bow_ids, double* bow_vals, int* n_bow, int32_t* fv_nodes, int32_t* fv_off,
                        int32_t* fv_feat, int* n_fv);
 
+/* ---------------------------------------------------------------- Vocabulary::create / save (training a vocabulary)
+ *
+ * DBoW3::Vocabulary::create(training_features, k, L, weighting, scoring) (thirdparty/DBoW3/DBoW3/src/Vocabulary.cpp:
+ * 157-571; tools/createVoc/createVoc.cpp:53-57 is its caller): hierarchical k-means over 32-byte binary descriptors
+ * -- k-means++ seeding (initiateClustersKMpp, :409-491), Lloyd passes with the bitwise majority of DescManip::meanValue
+ * (DescManip.cpp:25-73) until the association repeats, strict `<` so that the lowest cluster wins a tie, children in
+ * cluster order, word ids in node-id order, weights log(NDocs / Ni) over the training documents -- and
+ * Vocabulary::save (:1066-1079).  Everything is integer arithmetic or a libm double, so the device, the host twin
+ * (vslamh_voc_train in libvslam_host.so) and the tests' numpy restatement agree bit for bit.
+ *
+ * ONE deviation from the reference: it draws from the process-global rand() in depth-first order, which would serialise
+ * the tree.  Here a draw is a pure function of (seed, path from the root, draw counter of the node), the functions
+ * below; every use is the reference's own expression with vslamvoc_draw in place of rand():
+ *   first centre of a node with n features      vslamvoc_draw(key, 0, mask) % n
+ *   cut_d = (double(r) / double(RAND_MAX)) * dist_sum, RAND_MAX = 2147483647, each operation rounded on its own,
+ *           redrawn while r == 0 (cut_d == 0.0); after 64 zero draws in a row r = 1 (unreachable with the default mask).
+ * j counts the draws of the node, redraws included. */
+#if defined(__HIPCC__)
+#define VSLAM_VOC_HD __host__ __device__
+#else
+#define VSLAM_VOC_HD
+#endif
+static inline VSLAM_VOC_HD uint64_t vslamvoc_mix(uint64_t x) {
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+/* key of the root: vslamvoc_mix(seed); key of child c (cluster index) of a node with key `parent` */
+static inline VSLAM_VOC_HD uint64_t vslamvoc_child_key(uint64_t parent, int c) {
+    return vslamvoc_mix(parent ^ ((uint64_t)(c + 1) * 0x9E3779B97F4A7C15ull));
+}
+/* 31 bits in place of rand() */
+static inline VSLAM_VOC_HD uint32_t vslamvoc_draw(uint64_t key, uint32_t j, uint32_t rand_mask) {
+    return (uint32_t)(vslamvoc_mix(key ^ (((uint64_t)j + 1) * 0xD1B54A32D192ED03ull)) >> 33) & rand_mask;
+}
+
+#define VSLAM_VOC_MAX_FEATURES (1 << 24)
+typedef struct vslam_voc_train_params {
+    int32_t k;          /* branching factor, 2..64 (the reference tool uses 35) */
+    int32_t L;          /* depth levels, 1..10 */
+    int32_t weighting;  /* 0 TF_IDF, 1 TF, 2 IDF, 3 BINARY */
+    int32_t scoring;    /* 0 L1_NORM .. 5 DOT_PRODUCT; only stored in the file */
+    uint64_t seed;
+    uint32_t rand_mask; /* 0x7fffffff; a smaller mask is a diagnostic (mask 3: a quarter of the draws are zero).  0 is invalid */
+    int32_t max_iter;   /* bound on the Lloyd passes of one node (assign passes, the first included); 0 = 10000.  Not in the
+                           reference: a node that reaches it keeps the state of its last pass and is counted in the stats */
+} vslam_voc_train_params;
+typedef struct vslam_voc_train_stats {
+    int32_t nodes, words, deepest_level; /* nodes includes the root */
+    int32_t max_passes;                  /* Lloyd passes: most of any node, and the sum over the k-means nodes */
+    int64_t total_passes;
+    int32_t hit_max_iter;                /* nodes stopped by max_iter */
+    int32_t early_stops;                 /* seedings that ended with fewer than k centres (dist_sum == 0) */
+    int64_t draws, redraws;              /* vslamvoc_draw calls; those of them that were zero under cut_d */
+    int32_t small_nodes;                 /* HKmeansStep calls with n <= k: one cluster per feature */
+    int32_t single_leaves;               /* children with one feature above level L: leaves, no recursion */
+    int64_t empty_groups;               /* meanValue calls on an empty group (the centre stays) */
+    float ms_seed, ms_assign, ms_mean, ms_partition, ms_weights, ms_total; /* HIP events; the host twin fills ms_total */
+} vslam_voc_train_stats;
+/* desc: n_features x 32 bytes, n_features = doc_offsets[n_docs] in 1..VSLAM_VOC_MAX_FEATURES, in host memory
+ * (desc_location VSLAM_IMGS_HOST) or in HBM of `device` (VSLAM_IMGS_DEVICE); document d owns the rows doc_offsets[d] ..
+ * doc_offsets[d+1]) (n_docs + 1 non-decreasing entries from 0; empty documents are allowed).  *out is an in-memory
+ * vslam_voc_file (format 0) for vslam_voc_file_info / _arrays / _save / _upload / _close: the flat table in
+ * vslam_voc_create's layout and in DBoW3's node order (a HKmeansStep call numbers its children consecutively, then
+ * descends into them in turn).  stats may be NULL.  Bad parameters or offsets return VSLAM_ERR_INVALID before anything
+ * is launched.  The call is synchronous and runs on a stream of its own: a device block must be complete before it.
+ * vslamh_voc_train (libvslam_host.so only) is the same on one CPU core: tests, demo, timing baseline --
+ * not a fallback. */
+int vslam_voc_train(int device, const vslam_voc_train_params* params, const uint8_t* desc, int desc_location,
+                    const int64_t* doc_offsets, int n_docs, vslam_voc_file** out, vslam_voc_train_stats* stats);
+int vslamh_voc_train(const vslam_voc_train_params* params, const uint8_t* desc, const int64_t* doc_offsets, int n_docs,
+                     vslam_voc_file** out, vslam_voc_train_stats* stats);
+/* Vocabulary::save(filename) for a name without ".yml": the plain binary stream (toStream(out, false), :1292-1366), which
+ * Vocabulary::load and vslam_voc_load read under any name.  Works for trained and for loaded files (tools/convertVoc). */
+int vslam_voc_file_save(const vslam_voc_file* f, const char* path);
+/* an in-memory file (format 0) from a flat node table in vslam_voc_create's layout, with the same checks; n_words is
+ * the number of leaves.  For callers that hold the arrays and want _save or _upload. */
+int vslam_voc_file_from_arrays(int branching, int depth_levels, int scoring, int weighting, int n_nodes,
+                               const int32_t* child_start, const int32_t* child_count, const int32_t* child_ids,
+                               int n_child_ids, const uint8_t* node_desc, const double* node_weight,
+                               const int32_t* node_word_id, vslam_voc_file** out);
+/* the upload half of vslam_voc_load */
+int vslam_voc_file_upload(int device, const vslam_voc_file* f, vslam_voc** out);
+
 /* ---------------------------------------------------------------- KeyFrameDatabase (relocalisation / loop candidates)
  *
  * KeyFrameDatabase (src/datastructures/keyframedatabase.cpp) between Frame::ComputeBoW and SearchByBoW: the keyframes'

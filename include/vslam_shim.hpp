@@ -1140,5 +1140,110 @@ private:
 };
 
 } /* namespace geometry */
+
+/* ---------------------------------------------------------------------------------------------------
+ * DBoW3::Vocabulary (thirdparty/DBoW3/DBoW3/src/Vocabulary.h), the part tools/createVoc/createVoc.cpp:53-57 and the
+ * apps use: construct with (k, L, weighting, scoring), create(training_features), save(filename), load(filename).
+ * There is no cv::Mat here: the descriptors of one image are a row-major block of rows x 32 bytes (what the reference's
+ * `cv::Mat descriptors` of an ORB detector holds).  create() trains on the device (vslam_voc_train) and leaves the
+ * vocabulary uploaded; device() is what vslam_bow_transform takes.  The draws come from setSeed()'s value, not from
+ * rand(): the same seed gives the same vocabulary.
+ * ------------------------------------------------------------------------------------------------- */
+namespace DBoW3 {
+enum WeightingType { TF_IDF, TF, IDF, BINARY };
+enum ScoringType { L1_NORM, L2_NORM, CHI_SQUARE, KL, BHATTACHARYYA, DOT_PRODUCT };
+struct Descriptors { /* non-owning: rows x 32 bytes */
+    const uint8_t* data;
+    int rows;
+};
+class Vocabulary {
+public:
+    explicit Vocabulary(int k = 10, int L = 5, WeightingType weighting = TF_IDF, ScoringType scoring = L1_NORM, int device = 0)
+        : k_(k), L_(L), weighting_(weighting), scoring_(scoring), device_(device) {}
+    explicit Vocabulary(const std::string& filename, int device = 0) : device_(device) { load(filename); }
+    ~Vocabulary() { clear(); }
+    Vocabulary(const Vocabulary&) = delete;
+    Vocabulary& operator=(const Vocabulary&) = delete;
+
+    void setSeed(uint64_t seed) { seed_ = seed; }
+    void create(const std::vector<Descriptors>& training_features) {
+        std::vector<uint8_t> all;
+        std::vector<int64_t> offsets(1, 0);
+        for (const Descriptors& d : training_features) {
+            if (d.rows > 0) all.insert(all.end(), d.data, d.data + (size_t)d.rows * 32);
+            offsets.push_back(offsets.back() + (d.rows > 0 ? d.rows : 0));
+        }
+        vslam_voc_train_params p;
+        std::memset(&p, 0, sizeof(p));
+        p.k = k_, p.L = L_, p.weighting = (int)weighting_, p.scoring = (int)scoring_, p.seed = seed_, p.rand_mask = 0x7fffffffu;
+        vslam_voc_file* f = nullptr;
+        geometry::check(vslam_voc_train(device_, &p, all.empty() ? (const uint8_t*)"" : all.data(), VSLAM_IMGS_HOST, offsets.data(),
+                                        (int)training_features.size(), &f, &stats_));
+        adopt(f);
+    }
+    void create(const std::vector<Descriptors>& training_features, int k, int L) {
+        k_ = k, L_ = L;
+        create(training_features);
+    }
+    void create(const std::vector<Descriptors>& training_features, int k, int L, WeightingType weighting, ScoringType scoring) {
+        k_ = k, L_ = L, weighting_ = weighting, scoring_ = scoring;
+        create(training_features);
+    }
+    /* Vocabulary::save for a name without ".yml": the plain binary stream */
+    void save(const std::string& filename) const {
+        if (!file_) throw std::runtime_error("DBoW3::Vocabulary::save: empty vocabulary");
+        check_file(vslam_voc_file_save(file_, filename.c_str()));
+    }
+    void load(const std::string& filename) {
+        vslam_voc_file* f = nullptr;
+        check_file(vslam_voc_file_open(filename.c_str(), &f));
+        adopt(f);
+        int k = 0, L = 0, s = 0, w = 0;
+        vslam_voc_file_info(file_, &k, &L, &s, &w, nullptr, nullptr, nullptr, nullptr, nullptr);
+        k_ = k, L_ = L, scoring_ = (ScoringType)s, weighting_ = (WeightingType)w;
+    }
+    void clear() {
+        vslam_voc_destroy(voc_);
+        vslam_voc_file_close(file_);
+        voc_ = nullptr;
+        file_ = nullptr;
+    }
+    bool empty() const { return !file_; }
+    unsigned size() const { /* number of words */
+        int n = 0;
+        if (file_) vslam_voc_file_info(file_, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &n, nullptr, nullptr);
+        return (unsigned)n;
+    }
+    int getBranchingFactor() const { return k_; }
+    int getDepthLevels() const { return L_; }
+    const vslam_voc* device() const { return voc_; }
+    const vslam_voc_file* file() const { return file_; }
+    const vslam_voc_train_stats& stats() const { return stats_; }
+
+private:
+    static void check_file(int rc) {
+        if (rc != VSLAM_OK) throw std::runtime_error(std::string("libvslam_fe: ") + vslam_voc_file_last_error());
+    }
+    void adopt(vslam_voc_file* f) {
+        vslam_voc* v = nullptr;
+        const int rc = vslam_voc_file_upload(device_, f, &v);
+        if (rc != VSLAM_OK) {
+            vslam_voc_file_close(f);
+            geometry::check(rc);
+        }
+        clear();
+        file_ = f;
+        voc_ = v;
+    }
+    int k_ = 10, L_ = 5;
+    WeightingType weighting_ = TF_IDF;
+    ScoringType scoring_ = L1_NORM;
+    int device_ = 0;
+    uint64_t seed_ = 0;
+    vslam_voc_file* file_ = nullptr;
+    vslam_voc* voc_ = nullptr;
+    vslam_voc_train_stats stats_ = vslam_voc_train_stats();
+};
+} /* namespace DBoW3 */
 } /* namespace VSLAM_SHIM_NAMESPACE */
 #endif /* VSLAM_SHIM_HPP */

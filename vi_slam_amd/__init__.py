@@ -53,6 +53,7 @@ ABI_SYMBOLS = [
     "vslam_fe_stage_images_async", "vslam_fe_octree_stats", "vslam_fe_delivery_stats", "vslam_dbg_search_init_replay_stats", "vslam_tuning_init", "vslam_fe_set_tuning", "vslam_stereo_fisheye_candidates", "vslam_hamming_top2_batch", "vslam_hamming_top2_batch_dev_async", "vslam_fe_set_fast_gate",
     "vslam_voc_load", "vslam_voc_file_open", "vslam_voc_file_close", "vslam_voc_file_info", "vslam_voc_file_arrays",
     "vslam_voc_file_last_error", "vslam_dbg_qlz_decode",
+    "vslam_voc_train", "vslam_voc_file_save", "vslam_voc_file_from_arrays", "vslam_voc_file_upload",
     "vslam_fe_set_camera", "vslam_fe_slot_ukps", "vslam_fe_ukps_copy", "vslam_undistort_points", "vslam_fe_image_bounds",
     "vslam_fe_set_grid_bounds", "vslam_fe_get_grid_bounds",
     "vslam_search_for_initialization_ex", "vslam_search_for_initialization_batch_ex", "vslam_search_init_dev_async_ex",
@@ -312,6 +313,10 @@ def bind_voc_file(L):
     L.vslam_voc_file_last_error.restype = C.c_char_p
     L.vslam_dbg_qlz_decode.argtypes = [C.c_char_p, C.c_size_t, vp, C.c_size_t, vp]
     L.vslam_dbg_qlz_decode.restype = C.c_long
+    L.vslam_voc_file_save.argtypes = [vp, C.c_char_p]
+    L.vslam_voc_file_from_arrays.argtypes = [C.c_int] * 5 + [vp, vp, vp, C.c_int, vp, vp, vp, vp]
+    if hasattr(L, "vslamh_voc_train"):  # libvslam_host.so: the one-core twin of vslam_voc_train
+        L.vslamh_voc_train.argtypes = [vp, vp, vp, C.c_int, vp, vp]
     return L
 
 
@@ -335,7 +340,7 @@ def host_lib():
     """libvslam_host.so: the GPU-free host logic (selection stages, file readers)."""
     global _host_lib
     if _host_lib is None:
-        _host_lib = bind_kfdb_select(C.CDLL(HOST_LIB_PATH))
+        _host_lib = bind_voc_file(bind_kfdb_select(C.CDLL(HOST_LIB_PATH)))
     return _host_lib
 
 
@@ -440,6 +445,8 @@ def lib():
         L.vslam_voc_destroy.argtypes = [vp]
         L.vslam_voc_load.argtypes = [i, C.c_char_p, vp]
         bind_voc_file(L)
+        L.vslam_voc_train.argtypes = [i, vp, vp, i, vp, i, vp, vp]
+        L.vslam_voc_file_upload.argtypes = [i, vp, vp]
         L.vslam_voc_destroy.restype = None
         L.vslam_voc_info.argtypes = [vp, vp, vp, vp, vp]
         L.vslam_bow_transform.argtypes = [vp, vp, vp, i, i, vp, vp, vp]
@@ -1584,7 +1591,30 @@ def bow_assemble(weighting, norm, word, weight, nid):
                 fv_feat=ff[:fo[nf.value]])
 
 
-VOC_FORMATS = {1: "dbow3-binary", 2: "dbow3-binary-quicklz", 3: "dbow3-text"}
+VOC_FORMATS = {0: "trained", 1: "dbow3-binary", 2: "dbow3-binary-quicklz", 3: "dbow3-text"}
+
+
+def _voc_file_dict(L, h):
+    """the flat node table behind a vslam_voc_file handle, copied into a dict"""
+    iv = [C.c_int() for _ in range(9)]
+    L.vslam_voc_file_info(h, *[C.byref(x) for x in iv])
+    k, depth, scoring, weighting, norm, n_nodes, n_words, n_child, fmt = (x.value for x in iv)
+    ptrs = [C.c_void_p() for _ in range(6)]
+    L.vslam_voc_file_arrays(h, *[C.byref(x) for x in ptrs])
+
+    def arr(ptr, n, ctype, dtype):
+        if n == 0:
+            return np.zeros(0, dtype)
+        return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), (n,)).astype(dtype, copy=True)
+
+    return dict(k=k, L=depth, scoring=scoring, weighting=weighting, norm=norm, n_words=n_words,
+                format=VOC_FORMATS.get(fmt, str(fmt)),
+                child_start=arr(ptrs[0], n_nodes, C.c_int32, np.int32),
+                child_count=arr(ptrs[1], n_nodes, C.c_int32, np.int32),
+                child_ids=arr(ptrs[2], n_child, C.c_int32, np.int32),
+                desc=arr(ptrs[3], n_nodes * 32, C.c_uint8, np.uint8).reshape(n_nodes, 32),
+                weight=arr(ptrs[4], n_nodes, C.c_double, np.float64),
+                word_id=arr(ptrs[5], n_nodes, C.c_int32, np.int32))
 
 
 def read_vocabulary_file(path, library=None):
@@ -1596,27 +1626,102 @@ def read_vocabulary_file(path, library=None):
     if rc != VSLAM_OK:
         raise VslamError(rc, (L.vslam_voc_file_last_error() or b"").decode())
     try:
-        iv = [C.c_int() for _ in range(9)]
-        L.vslam_voc_file_info(h, *[C.byref(x) for x in iv])
-        k, depth, scoring, weighting, norm, n_nodes, n_words, n_child, fmt = (x.value for x in iv)
-        ptrs = [C.c_void_p() for _ in range(6)]
-        L.vslam_voc_file_arrays(h, *[C.byref(x) for x in ptrs])
-
-        def arr(ptr, n, ctype, dtype):
-            if n == 0:
-                return np.zeros(0, dtype)
-            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), (n,)).astype(dtype, copy=True)
-
-        return dict(k=k, L=depth, scoring=scoring, weighting=weighting, norm=norm, n_words=n_words,
-                    format=VOC_FORMATS.get(fmt, str(fmt)),
-                    child_start=arr(ptrs[0], n_nodes, C.c_int32, np.int32),
-                    child_count=arr(ptrs[1], n_nodes, C.c_int32, np.int32),
-                    child_ids=arr(ptrs[2], n_child, C.c_int32, np.int32),
-                    desc=arr(ptrs[3], n_nodes * 32, C.c_uint8, np.uint8).reshape(n_nodes, 32),
-                    weight=arr(ptrs[4], n_nodes, C.c_double, np.float64),
-                    word_id=arr(ptrs[5], n_nodes, C.c_int32, np.int32))
+        return _voc_file_dict(L, h)
     finally:
         L.vslam_voc_file_close(h)
+
+
+class _VocTrainParams(C.Structure):  # vslam_voc_train_params
+    _fields_ = [("k", C.c_int32), ("L", C.c_int32), ("weighting", C.c_int32), ("scoring", C.c_int32),
+                ("seed", C.c_uint64), ("rand_mask", C.c_uint32), ("max_iter", C.c_int32)]
+
+
+class _VocTrainStats(C.Structure):  # vslam_voc_train_stats
+    _fields_ = [("nodes", C.c_int32), ("words", C.c_int32), ("deepest_level", C.c_int32), ("max_passes", C.c_int32),
+                ("total_passes", C.c_int64), ("hit_max_iter", C.c_int32), ("early_stops", C.c_int32),
+                ("draws", C.c_int64), ("redraws", C.c_int64), ("small_nodes", C.c_int32), ("single_leaves", C.c_int32),
+                ("empty_groups", C.c_int64), ("ms_seed", C.c_float), ("ms_assign", C.c_float), ("ms_mean", C.c_float),
+                ("ms_partition", C.c_float), ("ms_weights", C.c_float), ("ms_total", C.c_float)]
+
+
+def _train_vocabulary_handle(desc, doc_offsets, k, L, weighting, scoring, seed, rand_mask, max_iter, device, library):
+    """-> (library, vslam_voc_file handle, stats dict); the caller closes the handle"""
+    host = library is not None and hasattr(library, "vslamh_voc_train")
+    lb = library if library is not None else lib()
+    off = np.ascontiguousarray(doc_offsets, np.int64)
+    if off.ndim != 1 or len(off) < 2:
+        raise VslamError(ERR_INVALID, "doc_offsets holds n_docs + 1 entries")
+    keep = None
+    if hasattr(desc, "data_ptr"):  # a device tensor: trained in place
+        if host:
+            raise VslamError(ERR_INVALID, "the host twin takes host descriptors")
+        keep = desc.contiguous()
+        if keep.numel() * keep.element_size() < int(off[-1]) * 32 or not keep.is_cuda:
+            raise VslamError(ERR_INVALID, "desc must be a device tensor of at least doc_offsets[-1] x 32 bytes")
+        ptr, where = C.c_void_p(keep.data_ptr()), IMGS_DEVICE
+    else:
+        keep = np.ascontiguousarray(desc, np.uint8)
+        if keep.size < int(off[-1]) * 32:
+            raise VslamError(ERR_INVALID, "desc must hold doc_offsets[-1] x 32 bytes")
+        ptr, where = _p(keep), IMGS_HOST
+    P = _VocTrainParams(int(k), int(L), int(weighting), int(scoring), int(seed) & (2 ** 64 - 1), int(rand_mask), int(max_iter))
+    S, h = _VocTrainStats(), C.c_void_p()
+    if host:
+        rc = lb.vslamh_voc_train(C.byref(P), ptr, _p(off), len(off) - 1, C.byref(h), C.byref(S))
+    else:
+        rc = lb.vslam_voc_train(int(device), C.byref(P), ptr, where, _p(off), len(off) - 1, C.byref(h), C.byref(S))
+    if rc != VSLAM_OK:
+        msg = lb.vslam_voc_file_last_error() if (host or rc == ERR_INVALID) else lb.vslam_last_error()
+        raise VslamError(rc, (msg or b"").decode())
+    return lb, h, {name: getattr(S, name) for name, _ in _VocTrainStats._fields_}
+
+
+def train_vocabulary(desc, doc_offsets, k=10, L=5, weighting=0, scoring=0, seed=0, rand_mask=0x7fffffff, max_iter=0,
+                     device=0, library=None):
+    """DBoW3::Vocabulary::create(training_features, k, L, weighting, scoring) on the device (vslam_voc_train): desc is
+    an (N, 32) uint8 numpy array or a device tensor of N x 32 bytes, document d owns the rows doc_offsets[d] ..
+    doc_offsets[d+1]).  Returns read_vocabulary_file's dict (DBoW3's node order) plus "stats" (vslam_voc_train_stats).
+    library=host_lib() runs the one-core host twin instead (tests and timing baselines; not a fallback)."""
+    lb, h, stats = _train_vocabulary_handle(desc, doc_offsets, k, L, weighting, scoring, seed, rand_mask, max_iter, device,
+                                            library)
+    try:
+        voc = _voc_file_dict(lb, h)
+    finally:
+        lb.vslam_voc_file_close(h)
+    voc["stats"] = stats
+    return voc
+
+
+def _voc_file_from_dict(lb, voc):
+    cs = np.ascontiguousarray(voc["child_start"], np.int32)
+    cc = np.ascontiguousarray(voc["child_count"], np.int32)
+    ci = np.ascontiguousarray(voc["child_ids"], np.int32)
+    nd = np.ascontiguousarray(voc["desc"], np.uint8)
+    nw = np.ascontiguousarray(voc["weight"], np.float64)
+    wi = np.ascontiguousarray(voc["word_id"], np.int32)
+    h = C.c_void_p()
+    rc = lb.vslam_voc_file_from_arrays(int(voc["k"]), int(voc["L"]), int(voc.get("scoring", 0)), int(voc.get("weighting", 0)),
+                                       len(cs), _p(cs), _p(cc), _p(ci), len(ci), _p(nd), _p(nw), _p(wi), C.byref(h))
+    if rc != VSLAM_OK:
+        raise VslamError(rc, (lb.vslam_voc_file_last_error() or b"").decode())
+    return h
+
+
+def save_vocabulary_file(voc, path, library=None):
+    """DBoW3::Vocabulary::save(filename) for a name without ".yml" (vslam_voc_file_save; no GPU needed): the plain binary
+    stream, which Vocabulary.load and read_vocabulary_file read under any name.  voc is a dict in read_vocabulary_file's
+    layout, trained or loaded; returns what read_vocabulary_file(path) would."""
+    lb = library if library is not None else lib()
+    h = _voc_file_from_dict(lb, voc)
+    try:
+        rc = lb.vslam_voc_file_save(h, os.fsencode(path))
+        if rc != VSLAM_OK:
+            raise VslamError(rc, (lb.vslam_voc_file_last_error() or b"").decode())
+        out = _voc_file_dict(lb, h)
+    finally:
+        lb.vslam_voc_file_close(h)
+    out["format"] = VOC_FORMATS[1]
+    return out
 
 
 class Vocabulary:
@@ -1645,6 +1750,26 @@ class Vocabulary:
         iv = [C.c_int() for _ in range(4)]
         lib().vslam_voc_info(h, *[C.byref(x) for x in iv])
         self.L, self.weighting, self.norm, self.n_nodes = (x.value for x in iv)
+        return self
+
+    @classmethod
+    def from_trained(cls, desc, doc_offsets, k=10, L=5, weighting=0, scoring=0, seed=0, rand_mask=0x7fffffff, max_iter=0,
+                     device=0):
+        """Vocabulary::create on the device, then the upload half of load: the vocabulary stays in HBM, ready for
+        transform.  self.trained is train_vocabulary's dict."""
+        lb, h, stats = _train_vocabulary_handle(desc, doc_offsets, k, L, weighting, scoring, seed, rand_mask, max_iter,
+                                                device, None)
+        self = cls.__new__(cls)
+        try:
+            self.trained = _voc_file_dict(lb, h)
+            self.trained["stats"] = stats
+            v = C.c_void_p()
+            _check(lb.vslam_voc_file_upload(device, h, C.byref(v)))
+            self._h = v
+        finally:
+            lb.vslam_voc_file_close(h)
+        self.L, self.weighting, self.norm = self.trained["L"], self.trained["weighting"], self.trained["norm"]
+        self.n_nodes = len(self.trained["child_start"])
         return self
 
     def close(self):

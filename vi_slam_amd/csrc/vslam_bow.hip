@@ -75,15 +75,23 @@ extern "C" int vslam_voc_load(int device, const char* path, vslam_voc** out) {
         g_err = vslam_voc_file_last_error();
         return rc;
     }
+    rc = vslam_voc_file_upload(device, f, out);
+    vslam_voc_file_close(f);
+    return rc;
+}
+
+extern "C" int vslam_voc_file_upload(int device, const vslam_voc_file* f, vslam_voc** out) {
+    if (!f || !out) {
+        g_err = "invalid arguments";
+        return VSLAM_ERR_INVALID;
+    }
     int L = 0, weighting = 0, norm = 0, n_nodes = 0, n_child = 0;
     const int32_t *cs, *cc, *ci, *wi;
     const uint8_t* nd;
     const double* nw;
     vslam_voc_file_info(f, nullptr, &L, nullptr, &weighting, &norm, &n_nodes, nullptr, &n_child, nullptr);
     vslam_voc_file_arrays(f, &cs, &cc, &ci, &nd, &nw, &wi);
-    rc = vslam_voc_create(device, L, weighting, norm, n_nodes, cs, cc, ci, n_child, nd, nw, wi, out);
-    vslam_voc_file_close(f);
-    return rc;
+    return vslam_voc_create(device, L, weighting, norm, n_nodes, cs, cc, ci, n_child, nd, nw, wi, out);
 }
 
 extern "C" void vslam_voc_destroy(vslam_voc* v) {
@@ -177,6 +185,28 @@ static void bow_launch(vslam_fe* fe, const vslam_voc* v, int njobs, const uint8_
         hipLaunchKernelGGL(k_bow_descend, dim3((maxn + 15) / 16, njobs), dim3(256), 0, fe->stream, J, v->d_childStart,
                            v->d_childCount, v->d_childIds, v->d_desc, v->d_weight, v->d_word, v->L, levelsup);
     fe->bow.down(fe->stream, 0, (size_t)njobs * per * 16);
+}
+
+/* the descent alone, for n descriptors in HBM into device arrays, on a stream of the caller (vslam_voc_train's
+ * setNodeWeights has no context); jobs of at most 2^20 features keep the grid's x below the launch limits */
+int vslam_bow_descend_words(const vslam_voc* v, const uint8_t* dev_desc, int n, int32_t* dev_word, double* dev_weight,
+                            int32_t* dev_nid, hipStream_t stream) {
+    constexpr int kPer = 1 << 20;
+    for (int first = 0; first < n; first += kPer * VSLAM_MAX_BATCH) {
+        BowJobsDev J;
+        memset(&J, 0, sizeof(J));
+        int njobs = 0, maxn = 0;
+        for (int o = first; o < n && njobs < VSLAM_MAX_BATCH; o += kPer, njobs++) {
+            J.desc[njobs] = dev_desc + (size_t)o * 32;
+            J.n[njobs] = std::min(kPer, n - o);
+            J.word[njobs] = dev_word + o, J.weight[njobs] = dev_weight + o, J.nid[njobs] = dev_nid + o;
+            maxn = std::max(maxn, J.n[njobs]);
+        }
+        hipLaunchKernelGGL(k_bow_descend, dim3((maxn + 15) / 16, njobs), dim3(256), 0, stream, J, v->d_childStart,
+                           v->d_childCount, v->d_childIds, v->d_desc, v->d_weight, v->d_word, v->L, 0);
+    }
+    HIPCHK(hipGetLastError());
+    return VSLAM_OK;
 }
 
 extern "C" int vslam_bow_transform(vslam_fe* fe, const vslam_voc* voc, const uint8_t* dev_desc, int n, int levelsup,

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "../../include/vslam_fe.h"
+#include "vslam_voc_train.h" /* struct vslam_voc_file */
 
 namespace {
 
@@ -154,12 +155,7 @@ bool qlz_packet(Cursor& in, std::vector<uint8_t>& out) {
 
 }  // namespace
 
-struct vslam_voc_file {
-    int k = 0, L = 0, scoring = 0, weighting = 0, format = 0, n_words = 0;
-    std::vector<int32_t> child_start, child_count, child_ids, word_id;
-    std::vector<uint8_t> desc;
-    std::vector<double> weight;
-};
+int vslam_voc_file_fail(int code, const std::string& what) { return fail(code, what); }
 
 namespace {
 
