@@ -669,7 +669,8 @@ int vslam_search_by_projection_mappoints(vslam_fe* fe, const vslam_mp_track* mps
 /* Frame::isInFrustum(pMP, viewingCosLimit) (frame.cpp:529-595; the pinhole branch Nleft == -1) over a local map, and the
  * second loop of Tracking::SearchLocalPoints with the matcher behind it (tracking.cpp:3214-3263) in one enqueue: the caller
  * hands in the MapPoints as the map holds them, not the records above, and the list may be longer than the matcher's cap.
- * isInFrustumChecks (two-camera fisheye rigs, Nleft != -1) is not covered.
+ * With a KB8 camera set (vslam_fe_set_kb8_camera, below) the projection is KannalaBrandt8::project; isInFrustumChecks
+ * (two-camera fisheye rigs, Nleft != -1) is vslam_frame_in_frustum_rig, the records only.
  *
  * Per MapPoint the arithmetic of vi_slam_amd/csrc/vslam_frustum.h: Matx algebra in float, both cv::norm in double,
  * Pinhole::project, the closed-interval bounds test over the context's float grid bounds (vslam_fe_set_grid_bounds) or
@@ -729,6 +730,56 @@ int vslam_search_local_points(vslam_fe* fe, const vslam_frustum_params* p, const
 /* With vslam_fe_set_profiling on: HIP-event time of k_frustum and of k_frustum_compact alone, summed over the local-points
  * searches waited for since profiling was switched on.  Any pointer may be NULL. */
 int vslam_fe_get_local_points_profile(vslam_fe* fe, double* frustum_ms, double* compact_ms, long* passes);
+
+/* ---------------------------------------------------------------- fisheye cameras (Camera.type: "KannalaBrandt8")
+ *
+ * KannalaBrandt8::project / unproject (kannalabrandt8.cpp:11-27, :82-109) and the frustum test of a fisheye Frame, by the
+ * arithmetic of vi_slam_amd/csrc/vslam_kb8.h: float operations rounded one by one and the host libm's atan2f, sqrtf, cosf,
+ * sinf and tanf restated bit for bit (glibc 2.35; tanf for |x| < 3*pi/4, the quiet NaN beyond).
+ *
+ * With a KB8 camera set:
+ *   - vslam_frame_in_frustum and vslam_search_local_points[_async/_wait] run Frame::isInFrustum (frame.cpp:529-595, Nleft == -1)
+ *     with KannalaBrandt8::project in place of Pinhole::project; fx, fy, cx, cy of vslam_frustum_params must equal the camera's
+ *     bit for bit (VSLAM_ERR_INVALID otherwise).  Compaction, matcher and _wait do not know the camera.
+ *   - the entry points that project with intrinsics of their own -- vslam_search_by_projection_frame / _keyframe / _sim3,
+ *     vslam_search_by_projection_dev_async, vslam_fuse_search, vslam_search_for_triangulation -- return VSLAM_ERR_UNSUPPORTED:
+ *     they hold Pinhole::project and would silently project a fisheye frame as a pinhole.
+ * A KB8 camera and a distorted pinhole camera (vslam_fe_set_camera with k1 != 0) exclude each other: the reference's fisheye
+ * frames have zero mDistCoef.  Setting one while the other is set is VSLAM_ERR_INVALID.
+ * Not covered: the right-camera branch of SearchByProjection(F, vpMapPoints) (fmatcher.cpp:422-485) and every other matcher's
+ * fisheye branch, TriangulateMatches / epipolarConstrain / matchAndtriangulate (cv::SVD), ReconstructWithTwoViews
+ * (cv::fisheye::undistortPoints), projectJac, tanf beyond 3*pi/4. */
+typedef struct vslam_kb8_camera {
+    float fx, fy, cx, cy; /* mvParameters[0..3] */
+    float k[4];           /* mvParameters[4..7] */
+    float precision;      /* the Newton loop's exit of unproject; <= 0: the reference default 1e-6f */
+} vslam_kb8_camera;
+/* NULL = pinhole (the default).  Waits for the context's stream.  Does not touch the extraction or its captured graph. */
+int vslam_fe_set_kb8_camera(vslam_fe* fe, const vslam_kb8_camera* cam);
+/* n points: xyz_host 3n floats -> uv_out 2n floats, and uv_host 2n floats -> xyz_out 3n floats (x * scale, y * scale, 1).
+ * Blocking, evaluated on the device.  VSLAM_ERR_INVALID without a KB8 camera. */
+int vslam_kb8_project(vslam_fe* fe, const float* xyz_host, int n, float* uv_out);
+int vslam_kb8_unproject(vslam_fe* fe, const float* uv_host, int n, float* xyz_out);
+/* The rays of a slot's keypoints (what CreateNewMapPoints' unprojectMat_ and MLPnPsolver's bearing vectors consume): one
+ * launch on the context's stream behind whatever is enqueued there; reads the slot's device keypoints and its device count
+ * (vslam_fe_slot_count_ptr), writes 3 floats per keypoint to dev_rays (DEVICE memory of 3 * vslam_fe_capacity floats, entries
+ * beyond the count untouched).  No host wait. */
+int vslam_kb8_unproject_slot_async(vslam_fe* fe, int slot, float* dev_rays);
+/* Frame::isInFrustum for a two-fisheye rig (frame.cpp:596-606, Nleft != -1; isInFrustumChecks :1191-1271): the frustum records
+ * only.  The left camera is the context's KB8 camera (its intrinsics must equal p's), the right one rig->cam2; Tlr / Trl are
+ * rows [R | t] of mTlrx / mTrlx.  Restated as written: tcw = mOwx in the right branch, mRx = Rrl * Rcw and mtx = Rrl * tcw + trl,
+ * twcx = Rwc * tlr + tcw, no invz (p->mbf is not read).  track_left[i] / track_right[i]: proj_x / proj_y = the camera's uv
+ * (mTrackProjX/Y, mTrackProjXR/YR), view_cos, level, flags bit 0 = mbTrackInView / mbTrackInViewR, bit 1 = the input's; proj_xr
+ * is 0.  Where a camera does not see the point: level -1 (frame.cpp:599-600), flags bit 0 clear, zero elsewhere (the reference
+ * leaves an earlier frame's values).  depth_left / depth_right (mTrackDepth / mTrackDepthR) may be NULL.  *n_in_view counts
+ * left || right.  n <= VSLAM_LOCAL_POINTS_MAX.  Blocking. */
+typedef struct vslam_kb8_rig {
+    vslam_kb8_camera cam2;
+    float Tlr[12], Trl[12];
+} vslam_kb8_rig;
+int vslam_frame_in_frustum_rig(vslam_fe* fe, const vslam_frustum_params* p, const vslam_kb8_rig* rig,
+                               const vslam_map_point* points_host, int n, vslam_mp_track* track_left,
+                               vslam_mp_track* track_right, float* depth_left, float* depth_right, int* n_in_view);
 
 /* Device-resident, batched form of the same matcher: every pointer of a job is a DEVICE pointer; counts are
  * int32 in HBM (vslam_fe_slot_count_ptr); keypoint arrays hold up to the context's capacity (<= 4096).  Up to 16

@@ -578,6 +578,91 @@ inline void ComputeStereoMatches(const FExtractor& left, const FExtractor& right
 }
 
 /* ---------------------------------------------------------------------------------------------------
+ * geometry::KannalaBrandt8 (cameramodels/kannalabrandt8.h): the fisheye camera of a Frame whose extractor is `extractor`.
+ * Constructed from the reference's mvParameters (fx, fy, cx, cy, k0..k3) it becomes the context's camera: project /
+ * unproject run on the device with the host libm's results bit for bit, and FMatcher::SearchLocalPoints on that extractor
+ * tests the frustum with this projection (its LocalFrameView carries the same fx, fy, cx, cy).  The matchers that project
+ * with intrinsics of their own throw while it is attached (VSLAM_ERR_UNSUPPORTED).  Detach() or the destructor returns the
+ * context to pinhole.  The extractor must have processed an image (the context is created by the first one).
+ *     KannalaBrandt8 cam(extractor, vParameters);
+ *     cv::Point2f uv = cam.project(p3D);   cam.unproject(keys, rays);   cam.unprojectSlotAsync(dev_rays);
+ * Not here: projectJac, TriangulateMatches / epipolarConstrain (cv::SVD), ReconstructWithTwoViews
+ * (cv::fisheye::undistortPoints).
+ * ------------------------------------------------------------------------------------------------- */
+#ifdef VSLAM_SHIM_WITH_OPENCV
+typedef cv::Point3f Point3f;
+#else
+struct Point3f {
+    float x, y, z;
+};
+#endif
+static_assert(sizeof(Point3f) == 12 && sizeof(Point2f) == 8, "vectors of points are packed floats");
+
+class KannalaBrandt8 {
+public:
+    KannalaBrandt8(const FExtractor& extractor, const std::vector<float>& vParameters, float precision = 1e-6f)
+        : extractor_(&extractor) {
+        if (vParameters.size() != 8) throw std::invalid_argument("KannalaBrandt8: 8 parameters (fx, fy, cx, cy, k0..k3)");
+        if (!extractor.context()) throw std::runtime_error("KannalaBrandt8: the extractor has not processed an image yet");
+        cam_.fx = vParameters[0]; cam_.fy = vParameters[1]; cam_.cx = vParameters[2]; cam_.cy = vParameters[3];
+        for (int i = 0; i < 4; i++) cam_.k[i] = vParameters[4 + i];
+        cam_.precision = precision;
+        check(vslam_fe_set_kb8_camera(extractor.context(), &cam_));
+        attached_ = true;
+    }
+    ~KannalaBrandt8() {
+        if (attached_) (void)vslam_fe_set_kb8_camera(extractor_->context(), nullptr);
+    }
+    KannalaBrandt8(const KannalaBrandt8&) = delete;
+    KannalaBrandt8& operator=(const KannalaBrandt8&) = delete;
+    void Detach() {
+        if (attached_) check(vslam_fe_set_kb8_camera(extractor_->context(), nullptr));
+        attached_ = false;
+    }
+    const vslam_kb8_camera& parameters() const { return cam_; }
+
+    void project(const std::vector<Point3f>& p3D, std::vector<Point2f>& uv) const {
+        uv.resize(p3D.size());
+        check(vslam_kb8_project(extractor_->context(), reinterpret_cast<const float*>(p3D.data()), (int)p3D.size(),
+                                reinterpret_cast<float*>(uv.data())));
+    }
+    Point2f project(const Point3f& p3D) const {
+        Point2f uv;
+        check(vslam_kb8_project(extractor_->context(), &p3D.x, 1, &uv.x));
+        return uv;
+    }
+    void unproject(const std::vector<Point2f>& p2D, std::vector<Point3f>& rays) const {
+        rays.resize(p2D.size());
+        check(vslam_kb8_unproject(extractor_->context(), reinterpret_cast<const float*>(p2D.data()), (int)p2D.size(),
+                                  reinterpret_cast<float*>(rays.data())));
+    }
+    Point3f unproject(const Point2f& p2D) const {
+        Point3f r;
+        check(vslam_kb8_unproject(extractor_->context(), &p2D.x, 1, &r.x));
+        return r;
+    }
+    /* the rays of the keypoints of the extractor's last image into DEVICE memory of 3 * vslam_fe_capacity floats; enqueued,
+     * not waited for */
+    void unprojectSlotAsync(float* dev_rays) const { check(vslam_kb8_unproject_slot_async(extractor_->context(), 0, dev_rays)); }
+    /* Frame::isInFrustum of a two-fisheye rig (Nleft != -1) over a local map: this camera is the left one.  Returns the number
+     * of points either camera sees. */
+    int isInFrustumRig(const vslam_frustum_params& p, const vslam_kb8_rig& rig, const std::vector<vslam_map_point>& points,
+                       std::vector<vslam_mp_track>& left, std::vector<vslam_mp_track>& right) const {
+        left.resize(points.size());
+        right.resize(points.size());
+        int n = 0;
+        check(vslam_frame_in_frustum_rig(extractor_->context(), &p, &rig, points.data(), (int)points.size(), left.data(),
+                                         right.data(), nullptr, nullptr, &n));
+        return n;
+    }
+
+private:
+    const FExtractor* extractor_;
+    vslam_kb8_camera cam_;
+    bool attached_ = false;
+};
+
+/* ---------------------------------------------------------------------------------------------------
  * The scoring half of MotionEstimator::Reconstruct (motion_estimation.cpp:2006-2094).  FindHomography and FindFundamental
  * (:2096-2195) split in two: loop one stays in the caller and computes every H21i = T2inv*Hn*T1, H12i = H21i.inv() and
  * F21i = T2t*Fn*T1 (ComputeH21 / ComputeF21 run cv::SVDecomp, which this library does not restate); then ONE call scores

@@ -61,6 +61,8 @@ ABI_SYMBOLS = [
     "vslam_fe_get_rgbd_profile",
     "vslam_frame_in_frustum", "vslam_search_local_points_async", "vslam_search_local_points_wait",
     "vslam_search_local_points", "vslam_fe_get_local_points_profile",
+    "vslam_fe_set_kb8_camera", "vslam_kb8_project", "vslam_kb8_unproject", "vslam_kb8_unproject_slot_async",
+    "vslam_frame_in_frustum_rig",
     "vslam_two_view_score_async", "vslam_two_view_score_wait", "vslam_two_view_score", "vslam_fe_get_two_view_profile",
     "vslam_kfdb_create", "vslam_kfdb_create_ex", "vslam_kfdb_destroy", "vslam_kfdb_add", "vslam_kfdb_erase",
     "vslam_kfdb_clear", "vslam_kfdb_clear_map", "vslam_kfdb_size", "vslam_kfdb_stats", "vslam_kfdb_query_async",
@@ -266,6 +268,32 @@ class _InitJob(C.Structure):  # vslam_init_job
 class _Camera(C.Structure):  # vslam_camera
     _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("dist", C.c_float * 5),
                 ("ndist", C.c_int32)]
+
+
+class _Kb8Camera(C.Structure):  # vslam_kb8_camera
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("k", C.c_float * 4),
+                ("precision", C.c_float)]
+
+
+class _Kb8Rig(C.Structure):  # vslam_kb8_rig
+    _fields_ = [("cam2", _Kb8Camera), ("Tlr", C.c_float * 12), ("Trl", C.c_float * 12)]
+
+
+def kb8_camera(fx, fy, cx, cy, k, precision=0.0):
+    """vslam_kb8_camera: KannalaBrandt8 mvParameters (fx, fy, cx, cy, k0..k3); precision <= 0: the reference's 1e-6"""
+    return _Kb8Camera(*[float(np.float32(v)) for v in (fx, fy, cx, cy)], (C.c_float * 4)(*[float(np.float32(v)) for v in k]),
+                      float(np.float32(precision)))
+
+
+def kb8_rig(cam2, Tlr, Trl):
+    """vslam_kb8_rig: the right camera and rows [R | t] (3 x 4) of mTlrx, mTrlx"""
+    r = _Kb8Rig()
+    r.cam2 = cam2
+    for name, T in (("Tlr", Tlr), ("Trl", Trl)):
+        T = np.asarray(T, np.float32).reshape(-1)
+        for j in range(12):
+            getattr(r, name)[j] = float(T[j])
+    return r
 
 
 class _Bounds(C.Structure):  # vslam_bounds
@@ -530,6 +558,11 @@ def lib():
         L.vslam_fe_get_local_points_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_long)]
         L.vslam_search_local_points.argtypes = [vp, fp, vp, vp, i, i, vp, vp, i, vp, vp, f, f, vp, C.POINTER(i),
                                                 C.POINTER(i), C.POINTER(i), vp]
+        L.vslam_fe_set_kb8_camera.argtypes = [vp, C.POINTER(_Kb8Camera)]
+        L.vslam_kb8_project.argtypes = [vp, vp, i, vp]
+        L.vslam_kb8_unproject.argtypes = [vp, vp, i, vp]
+        L.vslam_kb8_unproject_slot_async.argtypes = [vp, i, vp]
+        L.vslam_frame_in_frustum_rig.argtypes = [vp, fp, C.POINTER(_Kb8Rig), vp, i, vp, vp, vp, vp, C.POINTER(i)]
         L.vslam_two_view_score_async.argtypes = [vp, i, C.POINTER(_TwoViewJob)]
         L.vslam_two_view_score_wait.argtypes = [vp, C.POINTER(_TwoViewResult)]
         L.vslam_two_view_score.argtypes = [vp, C.POINTER(_TwoViewJob), C.POINTER(_TwoViewResult)]
@@ -978,6 +1011,43 @@ class FExtractor:
         _check(lib().vslam_frame_in_frustum(self._h, C.byref(params), _p(pts), len(pts), _p(track), _p(depth),
                                             C.byref(nv)))
         return track, depth, nv.value
+
+    # ---- fisheye cameras: KannalaBrandt8 (kannalabrandt8.cpp) on the device
+    def set_kb8_camera(self, cam):
+        """cam from kb8_camera(), or None for pinhole (the default).  While set, frame_in_frustum / search_local_points
+        project with KannalaBrandt8::project and the matchers that project with intrinsics of their own raise
+        ERR_UNSUPPORTED."""
+        _check(lib().vslam_fe_set_kb8_camera(self._h, None if cam is None else C.byref(cam)))
+
+    def kb8_project(self, xyz):
+        """KannalaBrandt8::project of n x 3 float32 points -> n x 2 float32, evaluated on the device"""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        out = np.zeros((len(xyz), 2), np.float32)
+        _check(lib().vslam_kb8_project(self._h, _p(xyz), len(xyz), _p(out)))
+        return out
+
+    def kb8_unproject(self, uv):
+        """KannalaBrandt8::unproject of n x 2 float32 pixels -> n x 3 float32 rays, evaluated on the device"""
+        uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+        out = np.zeros((len(uv), 3), np.float32)
+        _check(lib().vslam_kb8_unproject(self._h, _p(uv), len(uv), _p(out)))
+        return out
+
+    def kb8_unproject_slot_async(self, slot, dev_rays):
+        """enqueue the rays of the slot's keypoints into dev_rays (device address of 3 * cap floats); no host wait"""
+        _check(lib().vslam_kb8_unproject_slot_async(self._h, slot, C.c_void_p(dev_rays)))
+
+    def frame_in_frustum_rig(self, params, rig, points):
+        """Frame::isInFrustum of a two-fisheye rig (frame.cpp:596-606, isInFrustumChecks) -> (left records, right records,
+        mTrackDepth, mTrackDepthR, points either camera sees); rig from kb8_rig()"""
+        pts = np.ascontiguousarray(points, MAP_POINT_DTYPE)
+        n = len(pts)
+        tl, tr = np.zeros(n, MP_TRACK_DTYPE), np.zeros(n, MP_TRACK_DTYPE)
+        dl, dr = np.zeros(n, np.float32), np.zeros(n, np.float32)
+        nv = C.c_int(0)
+        _check(lib().vslam_frame_in_frustum_rig(self._h, C.byref(params), C.byref(rig), _p(pts), n, _p(tl), _p(tr), _p(dl),
+                                                _p(dr), C.byref(nv)))
+        return tl, tr, dl, dr, nv.value
 
     def search_local_points_async(self, params, points, mp_desc, dev_cur_kps, dev_cur_desc, n_cur, cur_u_right=None,
                                   occupied=None, th=1.0, nnratio=0.8, n_mp=None):

@@ -613,6 +613,10 @@ extern "C" int vslam_search_for_triangulation(vslam_fe* fe, const vslam_tri_para
         g_err = "invalid arguments";
         return VSLAM_ERR_INVALID;
     }
+    if (vslamh_kb8_projecting_entry(fe->has_kb8)) { /* the epipole and the epipolar test are Pinhole's */
+        g_err = "a KB8 camera is set: this entry point projects as a pinhole (vslam_fe_set_kb8_camera)";
+        return VSLAM_ERR_UNSUPPORTED;
+    }
     *nmatches = 0;
     for (int i = 0; i < n1; i++) match12[i] = -1;
     if (n1 == 0 || n2 == 0 || n1_nodes == 0 || n2_nodes == 0) return VSLAM_OK;

@@ -223,6 +223,11 @@ struct vslam_fe {
     long prof_batches = 0, prof_images = 0;
 
     WorkerPool* pool = nullptr;
+
+    /* vslam_fe_set_kb8_camera: the frustum stage projects with KannalaBrandt8::project, the entry points that project with
+     * intrinsics of their own refuse (vslam_kb8.hip).  Behind everything an extraction pass reads. */
+    bool has_kb8 = false;
+    vslam_kb8_camera kb8 = {};
 };
 
 

@@ -221,4 +221,11 @@ extern "C" int vslamh_local_points_finish(const int32_t* match_compact, int n_cu
                                           int capacity, int32_t* match_cur);
 /* vslam_host.cpp: vslam_two_view_score over host arrays by the shared vslam_two_view.h code (CPU tests, the demo) */
 extern "C" int vslamh_two_view_score(const vslam_two_view_job* job, vslam_two_view_result* result);
+/* vslam_host.cpp: the decisions around a KB8 camera, as the entry points take them (each returns a VSLAM_* code):
+ * _exclusive: setting a KB8 camera beside a pinhole camera with that k1, or a pinhole camera with that k1 beside a KB8 camera
+ * (other_set: the other kind is set); _frustum_check: the frustum parameters against the camera (NULL: pinhole, nothing to check); _projecting_entry:
+ * an entry point that projects with intrinsics of its own */
+extern "C" int vslamh_kb8_exclusive(int other_set, float k1);
+extern "C" int vslamh_kb8_frustum_check(const vslam_frustum_params* p, const vslam_kb8_camera* cam);
+extern "C" int vslamh_kb8_projecting_entry(int has_kb8);
 #endif

@@ -109,6 +109,10 @@ struct FrustumArgsDev;
 struct FrustumCompactDev;
 void vk_frustum(hipStream_t st, const FrustumArgsDev& A);
 void vk_frustum_compact(hipStream_t st, const FrustumCompactDev& A);
+/* the same records with KannalaBrandt8::project, and isInFrustumChecks for both cameras of a fisheye rig (vslam_kb8.hip) */
+struct FrustumRigDev;
+void vk_frustum_kb8(hipStream_t st, const FrustumArgsDev& A, const vslam_kb8_camera& cam);
+void vk_frustum_rig(hipStream_t st, const FrustumRigDev& A);
 /* the pair list, every hypothesis' score and flags, the selection (vslam_two_view.hip): njobs TvJobDev in HBM, max_groups =
  * the most 64-hypothesis groups (H and F together) of any job, ev = four events around the three launches or NULL */
 struct TvJobDev;

@@ -3,6 +3,7 @@
  * and Frame::isInFrustum / SearchLocalPoints.  Every entry stages through a vslam_staging block (vslam_staging.h). */
 #include "vslam_ctx.h"
 #include "vslam_frustum.h"
+#include "vslam_kb8.h"
 
 /* ------------------------------------------------------------------ SearchByProjection(CurrentFrame, LastFrame) */
 extern "C" int vslam_projection_direction(const float* Tcw, const float* Tlw, float mb, int mono, int gemm_float,
@@ -33,6 +34,14 @@ extern "C" int vslam_projection_direction(const float* Tcw, const float* Tlw, fl
     *forward = (tlc2 > mb && !mono) ? 1 : 0;
     *backward = (-tlc2 > mb && !mono) ? 1 : 0;
     return VSLAM_OK;
+}
+
+/* With a KB8 camera set (vslam_fe_set_kb8_camera) an entry point that projects with Pinhole::project over intrinsics of its own
+ * refuses: better than silently projecting a fisheye frame as a pinhole. */
+static int kb8_refuse(const vslam_fe* fe) {
+    const int rc = vslamh_kb8_projecting_entry(fe->has_kb8);
+    if (rc) g_err = "a KB8 camera is set: this entry point projects as a pinhole (vslam_fe_set_kb8_camera)";
+    return rc;
 }
 
 /* ---- what every entry point of the family does around k_sbp_* (vk_search_by_projection) ---- */
@@ -109,6 +118,7 @@ static int sbp_frame_impl(vslam_fe* fe, const vslam_proj_params* p, const vslam_
         g_err = "invalid arguments";
         return VSLAM_ERR_INVALID;
     }
+    if (int rc = kb8_refuse(fe)) return rc;
     *nmatches = 0;
     if (n_cur == 0 || n_last == 0) {
         for (int i = 0; i < n_cur; i++) match_cur[i] = -1;
@@ -258,6 +268,7 @@ extern "C" int vslam_search_by_projection_dev_async(vslam_fe* fe, int njobs, con
         g_err = "invalid arguments";
         return VSLAM_ERR_INVALID;
     }
+    if (int rc = kb8_refuse(fe)) return rc; /* modes 0, 2, 3 of the batch form all project with the job's intrinsics */
     const int cap = fe->cap;
     if (cap > 4096) {
         g_err = "SearchByProjection on the device supports at most 4096 keypoints per frame";
@@ -442,6 +453,7 @@ extern "C" int vslam_fuse_search(vslam_fe* fe, const vslam_fuse_params* p, const
         g_err = "invalid arguments";
         return VSLAM_ERR_INVALID;
     }
+    if (int rc = kb8_refuse(fe)) return rc;
     for (int i = 0; i < n_points; i++) {
         best_idx[i] = -1;
         best_dist[i] = 256;
@@ -519,12 +531,25 @@ static vslam_fr::Frame frustum_frame(const vslam_fe* fe, const vslam_frustum_par
     return vslam_fr::make_frame(*p, bb, fe->p.nlevels);
 }
 
+/* with a KB8 camera the frustum parameters carry the camera's own fx, fy, cx, cy, bit for bit */
+static int frustum_camera_ok(const vslam_fe* fe, const vslam_frustum_params* p) {
+    const int rc = vslamh_kb8_frustum_check(p, fe->has_kb8 ? &fe->kb8 : nullptr);
+    if (rc) g_err = "fx, fy, cx, cy of the frustum parameters differ from the KB8 camera's (vslam_fe_set_kb8_camera)";
+    return rc;
+}
+/* k_frustum, or its fisheye form while a KB8 camera is set: same arguments, same outputs */
+static void frustum_launch(const vslam_fe* fe, hipStream_t st, const FrustumArgsDev& A) {
+    if (fe->has_kb8) vk_frustum_kb8(st, A, fe->kb8);
+    else vk_frustum(st, A);
+}
+
 extern "C" int vslam_frame_in_frustum(vslam_fe* fe, const vslam_frustum_params* p, const vslam_map_point* points_host, int n,
                                       vslam_mp_track* track_out, float* depth_out, int* n_in_view) {
     if (!fe || !n_in_view || n < 0 || (n && (!points_host || !track_out)) || !frustum_params_ok(p)) {
         g_err = "invalid arguments";
         return VSLAM_ERR_INVALID;
     }
+    if (int rc = frustum_camera_ok(fe, p)) return rc;
     *n_in_view = 0;
     if (n == 0) return VSLAM_OK;
     if (n > VSLAM_LOCAL_POINTS_MAX) {
@@ -556,13 +581,82 @@ extern "C" int vslam_frame_in_frustum(vslam_fe* fe, const vslam_frustum_params* 
     A.depth = (float*)(d + o_depth);
     A.chunkInView = (int32_t*)(d + o_cv);
     A.chunkKeep = (int32_t*)(d + o_ck);
-    vk_frustum(st, A);
+    frustum_launch(fe, st, A);
     HIPCHK(hipGetLastError());
     fe->lp.down(st, o_track, o_ck - o_track); /* records | depths | in-view counts */
     HIPCHK(hipGetLastError());
     HIPCHK(vslam_stream_wait(st));
     memcpy(track_out, h + o_track, (size_t)n * sizeof(vslam_mp_track));
     if (depth_out) memcpy(depth_out, h + o_depth, (size_t)n * 4);
+    int nv = 0;
+    for (int c = 0; c < nchunks; c++) nv += ((const int32_t*)(h + o_cv))[c];
+    *n_in_view = nv;
+    return VSLAM_OK;
+}
+
+/* Frame::isInFrustum of a two-fisheye rig (Nleft != -1): one upload, k_frustum_rig, one copy of both record arrays, both
+ * depth arrays and the chunk counts */
+extern "C" int vslam_frame_in_frustum_rig(vslam_fe* fe, const vslam_frustum_params* p, const vslam_kb8_rig* rig,
+                                          const vslam_map_point* points_host, int n, vslam_mp_track* track_left,
+                                          vslam_mp_track* track_right, float* depth_left, float* depth_right, int* n_in_view) {
+    if (!fe || !rig || !n_in_view || n < 0 || (n && (!points_host || !track_left || !track_right)) || !frustum_params_ok(p) ||
+        !vslam_kb8::camera_ok(&rig->cam2)) {
+        g_err = "invalid arguments";
+        return VSLAM_ERR_INVALID;
+    }
+    for (int i = 0; i < 12; i++)
+        if (!std::isfinite(rig->Tlr[i]) || !std::isfinite(rig->Trl[i])) {
+            g_err = "invalid arguments";
+            return VSLAM_ERR_INVALID;
+        }
+    if (!fe->has_kb8) {
+        g_err = "no KB8 camera set (vslam_fe_set_kb8_camera)";
+        return VSLAM_ERR_INVALID;
+    }
+    if (int rc = frustum_camera_ok(fe, p)) return rc;
+    *n_in_view = 0;
+    if (n == 0) return VSLAM_OK;
+    if (n > VSLAM_LOCAL_POINTS_MAX) {
+        g_err = "Frame::isInFrustum on the device supports at most 65536 MapPoints per call";
+        return VSLAM_ERR_UNSUPPORTED;
+    }
+    if (fe->lp_state == 1) {
+        g_err = "a local-points search is in flight (vslam_search_local_points_wait)";
+        return VSLAM_ERR_INVALID;
+    }
+    HIPCHK(hipSetDevice(fe->p.device));
+    const int nchunks = (n + VSLAM_FRUSTUM_CHUNK - 1) / VSLAM_FRUSTUM_CHUNK;
+    const size_t nn = (size_t)n;
+    const auto [o_pts, o_tl, o_tr, o_dl, o_dr, o_cv, total] =
+        vslam::layout(256, {nn * sizeof(vslam_map_point), nn * sizeof(vslam_mp_track), nn * sizeof(vslam_mp_track), nn * 4,
+                            nn * 4, (size_t)nchunks * 4});
+    int rc = fe->lp.ensure(total);
+    if (rc) return rc;
+    uint8_t *h = fe->lp.h, *d = fe->lp.d;
+    memcpy(h + o_pts, points_host, nn * sizeof(vslam_map_point));
+    hipStream_t st = fe->stream;
+    fe->lp.up(st, o_pts, o_tl);
+    FrustumRigDev A;
+    A.F = frustum_frame(fe, p);
+    A.cam1 = fe->kb8;
+    A.cam2 = rig->cam2;
+    A.right = vslam_kb8::rig_right(A.F, *rig);
+    A.n = n;
+    A.pts = (const vslam_map_point*)(d + o_pts);
+    A.trackL = (vslam_mp_track*)(d + o_tl);
+    A.trackR = (vslam_mp_track*)(d + o_tr);
+    A.depthL = (float*)(d + o_dl);
+    A.depthR = (float*)(d + o_dr);
+    A.chunkInView = (int32_t*)(d + o_cv);
+    vk_frustum_rig(st, A);
+    HIPCHK(hipGetLastError());
+    fe->lp.down(st, o_tl, total - o_tl);
+    HIPCHK(hipGetLastError());
+    HIPCHK(vslam_stream_wait(st));
+    memcpy(track_left, h + o_tl, nn * sizeof(vslam_mp_track));
+    memcpy(track_right, h + o_tr, nn * sizeof(vslam_mp_track));
+    if (depth_left) memcpy(depth_left, h + o_dl, nn * 4);
+    if (depth_right) memcpy(depth_right, h + o_dr, nn * 4);
     int nv = 0;
     for (int c = 0; c < nchunks; c++) nv += ((const int32_t*)(h + o_cv))[c];
     *n_in_view = nv;
@@ -600,6 +694,7 @@ extern "C" int vslam_search_local_points_async(vslam_fe* fe, const vslam_frustum
         g_err = "SearchByProjection on the device needs nnratio >= 0.4";
         return VSLAM_ERR_UNSUPPORTED;
     }
+    if (int rc = frustum_camera_ok(fe, p)) return rc;
     fe->lp_n_mp = n_mp;
     fe->lp_n_cur = n_cur;
     if (n_mp == 0 || n_cur == 0) {
@@ -645,7 +740,7 @@ extern "C" int vslam_search_local_points_async(vslam_fe* fe, const vslam_frustum
     A.chunkInView = (int32_t*)(d + o_cv);
     A.chunkKeep = (int32_t*)(d + o_ck);
     if (prof) (void)hipEventRecord(fe->ev_lp[0], st);
-    vk_frustum(st, A);
+    frustum_launch(fe, st, A);
     if (prof) (void)hipEventRecord(fe->ev_lp[1], st);
     FrustumCompactDev K;
     K.n = n_mp;

@@ -8,8 +8,10 @@
  * polynomial in double, one final rounding to float.  The constants below are the published
  * __sincosf_table values (also readable in libm.so.6's .rodata).
  *
- * Domain used here: 0 <= y < 120 (angles are degrees in [0,360] times pi/180).  Larger inputs take
- * glibc's reduce_large path, which this header does not restate; they return NaN so a misuse is loud.
+ * Domain: |y| < 120, either sign (abstop12 drops the sign bit and reduce_fast is signed).  The extractor feeds angles in
+ * degrees in [0,360] times pi/180, KannalaBrandt8::project (vslam_kb8.h) feeds psi in [-pi, pi]; both functions are compared
+ * with the platform libm for every float with |y| <= pi (tests/tools/kb8_libm_exhaustive.cpp).  Larger inputs take glibc's
+ * reduce_large path, which this header does not restate; they return NaN so a misuse is loud.
  *
  * Must be compiled with -ffp-contract=off (glibc's generic build does not contract; its FMA ifunc
  * variant differs from this in < 1e-8 of all inputs, see tests/test_trig.py).

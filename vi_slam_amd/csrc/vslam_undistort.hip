@@ -62,6 +62,10 @@ extern "C" int vslam_fe_set_camera(vslam_fe* fe, const vslam_camera* cam) {
             g_err = "invalid camera (ndist 4 or 5, finite values, fx and fy not zero)";
             return VSLAM_ERR_INVALID;
         }
+        if (vslamh_kb8_exclusive(fe->has_kb8, cam->dist[0])) {
+            g_err = "a KB8 camera is set (vslam_fe_set_kb8_camera): fisheye frames have zero mDistCoef";
+            return VSLAM_ERR_INVALID;
+        }
     }
     HIPCHK(hipSetDevice(fe->p.device));
     if (fe->stream) HIPCHK(hipStreamSynchronize(fe->stream)); /* a pass in flight may still read the old camera */
