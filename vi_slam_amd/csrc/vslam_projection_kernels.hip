@@ -746,6 +746,7 @@ k_fuse_rank(FuseArgsDev A) {
     for (int q = blockIdx.x * FUSE_QPB + wave; q < min(A.nPoints, (int)(blockIdx.x + 1) * FUSE_QPB); q += 4) {
         const FusePoint mp = A.pts[q];
         uint32_t best = 0xFFFFFFFFu;
+        uint32_t far = 0xFFFFFFFFu; /* cell << 12 | index of the first candidate at distance 256, which the key cannot hold */
         bool go = mp.valid != 0;
         float u = 0.f, v = 0.f, ur = 0.f, radius = 0.f;
         int level = 0;
@@ -814,14 +815,25 @@ k_fuse_rank(FuseArgsDev A) {
                         }
                     }
                     const uint4 ta = ((const uint4*)A.kfDesc)[(size_t)c * 2], tb = ((const uint4*)A.kfDesc)[(size_t)c * 2 + 1];
-                    best = min(best, si_key(si_hamming(da, db, ta, tb), cd.cell, (uint32_t)c));
+                    const uint32_t dist = si_hamming(da, db, ta, tb);
+                    if (dist > 255u) { /* `dist < bestDist`: never from bestDist = 256 (:2039); from INT_MAX (:2203, :2342) it is */
+                        if (A.sim3) far = min(far, ((uint32_t)cd.cell << 12) | (uint32_t)c);
+                        continue;
+                    }
+                    best = min(best, si_key(dist, cd.cell, (uint32_t)c));
                 }
             }
         }
         const uint32_t g = wave_min_u32(best);
+        int32_t idx = g == 0xFFFFFFFFu ? -1 : (int32_t)si_key_index(g);
+        int32_t bd = g == 0xFFFFFFFFu ? 256 : (int32_t)si_key_dist(g);
+        if (g == 0xFFFFFFFFu && A.sim3) { /* wave-uniform: nothing nearer than 256 */
+            const uint32_t f = wave_min_u32(far);
+            if (f != 0xFFFFFFFFu) idx = (int32_t)(f & 0xFFFu);
+        }
         if (lane == 0) {
-            A.bestIdx[q] = g == 0xFFFFFFFFu ? -1 : (int32_t)si_key_index(g);
-            A.bestDist[q] = g == 0xFFFFFFFFu ? 256 : (int32_t)si_key_dist(g);
+            A.bestIdx[q] = idx;
+            A.bestDist[q] = bd;
         }
     }
 }
