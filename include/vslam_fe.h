@@ -670,7 +670,8 @@ int vslam_search_by_projection_mappoints(vslam_fe* fe, const vslam_mp_track* mps
  * second loop of Tracking::SearchLocalPoints with the matcher behind it (tracking.cpp:3214-3263) in one enqueue: the caller
  * hands in the MapPoints as the map holds them, not the records above, and the list may be longer than the matcher's cap.
  * With a KB8 camera set (vslam_fe_set_kb8_camera, below) the projection is KannalaBrandt8::project; isInFrustumChecks
- * (two-camera fisheye rigs, Nleft != -1) is vslam_frame_in_frustum_rig, the records only.
+ * (two-camera fisheye rigs, Nleft != -1) is vslam_frame_in_frustum_rig for the records and vslam_search_local_points_rig for the
+ * whole chain (below).
  *
  * Per MapPoint the arithmetic of vi_slam_amd/csrc/vslam_frustum.h: Matx algebra in float, both cv::norm in double,
  * Pinhole::project, the closed-interval bounds test over the context's float grid bounds (vslam_fe_set_grid_bounds) or
@@ -746,8 +747,10 @@ int vslam_fe_get_local_points_profile(vslam_fe* fe, double* frustum_ms, double* 
  *     they hold Pinhole::project and would silently project a fisheye frame as a pinhole.
  * A KB8 camera and a distorted pinhole camera (vslam_fe_set_camera with k1 != 0) exclude each other: the reference's fisheye
  * frames have zero mDistCoef.  Setting one while the other is set is VSLAM_ERR_INVALID.
- * Not covered: the right-camera branch of SearchByProjection(F, vpMapPoints) (fmatcher.cpp:422-485) and every other matcher's
- * fisheye branch, TriangulateMatches / epipolarConstrain / matchAndtriangulate (cv::SVD), ReconstructWithTwoViews
+ * The rig form of SearchByProjection(F, vpMapPoints), right-camera branch included (fmatcher.cpp:321-491), is
+ * vslam_search_by_projection_mappoints_rig / vslam_search_local_points_rig below.
+ * Not covered: every other matcher's fisheye or right-camera branch (SearchByProjection(CurrentFrame, LastFrame) :2593-2659,
+ * Fuse(.., bRight), SearchByBoW, SearchForTriangulation), TriangulateMatches / epipolarConstrain / matchAndtriangulate (cv::SVD), ReconstructWithTwoViews
  * (cv::fisheye::undistortPoints), projectJac, tanf beyond 3*pi/4. */
 typedef struct vslam_kb8_camera {
     float fx, fy, cx, cy; /* mvParameters[0..3] */
@@ -766,7 +769,7 @@ int vslam_kb8_unproject(vslam_fe* fe, const float* uv_host, int n, float* xyz_ou
  * beyond the count untouched).  No host wait. */
 int vslam_kb8_unproject_slot_async(vslam_fe* fe, int slot, float* dev_rays);
 /* Frame::isInFrustum for a two-fisheye rig (frame.cpp:596-606, Nleft != -1; isInFrustumChecks :1191-1271): the frustum records
- * only.  The left camera is the context's KB8 camera (its intrinsics must equal p's), the right one rig->cam2; Tlr / Trl are
+ * alone (vslam_search_local_points_rig consumes them on the device).  The left camera is the context's KB8 camera (its intrinsics must equal p's), the right one rig->cam2; Tlr / Trl are
  * rows [R | t] of mTlrx / mTrlx.  Restated as written: tcw = mOwx in the right branch, mRx = Rrl * Rcw and mtx = Rrl * tcw + trl,
  * twcx = Rwc * tlr + tcw, no invz (p->mbf is not read).  track_left[i] / track_right[i]: proj_x / proj_y = the camera's uv
  * (mTrackProjX/Y, mTrackProjXR/YR), view_cos, level, flags bit 0 = mbTrackInView / mbTrackInViewR, bit 1 = the input's; proj_xr
@@ -780,6 +783,60 @@ typedef struct vslam_kb8_rig {
 int vslam_frame_in_frustum_rig(vslam_fe* fe, const vslam_frustum_params* p, const vslam_kb8_rig* rig,
                                const vslam_map_point* points_host, int n, vslam_mp_track* track_left,
                                vslam_mp_track* track_right, float* depth_left, float* depth_right, int* n_in_view);
+
+/* SearchByProjection(F, vpMapPoints, th, bFarPoints, thFarPoints) and Tracking::SearchLocalPoints for a two-fisheye rig
+ * (fmatcher.cpp:321-491 with Nleft != -1; tracking.cpp:3214-3263).  F.mvpMapPoints has n_left + n_right slots: [0, n_left) the
+ * left keypoints, [n_left, n_left + n_right) the right ones.  Restated as written:
+ *   - the left branch (window r * scale[level] with r times th, levels [level - 1, level], NO mvuRight gate in a rig) writes
+ *     its best keypoint's slot and, where mvLeftToRightMatch names one, the right slot L2R + n_left without looking at it
+ *   - a left ratio failure is a `continue`: the right branch of that point is skipped (:403-404)
+ *   - the right branch (r NOT times th, :425; a record with level -1 takes none, :424) writes R2L unchecked, then its own slot
+ *   - a slot is occupied iff its last writer has Observations() > 0, so a cross-write by a point without observations frees it
+ *   - nmatches counts writes, not slots.
+ * Records: flags bit 0 = mbTrackInView / mbTrackInViewR with the far test and isBad folded in, bit 1 = Observations() > 0 (one
+ * MapPoint: the bit of either record counts).  n_left, n_right <= 4096 each (0 is an ordinary input), n_mp <= 4096, nnratio >=
+ * 0.4 (VSLAM_ERR_UNSUPPORTED beyond).  An L2R / R2L entry outside [-1, n_other) is VSLAM_ERR_INVALID, checked before anything is
+ * enqueued.  Both grids use the context's float grid bounds, or {0, img_w, 0, img_h}.  The matcher does not project, so it
+ * runs with or without a KB8 camera set. */
+typedef struct vslam_rig_frame {
+    const vslam_kp* dev_kps_left;  const uint8_t* dev_desc_left;  int n_left;   /* keypoints_, descriptor rows [0, Nleft)      */
+    const vslam_kp* dev_kps_right; const uint8_t* dev_desc_right; int n_right;  /* keypointsRight_, rows [Nleft, Nleft+Nright) */
+    const int32_t* left_to_right_host;   /* mvLeftToRightMatch: n_left entries, -1 or an index < n_right   */
+    const int32_t* right_to_left_host;   /* mvRightToLeftMatch: n_right entries, -1 or an index < n_left   */
+    const uint8_t* occupied_host;        /* n_left + n_right, may be NULL */
+} vslam_rig_frame;
+/* The matcher alone, from caller-made records (the sibling of vslam_search_by_projection_mappoints): match_cur has n_left +
+ * n_right entries, each the index of the last MapPoint written to the slot or -1.  Blocking. */
+int vslam_search_by_projection_mappoints_rig(vslam_fe* fe, const vslam_mp_track* track_left_host,
+                                             const vslam_mp_track* track_right_host, const uint8_t* mp_desc_host, int n_mp,
+                                             const vslam_rig_frame* frame, int img_w, int img_h, float th, float nnratio,
+                                             int32_t* match_cur, int* nmatches);
+/* upload -> k_frustum_rig -> k_rig_keep / k_rig_compact -> k_sbp_rank (two jobs) -> k_rig_resolve -> one result copy, on the
+ * context's stream without a host wait in between.  p, rig: as for vslam_frame_in_frustum_rig (a KB8 camera must be set and
+ * its intrinsics equal p's: VSLAM_ERR_INVALID otherwise).  points / mp_desc / points_where: as for
+ * vslam_search_local_points_async.  A point goes on to the matcher when left OR right sees it and it is not far, in original
+ * order, at most 4096.  The far test (fmatcher.cpp:333) reads mTrackDepth, the left depth, as vslam_frame_in_frustum_rig delivers
+ * it: 0 where the left camera does not see the point (the reference reads an earlier frame's value there), so a right-only
+ * point is never far.
+ * _wait: match_cur (n_left + n_right entries) indexes the caller's points array; *n_to_match counts left || right before the
+ * far test (tracking.cpp:3226-3230); *n_matched_against = points handed on; track_left / track_right (may be NULL): the n_mp
+ * records, identical to vslam_frame_in_frustum_rig's.  More than 4096 points handed on: VSLAM_ERR_UNSUPPORTED with match_cur all
+ * -1, *nmatches = 0 and the two counts delivered.  One local-points search (rig or not) per context may be in flight.  n_mp == 0
+ * or n_left + n_right == 0: an empty result, nothing is launched (and no records: asking for them then is VSLAM_ERR_INVALID). */
+int vslam_search_local_points_rig_async(vslam_fe* fe, const vslam_frustum_params* p, const vslam_kb8_rig* rig,
+                                        const vslam_map_point* points, const uint8_t* mp_desc, int n_mp, int points_where,
+                                        const vslam_rig_frame* frame, float th, float nnratio);
+int vslam_search_local_points_rig_wait(vslam_fe* fe, int32_t* match_cur, int* nmatches, int* n_to_match,
+                                       int* n_matched_against, vslam_mp_track* track_left, vslam_mp_track* track_right);
+/* _async + _wait */
+int vslam_search_local_points_rig(vslam_fe* fe, const vslam_frustum_params* p, const vslam_kb8_rig* rig,
+                                  const vslam_map_point* points, const uint8_t* mp_desc, int n_mp, int points_where,
+                                  const vslam_rig_frame* frame, float th, float nnratio, int32_t* match_cur, int* nmatches,
+                                  int* n_to_match, int* n_matched_against, vslam_mp_track* track_left,
+                                  vslam_mp_track* track_right);
+/* With vslam_fe_set_profiling on: HIP-event time of the two-job k_sbp_rank launch and of k_rig_resolve alone, summed over the
+ * rig searches waited for since profiling was switched on.  Any pointer may be NULL. */
+int vslam_fe_get_local_points_rig_profile(vslam_fe* fe, double* rank_ms, double* resolve_ms, long* passes);
 
 /* Device-resident, batched form of the same matcher: every pointer of a job is a DEVICE pointer; counts are
  * int32 in HBM (vslam_fe_slot_count_ptr); keypoint arrays hold up to the context's capacity (<= 4096).  Up to 16

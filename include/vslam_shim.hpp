@@ -552,6 +552,64 @@ public:
         return nm;
     }
 
+    /* The same for a two-fisheye rig (Frame::Nleft != -1; isInFrustumChecks frame.cpp:1191-1271 and both branches of
+     * SearchByProjection(F, vpMapPoints), fmatcher.cpp:321-491).  cur.left is the left camera: its pose, its intrinsics (those
+     * of the KannalaBrandt8 attached to its extractor) and keypoints_ in its extractor's slot 0; `right` is the extractor that
+     * holds keypointsRight_ (mpORBextractorRight), rig the right camera with mTlr / mTrl.  F.mvpMapPoints has Nleft + Nright
+     * slots, left first: mvpMapPointIndex and `occupied` are laid out that way.  mTrack / mTrackR (may be NULL) receive
+     * the records of the left and of the right camera; nToMatch counts left || right (tracking.cpp:3226-3230). */
+    struct RigFrameView {
+        LocalFrameView left;
+        const FExtractor* right = nullptr;
+        vslam_kb8_rig rig;
+        const std::vector<int>* mvLeftToRightMatch = nullptr;
+        const std::vector<int>* mvRightToLeftMatch = nullptr;
+    };
+    int SearchLocalPoints(const RigFrameView& cur, const std::vector<vslam_map_point>& mvpLocalMapPoints,
+                          const std::vector<uint8_t>& mapPointDescriptors, const std::vector<uint8_t>* occupied,
+                          const float th, const bool bFarPoints, const float thFarPoints,
+                          std::vector<int>& mvpMapPointIndex, int& nToMatch, std::vector<vslam_mp_track>* mTrack = nullptr,
+                          std::vector<vslam_mp_track>* mTrackR = nullptr, const float viewingCosLimit = 0.5f) {
+        static_assert(sizeof(int) == sizeof(int32_t), "mvLeftToRightMatch is handed over as int32");
+        if (!cur.right || !cur.mvLeftToRightMatch || !cur.mvRightToLeftMatch)
+            throw std::invalid_argument("SearchLocalPoints: a rig frame needs its right extractor and both match maps");
+        const LocalFrameView& L = cur.left;
+        vslam_frustum_params p;
+        std::memset(&p, 0, sizeof(p));
+        std::memcpy(p.Tcw, L.Tcw, sizeof(p.Tcw));
+        std::memcpy(p.Ow, L.Ow, sizeof(p.Ow));
+        p.fx = L.fx; p.fy = L.fy; p.cx = L.cx; p.cy = L.cy; p.mbf = L.mbf;
+        p.viewing_cos_limit = viewingCosLimit;
+        p.log_scale_factor = L.mfLogScaleFactor;
+        p.img_w = L.frame.mnMaxX;
+        p.img_h = L.frame.mnMaxY;
+        p.far_points = bFarPoints ? 1 : 0;
+        p.th_far_points = thFarPoints;
+        vslam_rig_frame f;
+        std::memset(&f, 0, sizeof(f));
+        check(vslam_fe_slot_buffers(L.frame.extractor->context(), 0, &f.dev_kps_left, &f.dev_desc_left, &f.n_left));
+        check(vslam_fe_slot_buffers(cur.right->context(), 0, &f.dev_kps_right, &f.dev_desc_right, &f.n_right));
+        if ((int)cur.mvLeftToRightMatch->size() != f.n_left || (int)cur.mvRightToLeftMatch->size() != f.n_right ||
+            (occupied && (int)occupied->size() != f.n_left + f.n_right))
+            throw std::invalid_argument("SearchLocalPoints: match maps / occupancy do not fit the rig's keypoints");
+        f.left_to_right_host = cur.mvLeftToRightMatch->data();
+        f.right_to_left_host = cur.mvRightToLeftMatch->data();
+        f.occupied_host = occupied ? occupied->data() : nullptr;
+        const int N = f.n_left + f.n_right;
+        int nm = 0, against = 0;
+        mvpMapPointIndex.assign(N, -1);
+        nToMatch = 0;
+        if (mTrack) mTrack->resize(mvpLocalMapPoints.size());
+        if (mTrackR) mTrackR->resize(mvpLocalMapPoints.size());
+        const bool records = N > 0 && !mvpLocalMapPoints.empty();
+        check(vslam_search_local_points_rig(L.frame.extractor->context(), &p, &cur.rig, mvpLocalMapPoints.data(),
+                                            mapPointDescriptors.data(), (int)mvpLocalMapPoints.size(), VSLAM_IMGS_HOST, &f, th,
+                                            mfNNratio, mvpMapPointIndex.data(), &nm, &nToMatch, &against,
+                                            (mTrack && records) ? mTrack->data() : nullptr,
+                                            (mTrackR && records) ? mTrackR->data() : nullptr));
+        return nm;
+    }
+
 protected:
     /* the current frame's keypoints for the projection matchers: keypoints_ of slot 0 as before, ukeypoints_ once the
      * context holds grid bounds (SetGridBounds) -- the undistorted grid bins undistorted keypoints */

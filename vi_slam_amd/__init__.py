@@ -63,6 +63,8 @@ ABI_SYMBOLS = [
     "vslam_search_local_points", "vslam_fe_get_local_points_profile",
     "vslam_fe_set_kb8_camera", "vslam_kb8_project", "vslam_kb8_unproject", "vslam_kb8_unproject_slot_async",
     "vslam_frame_in_frustum_rig",
+    "vslam_search_by_projection_mappoints_rig", "vslam_search_local_points_rig_async", "vslam_search_local_points_rig_wait",
+    "vslam_search_local_points_rig", "vslam_fe_get_local_points_rig_profile",
     "vslam_two_view_score_async", "vslam_two_view_score_wait", "vslam_two_view_score", "vslam_fe_get_two_view_profile",
     "vslam_kfdb_create", "vslam_kfdb_create_ex", "vslam_kfdb_destroy", "vslam_kfdb_add", "vslam_kfdb_erase",
     "vslam_kfdb_clear", "vslam_kfdb_clear_map", "vslam_kfdb_size", "vslam_kfdb_stats", "vslam_kfdb_query_async",
@@ -294,6 +296,33 @@ def kb8_rig(cam2, Tlr, Trl):
         for j in range(12):
             getattr(r, name)[j] = float(T[j])
     return r
+
+
+class _RigFrame(C.Structure):  # vslam_rig_frame
+    _fields_ = [("dev_kps_left", C.c_void_p), ("dev_desc_left", C.c_void_p), ("n_left", C.c_int),
+                ("dev_kps_right", C.c_void_p), ("dev_desc_right", C.c_void_p), ("n_right", C.c_int),
+                ("left_to_right_host", C.c_void_p), ("right_to_left_host", C.c_void_p), ("occupied_host", C.c_void_p)]
+
+
+def rig_frame(dev_kps_left, dev_desc_left, n_left, dev_kps_right, dev_desc_right, n_right, left_to_right, right_to_left,
+              occupied=None):
+    """vslam_rig_frame: device addresses of both cameras' keypoints / descriptors, mvLeftToRightMatch / mvRightToLeftMatch
+    (host int32 arrays, -1 or an index of the other side) and the occupancy of the n_left + n_right slots (or None).  The
+    host arrays are kept alive by the returned object."""
+    f = _RigFrame()
+    f.dev_kps_left, f.dev_desc_left, f.n_left = dev_kps_left or None, dev_desc_left or None, int(n_left)
+    f.dev_kps_right, f.dev_desc_right, f.n_right = dev_kps_right or None, dev_desc_right or None, int(n_right)
+    l2r, r2l = np.ascontiguousarray(left_to_right, np.int32), np.ascontiguousarray(right_to_left, np.int32)
+    if len(l2r) != f.n_left or len(r2l) != f.n_right:
+        raise ValueError("left_to_right / right_to_left must have n_left / n_right entries")
+    oc = None if occupied is None else np.ascontiguousarray(occupied, np.uint8)
+    if oc is not None and len(oc) != f.n_left + f.n_right:
+        raise ValueError("occupied must have n_left + n_right entries")
+    f.left_to_right_host = l2r.ctypes.data if len(l2r) else None
+    f.right_to_left_host = r2l.ctypes.data if len(r2l) else None
+    f.occupied_host = oc.ctypes.data if oc is not None and len(oc) else None
+    f._keep = (l2r, r2l, oc)
+    return f
 
 
 class _Bounds(C.Structure):  # vslam_bounds
@@ -563,6 +592,14 @@ def lib():
         L.vslam_kb8_unproject.argtypes = [vp, vp, i, vp]
         L.vslam_kb8_unproject_slot_async.argtypes = [vp, i, vp]
         L.vslam_frame_in_frustum_rig.argtypes = [vp, fp, C.POINTER(_Kb8Rig), vp, i, vp, vp, vp, vp, C.POINTER(i)]
+        rf = C.POINTER(_RigFrame)
+        L.vslam_search_by_projection_mappoints_rig.argtypes = [vp, vp, vp, vp, i, rf, i, i, f, f, vp, C.POINTER(i)]
+        L.vslam_search_local_points_rig_async.argtypes = [vp, fp, C.POINTER(_Kb8Rig), vp, vp, i, i, rf, f, f]
+        L.vslam_search_local_points_rig_wait.argtypes = [vp, vp, C.POINTER(i), C.POINTER(i), C.POINTER(i), vp, vp]
+        L.vslam_search_local_points_rig.argtypes = [vp, fp, C.POINTER(_Kb8Rig), vp, vp, i, i, rf, f, f, vp, C.POINTER(i),
+                                                    C.POINTER(i), C.POINTER(i), vp, vp]
+        L.vslam_fe_get_local_points_rig_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                            C.POINTER(C.c_long)]
         L.vslam_two_view_score_async.argtypes = [vp, i, C.POINTER(_TwoViewJob)]
         L.vslam_two_view_score_wait.argtypes = [vp, C.POINTER(_TwoViewResult)]
         L.vslam_two_view_score.argtypes = [vp, C.POINTER(_TwoViewJob), C.POINTER(_TwoViewResult)]
@@ -1095,6 +1132,72 @@ class FExtractor:
         self.search_local_points_async(params, points, mp_desc, dev_cur_kps, dev_cur_desc, n_cur, cur_u_right, occupied, th,
                                        nnratio, n_mp)
         return self.search_local_points_wait(want_track)
+
+    def search_by_projection_mappoints_rig(self, track_left, track_right, mp_desc, frame, th=1.0, nnratio=0.8,
+                                           img_size=None):
+        """FMatcher::SearchByProjection(F, vpMapPoints, th, ...) for a two-fisheye rig (fmatcher.cpp:321-491, Nleft != -1)
+        from caller-made records (MP_TRACK_DTYPE, far test folded into bit 0); frame from rig_frame().
+        -> (nmatches, match_cur[n_left + n_right] = index of the last MapPoint written to the slot or -1)"""
+        tl = np.ascontiguousarray(track_left, MP_TRACK_DTYPE)
+        tr = np.ascontiguousarray(track_right, MP_TRACK_DTYPE)
+        md = np.ascontiguousarray(mp_desc, np.uint8)
+        if not (len(tl) == len(tr) == len(md)):
+            raise ValueError("one left record, one right record and one descriptor per MapPoint")
+        w, h = img_size or (self.width, self.height)
+        n = frame.n_left + frame.n_right
+        m = np.full(max(n, 1), -1, np.int32)
+        nm = C.c_int(0)
+        _check(lib().vslam_search_by_projection_mappoints_rig(self._h, _p(tl), _p(tr), _p(md), len(tl), C.byref(frame), w, h,
+                                                              C.c_float(th), C.c_float(nnratio), _p(m), C.byref(nm)))
+        return nm.value, m[:n]
+
+    def search_local_points_rig_async(self, params, rig, points, mp_desc, frame, th=1.0, nnratio=0.8, n_mp=None):
+        """Enqueue isInFrustum of both cameras + ordered compaction (left || right, not far) + the rig matcher and return.
+        points / mp_desc: numpy arrays or two device addresses with n_mp given, as for search_local_points_async; rig from
+        kb8_rig(), frame from rig_frame()."""
+        on_dev = isinstance(points, int)
+        if on_dev:
+            if n_mp is None:
+                raise ValueError("n_mp is required with device addresses")
+            pp, dp = C.c_void_p(points), C.c_void_p(int(mp_desc))
+        else:
+            self._lp_keep = (np.ascontiguousarray(points, MAP_POINT_DTYPE), np.ascontiguousarray(mp_desc, np.uint8))
+            n_mp = len(self._lp_keep[0])
+            pp, dp = _p(self._lp_keep[0]), _p(self._lp_keep[1])
+        _check(lib().vslam_search_local_points_rig_async(self._h, C.byref(params), C.byref(rig), pp, dp, n_mp,
+                                                         IMGS_DEVICE if on_dev else IMGS_HOST, C.byref(frame), C.c_float(th),
+                                                         C.c_float(nnratio)))
+        self._lp_rig_shape = (n_mp, frame.n_left + frame.n_right)
+
+    def search_local_points_rig_wait(self, want_track=False):
+        """-> (nmatches, match_cur[n_left + n_right] = index into `points` or -1, points either camera sees, points handed to
+        the matcher[, left records, right records]).  Raises VslamError(ERR_UNSUPPORTED) when more than 4096 points went on
+        to the matcher; the error carries .n_to_match, .n_matched_against and .match_cur."""
+        n_mp, n = self._lp_rig_shape
+        m = np.full(max(n, 1), -1, np.int32)
+        tl = np.zeros(max(n_mp, 1), MP_TRACK_DTYPE) if want_track else None
+        tr = np.zeros(max(n_mp, 1), MP_TRACK_DTYPE) if want_track else None
+        nm, nt, na = C.c_int(0), C.c_int(0), C.c_int(0)
+        rc = lib().vslam_search_local_points_rig_wait(self._h, _p(m), C.byref(nm), C.byref(nt), C.byref(na),
+                                                      _p(tl) if want_track else None, _p(tr) if want_track else None)
+        self._lp_keep = None
+        if rc != VSLAM_OK:
+            e = VslamError(rc, lib().vslam_last_error().decode())
+            e.n_to_match, e.n_matched_against, e.match_cur = nt.value, na.value, m[:n]
+            raise e
+        out = (nm.value, m[:n], nt.value, na.value)
+        return out + (tl[:n_mp], tr[:n_mp]) if want_track else out
+
+    def search_local_points_rig(self, params, rig, points, mp_desc, frame, th=1.0, nnratio=0.8, n_mp=None, want_track=False):
+        """search_local_points_rig_async + search_local_points_rig_wait"""
+        self.search_local_points_rig_async(params, rig, points, mp_desc, frame, th, nnratio, n_mp)
+        return self.search_local_points_rig_wait(want_track)
+
+    def get_local_points_rig_profile(self):
+        """-> (ms in the two-job k_sbp_rank launch, ms in k_rig_resolve, rig searches) since set_profiling(True)"""
+        a, b, n = C.c_double(0), C.c_double(0), C.c_long(0)
+        _check(lib().vslam_fe_get_local_points_rig_profile(self._h, C.byref(a), C.byref(b), C.byref(n)))
+        return a.value, b.value, n.value
 
     def two_view_score_async(self, jobs):
         """Enqueue MotionEstimator::CheckHomography / CheckFundamental of every hypothesis and the selection of

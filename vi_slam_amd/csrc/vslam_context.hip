@@ -534,6 +534,8 @@ extern "C" int vslam_fe_set_profiling(vslam_fe* fe, int on) {
     fe->rgbd_passes = 0;
     fe->lp_ms[0] = fe->lp_ms[1] = 0;
     fe->lp_passes = 0;
+    fe->rig_ms[0] = fe->rig_ms[1] = 0;
+    fe->rig_passes = 0;
     return VSLAM_OK;
 }
 

@@ -148,9 +148,10 @@ struct vslam_fe {
     int bow_jobs = 0;
     vslam_staging kfdb;         /* KeyFrameDatabase query: uploaded BowVectors | dense per-slot results (vslam_kfdb.hip) */
     vslam_staging lp;           /* SearchLocalPoints: inputs | frustum records | compacted arrays | matcher scratch | results (vslam_projection.hip) */
-    int lp_state = 0;           /* 0: nothing enqueued, 1: a search is in flight, 2: an empty search (nothing launched) */
+    int lp_state = 0;           /* 0: nothing enqueued, 1: a search is in flight, 2: an empty search (nothing launched); 3, 4: the same two of a rig search (vslam_search_local_points_rig_async), whose lp_n_cur counts the slots of both sides */
     int lp_n_mp = 0, lp_n_cur = 0, lp_cap = 0;
     size_t lp_o_track = 0, lp_o_res = 0, lp_o_cnt = 0, lp_o_idx = 0; /* where the records and the result block (matches | counts | indices) start */
+    size_t lp_o_track_r = 0;    /* a rig search: the right camera's records */
     bool use_graph = true;          /* host-image passes replay a captured HIP graph (VSLAM_GRAPH=0 disables) */
     hipGraphExec_t graph_exec = nullptr;
     long long graph_key = 0;
@@ -199,6 +200,10 @@ struct vslam_fe {
     bool lp_timed = false;
     double lp_ms[2] = {0, 0};
     long lp_passes = 0;
+    vslam_event ev_rig[3];      /* profiling of a rig search: before k_sbp_rank | between | behind k_rig_resolve */
+    bool rig_timed = false;
+    double rig_ms[2] = {0, 0};
+    long rig_passes = 0;
 
     /* GPU quadtree distribution */
     bool dev_octree = false;

@@ -242,6 +242,19 @@ struct SbpJobs { /* by-value kernel argument (< 4 KB) */
     SbpKfDev kf;
 };
 
+/* k_rig_resolve (SearchByProjection(F, vpMapPoints) of a two-camera rig): job 0 of the SbpJobs beside it is the left side, job
+ * 1 the right one; every pointer a DEVICE pointer */
+struct RigResolveDev {
+    int32_t nLeft, nRight;      /* keypoints per side, <= 4096 each; slots [0, nLeft) left, [nLeft, nLeft + nRight) right */
+    int32_t forceSeq;           /* 1: re-scan every window in full, read no prefix */
+    const int32_t* leftToRight; /* nLeft: mvLeftToRightMatch */
+    const int32_t* rightToLeft; /* nRight: mvRightToLeftMatch */
+    const uint8_t* occupied0;   /* nLeft + nRight, may be null */
+    int32_t* matchCur;          /* out: nLeft + nRight */
+    int32_t* nmatches;          /* out: 1 */
+    int32_t* fallbacks;         /* diagnostics: full re-scans, may be null */
+};
+
 /* k_unproject_stereo: one stereo pair's left keypoints -> world points (Frame::UnprojectStereo) */
 struct UnprojJob {
     float Twc[12]; /* rows [mRwc | mOw] */

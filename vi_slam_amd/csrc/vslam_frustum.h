@@ -154,4 +154,19 @@ struct FrustumCompactDev {
     int32_t* indexC;
     int32_t* counts; /* out: [0] kept, [1] min(kept, cap), [2] nToMatch */
 };
+/* the rig's compaction (k_rig_keep, k_rig_compact): two record arrays in, two compacted ones out; chunkKeep is its own scratch */
+struct FrustumRigCompactDev {
+    int32_t n, nchunks, farPoints, cap;
+    float thFarPoints;
+    const vslam_mp_track *trackL, *trackR;
+    const float* depthL; /* mTrackDepth: the far test reads the left depth for every point */
+    const uint8_t* desc;
+    int32_t* chunkKeep;          /* scratch: nchunks */
+    const int32_t* chunkInView;  /* per chunk, left || right (k_frustum_rig) */
+    vslam_mp_track *trackLC, *trackRC;
+    uint8_t* descC;
+    uint8_t* flagsC;
+    int32_t* indexC;
+    int32_t* counts; /* out: [0] kept, [1] min(kept, cap), [2] nToMatch */
+};
 #endif

@@ -1117,6 +1117,175 @@ int vslamh_local_points_finish(const int32_t* match_compact, int n_cur, const in
     return VSLAM_OK;
 }
 
+/* mvLeftToRightMatch / mvRightToLeftMatch of a rig frame: every entry -1 or an index of the other side */
+int vslamh_rig_maps_check(const int32_t* left_to_right, int n_left, const int32_t* right_to_left, int n_right) {
+    if (n_left < 0 || n_right < 0 || (n_left && !left_to_right) || (n_right && !right_to_left)) return VSLAM_ERR_INVALID;
+    for (int i = 0; i < n_left; i++)
+        if (left_to_right[i] < -1 || left_to_right[i] >= n_right) return VSLAM_ERR_INVALID;
+    for (int i = 0; i < n_right; i++)
+        if (right_to_left[i] < -1 || right_to_left[i] >= n_left) return VSLAM_ERR_INVALID;
+    return VSLAM_OK;
+}
+
+namespace {
+/* Frame::AssignFeaturesToGrid / PosInGrid (frame.cpp:322-323, :746-756) and GetFeaturesInArea (:678-744) over one keypoint set */
+struct RigGrid {
+    static const int COLS = 64, ROWS = 48;
+    const vslam_kp* kps;
+    float minX, minY, invW, invH;
+    std::vector<std::vector<int>> cell;
+    RigGrid(const vslam_kp* k, int n, const float* b) : kps(k), cell((size_t)COLS * ROWS) {
+        minX = b[0];
+        minY = b[2];
+        invW = (float)COLS / (b[1] - b[0]);
+        invH = (float)ROWS / (b[3] - b[2]);
+        for (int i = 0; i < n; i++) {
+            const int px = (int)roundf((k[i].x - minX) * invW), py = (int)roundf((k[i].y - minY) * invH);
+            if (px < 0 || px >= COLS || py < 0 || py >= ROWS) continue;
+            cell[(size_t)px * ROWS + py].push_back(i);
+        }
+    }
+    void query(float x, float y, float r, int minLevel, int maxLevel, std::vector<int>& out) const {
+        out.clear();
+        const int c0 = std::max(0, (int)floorf((x - minX - r) * invW));
+        if (c0 >= COLS) return;
+        const int c1 = std::min(COLS - 1, (int)ceilf((x - minX + r) * invW));
+        if (c1 < 0) return;
+        const int r0 = std::max(0, (int)floorf((y - minY - r) * invH));
+        if (r0 >= ROWS) return;
+        const int r1 = std::min(ROWS - 1, (int)ceilf((y - minY + r) * invH));
+        if (r1 < 0) return;
+        const bool check = minLevel > 0 || maxLevel >= 0;
+        for (int ix = c0; ix <= c1; ix++)
+            for (int iy = r0; iy <= r1; iy++)
+                for (int i : cell[(size_t)ix * ROWS + iy]) {
+                    if (check) {
+                        if (kps[i].octave < minLevel) continue;
+                        if (maxLevel >= 0 && kps[i].octave > maxLevel) continue;
+                    }
+                    if (fabsf(kps[i].x - x) < r && fabsf(kps[i].y - y) < r) out.push_back(i);
+                }
+    }
+};
+int rig_hamming(const uint8_t* a, const uint8_t* b) {
+    int d = 0;
+    for (int i = 0; i < 32; i++) d += __builtin_popcount((unsigned)(a[i] ^ b[i]));
+    return d;
+}
+struct RigBest {
+    int bestDist = 256, bestLevel = -1, bestDist2 = 256, bestLevel2 = -1, bestIdx = -1;
+    void take(int dist, int level, int idx) { /* fmatcher.cpp:381-397 */
+        if (dist < bestDist) {
+            bestDist2 = bestDist;
+            bestDist = dist;
+            bestLevel2 = bestLevel;
+            bestLevel = level;
+            bestIdx = idx;
+        } else if (dist < bestDist2) {
+            bestLevel2 = level;
+            bestDist2 = dist;
+        }
+    }
+};
+} // namespace
+
+/* FMatcher::SearchByProjection(Frame& F, const vector<MapPoint*>&, th, ...) (fmatcher.cpp:321-491) as it is written, for both
+ * kinds of Frame; the sequential statement the device resolver (k_rig_resolve) is tested against, CPU tests and the demo.
+ * track_right == NULL: Nleft == -1 (the right arguments are not read; u_right, may be NULL, is the frame's mvuRight).
+ * Otherwise a rig: slots [0, n_left) are the left keypoints, [n_left, n_left + n_right) the right ones.  Records as
+ * Frame::isInFrustum leaves them, far test and isBad folded into flag bit 0; bit 1 (of either record) = Observations() > 0.
+ * scale_factors: mvScaleFactors, nlevels entries; bounds: mnMinX, mnMaxX, mnMinY, mnMaxY.  occupied (may be NULL): per slot. */
+int vslamh_search_by_projection_mappoints_rig(const vslam_mp_track* track_left, const vslam_mp_track* track_right,
+                                              const uint8_t* mp_desc, int n_mp, const vslam_kp* kps_left,
+                                              const uint8_t* desc_left, int n_left, const vslam_kp* kps_right,
+                                              const uint8_t* desc_right, int n_right, const int32_t* left_to_right,
+                                              const int32_t* right_to_left, const float* u_right, const uint8_t* occupied,
+                                              const float* scale_factors, int nlevels, const float* bounds, float th,
+                                              float nnratio, int32_t* match_cur, int* nmatches) {
+    const bool rig = track_right != nullptr;
+    if (!rig) n_right = 0;
+    if (n_mp < 0 || n_left < 0 || n_right < 0 || nlevels < 1 || !scale_factors || !bounds || !nmatches ||
+        (n_mp && (!track_left || !mp_desc)) || (n_left && (!kps_left || !desc_left)) || (n_right && (!kps_right || !desc_right)) ||
+        ((n_left + n_right) && !match_cur))
+        return VSLAM_ERR_INVALID;
+    if (rig)
+        if (int rc = vslamh_rig_maps_check(left_to_right, n_left, right_to_left, n_right)) return rc;
+    const int TH_HIGH = 100;
+    const int N = n_left + n_right;
+    std::vector<uint8_t> occ((size_t)N, 0);
+    for (int i = 0; i < N; i++) {
+        match_cur[i] = -1;
+        if (occupied) occ[i] = occupied[i] != 0;
+    }
+    const RigGrid gl(kps_left, n_left, bounds), gr(kps_right, n_right, bounds);
+    std::vector<int> vIndices;
+    const bool bFactor = th != 1.0f;
+    int nm = 0;
+    /* mvScaleFactors[level]: a caller-made record's level is clamped into the table, as k_sbp_rank does */
+    auto scale_of = [&](int l) { return scale_factors[std::min(std::max(l, 0), nlevels - 1)]; };
+    for (int iMP = 0; iMP < n_mp; iMP++) {
+        const vslam_mp_track& L = track_left[iMP];
+        const bool inL = (L.flags & 1u) != 0, inR = rig && (track_right[iMP].flags & 1u) != 0;
+        if (!inL && !inR) continue;
+        const uint8_t obs = ((L.flags | (rig ? track_right[iMP].flags : 0u)) & 2u) ? 1 : 0;
+        const uint8_t* d = mp_desc + (size_t)iMP * 32;
+        if (inL) {
+            float r = (double)L.view_cos > 0.998 ? 2.5f : 4.0f;
+            if (bFactor) r *= th;
+            const float rs = r * scale_of(L.level);
+            gl.query(L.proj_x, L.proj_y, rs, L.level - 1, L.level, vIndices);
+            if (!vIndices.empty()) {
+                RigBest b;
+                for (int idx : vIndices) {
+                    if (occ[idx]) continue;
+                    if (!rig && u_right && u_right[idx] > 0) {
+                        const float er = fabsf(L.proj_xr - u_right[idx]);
+                        if (er > rs) continue;
+                    }
+                    b.take(rig_hamming(d, desc_left + (size_t)idx * 32), kps_left[idx].octave, idx);
+                }
+                if (b.bestDist <= TH_HIGH) {
+                    if (b.bestLevel == b.bestLevel2 && (float)b.bestDist > nnratio * (float)b.bestDist2) continue;
+                    match_cur[b.bestIdx] = iMP;
+                    occ[b.bestIdx] = obs;
+                    if (rig && left_to_right[b.bestIdx] != -1) {
+                        const int s = left_to_right[b.bestIdx] + n_left;
+                        match_cur[s] = iMP;
+                        occ[s] = obs;
+                        nm++;
+                    }
+                    nm++;
+                }
+            }
+        }
+        if (inR) {
+            const vslam_mp_track& R = track_right[iMP];
+            if (R.level == -1) continue;
+            const float r = (double)R.view_cos > 0.998 ? 2.5f : 4.0f; /* no bFactor here (fmatcher.cpp:425) */
+            gr.query(R.proj_x, R.proj_y, r * scale_of(R.level), R.level - 1, R.level, vIndices);
+            if (vIndices.empty()) continue;
+            RigBest b;
+            for (int idx : vIndices) {
+                if (occ[idx + n_left]) continue;
+                b.take(rig_hamming(d, desc_right + (size_t)idx * 32), kps_right[idx].octave, idx);
+            }
+            if (b.bestDist <= TH_HIGH) {
+                if (b.bestLevel == b.bestLevel2 && (float)b.bestDist > nnratio * (float)b.bestDist2) continue;
+                if (right_to_left[b.bestIdx] != -1) {
+                    match_cur[right_to_left[b.bestIdx]] = iMP;
+                    occ[right_to_left[b.bestIdx]] = obs;
+                    nm++;
+                }
+                match_cur[b.bestIdx + n_left] = iMP;
+                occ[b.bestIdx + n_left] = obs;
+                nm++;
+            }
+        }
+    }
+    *nmatches = nm;
+    return VSLAM_OK;
+}
+
 /* ---- fisheye cameras: the shared vslam_kb8.h code on the host (CPU tests, the stand-alone demo; the product runs the kernels
  * of vslam_kb8.hip) ---- */
 /* the libm restatements over n arguments: fn 0 atanf, 1 tanf, 2 sinf, 3 cosf (a, out), 4 atan2f (a = y, b = x) */

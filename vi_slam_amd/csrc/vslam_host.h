@@ -219,6 +219,9 @@ extern "C" uint64_t vslamh_layout(uint64_t align, const uint64_t* sizes, int n, 
 /* vslam_host.cpp: index map-back and over-capacity decision of vslam_search_local_points_wait */
 extern "C" int vslamh_local_points_finish(const int32_t* match_compact, int n_cur, const int32_t* orig_index, int n_kept,
                                           int capacity, int32_t* match_cur);
+/* vslam_host.cpp: the range check of a rig frame's mvLeftToRightMatch / mvRightToLeftMatch (each entry -1 or an index of the
+ * other side), as vslam_search_by_projection_mappoints_rig makes it before anything is enqueued */
+extern "C" int vslamh_rig_maps_check(const int32_t* left_to_right, int n_left, const int32_t* right_to_left, int n_right);
 /* vslam_host.cpp: vslam_two_view_score over host arrays by the shared vslam_two_view.h code (CPU tests, the demo) */
 extern "C" int vslamh_two_view_score(const vslam_two_view_job* job, vslam_two_view_result* result);
 /* vslam_host.cpp: the decisions around a KB8 camera, as the entry points take them (each returns a VSLAM_* code):

@@ -79,6 +79,11 @@ size_t vk_sbp_replay_lds(int nCur, int nLast);
 size_t vk_sbp_scratch_bytes(int nLast, int M);
 size_t vk_sbp_proj_bytes(int nLast);
 int vk_sbp_set_max_lds(size_t bytes);
+struct RigResolveDev;
+/* the rig form of SearchByProjection(F, vpMapPoints): k_sbp_rank over JS.job[0] (left) and JS.job[1] (right) in one launch, then
+ * k_rig_resolve; maxMp sizes the grid (capacity of the MapPoint list); `between` (may be null) is recorded between the two */
+size_t vk_rig_resolve_lds(int nSlots);
+void vk_search_rig(hipStream_t st, const SbpJobs& JS, const RigResolveDev& A, int maxMp, hipEvent_t between = nullptr);
 void vk_search_by_projection(hipStream_t st, const SbpJobs& JS, int njobs, int maxLast, int maxCur, int* fallbacks,
                              int forceSeq);
 int vk_distinctive_set_max_lds(size_t bytes);
@@ -109,6 +114,8 @@ struct FrustumArgsDev;
 struct FrustumCompactDev;
 void vk_frustum(hipStream_t st, const FrustumArgsDev& A);
 void vk_frustum_compact(hipStream_t st, const FrustumCompactDev& A);
+struct FrustumRigCompactDev;
+void vk_rig_compact(hipStream_t st, const FrustumRigCompactDev& A);
 /* the same records with KannalaBrandt8::project, and isInFrustumChecks for both cameras of a fisheye rig (vslam_kb8.hip) */
 struct FrustumRigDev;
 void vk_frustum_kb8(hipStream_t st, const FrustumArgsDev& A, const vslam_kb8_camera& cam);

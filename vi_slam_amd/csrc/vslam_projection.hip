@@ -514,6 +514,9 @@ extern "C" int vslam_fuse_search(vslam_fe* fe, const vslam_fuse_params* p, const
  * k_sbpm_resolve and k_sbpm_replay read their MapPoint count as min(*nLastPtr, nLast) in mode 1 exactly as in mode 0, so the
  * matcher is enqueued behind the compaction with nLast = the capacity and nLastPtr = the clamped count in HBM: no host
  * wait between the stages. */
+/* a local-points search, rig or not, holds fe->lp until its _wait */
+static bool lp_in_flight(const vslam_fe* fe) { return fe->lp_state == 1 || fe->lp_state == 3; }
+
 static bool frustum_params_ok(const vslam_frustum_params* p) {
     if (!p || p->img_w < 1 || p->img_h < 1) return false;
     for (int i = 0; i < 12; i++)
@@ -556,7 +559,7 @@ extern "C" int vslam_frame_in_frustum(vslam_fe* fe, const vslam_frustum_params* 
         g_err = "Frame::isInFrustum on the device supports at most 65536 MapPoints per call";
         return VSLAM_ERR_UNSUPPORTED;
     }
-    if (fe->lp_state == 1) {
+    if (lp_in_flight(fe)) {
         g_err = "a local-points search is in flight (vslam_search_local_points_wait)";
         return VSLAM_ERR_INVALID;
     }
@@ -620,7 +623,7 @@ extern "C" int vslam_frame_in_frustum_rig(vslam_fe* fe, const vslam_frustum_para
         g_err = "Frame::isInFrustum on the device supports at most 65536 MapPoints per call";
         return VSLAM_ERR_UNSUPPORTED;
     }
-    if (fe->lp_state == 1) {
+    if (lp_in_flight(fe)) {
         g_err = "a local-points search is in flight (vslam_search_local_points_wait)";
         return VSLAM_ERR_INVALID;
     }
@@ -678,7 +681,7 @@ extern "C" int vslam_search_local_points_async(vslam_fe* fe, const vslam_frustum
         g_err = "device MapPoint descriptors must be 16-byte aligned, device MapPoints 4-byte aligned";
         return VSLAM_ERR_INVALID;
     }
-    if (fe->lp_state == 1) {
+    if (lp_in_flight(fe)) {
         g_err = "a local-points search is already in flight (vslam_search_local_points_wait)";
         return VSLAM_ERR_INVALID;
     }
@@ -800,6 +803,10 @@ extern "C" int vslam_search_local_points_wait(vslam_fe* fe, int32_t* match_cur, 
         g_err = "nothing enqueued";
         return VSLAM_ERR_INVALID;
     }
+    if (fe->lp_state >= 3) {
+        g_err = "the search enqueued is a rig search (vslam_search_local_points_rig_wait)";
+        return VSLAM_ERR_INVALID;
+    }
     const int n_mp = fe->lp_n_mp, n_cur = fe->lp_n_cur;
     if (!nmatches || !n_to_match || !n_matched_against || (n_cur && !match_cur)) {
         g_err = "invalid arguments";
@@ -866,5 +873,340 @@ extern "C" int vslam_fe_get_local_points_profile(vslam_fe* fe, double* frustum_m
     if (frustum_ms) *frustum_ms = fe->lp_ms[0];
     if (compact_ms) *compact_ms = fe->lp_ms[1];
     if (passes) *passes = fe->lp_passes;
+    return VSLAM_OK;
+}
+
+/* ------------------------------------------------------------------ SearchByProjection(F, vpMapPoints), SearchLocalPoints: rig
+ * fmatcher.cpp:321-491 with Nleft != -1.  Ranking is k_sbp_rank mode 1 as two jobs of one launch (left keypoints with the
+ * caller's th, right keypoints with th = 1); the coupled resolution is k_rig_resolve (vslam_projection_kernels.hip). */
+static int rig_frame_check(const vslam_rig_frame* f) {
+    if (!f || f->n_left < 0 || f->n_right < 0 || (f->n_left && (!f->dev_kps_left || !f->dev_desc_left)) ||
+        (f->n_right && (!f->dev_kps_right || !f->dev_desc_right))) {
+        g_err = "invalid arguments";
+        return VSLAM_ERR_INVALID;
+    }
+    if (f->n_left > 4096 || f->n_right > 4096) { /* the 12-bit index of the ordering key */
+        g_err = "SearchByProjection on the device supports at most 4096 keypoints per camera";
+        return VSLAM_ERR_UNSUPPORTED;
+    }
+    if (vslamh_rig_maps_check(f->left_to_right_host, f->n_left, f->right_to_left_host, f->n_right)) {
+        g_err = "mvLeftToRightMatch / mvRightToLeftMatch: every entry is -1 or an index of the other camera's keypoints";
+        return VSLAM_ERR_INVALID;
+    }
+    return VSLAM_OK;
+}
+
+/* maps and occupancy of a rig frame into the mirror at o_l | o_r | o_o */
+static void rig_frame_stage(const vslam_rig_frame& f, uint8_t* h, size_t o_l, size_t o_r, size_t o_o) {
+    if (f.n_left) memcpy(h + o_l, f.left_to_right_host, (size_t)f.n_left * 4);
+    if (f.n_right) memcpy(h + o_r, f.right_to_left_host, (size_t)f.n_right * 4);
+    if (f.occupied_host) memcpy(h + o_o, f.occupied_host, (size_t)f.n_left + (size_t)f.n_right);
+}
+
+/* the two ranking jobs and the resolver's arguments over device arrays: records, descriptors and flags of n_mp MapPoints
+ * (n_mp_ptr: their count in HBM, or null), scratch of vk_sbp_scratch_bytes(n_mp, M) per side */
+static void rig_jobs(const vslam_fe* fe, int M, const vslam_rig_frame& f, int img_w, int img_h, float th, float nnratio,
+                     const MpTrack* recL, const MpTrack* recR, const uint8_t* desc, const uint8_t* flags, int n_mp,
+                     const int32_t* n_mp_ptr, uint8_t* scrL, uint8_t* scrR, const int32_t* d_l2r, const int32_t* d_r2l,
+                     const uint8_t* d_occ, int32_t* d_match, int32_t* d_nm, SbpJobs* JS, RigResolveDev* A) {
+    sbp_jobs_header(fe, M, JS);
+    for (int side = 0; side < 2; side++) {
+        SbpJobDev& J = JS->job[side];
+        J.mode = 1;
+        J.th = side == 0 ? th : 1.0f; /* fmatcher.cpp:425: the right radius is not multiplied by th */
+        J.nnratio = nnratio;
+        J.bnd = matcher_bounds(fe, img_w, img_h);
+        J.nLast = n_mp;
+        J.nLastPtr = n_mp_ptr;
+        J.nCur = side == 0 ? f.n_left : f.n_right;
+        J.mps = side == 0 ? recL : recR;
+        J.mpDesc = desc;
+        J.flags = flags;
+        J.curKps = side == 0 ? f.dev_kps_left : f.dev_kps_right;
+        J.curDesc = side == 0 ? f.dev_desc_left : f.dev_desc_right;
+        sbp_job_outputs(&J, side == 0 ? scrL : scrR, n_mp, nullptr, nullptr, nullptr);
+    }
+    A->nLeft = f.n_left;
+    A->nRight = f.n_right;
+    A->forceSeq = fe->tune.sbp_sequential == 1;
+    A->leftToRight = d_l2r;
+    A->rightToLeft = d_r2l;
+    A->occupied0 = d_occ;
+    A->matchCur = d_match;
+    A->nmatches = d_nm;
+    A->fallbacks = fe->d_init_fb;
+}
+
+extern "C" int vslam_search_by_projection_mappoints_rig(vslam_fe* fe, const vslam_mp_track* track_left_host,
+                                                        const vslam_mp_track* track_right_host, const uint8_t* mp_desc_host,
+                                                        int n_mp, const vslam_rig_frame* frame, int img_w, int img_h, float th,
+                                                        float nnratio, int32_t* match_cur, int* nmatches) {
+    if (!fe || n_mp < 0 || !nmatches || (n_mp && (!track_left_host || !track_right_host || !mp_desc_host)) || img_w < 1 ||
+        img_h < 1 || !std::isfinite(th)) {
+        g_err = "invalid arguments";
+        return VSLAM_ERR_INVALID;
+    }
+    if (int rc = rig_frame_check(frame)) return rc;
+    const vslam_rig_frame& f = *frame;
+    const int N = f.n_left + f.n_right;
+    if (N && !match_cur) {
+        g_err = "invalid arguments";
+        return VSLAM_ERR_INVALID;
+    }
+    *nmatches = 0;
+    for (int i = 0; i < N; i++) match_cur[i] = -1;
+    if (N == 0 || n_mp == 0) return VSLAM_OK;
+    if (n_mp > 4096) {
+        g_err = "SearchByProjection on the device supports at most 4096 MapPoints per call";
+        return VSLAM_ERR_UNSUPPORTED;
+    }
+    if (!(nnratio >= 0.4f)) { /* see vslam_search_by_projection_mappoints */
+        g_err = "SearchByProjection on the device needs nnratio >= 0.4";
+        return VSLAM_ERR_UNSUPPORTED;
+    }
+    HIPCHK(hipSetDevice(fe->p.device));
+    int M;
+    int rc = sbp_prepare(fe, &M);
+    if (rc) return rc;
+    const size_t nm = (size_t)n_mp, nl = (size_t)f.n_left, nr = (size_t)f.n_right;
+    /* inputs (one upload): left records | right records | descriptors | flags | L2R | R2L | occupied; then the scratch of both
+     * sides | match table | nmatches */
+    const auto [o_tl, o_tr, o_d, o_f, o_l, o_r, o_o, o_sl, o_sr, o_m, o_n, total] =
+        vslam::layout(16, {nm * sizeof(MpTrack), nm * sizeof(MpTrack), nm * 32, nm, nl * 4, nr * 4, nl + nr,
+                           vk_sbp_scratch_bytes(n_mp, M), vk_sbp_scratch_bytes(n_mp, M), (nl + nr) * 4, 16});
+    if ((rc = fe->proj.ensure(total))) return rc;
+    uint8_t *h = fe->proj.h, *d = fe->proj.d;
+    memcpy(h + o_tl, track_left_host, nm * sizeof(MpTrack));
+    memcpy(h + o_tr, track_right_host, nm * sizeof(MpTrack));
+    memcpy(h + o_d, mp_desc_host, nm * 32);
+    MpTrack* hr = (MpTrack*)(h + o_tr);
+    for (int i = 0; i < n_mp; i++) {
+        /* one MapPoint: Observations() > 0 of either record; a right record with level -1 takes no right branch (:424) */
+        h[o_f + i] = (uint8_t)((track_left_host[i].flags | track_right_host[i].flags) & 2u);
+        if (hr[i].level == -1) hr[i].flags &= ~1u;
+    }
+    rig_frame_stage(f, h, o_l, o_r, o_o);
+    hipStream_t st = fe->stream;
+    fe->proj.up(st, 0, o_sl);
+    SbpJobs JS;
+    RigResolveDev A;
+    rig_jobs(fe, M, f, img_w, img_h, th, nnratio, (const MpTrack*)(d + o_tl), (const MpTrack*)(d + o_tr), d + o_d, d + o_f, n_mp,
+             nullptr, d + o_sl, d + o_sr, (const int32_t*)(d + o_l), (const int32_t*)(d + o_r),
+             f.occupied_host ? d + o_o : nullptr, (int32_t*)(d + o_m), (int32_t*)(d + o_n), &JS, &A);
+    vk_search_rig(st, JS, A, n_mp);
+    HIPCHK(hipGetLastError());
+    fe->proj.down(st, o_m, total - o_m);
+    HIPCHK(hipGetLastError());
+    HIPCHK(vslam_stream_wait(st));
+    memcpy(match_cur, h + o_m, (size_t)N * 4);
+    *nmatches = *(const int32_t*)(h + o_n);
+    return VSLAM_OK;
+}
+
+extern "C" int vslam_search_local_points_rig_async(vslam_fe* fe, const vslam_frustum_params* p, const vslam_kb8_rig* rig,
+                                                   const vslam_map_point* points, const uint8_t* mp_desc, int n_mp,
+                                                   int points_where, const vslam_rig_frame* frame, float th, float nnratio) {
+    if (!fe || !rig || n_mp < 0 || (n_mp && (!points || !mp_desc)) ||
+        (points_where != VSLAM_IMGS_HOST && points_where != VSLAM_IMGS_DEVICE) || !frustum_params_ok(p) || !std::isfinite(th) ||
+        !vslam_kb8::camera_ok(&rig->cam2)) {
+        g_err = "invalid arguments";
+        return VSLAM_ERR_INVALID;
+    }
+    for (int i = 0; i < 12; i++)
+        if (!std::isfinite(rig->Tlr[i]) || !std::isfinite(rig->Trl[i])) {
+            g_err = "invalid arguments";
+            return VSLAM_ERR_INVALID;
+        }
+    if (int rc = rig_frame_check(frame)) return rc;
+    if (points_where == VSLAM_IMGS_DEVICE && n_mp && ((((uintptr_t)mp_desc) & 15) || (((uintptr_t)points) & 3))) {
+        g_err = "device MapPoint descriptors must be 16-byte aligned, device MapPoints 4-byte aligned";
+        return VSLAM_ERR_INVALID;
+    }
+    if (!fe->has_kb8) {
+        g_err = "no KB8 camera set (vslam_fe_set_kb8_camera)";
+        return VSLAM_ERR_INVALID;
+    }
+    if (int rc = frustum_camera_ok(fe, p)) return rc;
+    if (lp_in_flight(fe)) {
+        g_err = "a local-points search is already in flight (vslam_search_local_points_wait / _rig_wait)";
+        return VSLAM_ERR_INVALID;
+    }
+    if (n_mp > VSLAM_LOCAL_POINTS_MAX) {
+        g_err = "SearchLocalPoints on the device supports at most 65536 MapPoints per call";
+        return VSLAM_ERR_UNSUPPORTED;
+    }
+    if (!(nnratio >= 0.4f)) {
+        g_err = "SearchByProjection on the device needs nnratio >= 0.4";
+        return VSLAM_ERR_UNSUPPORTED;
+    }
+    const vslam_rig_frame& f = *frame;
+    const int N = f.n_left + f.n_right;
+    fe->lp_n_mp = n_mp;
+    fe->lp_n_cur = N;
+    if (n_mp == 0 || N == 0) {
+        fe->lp_state = 4;
+        return VSLAM_OK;
+    }
+    HIPCHK(hipSetDevice(fe->p.device));
+    int M;
+    int rc = sbp_prepare(fe, &M);
+    if (rc) return rc;
+    const bool from_host = points_where == VSLAM_IMGS_HOST;
+    const int cap = std::min(n_mp, VSLAM_FRUSTUM_MAX_KEPT);
+    const int nchunks = (n_mp + VSLAM_FRUSTUM_CHUNK - 1) / VSLAM_FRUSTUM_CHUNK;
+    /* uploaded inputs | records and depths of all points | chunk counts | compacted arrays | matcher scratch | results (one copy) */
+    const size_t nm = (size_t)n_mp, nl = (size_t)f.n_left, nr = (size_t)f.n_right, host_mp = from_host ? nm : 0;
+    const size_t rec = sizeof(vslam_mp_track);
+    const auto [o_l, o_r, o_o, o_pts, o_desc, o_tl, o_tr, o_dl, o_dr, o_cv, o_ck, o_tlc, o_trc, o_dc, o_fc, o_sl, o_sr, o_m, o_cnt,
+                o_idx, total] =
+        vslam::layout(256, {nl * 4, nr * 4, nl + nr, host_mp * sizeof(vslam_map_point), host_mp * 32, nm * rec, nm * rec, nm * 4,
+                            nm * 4, (size_t)nchunks * 4, (size_t)nchunks * 4, (size_t)cap * rec, (size_t)cap * rec,
+                            (size_t)cap * 32, (size_t)cap, vk_sbp_scratch_bytes(cap, M), vk_sbp_scratch_bytes(cap, M),
+                            (nl + nr) * 4, 256, (size_t)cap * 4});
+    if ((rc = fe->lp.ensure(total))) return rc;
+    uint8_t *h = fe->lp.h, *d = fe->lp.d;
+    rig_frame_stage(f, h, o_l, o_r, o_o);
+    if (from_host) {
+        memcpy(h + o_pts, points, nm * sizeof(vslam_map_point));
+        memcpy(h + o_desc, mp_desc, nm * 32);
+    }
+    hipStream_t st = fe->stream;
+    fe->lp.up(st, 0, o_tl);
+    const bool prof = fe->profiling;
+    for (int i = 0; i < 3 && prof; i++)
+        if (int rc = fe->ev_rig[i].ensure()) return rc;
+    FrustumRigDev R;
+    R.F = frustum_frame(fe, p);
+    R.cam1 = fe->kb8;
+    R.cam2 = rig->cam2;
+    R.right = vslam_kb8::rig_right(R.F, *rig);
+    R.n = n_mp;
+    R.pts = from_host ? (const vslam_map_point*)(d + o_pts) : points;
+    R.trackL = (vslam_mp_track*)(d + o_tl);
+    R.trackR = (vslam_mp_track*)(d + o_tr);
+    R.depthL = (float*)(d + o_dl);
+    R.depthR = (float*)(d + o_dr);
+    R.chunkInView = (int32_t*)(d + o_cv);
+    vk_frustum_rig(st, R);
+    int32_t* cnt = (int32_t*)(d + o_cnt); /* nmatches, - | kept, min(kept, cap), nToMatch */
+    FrustumRigCompactDev K;
+    K.n = n_mp;
+    K.nchunks = nchunks;
+    K.farPoints = p->far_points != 0;
+    K.cap = cap;
+    K.thFarPoints = p->th_far_points;
+    K.trackL = R.trackL;
+    K.trackR = R.trackR;
+    K.depthL = R.depthL;
+    K.desc = from_host ? d + o_desc : mp_desc;
+    K.chunkKeep = (int32_t*)(d + o_ck);
+    K.chunkInView = R.chunkInView;
+    K.trackLC = (vslam_mp_track*)(d + o_tlc);
+    K.trackRC = (vslam_mp_track*)(d + o_trc);
+    K.descC = d + o_dc;
+    K.flagsC = d + o_fc;
+    K.indexC = (int32_t*)(d + o_idx);
+    K.counts = cnt + 2;
+    vk_rig_compact(st, K);
+    HIPCHK(hipGetLastError());
+    SbpJobs JS;
+    RigResolveDev A;
+    rig_jobs(fe, M, f, p->img_w, p->img_h, th, nnratio, (const MpTrack*)(d + o_tlc), (const MpTrack*)(d + o_trc), d + o_dc,
+             d + o_fc, cap, cnt + 3, d + o_sl, d + o_sr, (const int32_t*)(d + o_l), (const int32_t*)(d + o_r),
+             f.occupied_host ? d + o_o : nullptr, (int32_t*)(d + o_m), cnt, &JS, &A);
+    if (prof) (void)hipEventRecord(fe->ev_rig[0], st);
+    vk_search_rig(st, JS, A, cap, prof ? (hipEvent_t)fe->ev_rig[1] : nullptr);
+    if (prof) (void)hipEventRecord(fe->ev_rig[2], st);
+    fe->rig_timed = prof;
+    HIPCHK(hipGetLastError());
+    fe->lp.down(st, o_m, total - o_m); /* match table | counts | original indices */
+    HIPCHK(hipGetLastError());
+    fe->lp_state = 3;
+    fe->lp_cap = cap;
+    fe->lp_o_track = o_tl;
+    fe->lp_o_track_r = o_tr;
+    fe->lp_o_res = o_m;
+    fe->lp_o_cnt = o_cnt;
+    fe->lp_o_idx = o_idx;
+    return VSLAM_OK;
+}
+
+extern "C" int vslam_search_local_points_rig_wait(vslam_fe* fe, int32_t* match_cur, int* nmatches, int* n_to_match,
+                                                  int* n_matched_against, vslam_mp_track* track_left,
+                                                  vslam_mp_track* track_right) {
+    if (!fe || fe->lp_state == 0) {
+        g_err = "nothing enqueued";
+        return VSLAM_ERR_INVALID;
+    }
+    if (fe->lp_state < 3) {
+        g_err = "the search enqueued is not a rig search (vslam_search_local_points_wait)";
+        return VSLAM_ERR_INVALID;
+    }
+    const int n_mp = fe->lp_n_mp, N = fe->lp_n_cur;
+    if (!nmatches || !n_to_match || !n_matched_against || (N && !match_cur)) {
+        g_err = "invalid arguments";
+        return VSLAM_ERR_INVALID;
+    }
+    *nmatches = *n_to_match = *n_matched_against = 0;
+    if (fe->lp_state == 4) { /* no MapPoints or no keypoints: nothing was launched */
+        fe->lp_state = 0;
+        for (int i = 0; i < N; i++) match_cur[i] = -1;
+        if ((track_left || track_right) && n_mp) {
+            g_err = "no records: a search without keypoints launches nothing; call vslam_frame_in_frustum_rig for the records";
+            return VSLAM_ERR_INVALID;
+        }
+        return VSLAM_OK;
+    }
+    HIPCHK(hipSetDevice(fe->p.device));
+    fe->lp_state = 0;
+    HIPCHK(vslam_stream_wait(fe->stream));
+    if (fe->rig_timed) {
+        float a = 0.0f, b = 0.0f;
+        fe->rig_timed = false;
+        HIPCHK(hipEventElapsedTime(&a, fe->ev_rig[0], fe->ev_rig[1]));
+        HIPCHK(hipEventElapsedTime(&b, fe->ev_rig[1], fe->ev_rig[2]));
+        fe->rig_ms[0] += a;
+        fe->rig_ms[1] += b;
+        fe->rig_passes++;
+    }
+    const uint8_t* h = fe->lp.h;
+    const int32_t* cnt = (const int32_t*)(h + fe->lp_o_cnt);
+    const int32_t* idx = (const int32_t*)(h + fe->lp_o_idx);
+    *n_matched_against = cnt[2];
+    *n_to_match = cnt[4];
+    const size_t bytes = (size_t)n_mp * sizeof(vslam_mp_track);
+    if (track_left) HIPCHK(hipMemcpy(track_left, fe->lp.d + fe->lp_o_track, bytes, hipMemcpyDeviceToHost));
+    if (track_right) HIPCHK(hipMemcpy(track_right, fe->lp.d + fe->lp_o_track_r, bytes, hipMemcpyDeviceToHost));
+    const int rc = vslamh_local_points_finish((const int32_t*)(h + fe->lp_o_res), N, idx, cnt[2], fe->lp_cap, match_cur);
+    if (rc == VSLAM_ERR_UNSUPPORTED)
+        g_err = "SearchLocalPoints: more than 4096 MapPoints in view; SearchByProjection on the device takes at most 4096";
+    else if (rc)
+        g_err = "invalid arguments";
+    else
+        *nmatches = cnt[0];
+    return rc;
+}
+
+extern "C" int vslam_search_local_points_rig(vslam_fe* fe, const vslam_frustum_params* p, const vslam_kb8_rig* rig,
+                                             const vslam_map_point* points, const uint8_t* mp_desc, int n_mp, int points_where,
+                                             const vslam_rig_frame* frame, float th, float nnratio, int32_t* match_cur,
+                                             int* nmatches, int* n_to_match, int* n_matched_against, vslam_mp_track* track_left,
+                                             vslam_mp_track* track_right) {
+    if (!nmatches || !n_to_match || !n_matched_against || (frame && frame->n_left + frame->n_right > 0 && !match_cur)) {
+        g_err = "invalid arguments";
+        return VSLAM_ERR_INVALID;
+    }
+    int rc = vslam_search_local_points_rig_async(fe, p, rig, points, mp_desc, n_mp, points_where, frame, th, nnratio);
+    if (rc) return rc;
+    return vslam_search_local_points_rig_wait(fe, match_cur, nmatches, n_to_match, n_matched_against, track_left, track_right);
+}
+
+/* with vslam_fe_set_profiling on: HIP-event time of the two-job k_sbp_rank launch and of k_rig_resolve alone, summed over the
+ * rig searches waited for since */
+extern "C" int vslam_fe_get_local_points_rig_profile(vslam_fe* fe, double* rank_ms, double* resolve_ms, long* passes) {
+    if (!fe) return VSLAM_ERR_INVALID;
+    if (rank_ms) *rank_ms = fe->rig_ms[0];
+    if (resolve_ms) *resolve_ms = fe->rig_ms[1];
+    if (passes) *passes = fe->rig_passes;
     return VSLAM_OK;
 }

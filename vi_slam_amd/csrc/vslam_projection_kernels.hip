@@ -684,6 +684,229 @@ void vk_search_by_projection(hipStream_t st, const SbpJobs& JS, int njobs, int m
 }
 
 /* ------------------------------------------------------------------------------------------------
+ * SearchByProjection(Frame& F, const vector<MapPoint*>&, th, ...) for a two-fisheye rig (fmatcher.cpp:321-491 with
+ * Nleft != -1).  All the Hamming work is k_sbp_rank mode 1, unedited, as two jobs of one launch: job 0 ranks the compacted
+ * MapPoints against the left keypoints with the caller's th, job 1 against the right keypoints with th = 1 (the bFactor line
+ * is missing at :425).  What is left is sequential and couples the two sides:
+ *   - a slot of F.mvpMapPoints (Nleft + Nright of them) is occupied iff its LAST writer has observations: a direct write
+ *     lands on a free slot only, but the cross-writes through mvLeftToRightMatch / mvRightToLeftMatch (:409-413, :476-480) land
+ *     anywhere, so a point without observations frees a slot again;
+ *   - the left ratio failure is a `continue` (:403-404): it skips the right branch of the same point;
+ *   - the right branch sees what the left branch of the same point has just written.
+ * k_rig_resolve is one wave that walks the points in order, as k_sbp_replay does: per point and side two ballots over the
+ * sorted prefix (valid, free) give best and second best; occupancy, keypoint octaves, both match maps and the slot owners of
+ * BOTH sides live in LDS.  When a block of 64 points is loaded, every prefix entry gathers its keypoint's octave and match-map
+ * entry beside its key, and the next point's entries are read while the current one is resolved, so that per point and side only
+ * the occupancy read and the write behind it wait for the point before.  A prefix that cannot decide -- it is full and holds fewer than two free entries, and neither
+ * "best is beyond TH_HIGH" nor "best passes the ratio test against the prefix's last entry, so against any second" settles
+ * it -- is re-scanned in full (rig_full_scan2, the loop body of the reference).  forceSeq (sbp_sequential = 1) re-scans every
+ * window and reads no prefix at all: the cross-check path.  Blocks of 64 points: the points without a candidate on either
+ * side cost one ballot per block.
+ * ---------------------------------------------------------------------------------------------- */
+struct RigTwo { /* the two smallest free keys of a window, ~0 = none */
+    uint32_t g1, g2;
+};
+__device__ RigTwo rig_full_scan2(const SbpProj& pr, const SbpJobDev& J, int nCur, const uint8_t* mpDescQ, const uint8_t* occ,
+                                 const SiBounds& bnd, const SiGridInv& inv, int lane) {
+    uint32_t k1 = 0xFFFFFFFFu, k2 = 0xFFFFFFFFu;
+    const SiWindow win = si_window_b(pr.u, pr.v, pr.radius, bnd, inv);
+    if (!win.empty) {
+        const uint4 da = ((const uint4*)mpDescQ)[0], db = ((const uint4*)mpDescQ)[1];
+        for (int c = lane; c < nCur; c += 64) {
+            const SbpCand cd = sbp_make_cand(J.curKps[c], -1.f, bnd, inv); /* no mvuRight gate in a rig (:370) */
+            if (cd.cell == 0xFFFF || occ[c] || !sbp_candidate_ok(cd, win, pr)) continue;
+            const uint4 ta = ((const uint4*)J.curDesc)[(size_t)c * 2], tb = ((const uint4*)J.curDesc)[(size_t)c * 2 + 1];
+            const uint32_t key = si_key(si_hamming(da, db, ta, tb), cd.cell, (uint32_t)c);
+            if (key < k1) { k2 = k1; k1 = key; }
+            else if (key < k2) k2 = key;
+        }
+    }
+    RigTwo r;
+    r.g1 = wave_min_u32(k1);
+    r.g2 = r.g1 == 0xFFFFFFFFu ? 0xFFFFFFFFu : wave_min_u32(k1 == r.g1 ? k2 : k1);
+    return r;
+}
+
+/* one side of one point: best = -1 nothing to assign (the reference falls through), -2 the ratio test failed (`continue`), else
+ * the keypoint to assign and cross = its entry of mvLeftToRightMatch / mvRightToLeftMatch; scanned = 1 if the window was
+ * re-scanned.  key, meta: this lane's entry of the point's sorted prefix (lanes >= M hold ~0) and, gathered when the block of
+ * points was loaded, that keypoint's octave | match-map entry << 8: best and second best then come out of two ballots and
+ * register reads, and the only LDS read that waits for the point before is the occupancy.  oct, cross: the same two tables
+ * in LDS, for a re-scanned window.  All results wave-uniform, and by value (vslam_matchdev.h). */
+struct RigPick {
+    int best, cross, scanned;
+};
+__device__ RigPick rig_side(uint32_t key, uint32_t meta, int M, int forceSeq, const SbpJobDev& J, int nCur, int q,
+                            const uint8_t* occ, const uint8_t* oct, const int16_t* cross, const SiBounds& bnd,
+                            const SiGridInv& inv, int lane) {
+    if (!forceSeq) {
+        const bool valid = key != 0xFFFFFFFFu;
+        const bool fr = valid && !occ[si_key_index(key)];
+        const unsigned long long mv = __ballot(valid), mf = __ballot(fr);
+        if (mv == 0) return RigPick{-1, -1, 0}; /* vIndices empty, or every candidate failed an order-free gate */
+        const bool full = __popcll(mv) >= M;
+        const int nfree = __popcll(mf);
+        bool decided = !full || nfree >= 2; /* a complete list: bestDist2 stays 256 and bestLevel2 -1 where it runs out */
+        uint32_t g1 = 0xFFFFFFFFu, m1 = 0;
+        if (mf) {
+            const int first = __builtin_amdgcn_readfirstlane(__ffsll((long long)mf) - 1);
+            g1 = (uint32_t)__builtin_amdgcn_readlane((int)key, first);
+            m1 = (uint32_t)__builtin_amdgcn_readlane((int)meta, first);
+        }
+        const uint32_t bd = si_key_dist(g1);
+        if (!decided && nfree == 1) {
+            /* beyond TH_HIGH nothing is assigned; or the best passes the ratio test against the prefix's last entry, and so
+             * against every possible second, whatever its level */
+            const uint32_t dlast = si_key_dist((uint32_t)__builtin_amdgcn_readlane((int)key, M - 1));
+            decided = bd > (uint32_t)SBP_TH_HIGH || (float)bd <= __fmul_rn(J.nnratio, (float)dlast);
+        }
+        if (decided) {
+            if (!mf || bd > (uint32_t)SBP_TH_HIGH) return RigPick{-1, -1, 0};
+            if (nfree >= 2) {
+                const unsigned long long mf2 = mf & (mf - 1ull);
+                const int second = __builtin_amdgcn_readfirstlane(__ffsll((long long)mf2) - 1);
+                const uint32_t g2 = (uint32_t)__builtin_amdgcn_readlane((int)key, second);
+                const uint32_t m2 = (uint32_t)__builtin_amdgcn_readlane((int)meta, second);
+                if ((m1 & 0xFFu) == (m2 & 0xFFu) && (float)bd > __fmul_rn(J.nnratio, (float)si_key_dist(g2)))
+                    return RigPick{-2, -1, 0};
+            }
+            return RigPick{(int)si_key_index(g1), (int)(int16_t)(m1 >> 8), 0};
+        }
+    }
+    const SbpProj pr = J.proj[q];
+    if (!pr.valid) return RigPick{-1, -1, 0};
+    const RigTwo t = rig_full_scan2(pr, J, nCur, J.mpDesc + (size_t)q * 32, occ, bnd, inv, lane);
+    if (t.g1 == 0xFFFFFFFFu) return RigPick{-1, -1, 1};
+    const int bd = (int)si_key_dist(t.g1), best = (int)si_key_index(t.g1);
+    if (bd > SBP_TH_HIGH) return RigPick{-1, -1, 1};
+    if (t.g2 != 0xFFFFFFFFu) {
+        const int sd = (int)si_key_dist(t.g2);
+        if (oct[best] == oct[si_key_index(t.g2)] && (float)bd > __fmul_rn(J.nnratio, (float)sd)) return RigPick{-2, -1, 1};
+    }
+    return RigPick{best, (int)cross[best], 1};
+}
+
+#define RIG_LDS_KEYS (2 * 64 * SI_MAX_M * 8)
+__global__ void __launch_bounds__(64)
+k_rig_resolve(SbpJobs JS, RigResolveDev A) {
+    extern __shared__ __align__(16) uint8_t sbsm[];
+    const SbpJobDev& JL = JS.job[0];
+    const SbpJobDev& JR = JS.job[1];
+    const int M = JS.M;
+    const int nL = A.nLeft, nR = A.nRight, N = nL + nR;
+    const int nMp = sbp_counts(JL).nLast;
+    uint2* kbufL = (uint2*)sbsm;                  /* 64 x M: (key, octave | match-map entry << 8) of a block's left prefixes */
+    uint2* kbufR = kbufL + 64 * SI_MAX_M;         /* 64 x M: the right ones */
+    int16_t* owner = (int16_t*)(sbsm + RIG_LDS_KEYS); /* N: last point written to the slot (compacted index < 4096), -1 */
+    int16_t* cross = owner + N;                   /* N: mvLeftToRightMatch | mvRightToLeftMatch */
+    uint8_t* occ = (uint8_t*)(cross + N);         /* N: the slot holds a MapPoint with Observations() > 0 */
+    uint8_t* oct = occ + N;                       /* N: keypoint octaves */
+    const int lane = threadIdx.x;
+    const SiBounds bnd = JL.bnd;
+    const SiGridInv inv = si_grid_inv(bnd);
+    for (int c = lane; c < N; c += 64) {
+        owner[c] = -1;
+        cross[c] = (int16_t)(c < nL ? A.leftToRight[c] : A.rightToLeft[c - nL]);
+        occ[c] = (A.occupied0 && A.occupied0[c]) ? 1 : 0;
+        oct[c] = (uint8_t)(c < nL ? JL.curKps[c].octave : JR.curKps[c - nL].octave);
+    }
+    __syncthreads();
+    const uint2 none = make_uint2(0xFFFFFFFFu, 0u);
+    int nm = 0, nfb = 0;
+    for (int qb = 0; qb < nMp; qb += 64) {
+        const int nq = min(64, nMp - qb);
+        __syncthreads();
+        if (!A.forceSeq)
+            for (int i = lane; i < nq * M; i += 64) {
+                const uint32_t kl = JL.topm[(size_t)qb * M + i], kr = JR.topm[(size_t)qb * M + i];
+                const int il = (int)si_key_index(kl), ir = nL + (int)si_key_index(kr);
+                kbufL[i] = kl == 0xFFFFFFFFu ? none : make_uint2(kl, oct[il] | ((uint32_t)(uint16_t)cross[il] << 8));
+                kbufR[i] = kr == 0xFFFFFFFFu ? none : make_uint2(kr, oct[ir] | ((uint32_t)(uint16_t)cross[ir] << 8));
+            }
+        const uint32_t myflags = lane < nq ? JL.flags[qb + lane] : 0u; /* lane t holds point qb + t's flags */
+        __syncthreads();
+        bool anyL, anyR;
+        if (A.forceSeq) {
+            anyL = lane < nq && JL.proj[qb + lane].valid;
+            anyR = lane < nq && JR.proj[qb + lane].valid;
+        } else {
+            anyL = lane < nq && kbufL[lane * M].x != 0xFFFFFFFFu;
+            anyR = lane < nq && kbufR[lane * M].x != 0xFFFFFFFFu;
+        }
+        const unsigned long long mL = __ballot(anyL), mR = __ballot(anyR);
+        unsigned long long todo = mL | mR;
+        /* the next point's prefixes are read while the current one is resolved: they do not depend on it */
+        uint2 nxL = none, nxR = none;
+        if (todo && !A.forceSeq && lane < M) {
+            const int t0 = __ffsll((long long)todo) - 1;
+            nxL = kbufL[t0 * M + lane];
+            nxR = kbufR[t0 * M + lane];
+        }
+        while (todo) {
+            const int tq = __builtin_amdgcn_readfirstlane(__ffsll((long long)todo) - 1);
+            todo &= todo - 1ull;
+            const uint2 eL = nxL, eR = nxR;
+            if (todo && !A.forceSeq && lane < M) {
+                const int t1 = __ffsll((long long)todo) - 1;
+                nxL = kbufL[t1 * M + lane];
+                nxR = kbufR[t1 * M + lane];
+            }
+            const int q = qb + tq;
+            const uint8_t blk = (__builtin_amdgcn_readlane((int)myflags, tq) & 2) ? 1 : 0;
+            if ((mL >> tq) & 1ull) { /* the left branch, fmatcher.cpp:339-420 */
+                const RigPick pk = rig_side(eL.x, eL.y, M, A.forceSeq, JL, nL, q, occ, oct, cross, bnd, inv, lane);
+                nfb += pk.scanned;
+                if (pk.best == -2) continue; /* :403-404 skips the right branch as well */
+                if (pk.best >= 0) {
+                    if (lane == 0) {
+                        owner[pk.best] = (int16_t)q;
+                        occ[pk.best] = blk;
+                        if (pk.cross != -1) { /* :409-413: the slot is not looked at */
+                            owner[nL + pk.cross] = (int16_t)q;
+                            occ[nL + pk.cross] = blk;
+                        }
+                    }
+                    nm += pk.cross != -1 ? 2 : 1;
+                    __syncthreads();
+                }
+            }
+            if ((mR >> tq) & 1ull) { /* the right branch, :422-488 */
+                const RigPick pk = rig_side(eR.x, eR.y, M, A.forceSeq, JR, nR, q, occ + nL, oct + nL, cross + nL, bnd, inv, lane);
+                nfb += pk.scanned;
+                if (pk.best >= 0) {
+                    if (lane == 0) {
+                        if (pk.cross != -1) { /* :476-480 */
+                            owner[pk.cross] = (int16_t)q;
+                            occ[pk.cross] = blk;
+                        }
+                        owner[nL + pk.best] = (int16_t)q;
+                        occ[nL + pk.best] = blk;
+                    }
+                    nm += pk.cross != -1 ? 2 : 1;
+                    __syncthreads();
+                }
+            }
+        }
+    }
+    __syncthreads();
+    for (int c = lane; c < N; c += 64) A.matchCur[c] = owner[c];
+    if (lane == 0) {
+        A.nmatches[0] = nm;
+        if (A.fallbacks && nfb) atomicAdd(A.fallbacks, nfb);
+    }
+}
+
+size_t vk_rig_resolve_lds(int nSlots) { return (size_t)RIG_LDS_KEYS + (size_t)nSlots * 6; }
+
+void vk_search_rig(hipStream_t st, const SbpJobs& JS, const RigResolveDev& A, int maxMp, hipEvent_t between) {
+    if (maxMp <= 0) return;
+    hipLaunchKernelGGL(k_sbp_rank, dim3((maxMp + SBP_QPB - 1) / SBP_QPB, 2), dim3(256),
+                       vk_sbp_rank_lds(max(A.nLeft, A.nRight)), st, JS);
+    if (between) (void)hipEventRecord(between, st);
+    hipLaunchKernelGGL(k_rig_resolve, dim3(1), dim3(64), vk_rig_resolve_lds(A.nLeft + A.nRight), st, JS, A);
+}
+
+/* ------------------------------------------------------------------------------------------------
  * Frame::UnprojectStereo (frame.cpp:1023-1037) for every left keypoint of up to VSLAM_MAX_SBP_JOBS stereo
  * pairs: z = mvDepth[i] > 0  ->  x3Dc = ((u-cx)*z*invfx, (v-cy)*z*invfy, z), x3Dw = mRwc*x3Dc + mOw (one
  * cv::gemm, sbp_transform).  These are the points UpdateLastFrame turns into (temporal) MapPoints for
@@ -851,6 +1074,8 @@ int vk_sbp_set_max_lds(size_t bytes) {
     rc = (int)hipFuncSetAttribute((const void*)k_sbp_rank, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (rc) return rc;
     rc = (int)hipFuncSetAttribute((const void*)k_fuse_rank, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (rc) return rc;
+    rc = (int)hipFuncSetAttribute((const void*)k_rig_resolve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (rc) return rc;
     return (int)hipFuncSetAttribute((const void*)k_sbp_replay, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
