@@ -748,9 +748,9 @@ int vslam_fe_get_local_points_profile(vslam_fe* fe, double* frustum_ms, double* 
  * A KB8 camera and a distorted pinhole camera (vslam_fe_set_camera with k1 != 0) exclude each other: the reference's fisheye
  * frames have zero mDistCoef.  Setting one while the other is set is VSLAM_ERR_INVALID.
  * The rig form of SearchByProjection(F, vpMapPoints), right-camera branch included (fmatcher.cpp:321-491), is
- * vslam_search_by_projection_mappoints_rig / vslam_search_local_points_rig below.
- * Not covered: every other matcher's fisheye or right-camera branch (SearchByProjection(CurrentFrame, LastFrame) :2593-2659,
- * Fuse(.., bRight), SearchByBoW, SearchForTriangulation), TriangulateMatches / epipolarConstrain / matchAndtriangulate (cv::SVD), ReconstructWithTwoViews
+ * vslam_search_by_projection_mappoints_rig / vslam_search_local_points_rig below; the rig form of
+ * SearchByProjection(CurrentFrame, LastFrame), right-camera branch :2593-2659 included, is vslam_search_by_projection_frame_rig.
+ * Not covered: every other matcher's fisheye or right-camera branch (Fuse(.., bRight), SearchByBoW, SearchForTriangulation), TriangulateMatches / epipolarConstrain / matchAndtriangulate (cv::SVD), ReconstructWithTwoViews
  * (cv::fisheye::undistortPoints), projectJac, tanf beyond 3*pi/4. */
 typedef struct vslam_kb8_camera {
     float fx, fy, cx, cy; /* mvParameters[0..3] */
@@ -837,6 +837,43 @@ int vslam_search_local_points_rig(vslam_fe* fe, const vslam_frustum_params* p, c
 /* With vslam_fe_set_profiling on: HIP-event time of the two-job k_sbp_rank launch and of k_rig_resolve alone, summed over the
  * rig searches waited for since profiling was switched on.  Any pointer may be NULL. */
 int vslam_fe_get_local_points_rig_profile(vslam_fe* fe, double* rank_ms, double* resolve_ms, long* passes);
+
+/* FMatcher::SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, th, bMono) for a two-fisheye rig
+ * (fmatcher.cpp:2494-2684 with CurrentFrame.Nleft != -1; TrackWithMotionModel, tracking.cpp:2728 / :2736).  Restated as written:
+ *   - queries are the n_last = Nleft + Nright entries of the last frame: last_kps_host is ONE array, keypoints_ followed by
+ *     keypointsRight_ (octave and angle are read); a MapPoint in a left and a right slot is two independent queries
+ *   - the left branch: Rcw * x3Dw + tcw as one gemm, invzc < 0 and uv outside the closed grid bounds are `continue`s,
+ *     KannalaBrandt8::project, radius th * scale[octave], the forward / backward / +-1 level rule, an EMPTY WINDOW IS A `continue`
+ *     (:2534-2535), no mvuRight gate, best distance <= TH_HIGH writes slot bestIdx2
+ *   - the three left `continue`s skip the right branch of the query; a left window whose candidates are all occupied does not
+ *   - the right branch (:2593-2658): x3Dr = Rrl * x3Dc + trl as one gemm (gemm_float as for Tcw), projected through the LEFT
+ *     camera's model (mpCamera, not mpCamera2), with no depth test, no in-frame test and no empty-window `continue`; window over
+ *     the right keypoints, same radius and level rule; reads and writes slot i2 + n_left
+ *   - a slot is occupied iff it holds a MapPoint with Observations() > 0: a match by a point without observations leaves the
+ *     slot free, a later query may overwrite it (the last writer stays, both are counted and both enter the histogram)
+ *   - ONE rotation histogram over left and right entries; every entry of a rejected bin clears its slot and decrements nmatches
+ *   - mvLeftToRightMatch / mvRightToLeftMatch are not read: there are no cross-writes.
+ * p: as for vslam_search_by_projection_frame; a KB8 camera must be set and p->fx, fy, cx, cy equal it bit for bit
+ * (VSLAM_ERR_INVALID otherwise); p->mbf is not read.  rig: only Trl is read.  cur: the keypoints, descriptors, counts and
+ * occupied_host (n_left + n_right, may be NULL) are read, the match maps may be NULL.  last_flags, last_x3dw, mp_desc_host: as for
+ * the pinhole form.  match_cur[slot] (n_left + n_right entries) = the index i of the last-frame entry that ends in the slot, or
+ * -1; *nmatches as the reference counts it.  n_last <= 4096 (both cameras together), n_left, n_right <= 4096 each:
+ * VSLAM_ERR_UNSUPPORTED beyond, nothing enqueued.  n_last == 0 or n_left + n_right == 0: an empty result, nothing is launched.
+ * _async: upload -> k_sbp_rank_rig (two jobs) -> k_sbp_rig_resolve -> k_sbp_rig_replay -> one result copy on the context's
+ * stream, no host wait in between; one such search per context may be in flight (a second _async is VSLAM_ERR_INVALID).
+ * vslam_search_by_projection_frame keeps refusing while a KB8 camera is set. */
+int vslam_search_by_projection_frame_rig_async(vslam_fe* fe, const vslam_proj_params* p, const vslam_kb8_rig* rig,
+                                               const vslam_kp* last_kps_host, int n_last, const uint8_t* last_flags,
+                                               const float* last_x3dw, const uint8_t* mp_desc_host, const vslam_rig_frame* cur);
+int vslam_search_by_projection_frame_rig_wait(vslam_fe* fe, int32_t* match_cur, int* nmatches);
+/* _async + _wait */
+int vslam_search_by_projection_frame_rig(vslam_fe* fe, const vslam_proj_params* p, const vslam_kb8_rig* rig,
+                                         const vslam_kp* last_kps_host, int n_last, const uint8_t* last_flags,
+                                         const float* last_x3dw, const uint8_t* mp_desc_host, const vslam_rig_frame* cur,
+                                         int32_t* match_cur, int* nmatches);
+/* With vslam_fe_set_profiling on: HIP-event time of the two-job k_sbp_rank_rig launch and of the resolution behind it
+ * (k_sbp_rig_resolve + k_sbp_rig_replay), summed over the rig frame searches waited for since.  Any pointer may be NULL. */
+int vslam_fe_get_frame_rig_profile(vslam_fe* fe, double* rank_ms, double* resolve_ms, long* passes);
 
 /* Device-resident, batched form of the same matcher: every pointer of a job is a DEVICE pointer; counts are
  * int32 in HBM (vslam_fe_slot_count_ptr); keypoint arrays hold up to the context's capacity (<= 4096).  Up to 16

@@ -65,6 +65,8 @@ ABI_SYMBOLS = [
     "vslam_frame_in_frustum_rig",
     "vslam_search_by_projection_mappoints_rig", "vslam_search_local_points_rig_async", "vslam_search_local_points_rig_wait",
     "vslam_search_local_points_rig", "vslam_fe_get_local_points_rig_profile",
+    "vslam_search_by_projection_frame_rig_async", "vslam_search_by_projection_frame_rig_wait",
+    "vslam_search_by_projection_frame_rig", "vslam_fe_get_frame_rig_profile",
     "vslam_two_view_score_async", "vslam_two_view_score_wait", "vslam_two_view_score", "vslam_fe_get_two_view_profile",
     "vslam_kfdb_create", "vslam_kfdb_create_ex", "vslam_kfdb_destroy", "vslam_kfdb_add", "vslam_kfdb_erase",
     "vslam_kfdb_clear", "vslam_kfdb_clear_map", "vslam_kfdb_size", "vslam_kfdb_stats", "vslam_kfdb_query_async",
@@ -109,6 +111,20 @@ class _ProjParams(C.Structure):  # vslam_proj_params
                 ("mbf", C.c_float), ("th", C.c_float), ("forward", C.c_int32), ("backward", C.c_int32),
                 ("check_orientation", C.c_int32), ("img_w", C.c_int32), ("img_h", C.c_int32),
                 ("gemm_float", C.c_int32)]
+
+
+def proj_params(Tcw, cam, th, img_size, forward=False, backward=False, check_orientation=True, gemm_float=False):
+    """vslam_proj_params: Tcw = rows [Rcw | tcw] (3 x 4), cam = (fx, fy, cx, cy[, mbf])"""
+    P = _ProjParams()
+    T = np.asarray(Tcw, np.float32).reshape(-1)
+    for k in range(12):
+        P.Tcw[k] = float(T[k])
+    P.fx, P.fy, P.cx, P.cy = [float(np.float32(v)) for v in cam[:4]]
+    P.mbf = float(np.float32(cam[4])) if len(cam) > 4 else 0.0
+    P.th = float(np.float32(th))
+    P.forward, P.backward, P.check_orientation = int(bool(forward)), int(bool(backward)), int(bool(check_orientation))
+    P.img_w, P.img_h, P.gemm_float = int(img_size[0]), int(img_size[1]), int(bool(gemm_float))
+    return P
 
 
 class _FrustumParams(C.Structure):  # vslam_frustum_params
@@ -312,8 +328,11 @@ def rig_frame(dev_kps_left, dev_desc_left, n_left, dev_kps_right, dev_desc_right
     f = _RigFrame()
     f.dev_kps_left, f.dev_desc_left, f.n_left = dev_kps_left or None, dev_desc_left or None, int(n_left)
     f.dev_kps_right, f.dev_desc_right, f.n_right = dev_kps_right or None, dev_desc_right or None, int(n_right)
-    l2r, r2l = np.ascontiguousarray(left_to_right, np.int32), np.ascontiguousarray(right_to_left, np.int32)
-    if len(l2r) != f.n_left or len(r2l) != f.n_right:
+    if left_to_right is None and right_to_left is None:  # search_by_projection_frame_rig reads neither map
+        l2r, r2l = np.zeros(0, np.int32), np.zeros(0, np.int32)
+    else:
+        l2r, r2l = np.ascontiguousarray(left_to_right, np.int32), np.ascontiguousarray(right_to_left, np.int32)
+    if (left_to_right is not None or right_to_left is not None) and (len(l2r) != f.n_left or len(r2l) != f.n_right):
         raise ValueError("left_to_right / right_to_left must have n_left / n_right entries")
     oc = None if occupied is None else np.ascontiguousarray(occupied, np.uint8)
     if oc is not None and len(oc) != f.n_left + f.n_right:
@@ -600,6 +619,11 @@ def lib():
                                                     C.POINTER(i), C.POINTER(i), vp, vp]
         L.vslam_fe_get_local_points_rig_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                                             C.POINTER(C.c_long)]
+        pp = C.POINTER(_ProjParams)
+        L.vslam_search_by_projection_frame_rig_async.argtypes = [vp, pp, C.POINTER(_Kb8Rig), vp, i, vp, vp, vp, rf]
+        L.vslam_search_by_projection_frame_rig_wait.argtypes = [vp, vp, C.POINTER(i)]
+        L.vslam_search_by_projection_frame_rig.argtypes = [vp, pp, C.POINTER(_Kb8Rig), vp, i, vp, vp, vp, rf, vp, C.POINTER(i)]
+        L.vslam_fe_get_frame_rig_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_long)]
         L.vslam_two_view_score_async.argtypes = [vp, i, C.POINTER(_TwoViewJob)]
         L.vslam_two_view_score_wait.argtypes = [vp, C.POINTER(_TwoViewResult)]
         L.vslam_two_view_score.argtypes = [vp, C.POINTER(_TwoViewJob), C.POINTER(_TwoViewResult)]
@@ -1197,6 +1221,55 @@ class FExtractor:
         """-> (ms in the two-job k_sbp_rank launch, ms in k_rig_resolve, rig searches) since set_profiling(True)"""
         a, b, n = C.c_double(0), C.c_double(0), C.c_long(0)
         _check(lib().vslam_fe_get_local_points_rig_profile(self._h, C.byref(a), C.byref(b), C.byref(n)))
+        return a.value, b.value, n.value
+
+    def search_by_projection_frame_rig_async(self, params, rig, last_kps, last_flags, last_x3dw, mp_desc, frame):
+        """Enqueue FMatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) for a two-fisheye rig
+        (fmatcher.cpp:2494-2684, Nleft != -1) and return.  params from proj_params() (fx, fy, cx, cy = the KB8 camera's);
+        rig from kb8_rig() (Trl is read); last_kps: ONE KP_DTYPE array, the last frame's keypoints_ then keypointsRight_;
+        last_flags bit 0 = has a non-outlier MapPoint, bit 1 = that MapPoint has observations; frame from rig_frame() (the
+        maps may be None)."""
+        kp = np.ascontiguousarray(last_kps, KP_DTYPE)
+        fl = np.ascontiguousarray(last_flags, np.uint8)
+        xw = np.ascontiguousarray(last_x3dw, np.float32).reshape(-1)
+        md = np.ascontiguousarray(mp_desc, np.uint8)
+        if not (len(kp) == len(fl) == len(md) and len(xw) == 3 * len(kp)):
+            raise ValueError("one keypoint, one flag byte, one position and one descriptor per last-frame entry")
+        self._fr_keep = (kp, fl, xw, md, frame)
+        _check(lib().vslam_search_by_projection_frame_rig_async(self._h, C.byref(params), C.byref(rig), _p(kp), len(kp), _p(fl),
+                                                                _p(xw), _p(md), C.byref(frame)))
+        self._fr_n = frame.n_left + frame.n_right
+
+    def search_by_projection_frame_rig_wait(self):
+        """-> (nmatches, match_cur[n_left + n_right] = index of the last-frame entry that ends in the slot, or -1)"""
+        n = getattr(self, "_fr_n", 0)
+        m = np.full(max(n, 1), -1, np.int32)
+        nm = C.c_int(0)
+        rc = lib().vslam_search_by_projection_frame_rig_wait(self._h, _p(m), C.byref(nm))
+        self._fr_keep = None
+        _check(rc)
+        return nm.value, m[:n]
+
+    def search_by_projection_frame_rig(self, params, rig, last_kps, last_flags, last_x3dw, mp_desc, frame):
+        """search_by_projection_frame_rig_async + search_by_projection_frame_rig_wait, through the blocking entry point"""
+        kp = np.ascontiguousarray(last_kps, KP_DTYPE)
+        fl = np.ascontiguousarray(last_flags, np.uint8)
+        xw = np.ascontiguousarray(last_x3dw, np.float32).reshape(-1)
+        md = np.ascontiguousarray(mp_desc, np.uint8)
+        if not (len(kp) == len(fl) == len(md) and len(xw) == 3 * len(kp)):
+            raise ValueError("one keypoint, one flag byte, one position and one descriptor per last-frame entry")
+        n = frame.n_left + frame.n_right
+        m = np.full(max(n, 1), -1, np.int32)
+        nm = C.c_int(0)
+        _check(lib().vslam_search_by_projection_frame_rig(self._h, C.byref(params), C.byref(rig), _p(kp), len(kp), _p(fl), _p(xw),
+                                                          _p(md), C.byref(frame), _p(m), C.byref(nm)))
+        return nm.value, m[:n]
+
+    def get_frame_rig_profile(self):
+        """-> (ms in the two-job k_sbp_rank_rig launch, ms in k_sbp_rig_resolve + k_sbp_rig_replay, searches) since
+        set_profiling(True)"""
+        a, b, n = C.c_double(0), C.c_double(0), C.c_long(0)
+        _check(lib().vslam_fe_get_frame_rig_profile(self._h, C.byref(a), C.byref(b), C.byref(n)))
         return a.value, b.value, n.value
 
     def two_view_score_async(self, jobs):

@@ -536,6 +536,8 @@ extern "C" int vslam_fe_set_profiling(vslam_fe* fe, int on) {
     fe->lp_passes = 0;
     fe->rig_ms[0] = fe->rig_ms[1] = 0;
     fe->rig_passes = 0;
+    fe->fr_ms[0] = fe->fr_ms[1] = 0;
+    fe->fr_passes = 0;
     return VSLAM_OK;
 }
 

@@ -204,6 +204,16 @@ struct vslam_fe {
     bool rig_timed = false;
     double rig_ms[2] = {0, 0};
     long rig_passes = 0;
+    /* SearchByProjection(CurrentFrame, LastFrame) of a rig (vslam_search_by_projection_frame_rig_async): a block of its own, so
+     * that the blocking matchers, which fill `proj` on the host at once, can run while a search is in flight */
+    vslam_staging fr;           /* inputs | scratch of both sides | match table | nmatches, needSeq */
+    int fr_state = 0;           /* 0: nothing enqueued, 1: a search is in flight, 2: an empty search (nothing launched) */
+    int fr_n_cur = 0;           /* n_left + n_right */
+    size_t fr_o_m = 0, fr_o_n = 0;
+    vslam_event ev_fr[3];       /* profiling: before k_sbp_rank_rig | between | behind k_sbp_rig_replay */
+    bool fr_timed = false;
+    double fr_ms[2] = {0, 0};
+    long fr_passes = 0;
 
     /* GPU quadtree distribution */
     bool dev_octree = false;

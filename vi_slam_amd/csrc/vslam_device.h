@@ -255,6 +255,21 @@ struct RigResolveDev {
     int32_t* fallbacks;         /* diagnostics: full re-scans, may be null */
 };
 
+/* SearchByProjection(CurrentFrame, LastFrame) of a two-fisheye rig (k_sbp_rank_rig, k_sbp_rig_resolve, k_sbp_rig_replay): what
+ * the two jobs of the SbpJobs beside it -- job 0 the left keypoints, job 1 the right ones, both over the same last-frame
+ * arrays -- do not hold; every pointer a DEVICE pointer */
+struct RigFrameDev {
+    vslam_kb8_camera cam;     /* CurrentFrame.mpCamera: BOTH branches project through it (fmatcher.cpp:2512, :2596) */
+    float Trl[12];            /* rows [Rrl | trl] of CurrentFrame.mTrl */
+    int32_t nLeft, nRight;    /* keypoints per side, <= 4096 each; slots [0, nLeft) left, [nLeft, nLeft + nRight) right */
+    int32_t forceSeq;         /* 1: the sequential wave, every window re-scanned in full */
+    const uint8_t* occupied0; /* nLeft + nRight, may be null */
+    int32_t* matchCur;        /* out: nLeft + nRight */
+    int32_t* nmatches;        /* out: 1 */
+    int32_t* needSeq;         /* k_sbp_rig_resolve -> k_sbp_rig_replay hand-over flag */
+    int32_t* fallbacks;       /* diagnostics: full re-scans, may be null */
+};
+
 /* k_unproject_stereo: one stereo pair's left keypoints -> world points (Frame::UnprojectStereo) */
 struct UnprojJob {
     float Twc[12]; /* rows [mRwc | mOw] */

@@ -1382,6 +1382,133 @@ int vslamh_kb8_frustum_check(const vslam_frustum_params* p, const vslam_kb8_came
     return vslam_kb8::intrinsics_match(*p, *cam) ? VSLAM_OK : VSLAM_ERR_INVALID;
 }
 int vslamh_kb8_projecting_entry(int has_kb8) { return has_kb8 ? VSLAM_ERR_UNSUPPORTED : VSLAM_OK; }
+/* vslam_search_by_projection_frame_rig: fx, fy, cx, cy of the projection parameters equal the KB8 camera's bit for bit */
+int vslamh_frame_rig_camera_check(const vslam_proj_params* p, const vslam_kb8_camera* cam) {
+    if (!p || !cam) return VSLAM_ERR_INVALID;
+    return (vslam_kb8::same_bits(p->fx, cam->fx) && vslam_kb8::same_bits(p->fy, cam->fy) && vslam_kb8::same_bits(p->cx, cam->cx) &&
+            vslam_kb8::same_bits(p->cy, cam->cy))
+               ? VSLAM_OK
+               : VSLAM_ERR_INVALID;
+}
+
+namespace {
+/* one row of R * x + t as ONE cv::gemm (double accumulation, rounded once), or in float */
+float rig_gemm_row(const float* r, const float* x, float t, int flt) {
+    if (!flt) {
+        double s = (double)r[0] * (double)x[0];
+        s = s + (double)r[1] * (double)x[1];
+        s = s + (double)r[2] * (double)x[2];
+        return (float)(s + (double)t);
+    }
+    float s = r[0] * x[0];
+    s = s + r[1] * x[1];
+    s = s + r[2] * x[2];
+    return s + t;
+}
+void rig_transform(const float* T, const float* x, int flt, float* out) {
+    for (int r = 0; r < 3; r++) out[r] = rig_gemm_row(T + 4 * r, x, T[4 * r + 3], flt);
+}
+} // namespace
+
+/* FMatcher::SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, th, bMono) for a two-fisheye rig
+ * (fmatcher.cpp:2494-2684 with CurrentFrame.Nleft != -1) as it is written, sequential: the statement the device form
+ * (vslam_search_by_projection_frame_rig) is tested against, and the shim's fallback.  Same arguments with host keypoints;
+ * cam = CurrentFrame.mpCamera, through which BOTH branches project; Trl = rows [R | t] of mTrl; scale_factors: mvScaleFactors,
+ * nlevels entries; bounds: mnMinX, mnMaxX, mnMinY, mnMaxY; occupied (may be NULL): per slot of n_left + n_right. */
+int vslamh_search_by_projection_frame_rig(const vslam_proj_params* p, const vslam_kb8_camera* cam, const float* Trl,
+                                          const vslam_kp* last_kps, int n_last, const uint8_t* last_flags, const float* last_x3dw,
+                                          const uint8_t* mp_desc, const vslam_kp* kps_left, const uint8_t* desc_left, int n_left,
+                                          const vslam_kp* kps_right, const uint8_t* desc_right, int n_right,
+                                          const uint8_t* occupied, const float* scale_factors, int nlevels, const float* bounds,
+                                          int32_t* match_cur, int* nmatches) {
+    if (!p || !cam || !Trl || n_last < 0 || n_left < 0 || n_right < 0 || nlevels < 1 || !scale_factors || !bounds || !nmatches ||
+        (n_last && (!last_kps || !last_flags || !last_x3dw || !mp_desc)) || (n_left && (!kps_left || !desc_left)) ||
+        (n_right && (!kps_right || !desc_right)) || ((n_left + n_right) && !match_cur))
+        return VSLAM_ERR_INVALID;
+    if (vslamh_frame_rig_camera_check(p, cam)) return VSLAM_ERR_INVALID;
+    const int TH_HIGH = 100, L = VSLAM_HISTO_LENGTH;
+    const int N = n_left + n_right;
+    std::vector<uint8_t> occ((size_t)N, 0);
+    for (int i = 0; i < N; i++) {
+        match_cur[i] = -1;
+        if (occupied) occ[i] = occupied[i] != 0;
+    }
+    const RigGrid gl(kps_left, n_left, bounds), gr(kps_right, n_right, bounds);
+    std::vector<int> vIndices2;
+    std::vector<int> rotHist[VSLAM_HISTO_LENGTH];
+    int nm = 0;
+    for (int i = 0; i < n_last; i++) {
+        if (!(last_flags[i] & 1)) continue; /* pMP && !LastFrame.mvbOutlier[i] */
+        const uint8_t obs = (last_flags[i] & 2) ? 1 : 0;
+        float x3Dc[3];
+        rig_transform(p->Tcw, last_x3dw + 3 * i, p->gemm_float, x3Dc);
+        const float invzc = (float)(1.0 / (double)x3Dc[2]);
+        if (invzc < 0) continue;
+        const vslam_kb8::Uv uv = vslam_kb8::kb8_project(*cam, x3Dc[0], x3Dc[1], x3Dc[2]);
+        if (uv.u < bounds[0] || uv.u > bounds[1]) continue;
+        if (uv.v < bounds[2] || uv.v > bounds[3]) continue;
+        const int nLastOctave = last_kps[i].octave; /* keypoints_[i] | keypointsRight_[i - Nleft]: the caller's one array */
+        const float radius = p->th * scale_factors[std::min(std::max(nLastOctave, 0), nlevels - 1)];
+        const int minLevel = p->forward ? nLastOctave : p->backward ? 0 : nLastOctave - 1;
+        const int maxLevel = p->forward ? -1 : p->backward ? nLastOctave : nLastOctave + 1;
+        gl.query(uv.u, uv.v, radius, minLevel, maxLevel, vIndices2);
+        if (vIndices2.empty()) continue;
+        const uint8_t* dMP = mp_desc + (size_t)i * 32;
+        {
+            int bestDist = 256, bestIdx2 = -1;
+            for (int i2 : vIndices2) {
+                if (occ[i2]) continue;
+                const int dist = rig_hamming(dMP, desc_left + (size_t)i2 * 32);
+                if (dist < bestDist) {
+                    bestDist = dist;
+                    bestIdx2 = i2;
+                }
+            }
+            if (bestDist <= TH_HIGH) {
+                match_cur[bestIdx2] = i;
+                occ[bestIdx2] = obs;
+                nm++;
+                if (p->check_orientation)
+                    rotHist[vslam_md::rot_bin(last_kps[i].angle, kps_left[bestIdx2].angle, L)].push_back(bestIdx2);
+            }
+        }
+        { /* :2593-2658: no depth test, no in-frame test, no empty-window `continue`; the LEFT camera's model */
+            float x3Dr[3];
+            rig_transform(Trl, x3Dc, p->gemm_float, x3Dr);
+            const vslam_kb8::Uv uvr = vslam_kb8::kb8_project(*cam, x3Dr[0], x3Dr[1], x3Dr[2]);
+            gr.query(uvr.u, uvr.v, radius, minLevel, maxLevel, vIndices2);
+            int bestDist = 256, bestIdx2 = -1;
+            for (int i2 : vIndices2) {
+                if (occ[i2 + n_left]) continue;
+                const int dist = rig_hamming(dMP, desc_right + (size_t)i2 * 32);
+                if (dist < bestDist) {
+                    bestDist = dist;
+                    bestIdx2 = i2;
+                }
+            }
+            if (bestDist <= TH_HIGH) {
+                match_cur[bestIdx2 + n_left] = i;
+                occ[bestIdx2 + n_left] = obs;
+                nm++;
+                if (p->check_orientation)
+                    rotHist[vslam_md::rot_bin(last_kps[i].angle, kps_right[bestIdx2].angle, L)].push_back(bestIdx2 + n_left);
+            }
+        }
+    }
+    if (p->check_orientation) {
+        int histo[VSLAM_HISTO_LENGTH];
+        for (int b = 0; b < L; b++) histo[b] = (int)rotHist[b].size();
+        const vslam_md::ThreeMaxima mx = vslam_md::three_maxima(histo, L);
+        for (int b = 0; b < L; b++)
+            if (!vslam_md::keeps_bin(mx, b))
+                for (int s : rotHist[b]) {
+                    match_cur[s] = -1;
+                    nm--;
+                }
+    }
+    *nmatches = nm;
+    return VSLAM_OK;
+}
 
 /* vslam_two_view_score on the host, every pointer of the job a HOST pointer (the placement fields are not read): the pair
  * list, CheckHomography / CheckFundamental for every hypothesis by the shared vslam_two_view.h code, the selection.  Same

@@ -231,4 +231,14 @@ extern "C" int vslamh_two_view_score(const vslam_two_view_job* job, vslam_two_vi
 extern "C" int vslamh_kb8_exclusive(int other_set, float k1);
 extern "C" int vslamh_kb8_frustum_check(const vslam_frustum_params* p, const vslam_kb8_camera* cam);
 extern "C" int vslamh_kb8_projecting_entry(int has_kb8);
+/* vslam_host.cpp: vslam_search_by_projection_frame_rig's intrinsics test (p's fx, fy, cx, cy against the KB8 camera, bit for
+ * bit), and the function itself over host arrays, sequential as the reference writes it (CPU tests, the shim's fallback) */
+extern "C" int vslamh_frame_rig_camera_check(const vslam_proj_params* p, const vslam_kb8_camera* cam);
+extern "C" int vslamh_search_by_projection_frame_rig(const vslam_proj_params* p, const vslam_kb8_camera* cam, const float* Trl,
+                                                     const vslam_kp* last_kps, int n_last, const uint8_t* last_flags,
+                                                     const float* last_x3dw, const uint8_t* mp_desc, const vslam_kp* kps_left,
+                                                     const uint8_t* desc_left, int n_left, const vslam_kp* kps_right,
+                                                     const uint8_t* desc_right, int n_right, const uint8_t* occupied,
+                                                     const float* scale_factors, int nlevels, const float* bounds,
+                                                     int32_t* match_cur, int* nmatches);
 #endif

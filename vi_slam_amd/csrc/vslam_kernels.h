@@ -84,6 +84,12 @@ struct RigResolveDev;
  * k_rig_resolve; maxMp sizes the grid (capacity of the MapPoint list); `between` (may be null) is recorded between the two */
 size_t vk_rig_resolve_lds(int nSlots);
 void vk_search_rig(hipStream_t st, const SbpJobs& JS, const RigResolveDev& A, int maxMp, hipEvent_t between = nullptr);
+struct RigFrameDev;
+/* the rig form of SearchByProjection(CurrentFrame, LastFrame): k_sbp_rank_rig over JS.job[0] (left) and JS.job[1] (right) in one
+ * launch, then k_sbp_rig_resolve and k_sbp_rig_replay; nLast sizes the grid; `between` (may be null) is recorded behind the ranking */
+size_t vk_sbp_rig_resolve_lds(int nSlots);
+size_t vk_sbp_rig_replay_lds(int nSlots, int nLast);
+void vk_search_frame_rig(hipStream_t st, const SbpJobs& JS, const RigFrameDev& R, int nLast, hipEvent_t between = nullptr);
 void vk_search_by_projection(hipStream_t st, const SbpJobs& JS, int njobs, int maxLast, int maxCur, int* fallbacks,
                              int forceSeq);
 int vk_distinctive_set_max_lds(size_t bytes);

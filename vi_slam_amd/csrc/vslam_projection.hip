@@ -1210,3 +1210,164 @@ extern "C" int vslam_fe_get_local_points_rig_profile(vslam_fe* fe, double* rank_
     if (passes) *passes = fe->rig_passes;
     return VSLAM_OK;
 }
+
+/* ------------------------------------------------------------------ SearchByProjection(CurrentFrame, LastFrame): rig
+ * fmatcher.cpp:2494-2684 with CurrentFrame.Nleft != -1.  Ranking is k_sbp_rank_rig (query mode 4) as two jobs of one launch over
+ * the same last-frame arrays -- job 0 against the left keypoints, job 1 against the right ones --, resolution and the joint
+ * finish k_sbp_rig_resolve / k_sbp_rig_replay (vslam_projection_kernels.hip). */
+extern "C" int vslam_search_by_projection_frame_rig_async(vslam_fe* fe, const vslam_proj_params* p, const vslam_kb8_rig* rig,
+                                                          const vslam_kp* last_kps_host, int n_last, const uint8_t* last_flags,
+                                                          const float* last_x3dw, const uint8_t* mp_desc_host,
+                                                          const vslam_rig_frame* cur) {
+    if (!fe || !p || !rig || !cur || n_last < 0 || cur->n_left < 0 || cur->n_right < 0 ||
+        (cur->n_left && (!cur->dev_kps_left || !cur->dev_desc_left)) ||
+        (cur->n_right && (!cur->dev_kps_right || !cur->dev_desc_right)) ||
+        (n_last && (!last_kps_host || !last_flags || !last_x3dw || !mp_desc_host)) || p->img_w < 1 || p->img_h < 1 ||
+        !std::isfinite(p->th)) {
+        g_err = "invalid arguments";
+        return VSLAM_ERR_INVALID;
+    }
+    for (int i = 0; i < 12; i++)
+        if (!std::isfinite(rig->Trl[i]) || !std::isfinite(p->Tcw[i])) {
+            g_err = "invalid arguments";
+            return VSLAM_ERR_INVALID;
+        }
+    if (!fe->has_kb8) {
+        g_err = "no KB8 camera set (vslam_fe_set_kb8_camera)";
+        return VSLAM_ERR_INVALID;
+    }
+    if (vslamh_frame_rig_camera_check(p, &fe->kb8)) {
+        g_err = "fx, fy, cx, cy of the projection parameters differ from the KB8 camera's (vslam_fe_set_kb8_camera)";
+        return VSLAM_ERR_INVALID;
+    }
+    if (fe->fr_state == 1) {
+        g_err = "a rig frame search is already in flight (vslam_search_by_projection_frame_rig_wait)";
+        return VSLAM_ERR_INVALID;
+    }
+    if (n_last > 4096 || cur->n_left > 4096 || cur->n_right > 4096) { /* the 12-bit index of the ordering key */
+        g_err = "SearchByProjection on the device supports at most 4096 last-frame entries and 4096 keypoints per camera";
+        return VSLAM_ERR_UNSUPPORTED;
+    }
+    const int N = cur->n_left + cur->n_right;
+    fe->fr_n_cur = N;
+    if (n_last == 0 || N == 0) {
+        fe->fr_state = 2;
+        return VSLAM_OK;
+    }
+    HIPCHK(hipSetDevice(fe->p.device));
+    int M;
+    int rc = sbp_prepare(fe, &M);
+    if (rc) return rc;
+    /* inputs (one upload): kps | x3Dw | mpDesc | flags | occupied; then the scratch of both sides | match table | nmatches, needSeq */
+    const size_t nl = (size_t)n_last, nc = (size_t)N;
+    const auto [o_kps, o_x, o_d, o_f, o_o, o_sl, o_sr, o_m, o_n, total] =
+        vslam::layout(16, {nl * sizeof(vslam_kp), nl * 12, nl * 32, nl, nc, vk_sbp_scratch_bytes(n_last, M),
+                           vk_sbp_scratch_bytes(n_last, M), nc * 4, 16});
+    if ((rc = fe->fr.ensure(total))) return rc;
+    const bool prof = fe->profiling;
+    for (int i = 0; i < 3 && prof; i++)
+        if (int rc = fe->ev_fr[i].ensure()) return rc;
+    uint8_t *h = fe->fr.h, *d = fe->fr.d;
+    memcpy(h + o_kps, last_kps_host, nl * sizeof(vslam_kp));
+    memcpy(h + o_x, last_x3dw, nl * 12);
+    memcpy(h + o_d, mp_desc_host, nl * 32);
+    memcpy(h + o_f, last_flags, nl);
+    if (cur->occupied_host) memcpy(h + o_o, cur->occupied_host, nc);
+    hipStream_t st = fe->stream;
+    fe->fr.up(st, 0, o_sl);
+    SbpJobs JS;
+    sbp_jobs_header(fe, M, &JS);
+    for (int side = 0; side < 2; side++) {
+        SbpJobDev& J = JS.job[side];
+        sbp_job_camera(fe, *p, &J); /* fx .. cy and mbf travel but are not read: both sides project through R.cam */
+        J.mode = 4;
+        J.nLast = n_last;
+        J.nCur = side == 0 ? cur->n_left : cur->n_right;
+        J.lastKps = (const vslam_kp*)(d + o_kps);
+        J.flags = d + o_f;
+        J.x3Dw = (const float*)(d + o_x);
+        J.mpDesc = d + o_d;
+        J.curKps = side == 0 ? cur->dev_kps_left : cur->dev_kps_right;
+        J.curDesc = side == 0 ? cur->dev_desc_left : cur->dev_desc_right;
+        sbp_job_outputs(&J, d + (side == 0 ? o_sl : o_sr), n_last, nullptr, nullptr, nullptr);
+    }
+    RigFrameDev R;
+    memset(&R, 0, sizeof(R));
+    R.cam = fe->kb8;
+    memcpy(R.Trl, rig->Trl, sizeof(R.Trl));
+    R.nLeft = cur->n_left;
+    R.nRight = cur->n_right;
+    R.forceSeq = fe->tune.sbp_sequential == 1;
+    R.occupied0 = cur->occupied_host ? d + o_o : nullptr;
+    R.matchCur = (int32_t*)(d + o_m);
+    R.nmatches = (int32_t*)(d + o_n);
+    R.needSeq = (int32_t*)(d + o_n) + 1;
+    R.fallbacks = fe->d_init_fb;
+    if (prof) (void)hipEventRecord(fe->ev_fr[0], st);
+    vk_search_frame_rig(st, JS, R, n_last, prof ? (hipEvent_t)fe->ev_fr[1] : nullptr);
+    if (prof) (void)hipEventRecord(fe->ev_fr[2], st);
+    fe->fr_timed = prof;
+    HIPCHK(hipGetLastError());
+    fe->fr.down(st, o_m, total - o_m);
+    HIPCHK(hipGetLastError());
+    fe->fr_state = 1;
+    fe->fr_o_m = o_m;
+    fe->fr_o_n = o_n;
+    return VSLAM_OK;
+}
+
+extern "C" int vslam_search_by_projection_frame_rig_wait(vslam_fe* fe, int32_t* match_cur, int* nmatches) {
+    if (!fe || fe->fr_state == 0) {
+        g_err = "nothing enqueued";
+        return VSLAM_ERR_INVALID;
+    }
+    const int N = fe->fr_n_cur;
+    if (!nmatches || (N && !match_cur)) {
+        g_err = "invalid arguments";
+        return VSLAM_ERR_INVALID;
+    }
+    *nmatches = 0;
+    if (fe->fr_state == 2) { /* no last-frame entries or no keypoints: nothing was launched */
+        fe->fr_state = 0;
+        for (int i = 0; i < N; i++) match_cur[i] = -1;
+        return VSLAM_OK;
+    }
+    HIPCHK(hipSetDevice(fe->p.device));
+    fe->fr_state = 0;
+    HIPCHK(vslam_stream_wait(fe->stream));
+    if (fe->fr_timed) {
+        float a = 0.0f, b = 0.0f;
+        fe->fr_timed = false;
+        HIPCHK(hipEventElapsedTime(&a, fe->ev_fr[0], fe->ev_fr[1]));
+        HIPCHK(hipEventElapsedTime(&b, fe->ev_fr[1], fe->ev_fr[2]));
+        fe->fr_ms[0] += a;
+        fe->fr_ms[1] += b;
+        fe->fr_passes++;
+    }
+    memcpy(match_cur, fe->fr.h + fe->fr_o_m, (size_t)N * 4);
+    *nmatches = *(const int32_t*)(fe->fr.h + fe->fr_o_n);
+    return VSLAM_OK;
+}
+
+extern "C" int vslam_search_by_projection_frame_rig(vslam_fe* fe, const vslam_proj_params* p, const vslam_kb8_rig* rig,
+                                                    const vslam_kp* last_kps_host, int n_last, const uint8_t* last_flags,
+                                                    const float* last_x3dw, const uint8_t* mp_desc_host,
+                                                    const vslam_rig_frame* cur, int32_t* match_cur, int* nmatches) {
+    if (!nmatches || (cur && cur->n_left + cur->n_right > 0 && !match_cur)) {
+        g_err = "invalid arguments";
+        return VSLAM_ERR_INVALID;
+    }
+    int rc = vslam_search_by_projection_frame_rig_async(fe, p, rig, last_kps_host, n_last, last_flags, last_x3dw, mp_desc_host, cur);
+    if (rc) return rc;
+    return vslam_search_by_projection_frame_rig_wait(fe, match_cur, nmatches);
+}
+
+/* with vslam_fe_set_profiling on: HIP-event time of the two-job k_sbp_rank_rig launch and of k_sbp_rig_resolve + k_sbp_rig_replay,
+ * summed over the rig frame searches waited for since */
+extern "C" int vslam_fe_get_frame_rig_profile(vslam_fe* fe, double* rank_ms, double* resolve_ms, long* passes) {
+    if (!fe) return VSLAM_ERR_INVALID;
+    if (rank_ms) *rank_ms = fe->fr_ms[0];
+    if (resolve_ms) *resolve_ms = fe->fr_ms[1];
+    if (passes) *passes = fe->fr_passes;
+    return VSLAM_OK;
+}

@@ -21,6 +21,7 @@
 #include "vslam_kernels.h"
 #include "vslam_wave.h"
 #include "vslam_matchdev.h"
+#include "vslam_kb8.h"
 
 #define SBP_TH_HIGH 100
 #define SBP_QPB 16 /* queries per k_sbp_rank workgroup (4 waves x 4) */
@@ -175,72 +176,47 @@ __device__ __forceinline__ SbpProj sbp_proj_sim3(const SbpJobs& JS, const SbpJob
     return sbp_proj_level(JS, J.th, uv, d, /* maxLevel = level + */ 0);
 }
 
+/* mode 4: the last frame's MapPoints into the current frame of a two-fisheye rig (fmatcher.cpp:2494-2659 with
+ * CurrentFrame.Nleft != -1).  Job 0 is the left branch: as mode 0 with KannalaBrandt8::project.  Job 1 is the right branch
+ * (:2593-2611): x3Dr = Rrl * x3Dc + trl as one gemm, projected through the LEFT camera's model (:2596 reads mpCamera, not
+ * mpCamera2), and no depth test and no in-frame test.  That the left branch's three `continue`s skip the right branch is not
+ * known here -- the blocks of a launch are unordered -- but to the resolver, which reads the left job's prefix. */
+__device__ __forceinline__ SbpProj sbp_proj_rig(const SbpJobs& JS, const SbpJobDev& J, const RigFrameDev& R, int right,
+                                                const SbpPoint& pc, int oct, const SiBounds& bnd) {
+    SbpProj pr = {};
+    vslam_kb8::Uv uv;
+    if (!right) {
+        const float invzc = (float)__ddiv_rn(1.0, (double)pc.z);
+        if (invzc < 0.f) return pr;
+        uv = vslam_kb8::kb8_project(R.cam, pc.x, pc.y, pc.z);
+        if (!sbp_in_frame(make_float2(uv.u, uv.v), bnd)) return pr;
+    } else {
+        const SbpPoint pr3 = sbp_transform(R.Trl, pc.x, pc.y, pc.z, J.gemmFloat);
+        uv = vslam_kb8::kb8_project(R.cam, pr3.x, pr3.y, pr3.z);
+    }
+    pr.u = uv.u;
+    pr.v = uv.v;
+    pr.radius = __fmul_rn(J.th, JS.scale[min(max(oct, 0), JS.nlevels - 1)]);
+    if (J.forward) { pr.minLevel = oct; pr.maxLevel = -1; }
+    else if (J.backward) { pr.minLevel = 0; pr.maxLevel = oct; }
+    else { pr.minLevel = oct - 1; pr.maxLevel = oct + 1; }
+    pr.valid = 1;
+    return pr;
+}
+
+/* one body, two kernels (vslam_sbp_rank_body.inc): the rig kernel adds query mode 4 and the struct it reads, and the kernel the
+ * pinhole matchers launch keeps its argument list and its code */
 __global__ void __launch_bounds__(256)
 k_sbp_rank(SbpJobs JS) {
-    extern __shared__ __align__(16) uint8_t sbsm[];
-    SbpCand* cand = (SbpCand*)sbsm; /* nCur */
-    const SbpJobDev& J = JS.job[blockIdx.y];
-    const int M = JS.M;
-    const auto [nLast, nCur] = sbp_counts(J);
-    if ((int)blockIdx.x * SBP_QPB >= nLast) return; /* grid is sized for the capacity */
-    const vslam_kp* __restrict__ lastKps = J.lastKps;
-    const vslam_kp* __restrict__ curKps = J.curKps;
-    const uint8_t* __restrict__ curDesc = J.curDesc;
-    const uint8_t* __restrict__ mpDesc = J.mpDesc;
-    const float* __restrict__ uRight = J.uRight;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const SiBounds bnd = J.bnd; /* the frame's grid bounds mnMinX.. (frame.cpp:793-821) */
-    const SiBounds wbnd = J.mode == 3 ? si_kf_bounds(bnd) : bnd; /* window origin / in-image test: a KeyFrame's are integers */
-    const SiGridInv inv = si_grid_inv(bnd);
-    for (int i = tid; i < nCur; i += 256) cand[i] = sbp_make_cand(curKps[i], uRight ? uRight[i] : -1.f, bnd, inv);
-    __syncthreads();
-    for (int q = blockIdx.x * SBP_QPB + wave; q < min(nLast, (int)(blockIdx.x + 1) * SBP_QPB); q += 4) {
-        SbpProj pr = {};
-        if (J.mode == 1) {
-            pr = sbp_proj_tracked(JS, J, J.mps[q]);
-        } else if (J.flags[q] & 1) {
-            const float X = J.x3Dw[3 * q], Y = J.x3Dw[3 * q + 1], Z = J.x3Dw[3 * q + 2];
-            const SbpPoint pc = sbp_transform(J.Tcw, X, Y, Z, J.gemmFloat);
-            if (J.mode == 2) pr = sbp_proj_keyframe(JS, J, q, pc, X, Y, Z, bnd);
-            else if (J.mode == 3) pr = sbp_proj_sim3(JS, J, q, pc, X, Y, Z, wbnd);
-            else pr = sbp_proj_last_frame(JS, J, pc, lastKps[q].octave, bnd);
-        }
-        /* per-lane sorted prefix (ascending), then an M-way merge across the wave */
-        uint32_t best[SI_MAX_M];
-#pragma unroll
-        for (int j = 0; j < SI_MAX_M; j++) best[j] = 0xFFFFFFFFu;
-        if (pr.valid) { /* wave-uniform */
-            const SiWindow win = si_window_b(pr.u, pr.v, pr.radius, wbnd, inv);
-            if (!win.empty) {
-                const uint4 da = ((const uint4*)mpDesc)[(size_t)q * 2], db = ((const uint4*)mpDesc)[(size_t)q * 2 + 1];
-                for (int c = lane; c < nCur; c += 64) {
-                    const SbpCand cd = cand[c];
-                    if (cd.cell == 0xFFFF || !sbp_candidate_ok(cd, win, pr)) continue;
-                    const uint4 ta = ((const uint4*)curDesc)[(size_t)c * 2], tb = ((const uint4*)curDesc)[(size_t)c * 2 + 1];
-                    uint32_t key = si_key(si_hamming(da, db, ta, tb), cd.cell, (uint32_t)c);
-#pragma unroll
-                    for (int j = 0; j < SI_MAX_M; j++) { /* insertion: keeps best[] ascending, drops the largest */
-                        const uint32_t lo = min(key, best[j]);
-                        key = max(key, best[j]);
-                        best[j] = lo;
-                    }
-                }
-            }
-        }
-        uint32_t mine = 0xFFFFFFFFu;
-        for (int j = 0; j < M; j++) {
-            const uint32_t g = wave_min_u32(best[0]);
-            if (g == 0xFFFFFFFFu) break;
-            if (lane == j) mine = g;
-            if (best[0] == g) { /* pop (keys are unique: they contain i2) */
-#pragma unroll
-                for (int t = 0; t + 1 < SI_MAX_M; t++) best[t] = best[t + 1];
-                best[SI_MAX_M - 1] = 0xFFFFFFFFu;
-            }
-        }
-        if (lane < M) J.topm[(size_t)q * M + lane] = mine;
-        if (lane == 0) J.proj[q] = pr;
-    }
+#define SBP_RANK_RIG 0
+#include "vslam_sbp_rank_body.inc"
+#undef SBP_RANK_RIG
+}
+__global__ void __launch_bounds__(256)
+k_sbp_rank_rig(SbpJobs JS, RigFrameDev R) {
+#define SBP_RANK_RIG 1
+#include "vslam_sbp_rank_body.inc"
+#undef SBP_RANK_RIG
 }
 
 /* full re-scan of one query's window in candidate order (the reference loop body) -> best key or ~0 */
@@ -907,6 +883,240 @@ void vk_search_rig(hipStream_t st, const SbpJobs& JS, const RigResolveDev& A, in
 }
 
 /* ------------------------------------------------------------------------------------------------
+ * SearchByProjection(CurrentFrame, LastFrame) for a two-fisheye rig (fmatcher.cpp:2494-2684 with Nleft != -1), behind
+ * k_sbp_rank_rig.  The left branch writes slots [0, nLeft) only and reads the occupancy of those alone, the right branch
+ * [nLeft, nLeft + nRight): each side by itself is the serial dictatorship k_sbp_resolve solves.  What couples them is order-free:
+ *   - the left branch's three `continue`s (invzc < 0, uv outside the bounds, vIndices2 empty) skip the right branch of the same
+ *     query.  A left record that is not valid leaves an empty prefix, and without an mvuRight gate the prefix is empty iff
+ *     vIndices2 is: "the left prefix's first key is ~0" is all three.  A left window whose candidates are all occupied has a
+ *     first key, and the right branch runs (bestDist stays 256 and control falls through to :2593).
+ *   - ONE rotation histogram and one nmatches over the entries of both sides.
+ * k_sbp_rig_resolve is k_sbp_resolve's fixpoint over both sides at once in one workgroup: a thread holds four left and four
+ * right queries, holder / owner are indexed by slot, and the finish -- last writer per slot, histogram, three maxima, nmatches
+ * -- runs over both.  A query that runs off a FULL prefix hands the call to k_sbp_rig_replay: one wave, the left queries in
+ * order, then the right ones (the sides do not see each other's writes), full re-scans where a prefix is exhausted; with
+ * forceSeq (sbp_sequential = 1) it reads no prefix but the left first keys and re-scans every window.
+ * ---------------------------------------------------------------------------------------------- */
+#define SBP_RIG_QPT (2 * SBP_QPT)
+__global__ void __launch_bounds__(SBP_RT)
+k_sbp_rig_resolve(SbpJobs JS, RigFrameDev R) {
+    extern __shared__ __align__(16) uint8_t sbsm[];
+    const SbpJobDev& JL = JS.job[0];
+    const SbpJobDev& JR = JS.job[1];
+    const int M = JS.M;
+    const int nLast = sbp_counts(JL).nLast;
+    const int nL = R.nLeft, N = R.nLeft + R.nRight;
+    int32_t* holder = (int32_t*)sbsm; /* N slots: lowest-index blocking query of the slot's side pointing here; -1 = occupied from the start */
+    int32_t* owner = holder + N;      /* N slots: highest-index query assigned here */
+    __shared__ int s_changed, s_seq, s_nlog, s_removed;
+    __shared__ int s_hist[VSLAM_HISTO_LENGTH];
+    const int tid = threadIdx.x;
+    if (tid == 0) {
+        s_seq = R.forceSeq;
+        s_nlog = 0;
+        s_removed = 0;
+    }
+    if (tid < VSLAM_HISTO_LENGTH) s_hist[tid] = 0;
+    for (int c = tid; c < N; c += SBP_RT) {
+        holder[c] = (R.occupied0 && R.occupied0[c]) ? -1 : 0x7FFFFFFF;
+        owner[c] = -1;
+    }
+    /* k < SBP_QPT: left query tid + k * SBP_RT; k >= SBP_QPT: the right branch of query tid + (k - SBP_QPT) * SBP_RT */
+    uint32_t key[SBP_RIG_QPT];
+    int ptr[SBP_RIG_QPT];
+    bool blocking[SBP_QPT];
+#pragma unroll
+    for (int k = 0; k < SBP_QPT; k++) {
+        const int q = tid + k * SBP_RT;
+        ptr[k] = ptr[k + SBP_QPT] = 0;
+        key[k] = q < nLast ? JL.topm[(size_t)q * M] : 0xFFFFFFFFu;
+        /* a left `continue` (:2509-2517, :2534-2535) skips the right branch */
+        key[k + SBP_QPT] = key[k] != 0xFFFFFFFFu ? JR.topm[(size_t)q * M] : 0xFFFFFFFFu;
+        blocking[k] = q < nLast && (JL.flags[q] & 2);
+    }
+    __syncthreads();
+    for (int round = 0; round < 4096 && !s_seq; round++) { /* s_seq / s_changed are block-uniform at the barriers */
+        if (tid == 0) s_changed = 0;
+#pragma unroll
+        for (int k = 0; k < SBP_RIG_QPT; k++)
+            if (key[k] != 0xFFFFFFFFu && blocking[k % SBP_QPT] && si_key_dist(key[k]) <= (uint32_t)SBP_TH_HIGH)
+                atomicMin(&holder[(k < SBP_QPT ? 0 : nL) + (int)si_key_index(key[k])], tid + (k % SBP_QPT) * SBP_RT);
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < SBP_RIG_QPT; k++) {
+            const int q = tid + (k % SBP_QPT) * SBP_RT;
+            const SbpJobDev& J = k < SBP_QPT ? JL : JR;
+            if (key[k] != 0xFFFFFFFFu && holder[(k < SBP_QPT ? 0 : nL) + (int)si_key_index(key[k])] < q) {
+                ptr[k]++;
+                if (ptr[k] >= M) {
+                    s_seq = 1; /* ran off a full prefix */
+                    key[k] = 0xFFFFFFFFu;
+                } else {
+                    key[k] = J.topm[(size_t)q * M + ptr[k]]; /* ~0: the list is complete and exhausted */
+                }
+                s_changed = 1;
+            }
+        }
+        __syncthreads();
+        if (!s_changed) break;
+        __syncthreads();
+    }
+    __syncthreads();
+    if (tid == 0) *R.needSeq = s_seq;
+    if (s_seq) return;
+    /* the joint finish: both sides' assignments into one log */
+    uint32_t bin[SBP_RIG_QPT];
+#pragma unroll
+    for (int k = 0; k < SBP_RIG_QPT; k++) {
+        const int q = tid + (k % SBP_QPT) * SBP_RT;
+        const SbpJobDev& J = k < SBP_QPT ? JL : JR;
+        bin[k] = 255;
+        if (key[k] != 0xFFFFFFFFu && si_key_dist(key[k]) <= (uint32_t)SBP_TH_HIGH) {
+            const int i2 = (int)si_key_index(key[k]);
+            atomicMax(&owner[(k < SBP_QPT ? 0 : nL) + i2], q);
+            atomicAdd(&s_nlog, 1);
+            bin[k] = 254;
+            if (JL.checkOri) { /* kpLF: keypoints_[i] | keypointsRight_[i - Nleft], the caller's one array; kpCF of the side */
+                const int b = vslam_md::rot_bin(JL.lastKps[q].angle, J.curKps[i2].angle, VSLAM_HISTO_LENGTH);
+                bin[k] = (uint32_t)b;
+                atomicAdd(&s_hist[b], 1);
+            }
+        }
+    }
+    __syncthreads();
+    for (int c = tid; c < N; c += SBP_RT) R.matchCur[c] = owner[c];
+    __syncthreads();
+    if (JL.checkOri) {
+        const vslam_md::ThreeMaxima mx = vslam_md::three_maxima(s_hist, VSLAM_HISTO_LENGTH);
+#pragma unroll
+        for (int k = 0; k < SBP_RIG_QPT; k++) {
+            const int b = (int)bin[k];
+            if (b < VSLAM_HISTO_LENGTH && !vslam_md::keeps_bin(mx, b)) { /* fmatcher.cpp:2668-2681 */
+                R.matchCur[(k < SBP_QPT ? 0 : nL) + (int)si_key_index(key[k])] = -1;
+                atomicAdd(&s_removed, 1);
+            }
+        }
+    }
+    __syncthreads();
+    if (tid == 0) R.nmatches[0] = s_nlog - s_removed;
+}
+
+__global__ void __launch_bounds__(64)
+k_sbp_rig_replay(SbpJobs JS, RigFrameDev R) {
+    extern __shared__ __align__(16) uint8_t sbsm[];
+    const SbpJobDev& JL = JS.job[0];
+    const SbpJobDev& JR = JS.job[1];
+    const int M = JS.M;
+    const int nLast = sbp_counts(JL).nLast;
+    const int nL = R.nLeft, N = R.nLeft + R.nRight;
+    uint32_t* occupied = (uint32_t*)sbsm;            /* N: the slot holds a MapPoint with Observations() > 0 */
+    int32_t* ownerEntry = (int32_t*)(occupied + N);  /* N: last log entry that wrote the slot */
+    uint32_t* alog = (uint32_t*)(ownerEntry + N);    /* 2 * nLast: (query << 13 | slot), left entries first */
+    uint8_t* logBin = (uint8_t*)(alog + 2 * nLast);  /* 2 * nLast: rotation bin of a log entry */
+    __shared__ int s_hist[VSLAM_HISTO_LENGTH];
+    const int lane = threadIdx.x;
+    if (*R.needSeq == 0) return; /* k_sbp_rig_resolve finished the call */
+    const SiBounds bnd = JL.bnd;
+    const SiGridInv inv = si_grid_inv(bnd);
+    for (int c = lane; c < N; c += 64) {
+        occupied[c] = (R.occupied0 && R.occupied0[c]) ? 1u : 0u;
+        ownerEntry[c] = -1;
+        R.matchCur[c] = -1;
+    }
+    if (lane < VSLAM_HISTO_LENGTH) s_hist[lane] = 0;
+    __syncthreads();
+    int nlog = 0, nfb = 0;
+    for (int side = 0; side < 2; side++) {
+        const SbpJobDev& J = side ? JR : JL;
+        const int base = side ? nL : 0, nCur = side ? R.nRight : nL;
+        for (int qb = 0; qb < nLast; qb += 64) {
+            const int nq = min(64, nLast - qb);
+            /* lane t: query qb + t is not walked -- the left branch left by a `continue`, or (no prefix read) nothing to scan */
+            bool skip = lane >= nq || JL.topm[(size_t)(qb + lane) * M] == 0xFFFFFFFFu;
+            if (!skip && R.forceSeq) skip = !J.proj[qb + lane].valid;
+            const unsigned long long todo = ~__ballot(skip);
+            const uint32_t myflags = lane < nq ? J.flags[qb + lane] : 0u;
+            for (int tq = 0; tq < nq; tq++) {
+                if (!((todo >> tq) & 1ull)) continue;
+                const int q = qb + tq;
+                uint32_t gBest = 0xFFFFFFFFu;
+                bool scan = R.forceSeq != 0;
+                if (!scan) {
+                    const uint32_t key = lane < M ? J.topm[(size_t)q * M + lane] : 0xFFFFFFFFu;
+                    const bool valid = key != 0xFFFFFFFFu;
+                    const bool fr = valid && !occupied[base + (int)si_key_index(key)];
+                    const unsigned long long mv = __ballot(valid), mk = __ballot(fr);
+                    if (mv == 0) continue; /* the right window holds nothing */
+                    if (mk) {
+                        const int first = __builtin_amdgcn_readfirstlane(__ffsll((long long)mk) - 1);
+                        gBest = (uint32_t)__builtin_amdgcn_readlane((int)key, first);
+                    } else if (__popcll(mv) < M) {
+                        continue; /* the list is complete and every entry is occupied: bestDist stays 256 */
+                    } else {
+                        scan = true;
+                    }
+                }
+                if (scan) {
+                    nfb++;
+                    gBest = sbp_full_scan(J.proj[q], J.curKps, nullptr, nCur, J.mpDesc + (size_t)q * 32, J.curDesc, occupied + base,
+                                          bnd, bnd, inv, lane);
+                }
+                if (gBest == 0xFFFFFFFFu || si_key_dist(gBest) > (uint32_t)SBP_TH_HIGH) continue;
+                const uint32_t slot = (uint32_t)base + si_key_index(gBest);
+                const uint32_t fl = (uint32_t)__builtin_amdgcn_readlane((int)myflags, tq);
+                if (lane == 0) {
+                    alog[nlog] = ((uint32_t)q << 13) | slot;
+                    if (fl & 2) occupied[slot] = 1u; /* pMP->Observations() > 0: later queries of this side skip the slot */
+                }
+                nlog++;
+                __syncthreads(); /* one wave: orders lane 0's write before the next query's reads */
+            }
+        }
+    }
+    __syncthreads();
+    if (R.fallbacks && lane == 0 && nfb) atomicAdd(R.fallbacks, nfb);
+    for (int e = lane; e < nlog; e += 64) atomicMax(&ownerEntry[alog[e] & 0x1FFF], e);
+    __syncthreads();
+    for (int e = lane; e < nlog; e += 64) {
+        const uint32_t le = alog[e];
+        const int q = (int)(le >> 13), slot = (int)(le & 0x1FFF);
+        if (ownerEntry[slot] == e) R.matchCur[slot] = q;
+        if (JL.checkOri) {
+            const float ang = slot < nL ? JL.curKps[slot].angle : JR.curKps[slot - nL].angle;
+            const int bin = vslam_md::rot_bin(JL.lastKps[q].angle, ang, VSLAM_HISTO_LENGTH);
+            logBin[e] = (uint8_t)bin;
+            atomicAdd(&s_hist[bin], 1);
+        }
+    }
+    __syncthreads();
+    int removed = 0;
+    if (JL.checkOri) {
+        const vslam_md::ThreeMaxima mx = vslam_md::three_maxima(s_hist, VSLAM_HISTO_LENGTH);
+        for (int e = lane; e < nlog; e += 64) {
+            if (!vslam_md::keeps_bin(mx, logBin[e])) {
+                R.matchCur[alog[e] & 0x1FFF] = -1;
+                removed++;
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) removed += __shfl_xor(removed, o, 64);
+    if (lane == 0) R.nmatches[0] = nlog - removed;
+}
+
+size_t vk_sbp_rig_resolve_lds(int nSlots) { return (size_t)nSlots * 8; }
+size_t vk_sbp_rig_replay_lds(int nSlots, int nLast) { return (size_t)nSlots * 8 + (size_t)nLast * 10; }
+
+void vk_search_frame_rig(hipStream_t st, const SbpJobs& JS, const RigFrameDev& R, int nLast, hipEvent_t between) {
+    if (nLast <= 0) return;
+    hipLaunchKernelGGL(k_sbp_rank_rig, dim3((nLast + SBP_QPB - 1) / SBP_QPB, 2), dim3(256),
+                       vk_sbp_rank_lds(max(R.nLeft, R.nRight)), st, JS, R);
+    if (between) (void)hipEventRecord(between, st);
+    hipLaunchKernelGGL(k_sbp_rig_resolve, dim3(1), dim3(SBP_RT), vk_sbp_rig_resolve_lds(R.nLeft + R.nRight), st, JS, R);
+    hipLaunchKernelGGL(k_sbp_rig_replay, dim3(1), dim3(64), vk_sbp_rig_replay_lds(R.nLeft + R.nRight, nLast), st, JS, R);
+}
+
+/* ------------------------------------------------------------------------------------------------
  * Frame::UnprojectStereo (frame.cpp:1023-1037) for every left keypoint of up to VSLAM_MAX_SBP_JOBS stereo
  * pairs: z = mvDepth[i] > 0  ->  x3Dc = ((u-cx)*z*invfx, (v-cy)*z*invfy, z), x3Dw = mRwc*x3Dc + mOw (one
  * cv::gemm, sbp_transform).  These are the points UpdateLastFrame turns into (temporal) MapPoints for
@@ -1076,6 +1286,12 @@ int vk_sbp_set_max_lds(size_t bytes) {
     rc = (int)hipFuncSetAttribute((const void*)k_fuse_rank, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (rc) return rc;
     rc = (int)hipFuncSetAttribute((const void*)k_rig_resolve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (rc) return rc;
+    rc = (int)hipFuncSetAttribute((const void*)k_sbp_rank_rig, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (rc) return rc;
+    rc = (int)hipFuncSetAttribute((const void*)k_sbp_rig_resolve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (rc) return rc;
+    rc = (int)hipFuncSetAttribute((const void*)k_sbp_rig_replay, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (rc) return rc;
     return (int)hipFuncSetAttribute((const void*)k_sbp_replay, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
