@@ -750,7 +750,7 @@ int vslam_fe_get_local_points_profile(vslam_fe* fe, double* frustum_ms, double* 
  * The rig form of SearchByProjection(F, vpMapPoints), right-camera branch included (fmatcher.cpp:321-491), is
  * vslam_search_by_projection_mappoints_rig / vslam_search_local_points_rig below; the rig form of
  * SearchByProjection(CurrentFrame, LastFrame), right-camera branch :2593-2659 included, is vslam_search_by_projection_frame_rig.
- * Not covered: every other matcher's fisheye or right-camera branch (Fuse(.., bRight), SearchByBoW, SearchForTriangulation), TriangulateMatches / epipolarConstrain / matchAndtriangulate (cv::SVD), ReconstructWithTwoViews
+ * Not covered: every other matcher's fisheye or right-camera branch (Fuse(.., bRight), SearchForTriangulation, the relocalisation SearchByProjection(CurrentFrame, KeyFrame, ..); SearchByBoW of a rig is vslam_search_by_bow_rig), TriangulateMatches / epipolarConstrain / matchAndtriangulate (cv::SVD), ReconstructWithTwoViews
  * (cv::fisheye::undistortPoints), projectJac, tanf beyond 3*pi/4. */
 typedef struct vslam_kb8_camera {
     float fx, fy, cx, cy; /* mvParameters[0..3] */
@@ -1146,6 +1146,70 @@ int vslam_search_by_bow_keyframes(vslam_fe* fe, const vslam_kp* kps1_host, const
                                   const uint8_t* dev_desc2, const uint8_t* flags2_host, int n2,
                                   const int32_t* fv2_nodes, const int32_t* fv2_off, const int32_t* fv2_feat,
                                   int n2_nodes, float nnratio, int check_orientation, int32_t* match12, int* nmatches);
+
+/* FMatcher::SearchByBoW(KeyFrame* pKF, Frame& F, vector<MapPoint*>& vpMapPointMatches) (fmatcher.cpp:546-748) for a two-fisheye
+ * rig (F.Nleft != -1): ONE frame against 1 to 16 keyframes in one pass of the kernels (TrackReferenceKeyFrame, tracking.cpp:2578:
+ * one keyframe; the Relocalization loop, tracking.cpp:3488-3509: every candidate at once).  Restated as written:
+ *   - F has N = n_left + n_right features; descriptor rows and FeatureVector indices run over [0, N), left first
+ *     (frame.cpp:1137).  A rig KeyFrame is indexed the same way; KeyFrame features of BOTH sides are queries
+ *   - only shared vocabulary nodes are paired (the lower_bound walk)
+ *   - for a KeyFrame feature with a good MapPoint ONE pass over the node's frame features skips occupied slots and keeps
+ *     bestDist1 / bestDist2 / bestIdxF over realIdxF < n_left, bestDist1R / bestIdxFR over the rest; the first candidate in
+ *     FeatureVector order wins a tie
+ *   - the left write happens iff bestDist1 <= TH_LOW and the ratio test passes
+ *   - the right branch is NESTED in `if (bestDist1 <= TH_LOW)` (:680 within :650): it runs whether or not the left ratio test
+ *     passed; it does not run when the left best is above TH_LOW or no free left candidate exists.  Its own ratio test is
+ *     `.. || true` (:682): bestDist1R <= TH_LOW alone writes bestIdxFR
+ *   - every write counts in nmatches and enters ONE rotation histogram over both sides, with the angles of keypoints_ /
+ *     keypointsRight_ by index on both the KeyFrame and the Frame side; a slot is written at most once
+ *   - with n_right == 0 on both sides this is vslam_search_by_bow.
+ * frame: the device keypoints (their angles) and descriptors of both extractor slots and the counts are read; the match maps and
+ * occupied_host are not (the reference starts from an empty vpMapPointMatches).  f_fv_*: the frame's FeatureVector over [0, N)
+ * (Vocabulary::transform of the concatenated descriptors), uploaded once for all jobs.  A keyframe job: device descriptors per
+ * side (n_right may be 0 and dev_desc_right NULL), ONE host keypoint array keypoints_ then keypointsRight_ (the angle is read),
+ * flags_host[i] != 0 iff the i-th feature has a MapPoint that is not bad, its FeatureVector.
+ * _async: one upload -> k_sbow_nodes_rig (one wave per job and keyframe node) -> k_sbow_finish_rig (one workgroup per job) -> one
+ * result copy on the context's stream, no host wait in between, in a staging block of its own: the blocking matchers may run
+ * while a search is in flight.  One such search per context may be in flight (a second _async is VSLAM_ERR_INVALID).
+ * _wait: match_f[j] (n_left + n_right entries) = the index of job j's KeyFrame feature whose MapPoint goes to the slot, or -1;
+ * nmatches[j] as the reference counts it.
+ * Limits: n_left, n_right <= 4096 on every side; at most 2048 frame features (both sides together) under a node that a keyframe
+ * shares.  Beyond either _async returns VSLAM_ERR_UNSUPPORTED and nothing is enqueued or in flight; the blocking form then
+ * leaves every match_f at -1 and every nmatches at 0.  A FeatureVector whose offsets do not ascend from 0 or whose indices
+ * leave [0, n) is VSLAM_ERR_INVALID, checked before anything is enqueued.  Empty inputs (no features, no nodes, an empty job)
+ * give an empty result of that job; when no job has anything to match nothing is launched.  The matcher does not project: it
+ * runs with or without a KB8 camera set. */
+typedef struct vslam_bow_rig_kf {
+    const uint8_t* dev_desc_left;  int n_left;   /* descriptor rows [0, NLeft) */
+    const uint8_t* dev_desc_right; int n_right;  /* rows [NLeft, NLeft + NRight); may be NULL with n_right == 0 */
+    const vslam_kp* kps_host;                    /* n_left + n_right: mvKeys then mvKeysRight */
+    const uint8_t* flags_host;                   /* n_left + n_right */
+    const int32_t *fv_nodes, *fv_off, *fv_feat;  /* mFeatVec: n_nodes ascending node ids, n_nodes + 1 offsets, indices */
+    int n_nodes;
+} vslam_bow_rig_kf;
+int vslam_search_by_bow_rig_async(vslam_fe* fe, const vslam_bow_rig_kf* kf_jobs, int n_kf_jobs, const vslam_rig_frame* frame,
+                                  const int32_t* f_fv_nodes, const int32_t* f_fv_off, const int32_t* f_fv_feat, int n_f_nodes,
+                                  float nnratio, int check_orientation);
+int vslam_search_by_bow_rig_wait(vslam_fe* fe, int32_t* const* match_f, int* nmatches);
+/* _async + _wait */
+int vslam_search_by_bow_rig(vslam_fe* fe, const vslam_bow_rig_kf* kf_jobs, int n_kf_jobs, const vslam_rig_frame* frame,
+                            const int32_t* f_fv_nodes, const int32_t* f_fv_off, const int32_t* f_fv_feat, int n_f_nodes,
+                            float nnratio, int check_orientation, int32_t* const* match_f, int* nmatches);
+/* With vslam_fe_set_profiling on: HIP-event time of k_sbow_nodes_rig and of k_sbow_finish_rig, summed over the rig BoW searches
+ * waited for since.  Any pointer may be NULL. */
+int vslam_fe_get_bow_rig_profile(vslam_fe* fe, double* nodes_ms, double* finish_ms, long* passes);
+
+/* The KeyFrame-KeyFrame overload (fmatcher.cpp:1100-1240) for rig KeyFrames.  The reference skips idx >= mvKeysUn.size() on
+ * both sides (:1135, :1155) and a rig's mvKeysUn is keypoints_ (NLeft entries): right features are neither queries nor
+ * candidates.  n1 / n2 = NLeft + NRight (flags, FeatureVector indices, match12 entries), n_left1 / n_left2 = NLeft; kps*_host
+ * hold n_left entries (mvKeysUn); only descriptor rows < n_left are read, so dev_desc* are the left arrays.  The flags are
+ * staged with the entries >= n_left cleared and vslam_search_by_bow_keyframes' kernels run as they are. */
+int vslam_search_by_bow_keyframes_rig(vslam_fe* fe, const vslam_kp* kps1_host, const uint8_t* dev_desc1,
+                                      const uint8_t* flags1_host, int n1, int n_left1, const int32_t* fv1_nodes,
+                                      const int32_t* fv1_off, const int32_t* fv1_feat, int n1_nodes, const vslam_kp* kps2_host,
+                                      const uint8_t* dev_desc2, const uint8_t* flags2_host, int n2, int n_left2,
+                                      const int32_t* fv2_nodes, const int32_t* fv2_off, const int32_t* fv2_feat, int n2_nodes,
+                                      float nnratio, int check_orientation, int32_t* match12, int* nmatches);
 
 /* FMatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo, bCoarse) (fmatcher.cpp:1242-1482)
  * and its cv::Matx twin SearchForTriangulation_ (:1484-1725, the one LocalMapping::CreateNewMapPoints calls,

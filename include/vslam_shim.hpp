@@ -51,6 +51,15 @@ extern "C" int vslamh_search_by_projection_frame_rig(const vslam_proj_params* p,
                                                      const float* scale_factors, int nlevels, const float* bounds,
                                                      int32_t* match_cur, int* nmatches);
 
+/* the same for SearchByBoW(KeyFrame, Frame) of a rig, one keyframe: FMatcher::SearchByBoW(.., RigFrameView, ..)'s fallback */
+extern "C" int vslamh_search_by_bow_rig(const vslam_kp* kf_kps, const uint8_t* kf_desc_left, int kf_n_left,
+                                        const uint8_t* kf_desc_right, int kf_n_right, const uint8_t* kf_flags,
+                                        const int32_t* kf_fv_nodes, const int32_t* kf_fv_off, const int32_t* kf_fv_feat,
+                                        int n_kf_nodes, const vslam_kp* f_kps_left, const uint8_t* f_desc_left, int n_left,
+                                        const vslam_kp* f_kps_right, const uint8_t* f_desc_right, int n_right,
+                                        const int32_t* f_fv_nodes, const int32_t* f_fv_off, const int32_t* f_fv_feat,
+                                        int n_f_nodes, float nnratio, int check_orientation, int32_t* match_f, int* nmatches);
+
 namespace VSLAM_SHIM_NAMESPACE {
 namespace geometry {
 
@@ -403,6 +412,12 @@ struct FrameRGBD : FrameView {
     FrameRGBD& operator=(const FrameRGBD&) = delete;
 };
 
+/* DBoW3::FeatureVector (a std::map in the reference) as the flat arrays the library takes: ascending node ids, nodes.size() + 1
+ * offsets into feat, the feature indices of each node in order.  (BowVector, its sibling, stands before KeyFrameDatabase.) */
+struct FeatureVector {
+    std::vector<int> nodes, off, feat;
+};
+
 /* ---------------------------------------------------------------------------------------------------
  * FMatcher (fmatcher.h:70-147), hot-path subset
  * ------------------------------------------------------------------------------------------------- */
@@ -583,6 +598,9 @@ public:
         const std::vector<KeyPoint>* keypointsRight = nullptr;
         const std::vector<uint8_t>* descriptorsLeft = nullptr;  /* 32 per keypoint */
         const std::vector<uint8_t>* descriptorsRight = nullptr;
+        /* read by SearchByBoW alone: mFeatVec over the Nleft + Nright features, left first (DBoW3::Vocabulary::transform of a
+         * RigFrameView) */
+        const FeatureVector* mFeatVec = nullptr;
     };
     int SearchLocalPoints(const RigFrameView& cur, const std::vector<vslam_map_point>& mvpLocalMapPoints,
                           const std::vector<uint8_t>& mapPointDescriptors, const std::vector<uint8_t>* occupied,
@@ -692,6 +710,127 @@ public:
                                                     reinterpret_cast<const vslam_kp*>(cur.keypointsRight->data()),
                                                     cur.descriptorsRight->data(), f.n_right, f.occupied_host, sf.data(),
                                                     (int)sf.size(), bounds, mvpMapPointIndex.data(), &nm));
+        return nm;
+    }
+
+    /* FMatcher::SearchByBoW(KeyFrame* pKF, Frame& F, vector<MapPoint*>& vpMapPointMatches) (fmatcher.cpp:546-748) for a
+     * two-fisheye rig (F.Nleft != -1).  A rig KeyFrame: its descriptor rows in HBM per camera (a KeyFrame made from a frame keeps
+     * the addresses of the slots it was extracted into, or of its own copies), ONE keypoint array mvKeys followed by mvKeysRight
+     * (the angle is read), one flag per feature (has a MapPoint that is not bad) and mFeatVec over NLeft + NRight features.
+     * `descriptors` (optional, (NLeft + NRight) x 32 bytes on the host) is read by the host fallback alone; `extractor` by the
+     * KeyFrame-KeyFrame overload alone (the context to run on).
+     * The vector form is the relocalisation loop (tracking.cpp:3488-3509): every candidate KeyFrame against the one frame in one
+     * enqueue, up to 16 per call (more are served in groups of 16).  vvpMapPointIndex[k][slot] = index of KeyFrame k's feature
+     * whose MapPoint goes to vpMapPointMatches[slot] (Nleft + Nright slots, left first), or -1; the returned vector holds the
+     * nmatches of each KeyFrame.  cur: both extractors' slot 0 and mFeatVec are read; no pose, no camera.
+     * Beyond the device's limits (4096 features per camera, 2048 frame features under one node) the call runs the sequential
+     * host form, if cur carries ukeypoints, keypointsRight and both descriptor arrays and every KeyFrame its descriptors;
+     * otherwise it throws. */
+    struct RigKeyFrameView {
+        const uint8_t* dev_desc_left = nullptr;
+        const uint8_t* dev_desc_right = nullptr;
+        int NLeft = 0, NRight = 0;
+        const std::vector<KeyPoint>* keys = nullptr;          /* mvKeys then mvKeysRight */
+        const std::vector<uint8_t>* mapPointFlags = nullptr;  /* NLeft + NRight */
+        const FeatureVector* mFeatVec = nullptr;
+        const std::vector<uint8_t>* descriptors = nullptr;
+        const FExtractor* extractor = nullptr;
+    };
+    std::vector<int> SearchByBoW(const std::vector<RigKeyFrameView>& vpKFs, const RigFrameView& cur,
+                                 std::vector<std::vector<int> >& vvpMapPointIndex) {
+        static_assert(sizeof(KeyPoint) == sizeof(vslam_kp) && sizeof(int) == sizeof(int32_t), "arrays are handed over as they are");
+        if (!cur.right || !cur.left.frame.extractor || !cur.mFeatVec)
+            throw std::invalid_argument("SearchByBoW: a rig frame needs both extractors and its FeatureVector");
+        const FeatureVector& ffv = *cur.mFeatVec;
+        if (ffv.off.size() != ffv.nodes.size() + 1) throw std::invalid_argument("SearchByBoW: FeatureVector offsets");
+        vslam_fe* fe = cur.left.frame.extractor->context();
+        vslam_rig_frame f;
+        std::memset(&f, 0, sizeof(f));
+        check(vslam_fe_slot_buffers(fe, 0, &f.dev_kps_left, &f.dev_desc_left, &f.n_left));
+        check(vslam_fe_slot_buffers(cur.right->context(), 0, &f.dev_kps_right, &f.dev_desc_right, &f.n_right));
+        const int N = f.n_left + f.n_right;
+        std::vector<int> nmatches(vpKFs.size(), 0);
+        vvpMapPointIndex.assign(vpKFs.size(), std::vector<int>((size_t)N, -1));
+        for (size_t first = 0; first < vpKFs.size(); first += 16) {
+            const int K = (int)std::min<size_t>(16, vpKFs.size() - first);
+            vslam_bow_rig_kf jobs[16];
+            int32_t* out[16];
+            std::memset(jobs, 0, sizeof(jobs));
+            for (int j = 0; j < K; j++) {
+                const RigKeyFrameView& k = vpKFs[first + j];
+                const size_t n = (size_t)k.NLeft + (size_t)k.NRight;
+                if (k.NLeft < 0 || k.NRight < 0 || !k.keys || !k.mapPointFlags || !k.mFeatVec || k.keys->size() != n ||
+                    k.mapPointFlags->size() != n || k.mFeatVec->off.size() != k.mFeatVec->nodes.size() + 1)
+                    throw std::invalid_argument("SearchByBoW: a rig KeyFrame holds NLeft + NRight keypoints and flags and a FeatureVector");
+                jobs[j].dev_desc_left = k.dev_desc_left;
+                jobs[j].n_left = k.NLeft;
+                jobs[j].dev_desc_right = k.dev_desc_right;
+                jobs[j].n_right = k.NRight;
+                jobs[j].kps_host = reinterpret_cast<const vslam_kp*>(k.keys->data());
+                jobs[j].flags_host = k.mapPointFlags->data();
+                jobs[j].fv_nodes = k.mFeatVec->nodes.data();
+                jobs[j].fv_off = k.mFeatVec->off.data();
+                jobs[j].fv_feat = k.mFeatVec->feat.data();
+                jobs[j].n_nodes = (int)k.mFeatVec->nodes.size();
+                out[j] = vvpMapPointIndex[first + j].data();
+            }
+            const int rc = vslam_search_by_bow_rig(fe, jobs, K, &f, ffv.nodes.data(), ffv.off.data(), ffv.feat.data(),
+                                                   (int)ffv.nodes.size(), mfNNratio, mbCheckOrientation ? 1 : 0, out,
+                                                   nmatches.data() + first);
+            if (rc != VSLAM_ERR_UNSUPPORTED) {
+                check(rc);
+                continue;
+            }
+            /* over the device's limits: the reference loop on the host, one KeyFrame after the other */
+            const std::vector<KeyPoint>* kl = cur.left.frame.ukeypoints;
+            if (!kl || !cur.keypointsRight || !cur.descriptorsLeft || !cur.descriptorsRight || (int)kl->size() != f.n_left ||
+                (int)cur.keypointsRight->size() != f.n_right || cur.descriptorsLeft->size() != 32 * (size_t)f.n_left ||
+                cur.descriptorsRight->size() != 32 * (size_t)f.n_right)
+                check(rc);
+            for (int j = 0; j < K; j++) {
+                const RigKeyFrameView& k = vpKFs[first + j];
+                if (!k.descriptors || k.descriptors->size() != 32 * ((size_t)k.NLeft + (size_t)k.NRight)) check(rc);
+                check(vslamh_search_by_bow_rig(jobs[j].kps_host, k.descriptors->data(), k.NLeft,
+                                               k.descriptors->data() + 32 * (size_t)k.NLeft, k.NRight, jobs[j].flags_host,
+                                               jobs[j].fv_nodes, jobs[j].fv_off, jobs[j].fv_feat, jobs[j].n_nodes,
+                                               reinterpret_cast<const vslam_kp*>(kl->data()), cur.descriptorsLeft->data(), f.n_left,
+                                               reinterpret_cast<const vslam_kp*>(cur.keypointsRight->data()),
+                                               cur.descriptorsRight->data(), f.n_right, ffv.nodes.data(), ffv.off.data(),
+                                               ffv.feat.data(), (int)ffv.nodes.size(), mfNNratio, mbCheckOrientation ? 1 : 0,
+                                               out[j], &nmatches[first + j]));
+            }
+        }
+        return nmatches;
+    }
+    /* one KeyFrame: TrackReferenceKeyFrame's call (tracking.cpp:2578).  Returns nmatches. */
+    int SearchByBoW(const RigKeyFrameView& pKF, const RigFrameView& cur, std::vector<int>& vpMapPointIndex) {
+        std::vector<std::vector<int> > all;
+        const std::vector<int> nm = SearchByBoW(std::vector<RigKeyFrameView>(1, pKF), cur, all);
+        vpMapPointIndex.swap(all[0]);
+        return nm[0];
+    }
+    /* FMatcher::SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches12) (fmatcher.cpp:1100-1240) for rig
+     * KeyFrames: idx >= mvKeysUn.size() is skipped on both sides and a rig's mvKeysUn has NLeft entries, so right features are
+     * neither queries nor candidates.  vpMatches12[idx1] = idx2 or -1, NLeft + NRight entries.  Runs on pKF1.extractor's
+     * context.  Returns nmatches. */
+    int SearchByBoW(const RigKeyFrameView& pKF1, const RigKeyFrameView& pKF2, std::vector<int>& vpMatches12) {
+        const RigKeyFrameView* k[2] = {&pKF1, &pKF2};
+        for (int i = 0; i < 2; i++)
+            if (!k[i]->keys || !k[i]->mapPointFlags || !k[i]->mFeatVec || k[i]->NLeft < 0 || k[i]->NRight < 0 ||
+                (int)k[i]->keys->size() < k[i]->NLeft || (int)k[i]->mapPointFlags->size() != k[i]->NLeft + k[i]->NRight ||
+                k[i]->mFeatVec->off.size() != k[i]->mFeatVec->nodes.size() + 1)
+                throw std::invalid_argument("SearchByBoW: a rig KeyFrame holds its keypoints, NLeft + NRight flags and a FeatureVector");
+        if (!pKF1.extractor) throw std::invalid_argument("SearchByBoW: the first KeyFrame names the extractor to run on");
+        const int n1 = pKF1.NLeft + pKF1.NRight, n2 = pKF2.NLeft + pKF2.NRight;
+        vpMatches12.assign((size_t)n1, -1);
+        int nm = 0;
+        check(vslam_search_by_bow_keyframes_rig(
+            pKF1.extractor->context(), reinterpret_cast<const vslam_kp*>(pKF1.keys->data()), pKF1.dev_desc_left,
+            pKF1.mapPointFlags->data(), n1, pKF1.NLeft, pKF1.mFeatVec->nodes.data(), pKF1.mFeatVec->off.data(),
+            pKF1.mFeatVec->feat.data(), (int)pKF1.mFeatVec->nodes.size(), reinterpret_cast<const vslam_kp*>(pKF2.keys->data()),
+            pKF2.dev_desc_left, pKF2.mapPointFlags->data(), n2, pKF2.NLeft, pKF2.mFeatVec->nodes.data(), pKF2.mFeatVec->off.data(),
+            pKF2.mFeatVec->feat.data(), (int)pKF2.mFeatVec->nodes.size(), mfNNratio, mbCheckOrientation ? 1 : 0,
+            vpMatches12.data(), &nm));
         return nm;
     }
 
@@ -1435,6 +1574,43 @@ public:
         vslam_voc_file_close(file_);
         voc_ = nullptr;
         file_ = nullptr;
+    }
+    /* Frame::ComputeBoW of a two-camera rig (frame.cpp:455-461 over the vconcat'ed descriptors, :1137): transform(features,
+     * mBowVec, mFeatVec, levelsup) with the per-feature descent of both extractors' slot 0 on the device and ONE assembly
+     * over the Nleft + Nright features, left first.  F: both extractors are read. */
+    void transform(const geometry::FMatcher::RigFrameView& F, geometry::BowVector& bow, geometry::FeatureVector& fv,
+                   int levelsup) const {
+        if (!voc_ || !F.left.frame.extractor || !F.right)
+            throw std::invalid_argument("DBoW3::Vocabulary::transform: an empty vocabulary or a rig frame without its extractors");
+        int weighting = 0, norm = 0;
+        geometry::check(vslam_voc_info(voc_, nullptr, &weighting, &norm, nullptr));
+        const geometry::FExtractor* ex[2] = {F.left.frame.extractor, F.right};
+        int n[2] = {0, 0};
+        const uint8_t* dd[2] = {nullptr, nullptr};
+        for (int s = 0; s < 2; s++) {
+            const vslam_kp* dk = nullptr;
+            geometry::check(vslam_fe_slot_buffers(ex[s]->context(), 0, &dk, &dd[s], &n[s]));
+        }
+        const size_t N = (size_t)n[0] + (size_t)n[1];
+        std::vector<int32_t> word(N + 1), nid(N + 1);
+        std::vector<double> weight(N + 1);
+        for (int s = 0, o = 0; s < 2; o += n[s], s++)
+            geometry::check(vslam_bow_transform(ex[s]->context(), voc_, dd[s], n[s], levelsup, word.data() + o, weight.data() + o,
+                                                nid.data() + o));
+        bow.ids.assign(N + 1, 0);
+        bow.values.assign(N + 1, 0.0);
+        fv.nodes.assign(N + 1, 0);
+        fv.off.assign(N + 2, 0);
+        fv.feat.assign(N + 1, 0);
+        int nb = 0, nf = 0;
+        if (vslam_bow_assemble(weighting, norm, word.data(), weight.data(), nid.data(), (int)N, bow.ids.data(), bow.values.data(),
+                               &nb, fv.nodes.data(), fv.off.data(), fv.feat.data(), &nf) != VSLAM_OK)
+            throw std::invalid_argument("DBoW3::Vocabulary::transform: vslam_bow_assemble refused its arguments");
+        bow.ids.resize((size_t)nb);
+        bow.values.resize((size_t)nb);
+        fv.nodes.resize((size_t)nf);
+        fv.off.resize((size_t)nf + 1);
+        fv.feat.resize((size_t)fv.off[(size_t)nf]);
     }
     bool empty() const { return !file_; }
     unsigned size() const { /* number of words */

@@ -67,6 +67,8 @@ ABI_SYMBOLS = [
     "vslam_search_local_points_rig", "vslam_fe_get_local_points_rig_profile",
     "vslam_search_by_projection_frame_rig_async", "vslam_search_by_projection_frame_rig_wait",
     "vslam_search_by_projection_frame_rig", "vslam_fe_get_frame_rig_profile",
+    "vslam_search_by_bow_rig_async", "vslam_search_by_bow_rig_wait", "vslam_search_by_bow_rig",
+    "vslam_fe_get_bow_rig_profile", "vslam_search_by_bow_keyframes_rig",
     "vslam_two_view_score_async", "vslam_two_view_score_wait", "vslam_two_view_score", "vslam_fe_get_two_view_profile",
     "vslam_kfdb_create", "vslam_kfdb_create_ex", "vslam_kfdb_destroy", "vslam_kfdb_add", "vslam_kfdb_erase",
     "vslam_kfdb_clear", "vslam_kfdb_clear_map", "vslam_kfdb_size", "vslam_kfdb_stats", "vslam_kfdb_query_async",
@@ -344,6 +346,43 @@ def rig_frame(dev_kps_left, dev_desc_left, n_left, dev_kps_right, dev_desc_right
     return f
 
 
+class _BowRigKf(C.Structure):  # vslam_bow_rig_kf
+    _fields_ = [("dev_desc_left", C.c_void_p), ("n_left", C.c_int), ("dev_desc_right", C.c_void_p), ("n_right", C.c_int),
+                ("kps_host", C.c_void_p), ("flags_host", C.c_void_p), ("fv_nodes", C.c_void_p), ("fv_off", C.c_void_p),
+                ("fv_feat", C.c_void_p), ("n_nodes", C.c_int)]
+
+
+def search_by_bow_rig_host(kf_kps, kf_desc, kf_n_left, kf_flags, kf_fv, f_kps, f_desc, n_left, f_fv, nnratio=0.7,
+                           check_ori=True, library=None):
+    """vslamh_search_by_bow_rig (libvslam_host.so, GPU-free): SearchByBoW(pKF, F) of a rig for one keyframe over host arrays.
+    kf_kps / kf_desc / kf_flags and f_kps / f_desc: left then right, kf_n_left / n_left of them left.
+    -> (nmatches, match_f[n_left + n_right])."""
+    L = library if library is not None else host_lib()
+    vp, i = C.c_void_p, C.c_int
+    L.vslamh_search_by_bow_rig.argtypes = [vp, vp, i, vp, i, vp, vp, vp, vp, i, vp, vp, i, vp, vp, i, vp, vp, vp, i,
+                                           C.c_float, i, vp, vp]
+    kk, fk = np.ascontiguousarray(kf_kps, KP_DTYPE), np.ascontiguousarray(f_kps, KP_DTYPE)
+    kd = np.ascontiguousarray(kf_desc, np.uint8).reshape(-1, 32)
+    fd = np.ascontiguousarray(f_desc, np.uint8).reshape(-1, 32)
+    kfl = np.ascontiguousarray(kf_flags, np.uint8)
+    a = [np.ascontiguousarray(kf_fv[k], np.int32) for k in ("fv_nodes", "fv_off", "fv_feat")]
+    b = [np.ascontiguousarray(f_fv[k], np.int32) for k in ("fv_nodes", "fv_off", "fv_feat")]
+    nk, n = len(kk), len(fk)
+    kl, nl = int(kf_n_left), int(n_left)
+    if len(kd) != nk or len(kfl) != nk or len(fd) != n or not (0 <= kl <= nk and 0 <= nl <= n):
+        raise ValueError("one descriptor (and keyframe flag) per keypoint, n_left within the count")
+    halves = [np.ascontiguousarray(x) for x in (kd[:kl], kd[kl:], fk[:nl], fd[:nl], fk[nl:], fd[nl:])]
+    kdl, kdr, fkl, fdl, fkr, fdr = [_p(x) if len(x) else None for x in halves]
+    m = np.full(max(n, 1), -1, np.int32)
+    nm = C.c_int(0)
+    rc = L.vslamh_search_by_bow_rig(_p(kk), kdl, kl, kdr, nk - kl, _p(kfl), _p(a[0]), _p(a[1]), _p(a[2]), len(a[0]), fkl, fdl,
+                                    nl, fkr, fdr, n - nl, _p(b[0]), _p(b[1]), _p(b[2]), len(b[0]), C.c_float(nnratio),
+                                    int(check_ori), _p(m), C.byref(nm))
+    if rc:
+        raise VslamError(rc, "vslamh_search_by_bow_rig: invalid arguments")
+    return nm.value, m[:n]
+
+
 class _Bounds(C.Structure):  # vslam_bounds
     _fields_ = [("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float)]
 
@@ -532,6 +571,12 @@ def lib():
         L.vslam_search_by_bow_keyframes.argtypes = [vp, vp, vp, vp, i, vp, vp, vp, i, vp, vp, vp, i, vp, vp, vp, i,
                                                     C.c_float, i, vp, vp]
         L.vslam_bow_assemble.argtypes = [i, i, vp, vp, vp, i, vp, vp, vp, vp, vp, vp, vp]
+        L.vslam_search_by_bow_rig_async.argtypes = [vp, vp, i, vp, vp, vp, vp, i, C.c_float, i]
+        L.vslam_search_by_bow_rig_wait.argtypes = [vp, vp, vp]
+        L.vslam_search_by_bow_rig.argtypes = [vp, vp, i, vp, vp, vp, vp, i, C.c_float, i, vp, vp]
+        L.vslam_fe_get_bow_rig_profile.argtypes = [vp, vp, vp, vp]
+        L.vslam_search_by_bow_keyframes_rig.argtypes = [vp, vp, vp, vp, i, i, vp, vp, vp, i, vp, vp, vp, i, i, vp, vp, vp, i,
+                                                        C.c_float, i, vp, vp]
         L.vslam_search_for_triangulation.argtypes = [vp, vp] + [vp, vp, vp, vp, i, vp, vp, vp, i] * 2 + [vp, vp]
         L.vslam_fuse_search.argtypes = [vp, vp, vp, vp, i, vp, vp, i, vp, vp, vp]
         L.vslam_dbg_logf.argtypes = [vp, vp, i, vp]
@@ -1639,6 +1684,83 @@ class FMatcher:
                                                    C.byref(nm)))
         return nm.value, m[:len(kps1)]
 
+    def _bow_rig_call(self, kf_jobs, frame, f_fv):
+        """the argument block of vslam_search_by_bow_rig[_async] and what keeps its host arrays alive"""
+        jobs = (_BowRigKf * max(len(kf_jobs), 1))()
+        keep = [frame]
+        for j, q in enumerate(kf_jobs):
+            nl, nr = int(q["n_left"]), int(q["n_right"])
+            kp = np.ascontiguousarray(q["kps"], KP_DTYPE)
+            fl = np.ascontiguousarray(q["flags"], np.uint8)
+            if not (len(kp) == len(fl) == nl + nr):
+                raise ValueError("a keyframe job holds n_left + n_right keypoints and flags")
+            a = [np.ascontiguousarray(q["fv"][k], np.int32) for k in ("fv_nodes", "fv_off", "fv_feat")]
+            jobs[j].dev_desc_left, jobs[j].n_left = q["dev_desc_left"] or None, nl
+            jobs[j].dev_desc_right, jobs[j].n_right = q.get("dev_desc_right") or None, nr
+            jobs[j].kps_host, jobs[j].flags_host = _p(kp).value if len(kp) else None, _p(fl).value if len(fl) else None
+            jobs[j].fv_nodes, jobs[j].fv_off, jobs[j].fv_feat = (_p(x).value if len(x) else None for x in a)
+            jobs[j].n_nodes = len(a[0])
+            keep += [kp, fl] + a
+        b = [np.ascontiguousarray(f_fv[k], np.int32) for k in ("fv_nodes", "fv_off", "fv_feat")]
+        keep += b
+        head = (self.fe._h, jobs, len(kf_jobs), C.byref(frame), _p(b[0]), _p(b[1]), _p(b[2]), len(b[0]),
+                C.c_float(self.mfNNratio), int(self.mbCheckOrientation))
+        return head, keep, frame.n_left + frame.n_right
+
+    @staticmethod
+    def _bow_rig_outputs(njobs, n):
+        m = np.full((max(njobs, 1), max(n, 1)), -1, np.int32)
+        ptrs = (C.c_void_p * max(njobs, 1))(*[m[j].ctypes.data for j in range(max(njobs, 1))])
+        return m, ptrs, (C.c_int * max(njobs, 1))()
+
+    def SearchByBoWRig_async(self, kf_jobs, frame, f_fv):
+        """Enqueue FMatcher::SearchByBoW(pKF, F, vpMapPointMatches) (fmatcher.cpp:546-748, F.Nleft != -1) of ONE rig frame
+        against 1 to 16 keyframes and return.  kf_jobs: dicts(kps (KP_DTYPE, left then right), dev_desc_left, n_left,
+        dev_desc_right, n_right, flags, fv); frame from rig_frame() (the maps may be None); f_fv: the frame's FeatureVector
+        over [0, n_left + n_right) (Vocabulary.transform_rig)."""
+        head, keep, n = self._bow_rig_call(kf_jobs, frame, f_fv)
+        _check(lib().vslam_search_by_bow_rig_async(*head))
+        self._sbr = (keep, len(kf_jobs), n)
+
+    def SearchByBoWRig_wait(self):
+        """-> [(nmatches, match_f[n_left + n_right] = KeyFrame feature index or -1)] per keyframe job"""
+        keep, k, n = getattr(self, "_sbr", None) or (None, 0, 0)
+        m, ptrs, nm = self._bow_rig_outputs(k, n)
+        rc = lib().vslam_search_by_bow_rig_wait(self.fe._h, ptrs, nm)
+        self._sbr = None
+        _check(rc)
+        return [(nm[j], m[j, :n]) for j in range(k)]
+
+    def SearchByBoWRig(self, kf_jobs, frame, f_fv):
+        """SearchByBoWRig_async + SearchByBoWRig_wait, through the blocking entry point"""
+        head, keep, n = self._bow_rig_call(kf_jobs, frame, f_fv)
+        m, ptrs, nm = self._bow_rig_outputs(len(kf_jobs), n)
+        m[:] = 0  # the entry point writes every entry, also where it refuses
+        self.last_bow_rig_outputs = (m, nm)  # what the call left in its outputs, for a caller that catches the refusal
+        _check(lib().vslam_search_by_bow_rig(*head, ptrs, nm))
+        return [(nm[j], m[j, :n]) for j in range(len(kf_jobs))]
+
+    def SearchByBoWKeyFramesRig(self, kps1, dev_desc1, flags1, n_left1, fv1, kps2, dev_desc2, flags2, n_left2, fv2):
+        """FMatcher::SearchByBoW(pKF1, pKF2, vpMatches12) (fmatcher.cpp:1100-1240) for rig KeyFrames: features >= n_left are
+        neither queries nor candidates (idx >= mvKeysUn.size() is skipped).  kps*: mvKeysUn, n_left entries (more are
+        ignored); flags*: n_left + n_right entries; dev_desc*: the left descriptor arrays.  -> (nmatches, match12[n1])."""
+        kps1 = np.ascontiguousarray(kps1, KP_DTYPE)[:n_left1]
+        kps2 = np.ascontiguousarray(kps2, KP_DTYPE)[:n_left2]
+        f1 = np.ascontiguousarray(flags1, np.uint8)
+        f2 = np.ascontiguousarray(flags2, np.uint8)
+        if len(kps1) != n_left1 or len(kps2) != n_left2:
+            raise ValueError("kps1 / kps2 hold n_left1 / n_left2 keypoints")
+        a = [np.ascontiguousarray(fv1[k], np.int32) for k in ("fv_nodes", "fv_off", "fv_feat")]
+        b = [np.ascontiguousarray(fv2[k], np.int32) for k in ("fv_nodes", "fv_off", "fv_feat")]
+        m = np.full(max(len(f1), 1), -1, np.int32)
+        nm = C.c_int(0)
+        _check(lib().vslam_search_by_bow_keyframes_rig(self.fe._h, _p(kps1), C.c_void_p(dev_desc1), _p(f1), len(f1),
+                                                       int(n_left1), _p(a[0]), _p(a[1]), _p(a[2]), len(a[0]), _p(kps2),
+                                                       C.c_void_p(dev_desc2), _p(f2), len(f2), int(n_left2), _p(b[0]),
+                                                       _p(b[1]), _p(b[2]), len(b[0]), C.c_float(self.mfNNratio),
+                                                       int(self.mbCheckOrientation), _p(m), C.byref(nm)))
+        return nm.value, m[:len(f1)]
+
     def SearchByProjectionKeyFrame(self, Tcw, Ow, cam, th, ORBdist, log_scale_factor, kf_kps, mp_flags, mp_x3dw,
                                    mp_min_dist, mp_max_dist, mp_desc, dev_cur_kps, dev_cur_desc, n_cur, occupied=None,
                                    img_size=None, gemm_float=False):
@@ -1835,6 +1957,15 @@ def bow_assemble(weighting, norm, word, weight, nid):
         raise VslamError(rc, "vslam_bow_assemble: invalid arguments")
     return dict(bow_ids=bi[:nb.value], bow_vals=bv[:nb.value], fv_nodes=fn[:nf.value], fv_off=fo[:nf.value + 1],
                 fv_feat=ff[:fo[nf.value]])
+
+
+def bow_assemble_rig(weighting, norm, left, right):
+    """Host half of Frame::ComputeBoW of a rig: (word, weight, nid) of the left and of the right features, concatenated left
+    first as the rig's descriptor rows are (frame.cpp:1137), through ONE bow_assemble over N = Nleft + Nright features."""
+    w, wt, nd = (np.concatenate([np.asarray(a), np.asarray(b)]) for a, b in zip(left, right))
+    out = bow_assemble(weighting, norm, w, wt, nd)
+    out.update(word=w, weight=wt, nid=nd, n_left=len(left[0]), n_right=len(right[0]))
+    return out
 
 
 VOC_FORMATS = {0: "trained", 1: "dbow3-binary", 2: "dbow3-binary-quicklz", 3: "dbow3-text"}
@@ -2040,6 +2171,18 @@ class Vocabulary:
         out = self.assemble(w[:n], wt[:n], nd[:n])
         out.update(word=w[:n], weight=wt[:n], nid=nd[:n])
         return out
+
+    def transform_rig(self, fe_left, slot_left, fe_right, slot_right, levelsup=4):
+        """Frame::ComputeBoW of a two-camera rig (frame.cpp:455-461 over the vconcat'ed descriptors, :1137): the per-feature
+        descent of both extractor slots on the device, (word, weight, node) concatenated left first, ONE assemble over
+        N = Nleft + Nright features -> as transform(), FeatureVector indices in [0, N), plus n_left / n_right."""
+        parts = []
+        for fe, slot in ((fe_left, slot_left), (fe_right, slot_right)):
+            _, d, n = fe.slot_buffers(slot)
+            w, wt, nd = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.float64), np.zeros(max(n, 1), np.int32)
+            _check(lib().vslam_bow_transform(fe._h, self._h, C.c_void_p(d), n, levelsup, _p(w), _p(wt), _p(nd)))
+            parts.append((w[:n], wt[:n], nd[:n]))
+        return bow_assemble_rig(self.weighting, self.norm, parts[0], parts[1])
 
     def transform_slots_async(self, fe, first_slot, nslots, levelsup=4):
         self._pending = (fe, nslots)

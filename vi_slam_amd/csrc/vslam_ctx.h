@@ -214,6 +214,16 @@ struct vslam_fe {
     bool fr_timed = false;
     double fr_ms[2] = {0, 0};
     long fr_passes = 0;
+    /* SearchByBoW(KeyFrame, Frame) of a rig against up to 16 keyframes (vslam_search_by_bow_rig_async, vslam_bow_rig.hip): a
+     * block of its own for the same reason */
+    vslam_staging sbr;          /* frame FeatureVector | per job: flags, angles, FeatureVector | match tables | bins | nmatches, overflow */
+    int sbr_state = 0;          /* 0: nothing enqueued, 1: a search is in flight, 2: an empty search (nothing launched) */
+    int sbr_jobs = 0, sbr_n_f = 0; /* keyframe jobs, n_left + n_right of the frame */
+    size_t sbr_o_m = 0, sbr_o_n = 0;
+    vslam_event ev_sbr[3];      /* profiling: before k_sbow_nodes_rig | between | behind k_sbow_finish_rig */
+    bool sbr_timed = false;
+    double sbr_ms[2] = {0, 0};
+    long sbr_passes = 0;
 
     /* GPU quadtree distribution */
     bool dev_octree = false;

@@ -1510,6 +1510,104 @@ int vslamh_search_by_projection_frame_rig(const vslam_proj_params* p, const vsla
     return VSLAM_OK;
 }
 
+/* FMatcher::SearchByBoW(KeyFrame* pKF, Frame& F, vpMapPointMatches) (fmatcher.cpp:546-748) with F.Nleft != -1 as it is
+ * written, sequential, for one keyframe: the statement vslam_search_by_bow_rig is tested against, and the shim's fallback
+ * beyond the device limits (there are none here).  Descriptor rows and FeatureVector indices of either side run over
+ * [0, n_left + n_right), left first; kf_kps is ONE array (mvKeys then mvKeysRight), the frame's keypoints come per camera.
+ * The right branch is nested in `bestDist1 <= TH_LOW` and its ratio test is `|| true`; one histogram takes both sides. */
+int vslamh_search_by_bow_rig(const vslam_kp* kf_kps, const uint8_t* kf_desc_left, int kf_n_left, const uint8_t* kf_desc_right,
+                             int kf_n_right, const uint8_t* kf_flags, const int32_t* kf_fv_nodes, const int32_t* kf_fv_off,
+                             const int32_t* kf_fv_feat, int n_kf_nodes, const vslam_kp* f_kps_left, const uint8_t* f_desc_left,
+                             int n_left, const vslam_kp* f_kps_right, const uint8_t* f_desc_right, int n_right,
+                             const int32_t* f_fv_nodes, const int32_t* f_fv_off, const int32_t* f_fv_feat, int n_f_nodes,
+                             float nnratio, int check_orientation, int32_t* match_f, int* nmatches) {
+    const int nKF = kf_n_left + kf_n_right, N = n_left + n_right;
+    if (kf_n_left < 0 || kf_n_right < 0 || n_left < 0 || n_right < 0 || n_kf_nodes < 0 || n_f_nodes < 0 || !nmatches ||
+        (nKF && (!kf_kps || !kf_flags)) || (kf_n_left && !kf_desc_left) || (kf_n_right && !kf_desc_right) ||
+        (n_left && (!f_kps_left || !f_desc_left)) || (n_right && (!f_kps_right || !f_desc_right)) || (N && !match_f) ||
+        (n_kf_nodes && (!kf_fv_nodes || !kf_fv_off || !kf_fv_feat)) || (n_f_nodes && (!f_fv_nodes || !f_fv_off || !f_fv_feat)))
+        return VSLAM_ERR_INVALID;
+    *nmatches = 0;
+    for (int i = 0; i < N; i++) match_f[i] = -1;
+    for (int side = 0; side < 2; side++) {
+        const int32_t *off = side ? f_fv_off : kf_fv_off, *feat = side ? f_fv_feat : kf_fv_feat;
+        const int nn = side ? n_f_nodes : n_kf_nodes, n = side ? N : nKF;
+        if (nn && off[0] != 0) return VSLAM_ERR_INVALID;
+        for (int j = 0; j < nn; j++) {
+            if (off[j + 1] < off[j]) return VSLAM_ERR_INVALID;
+            for (int a = off[j]; a < off[j + 1]; a++)
+                if (feat[a] < 0 || feat[a] >= n) return VSLAM_ERR_INVALID;
+        }
+    }
+    const int TH_LOW = 50, L = VSLAM_HISTO_LENGTH;
+    std::vector<int> rotHist[VSLAM_HISTO_LENGTH];
+    int nm = 0;
+    int KFit = 0, Fit = 0;
+    while (KFit != n_kf_nodes && Fit != n_f_nodes) {
+        if (kf_fv_nodes[KFit] == f_fv_nodes[Fit]) {
+            for (int a = kf_fv_off[KFit]; a < kf_fv_off[KFit + 1]; a++) {
+                const int realIdxKF = kf_fv_feat[a];
+                if (!kf_flags[realIdxKF]) continue; /* !pMP || pMP->isBad() */
+                const uint8_t* dKF = realIdxKF < kf_n_left ? kf_desc_left + (size_t)realIdxKF * 32
+                                                           : kf_desc_right + (size_t)(realIdxKF - kf_n_left) * 32;
+                int bestDist1 = 256, bestIdxF = -1, bestDist2 = 256;
+                int bestDist1R = 256, bestIdxFR = -1;
+                for (int b = f_fv_off[Fit]; b < f_fv_off[Fit + 1]; b++) {
+                    const int realIdxF = f_fv_feat[b];
+                    if (match_f[realIdxF] >= 0) continue;
+                    const uint8_t* dF = realIdxF < n_left ? f_desc_left + (size_t)realIdxF * 32
+                                                          : f_desc_right + (size_t)(realIdxF - n_left) * 32;
+                    const int dist = rig_hamming(dKF, dF);
+                    if (realIdxF < n_left && dist < bestDist1) {
+                        bestDist2 = bestDist1;
+                        bestDist1 = dist;
+                        bestIdxF = realIdxF;
+                    } else if (realIdxF < n_left && dist < bestDist2) {
+                        bestDist2 = dist;
+                    }
+                    if (realIdxF >= n_left && dist < bestDist1R) {
+                        bestDist1R = dist;
+                        bestIdxFR = realIdxF;
+                    }
+                }
+                if (bestDist1 <= TH_LOW) {
+                    const float angKF = kf_kps[realIdxKF].angle;
+                    if ((float)bestDist1 < nnratio * (float)bestDist2) {
+                        match_f[bestIdxF] = realIdxKF;
+                        if (check_orientation) rotHist[vslam_md::rot_bin(angKF, f_kps_left[bestIdxF].angle, L)].push_back(bestIdxF);
+                        nm++;
+                    }
+                    if (bestDist1R <= TH_LOW) { /* `|| true`, :682 */
+                        match_f[bestIdxFR] = realIdxKF;
+                        if (check_orientation)
+                            rotHist[vslam_md::rot_bin(angKF, f_kps_right[bestIdxFR - n_left].angle, L)].push_back(bestIdxFR);
+                        nm++;
+                    }
+                }
+            }
+            KFit++;
+            Fit++;
+        } else if (kf_fv_nodes[KFit] < f_fv_nodes[Fit]) {
+            KFit = (int)(std::lower_bound(kf_fv_nodes, kf_fv_nodes + n_kf_nodes, f_fv_nodes[Fit]) - kf_fv_nodes);
+        } else {
+            Fit = (int)(std::lower_bound(f_fv_nodes, f_fv_nodes + n_f_nodes, kf_fv_nodes[KFit]) - f_fv_nodes);
+        }
+    }
+    if (check_orientation) {
+        int histo[VSLAM_HISTO_LENGTH];
+        for (int b = 0; b < L; b++) histo[b] = (int)rotHist[b].size();
+        const vslam_md::ThreeMaxima mx = vslam_md::three_maxima(histo, L);
+        for (int b = 0; b < L; b++)
+            if (!vslam_md::keeps_bin(mx, b))
+                for (int s : rotHist[b]) {
+                    match_f[s] = -1;
+                    nm--;
+                }
+    }
+    *nmatches = nm;
+    return VSLAM_OK;
+}
+
 /* vslam_two_view_score on the host, every pointer of the job a HOST pointer (the placement fields are not read): the pair
  * list, CheckHomography / CheckFundamental for every hypothesis by the shared vslam_two_view.h code, the selection.  Same
  * limits, error codes and results as the device entry (include/vslam_fe.h).  CPU tests and the stand-alone demo; the

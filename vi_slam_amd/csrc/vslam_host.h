@@ -241,4 +241,13 @@ extern "C" int vslamh_search_by_projection_frame_rig(const vslam_proj_params* p,
                                                      const uint8_t* desc_right, int n_right, const uint8_t* occupied,
                                                      const float* scale_factors, int nlevels, const float* bounds,
                                                      int32_t* match_cur, int* nmatches);
+/* vslam_host.cpp: SearchByBoW(KeyFrame, Frame) of a rig (fmatcher.cpp:546-748, F.Nleft != -1) over host arrays for one keyframe,
+ * sequential as the reference writes it (CPU tests, the shim's fallback beyond the device limits) */
+extern "C" int vslamh_search_by_bow_rig(const vslam_kp* kf_kps, const uint8_t* kf_desc_left, int kf_n_left,
+                                        const uint8_t* kf_desc_right, int kf_n_right, const uint8_t* kf_flags,
+                                        const int32_t* kf_fv_nodes, const int32_t* kf_fv_off, const int32_t* kf_fv_feat,
+                                        int n_kf_nodes, const vslam_kp* f_kps_left, const uint8_t* f_desc_left, int n_left,
+                                        const vslam_kp* f_kps_right, const uint8_t* f_desc_right, int n_right,
+                                        const int32_t* f_fv_nodes, const int32_t* f_fv_off, const int32_t* f_fv_feat,
+                                        int n_f_nodes, float nnratio, int check_orientation, int32_t* match_f, int* nmatches);
 #endif
