@@ -478,7 +478,7 @@ int vslam_two_view_score_async(vslam_fe* fe, int njobs, const vslam_two_view_job
 int vslam_two_view_score_wait(vslam_fe* fe, vslam_two_view_result* results);
 int vslam_two_view_score(vslam_fe* fe, const vslam_two_view_job* job, vslam_two_view_result* result);
 /* With vslam_fe_set_profiling on: HIP-event time of k_tv_pairs, k_tv_score and k_tv_select alone, summed over the calls
- * waited for since.  Any pointer may be NULL. */
+ * waited for since vslam_fe_set_profiling was last called: it starts these sums anew.  Any pointer may be NULL. */
 int vslam_fe_get_two_view_profile(vslam_fe* fe, double* pairs_ms, double* score_ms, double* select_ms, long* passes);
 
 /* ---------------------------------------------------------------- distorted pinhole cameras (Frame::ukeypoints_)
@@ -1196,7 +1196,7 @@ int vslam_search_by_bow_rig(vslam_fe* fe, const vslam_bow_rig_kf* kf_jobs, int n
                             const int32_t* f_fv_nodes, const int32_t* f_fv_off, const int32_t* f_fv_feat, int n_f_nodes,
                             float nnratio, int check_orientation, int32_t* const* match_f, int* nmatches);
 /* With vslam_fe_set_profiling on: HIP-event time of k_sbow_nodes_rig and of k_sbow_finish_rig, summed over the rig BoW searches
- * waited for since.  Any pointer may be NULL. */
+ * waited for since vslam_fe_set_profiling was last called: it starts these sums anew.  Any pointer may be NULL. */
 int vslam_fe_get_bow_rig_profile(vslam_fe* fe, double* nodes_ms, double* finish_ms, long* passes);
 
 /* The KeyFrame-KeyFrame overload (fmatcher.cpp:1100-1240) for rig KeyFrames.  The reference skips idx >= mvKeysUn.size() on

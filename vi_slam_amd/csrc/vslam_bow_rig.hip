@@ -22,7 +22,7 @@
  * third wave reduction for the right key; k_sbow_finish_rig is k_sbow_finish with one workgroup per job.  A frame feature
  * belongs to one node and a match table to one job, so no workgroup waits for another.
  */
-#include "vslam_ctx.h"
+#include "vslam_sbp_host.h" /* vslam_ctx.h; rig_frame_ptrs_ok */
 #include "vslam_kernels.h"
 #include "vslam_wave.h"
 #include "vslam_matchdev.h"
@@ -195,10 +195,8 @@ static bool sbowr_fv_ok(const int32_t* off, const int32_t* feat, int nnodes, int
 extern "C" int vslam_search_by_bow_rig_async(vslam_fe* fe, const vslam_bow_rig_kf* kf_jobs, int n_kf_jobs,
                                              const vslam_rig_frame* frame, const int32_t* f_fv_nodes, const int32_t* f_fv_off,
                                              const int32_t* f_fv_feat, int n_f_nodes, float nnratio, int check_orientation) {
-    if (!fe || !kf_jobs || n_kf_jobs < 1 || n_kf_jobs > SBOWR_MAX_JOBS || !frame || frame->n_left < 0 || frame->n_right < 0 ||
-        n_f_nodes < 0 || (n_f_nodes && (!f_fv_nodes || !f_fv_off || !f_fv_feat)) ||
-        (frame->n_left && (!frame->dev_kps_left || !frame->dev_desc_left)) ||
-        (frame->n_right && (!frame->dev_kps_right || !frame->dev_desc_right))) {
+    if (!fe || !kf_jobs || n_kf_jobs < 1 || n_kf_jobs > SBOWR_MAX_JOBS || !rig_frame_ptrs_ok(frame) || n_f_nodes < 0 ||
+        (n_f_nodes && (!f_fv_nodes || !f_fv_off || !f_fv_feat))) {
         g_err = "invalid arguments";
         return VSLAM_ERR_INVALID;
     }
@@ -211,10 +209,7 @@ extern "C" int vslam_search_by_bow_rig_async(vslam_fe* fe, const vslam_bow_rig_k
             return VSLAM_ERR_INVALID;
         }
     }
-    if (fe->sbr_state == 1) {
-        g_err = "a rig SearchByBoW is already in flight (vslam_search_by_bow_rig_wait)";
-        return VSLAM_ERR_INVALID;
-    }
+    if (int rc = fe->sbr_op.begin("a rig SearchByBoW is already in flight (vslam_search_by_bow_rig_wait)")) return rc;
     const int N = frame->n_left + frame->n_right;
     bool big = frame->n_left > SBOWR_MAX_SIDE || frame->n_right > SBOWR_MAX_SIDE;
     for (int j = 0; j < n_kf_jobs; j++) big = big || kf_jobs[j].n_left > SBOWR_MAX_SIDE || kf_jobs[j].n_right > SBOWR_MAX_SIDE;
@@ -248,10 +243,10 @@ extern "C" int vslam_search_by_bow_rig_async(vslam_fe* fe, const vslam_bow_rig_k
                 return VSLAM_ERR_UNSUPPORTED;
             }
     }
-    fe->sbr_jobs = n_kf_jobs;
-    fe->sbr_n_f = N;
+    fe->sbr_op.jobs = n_kf_jobs;
+    fe->sbr_op.n = N;
     if (max_nodes == 0) {
-        fe->sbr_state = 2;
+        fe->sbr_op.set(true);
         return VSLAM_OK;
     }
     HIPCHK(hipSetDevice(fe->p.device));
@@ -279,9 +274,7 @@ extern "C" int vslam_search_by_bow_rig_async(vslam_fe* fe, const vslam_bow_rig_k
     const size_t total = vslam::layout_parts(16, sizes, np, off);
     int rc = fe->sbr.ensure(total);
     if (rc) return rc;
-    const bool prof = fe->profiling;
-    for (int i = 0; i < 3 && prof; i++)
-        if (int rc = fe->ev_sbr[i].ensure()) return rc;
+    if ((rc = fe->t_sbr.arm(fe->profiling))) return rc;
     uint8_t *h = fe->sbr.h, *d = fe->sbr.d;
     memcpy(h + off[0], f_fv_nodes, sizes[0]);
     memcpy(h + off[1], f_fv_off, sizes[1]);
@@ -329,27 +322,27 @@ extern "C" int vslam_search_by_bow_rig_async(vslam_fe* fe, const vslam_bow_rig_k
     const int n_match = n_kf_jobs * N;
     hipLaunchKernelGGL(k_sbow_rig_clear, dim3((std::max(n_match, SBOWR_MAX_JOBS + 4) + 255) / 256), dim3(256), 0, st, A.matchF,
                        n_match, A.nmatches, SBOWR_MAX_JOBS + 4);
-    if (prof) (void)hipEventRecord(fe->ev_sbr[0], st);
+    fe->t_sbr.mark(0, st);
     hipLaunchKernelGGL(k_sbow_nodes_rig, dim3(max_nodes, n_kf_jobs), dim3(64), 0, st, A);
-    if (prof) (void)hipEventRecord(fe->ev_sbr[1], st);
+    fe->t_sbr.mark(1, st);
     hipLaunchKernelGGL(k_sbow_finish_rig, dim3(n_kf_jobs), dim3(256), 0, st, A);
-    if (prof) (void)hipEventRecord(fe->ev_sbr[2], st);
-    fe->sbr_timed = prof;
+    fe->t_sbr.mark(2, st);
     HIPCHK(hipGetLastError());
     fe->sbr.down(st, off[p_m], off[p_m + 2] - off[p_m]); /* the match tables and the counts; the bins stay */
     HIPCHK(hipGetLastError());
-    fe->sbr_state = 1;
+    fe->sbr_op.set(false);
     fe->sbr_o_m = off[p_m];
     fe->sbr_o_n = off[p_m + 1];
     return VSLAM_OK;
 }
 
 extern "C" int vslam_search_by_bow_rig_wait(vslam_fe* fe, int32_t* const* match_f, int* nmatches) {
-    if (!fe || fe->sbr_state == 0) {
+    if (!fe) {
         g_err = "nothing enqueued";
         return VSLAM_ERR_INVALID;
     }
-    const int K = fe->sbr_jobs, N = fe->sbr_n_f;
+    if (int rc = fe->sbr_op.ready()) return rc;
+    const int K = fe->sbr_op.jobs, N = fe->sbr_op.n;
     bool ok = nmatches && (N == 0 || match_f);
     for (int j = 0; ok && j < K && N; j++) ok = match_f[j] != nullptr;
     if (!ok) {
@@ -357,24 +350,14 @@ extern "C" int vslam_search_by_bow_rig_wait(vslam_fe* fe, int32_t* const* match_
         return VSLAM_ERR_INVALID;
     }
     for (int j = 0; j < K; j++) nmatches[j] = 0;
-    if (fe->sbr_state == 2) { /* nothing to match: nothing was launched */
-        fe->sbr_state = 0;
+    if (fe->sbr_op.take()) { /* nothing to match: nothing was launched */
         for (int j = 0; j < K; j++)
             for (int i = 0; i < N; i++) match_f[j][i] = -1;
         return VSLAM_OK;
     }
     HIPCHK(hipSetDevice(fe->p.device));
-    fe->sbr_state = 0;
     HIPCHK(vslam_stream_wait(fe->stream));
-    if (fe->sbr_timed) {
-        float a = 0.0f, b = 0.0f;
-        fe->sbr_timed = false;
-        HIPCHK(hipEventElapsedTime(&a, fe->ev_sbr[0], fe->ev_sbr[1]));
-        HIPCHK(hipEventElapsedTime(&b, fe->ev_sbr[1], fe->ev_sbr[2]));
-        fe->sbr_ms[0] += a;
-        fe->sbr_ms[1] += b;
-        fe->sbr_passes++;
-    }
+    if (int rc = fe->t_sbr.collect()) return rc;
     const int32_t* cnt = (const int32_t*)(fe->sbr.h + fe->sbr_o_n);
     if (cnt[SBOWR_MAX_JOBS]) { /* the host test in _async keeps this from happening; the kernel's guard stays the last word */
         for (int j = 0; j < K; j++)
@@ -415,9 +398,7 @@ extern "C" int vslam_search_by_bow_rig(vslam_fe* fe, const vslam_bow_rig_kf* kf_
 
 extern "C" int vslam_fe_get_bow_rig_profile(vslam_fe* fe, double* nodes_ms, double* finish_ms, long* passes) {
     if (!fe) return VSLAM_ERR_INVALID;
-    if (nodes_ms) *nodes_ms = fe->sbr_ms[0];
-    if (finish_ms) *finish_ms = fe->sbr_ms[1];
-    if (passes) *passes = fe->sbr_passes;
+    fe->t_sbr.read({nodes_ms, finish_ms}, passes);
     return VSLAM_OK;
 }
 

@@ -530,14 +530,7 @@ extern "C" int vslam_fe_set_profiling(vslam_fe* fe, int on) {
     fe->profiling = on != 0;
     for (int i = 0; i < 5; i++) fe->prof_ms[i] = 0;
     fe->prof_batches = fe->prof_images = 0;
-    fe->rgbd_ms = 0;
-    fe->rgbd_passes = 0;
-    fe->lp_ms[0] = fe->lp_ms[1] = 0;
-    fe->lp_passes = 0;
-    fe->rig_ms[0] = fe->rig_ms[1] = 0;
-    fe->rig_passes = 0;
-    fe->fr_ms[0] = fe->fr_ms[1] = 0;
-    fe->fr_passes = 0;
+    fe->reset_span_timers();
     return VSLAM_OK;
 }
 

@@ -1,8 +1,9 @@
 /* vslam_ctx.h -- private: the vslam_fe context (HBM layout, scratch, worker pool) shared by
  * vslam_context.hip (its life and accessors), vslam_upload.hip (host images into level 0), vslam_fe.hip (the extraction
  * pipeline) and by the matcher ABI: vslam_stereo.hip (stereo, RGB-D), vslam_match.hip (SearchForInitialization),
- * vslam_projection.hip (SearchByProjection family, Fuse, SearchLocalPoints), vslam_two_view.hip (CheckHomography /
- * CheckFundamental), vslam_bow.hip and vslam_kfdb.hip. */
+ * vslam_projection.hip (SearchByProjection family, Fuse), vslam_local_points.hip (isInFrustum, SearchLocalPoints),
+ * vslam_projection_rig.hip (the rig forms), vslam_two_view.hip (CheckHomography / CheckFundamental), vslam_bow.hip,
+ * vslam_bow_rig.hip and vslam_kfdb.hip. */
 #ifndef VSLAM_CTX_H
 #define VSLAM_CTX_H
 #include <hip/hip_runtime.h>
@@ -26,9 +27,11 @@
 #include "vslam_tuning.h"
 #include "vslam_mem.h" /* g_err, HIPCHK, the owning buffers and events */
 #include "vslam_staging.h"
+#include "vslam_async.h" /* vslam_pending, vslam_span_timer */
 
 /* ------------------------------------------------------------------ context */
 enum { VSLAM_REGION_NONE = 0, VSLAM_REGION_INIT = 1, VSLAM_REGION_STEREO = 2 };
+enum { LP_SINGLE = 0, LP_RIG = 1 }; /* vslam_fe::lp_op.kind */
 /* Every vslam_dbuf / vslam_hbuf / vslam_event member is owned and goes with the context (vslam_mem.h); a raw d_* / h_*
  * pointer is a view into one of them and is commented as such. */
 struct vslam_fe {
@@ -147,9 +150,9 @@ struct vslam_fe {
     vslam_staging bow;          /* ComputeBoW: per-feature weight | word | node for nslots x cap features */
     int bow_jobs = 0;
     vslam_staging kfdb;         /* KeyFrameDatabase query: uploaded BowVectors | dense per-slot results (vslam_kfdb.hip) */
-    vslam_staging lp;           /* SearchLocalPoints: inputs | frustum records | compacted arrays | matcher scratch | results (vslam_projection.hip) */
-    int lp_state = 0;           /* 0: nothing enqueued, 1: a search is in flight, 2: an empty search (nothing launched); 3, 4: the same two of a rig search (vslam_search_local_points_rig_async), whose lp_n_cur counts the slots of both sides */
-    int lp_n_mp = 0, lp_n_cur = 0, lp_cap = 0;
+    vslam_staging lp;           /* SearchLocalPoints: inputs | frustum records | compacted arrays | matcher scratch | results (vslam_local_points.hip) */
+    vslam_pending lp_op;        /* kind LP_SINGLE or LP_RIG (vslam_search_local_points_rig_async); n: the keypoints, of a rig both sides' */
+    int lp_n_mp = 0, lp_cap = 0;
     size_t lp_o_track = 0, lp_o_res = 0, lp_o_cnt = 0, lp_o_idx = 0; /* where the records and the result block (matches | counts | indices) start */
     size_t lp_o_track_r = 0;    /* a rig search: the right camera's records */
     bool use_graph = true;          /* host-image passes replay a captured HIP graph (VSLAM_GRAPH=0 disables) */
@@ -179,51 +182,31 @@ struct vslam_fe {
     int pix_fmt = VSLAM_PIX_GRAY8, gray_shift = 15;
     vslam_hbuf<uint8_t> h_depth; /* staging of pageable depth images (vslam_frame_rgbd_batch_async, VSLAM_IMGS_HOST) */
     bool last_rgbd = false;     /* the last pass enqueued was an RGB-D pass: vslam_frame_rgbd_wait may deliver it */
-    vslam_event ev_rgbd[2];     /* profiling: around k_rgbd_depth */
-    bool rgbd_timed = false;
-    double rgbd_ms = 0;
-    long rgbd_passes = 0;
+    vslam_span_timer<1> t_rgbd; /* around k_rgbd_depth */
     /* two-view scoring (vslam_two_view.hip): job table | hypotheses | host inputs | results of every job; the gathered pairs
      * and the flag bytes of every hypothesis stay in HBM */
     vslam_staging tv;
     vslam_dbuf<uint8_t> d_tv_scratch;
-    int tv_state = 0, tv_njobs = 0; /* 1: a scoring is in flight */
+    vslam_pending tv_op;            /* jobs: the jobs of the scoring in flight */
     struct TvJobHost {              /* where a job's results start in the block, and the counts _wait copies by */
         size_t o_hdr, o_pairs, o_sh, o_sf, o_ih, o_if;
         int cap, nH, nF;
     } tv_jobs[VSLAM_TWO_VIEW_MAX_JOBS] = {};
-    vslam_event ev_tv[4];       /* profiling: before k_tv_pairs | k_tv_score | k_tv_select | behind it */
-    bool tv_timed = false;
-    double tv_ms[3] = {0, 0, 0};
-    long tv_passes = 0;
-    vslam_event ev_lp[3];       /* profiling: before k_frustum | between | behind k_frustum_compact */
-    bool lp_timed = false;
-    double lp_ms[2] = {0, 0};
-    long lp_passes = 0;
-    vslam_event ev_rig[3];      /* profiling of a rig search: before k_sbp_rank | between | behind k_rig_resolve */
-    bool rig_timed = false;
-    double rig_ms[2] = {0, 0};
-    long rig_passes = 0;
+    vslam_span_timer<3> t_tv;   /* before k_tv_pairs | k_tv_score | k_tv_select | behind it */
+    vslam_span_timer<2> t_lp;   /* before k_frustum | between | behind k_frustum_compact */
+    vslam_span_timer<2> t_rig;  /* a rig search: before k_sbp_rank | between | behind k_rig_resolve */
     /* SearchByProjection(CurrentFrame, LastFrame) of a rig (vslam_search_by_projection_frame_rig_async): a block of its own, so
      * that the blocking matchers, which fill `proj` on the host at once, can run while a search is in flight */
     vslam_staging fr;           /* inputs | scratch of both sides | match table | nmatches, needSeq */
-    int fr_state = 0;           /* 0: nothing enqueued, 1: a search is in flight, 2: an empty search (nothing launched) */
-    int fr_n_cur = 0;           /* n_left + n_right */
+    vslam_pending fr_op;        /* n: n_left + n_right */
     size_t fr_o_m = 0, fr_o_n = 0;
-    vslam_event ev_fr[3];       /* profiling: before k_sbp_rank_rig | between | behind k_sbp_rig_replay */
-    bool fr_timed = false;
-    double fr_ms[2] = {0, 0};
-    long fr_passes = 0;
+    vslam_span_timer<2> t_fr;   /* before k_sbp_rank_rig | between | behind k_sbp_rig_replay */
     /* SearchByBoW(KeyFrame, Frame) of a rig against up to 16 keyframes (vslam_search_by_bow_rig_async, vslam_bow_rig.hip): a
      * block of its own for the same reason */
     vslam_staging sbr;          /* frame FeatureVector | per job: flags, angles, FeatureVector | match tables | bins | nmatches, overflow */
-    int sbr_state = 0;          /* 0: nothing enqueued, 1: a search is in flight, 2: an empty search (nothing launched) */
-    int sbr_jobs = 0, sbr_n_f = 0; /* keyframe jobs, n_left + n_right of the frame */
+    vslam_pending sbr_op;       /* jobs: keyframe jobs, n: n_left + n_right of the frame */
     size_t sbr_o_m = 0, sbr_o_n = 0;
-    vslam_event ev_sbr[3];      /* profiling: before k_sbow_nodes_rig | between | behind k_sbow_finish_rig */
-    bool sbr_timed = false;
-    double sbr_ms[2] = {0, 0};
-    long sbr_passes = 0;
+    vslam_span_timer<2> t_sbr;  /* before k_sbow_nodes_rig | between | behind k_sbow_finish_rig */
 
     /* GPU quadtree distribution */
     bool dev_octree = false;
@@ -246,6 +229,15 @@ struct vslam_fe {
     vslam_event ev_prof[10];
     double prof_ms[5] = {0, 0, 0, 0, 0};
     long prof_batches = 0, prof_images = 0;
+    /* every span timer of the enqueue / wait operations above, once: vslam_fe_set_profiling starts their sums anew */
+    void reset_span_timers() {
+        t_rgbd.reset();
+        t_tv.reset();
+        t_lp.reset();
+        t_rig.reset();
+        t_fr.reset();
+        t_sbr.reset();
+    }
 
     WorkerPool* pool = nullptr;
 

@@ -242,8 +242,7 @@ extern "C" int vslam_frame_rgbd_batch_async(vslam_fe* fe, int nframes, const uin
     if (rc) return rc;
     fe->stereo_capR = fe->cap;
     rc = vslam_enqueue_extract(fe, nframes, imgs, pitch, imgs_where, 0, 0, blk ? 2 : (want_host != 0));
-    const bool prof = rc == VSLAM_OK && fe->profiling;
-    for (int i = 0; i < 2 && prof && rc == VSLAM_OK; i++) rc = fe->ev_rgbd[i].ensure();
+    if (rc == VSLAM_OK) rc = fe->t_rgbd.arm(fe->profiling);
     if (rc == VSLAM_OK) {
         if (blk) {
             sc.uRight = (float*)(fe->d_res + fe->res_feat_bytes);
@@ -253,10 +252,9 @@ extern "C" int vslam_frame_rgbd_batch_async(vslam_fe* fe, int nframes, const uin
         fe->d_stereo_depth = sc.depth;
         const vslam_kp* ukps = fe->d_kps; /* ukeypoints_ = keypoints_ without a camera or with k1 == 0 */
         if (fe->has_cam && vslam_fe_slot_ukps(fe, 0, &ukps) != VSLAM_OK) ukps = fe->d_kps;
-        if (prof) (void)hipEventRecord(fe->ev_rgbd[0], fe->stream);
+        fe->t_rgbd.mark(0, fe->stream);
         vk_rgbd_depth(fe->stream, fe->d_kps, ukps, fe->d_counts, fe->cap, nframes, D, sc.uRight, sc.depth);
-        if (prof) (void)hipEventRecord(fe->ev_rgbd[1], fe->stream);
-        fe->rgbd_timed = prof;
+        fe->t_rgbd.mark(1, fe->stream);
         if (hipGetLastError() != hipSuccess) {
             g_err = "k_rgbd_depth launch failed";
             rc = VSLAM_ERR_HIP;
@@ -278,13 +276,7 @@ extern "C" int vslam_frame_rgbd_wait(vslam_fe* fe, vslam_kp* const* kps, uint8_t
     }
     int rc = vslam_finish_extract(fe, fe->last_nimg);
     if (rc != VSLAM_OK) return rc;
-    if (fe->rgbd_timed) { /* vslam_fe_set_profiling: the depth gather's own span */
-        float ms = 0.0f;
-        HIPCHK(hipEventElapsedTime(&ms, fe->ev_rgbd[0], fe->ev_rgbd[1]));
-        fe->rgbd_ms += ms;
-        fe->rgbd_passes++;
-        fe->rgbd_timed = false;
-    }
+    if ((rc = fe->t_rgbd.collect())) return rc; /* vslam_fe_set_profiling: the depth gather's own span */
     rc = vslam_deliver(fe, fe->last_nimg, kps, desc, cap, n, nullptr);
     if (rc != VSLAM_OK) return rc;
     deliver_stereo(fe, u_right, depth);
@@ -294,8 +286,7 @@ extern "C" int vslam_frame_rgbd_wait(vslam_fe* fe, vslam_kp* const* kps, uint8_t
 /* with vslam_fe_set_profiling on: HIP-event time of k_rgbd_depth alone, summed over the RGB-D passes waited for since */
 extern "C" int vslam_fe_get_rgbd_profile(vslam_fe* fe, double* depth_ms, long* passes) {
     if (!fe) return VSLAM_ERR_INVALID;
-    if (depth_ms) *depth_ms = fe->rgbd_ms;
-    if (passes) *passes = fe->rgbd_passes;
+    fe->t_rgbd.read({depth_ms}, passes);
     return VSLAM_OK;
 }
 

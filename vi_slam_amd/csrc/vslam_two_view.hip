@@ -218,10 +218,7 @@ extern "C" int vslam_two_view_score_async(vslam_fe* fe, int njobs, const vslam_t
                     ": n1 <= 65536, nH / nF <= 1024, sigma finite and not zero, placements 0 or 1, device arrays 4-byte aligned";
             return VSLAM_ERR_INVALID;
         }
-    if (fe->tv_state == 1) {
-        g_err = "a two-view scoring is already in flight (vslam_two_view_score_wait)";
-        return VSLAM_ERR_INVALID;
-    }
+    if (int rc = fe->tv_op.begin("a two-view scoring is already in flight (vslam_two_view_score_wait)")) return rc;
     HIPCHK(hipSetDevice(fe->p.device));
     /* the staging block: job table | per job: H21 H12 F21, packed host keypoints, host matches  (one range up)
      *                    | per job: header, pairs, scores H / F, masks H / F                    (one range down)
@@ -260,9 +257,8 @@ extern "C" int vslam_two_view_score_async(vslam_fe* fe, int njobs, const vslam_t
     int rc = fe->tv.ensure(total);
     if (rc) return rc;
     if ((rc = fe->d_tv_scratch.ensure(std::max(stotal, (size_t)256)))) return rc;
-    const bool prof = fe->profiling; /* vslam_fe_set_profiling: the three kernels' own spans (vslam_fe_get_two_view_profile) */
-    for (int i = 0; i < 4 && prof; i++)
-        if ((rc = fe->ev_tv[i].ensure())) return rc;
+    /* vslam_fe_set_profiling: the three kernels' own spans (vslam_fe_get_two_view_profile) */
+    if ((rc = fe->t_tv.arm(fe->profiling))) return rc;
     uint8_t *h = fe->tv.h, *d = fe->tv.d, *s = fe->d_tv_scratch;
     TvJobDev* table = (TvJobDev*)(h + off[0]);
     for (int j = 0; j < njobs; j++) {
@@ -324,42 +320,33 @@ extern "C" int vslam_two_view_score_async(vslam_fe* fe, int njobs, const vslam_t
     hipStream_t st = fe->stream;
     const size_t o_res = off[first_res];
     fe->tv.up(st, 0, o_res);
-    hipEvent_t ev[4];
-    for (int i = 0; i < 4 && prof; i++) ev[i] = fe->ev_tv[i];
-    vk_two_view(st, (const TvJobDev*)(d + off[0]), njobs, max_groups, prof ? ev : nullptr);
+    hipEvent_t ev[4] = {fe->t_tv.event(0), fe->t_tv.event(1), fe->t_tv.event(2), fe->t_tv.event(3)};
+    vk_two_view(st, (const TvJobDev*)(d + off[0]), njobs, max_groups, fe->t_tv.armed ? ev : nullptr);
     HIPCHK(hipGetLastError());
     fe->tv.down(st, o_res, total - o_res);
     HIPCHK(hipGetLastError());
-    fe->tv_timed = prof;
-    fe->tv_state = 1;
-    fe->tv_njobs = njobs;
+    fe->tv_op.set(false);
+    fe->tv_op.jobs = njobs;
     return VSLAM_OK;
 }
 
 extern "C" int vslam_two_view_score_wait(vslam_fe* fe, vslam_two_view_result* results) {
-    if (!fe || fe->tv_state == 0) {
+    if (!fe) {
         g_err = "nothing enqueued";
         return VSLAM_ERR_INVALID;
     }
+    if (int rc = fe->tv_op.ready()) return rc;
     if (!results) {
         g_err = "invalid arguments";
         return VSLAM_ERR_INVALID;
     }
+    fe->tv_op.take();
     HIPCHK(hipSetDevice(fe->p.device));
-    fe->tv_state = 0;
     HIPCHK(vslam_stream_wait(fe->stream));
-    if (fe->tv_timed) {
-        fe->tv_timed = false;
-        for (int i = 0; i < 3; i++) {
-            float ms = 0.0f;
-            HIPCHK(hipEventElapsedTime(&ms, fe->ev_tv[i], fe->ev_tv[i + 1]));
-            fe->tv_ms[i] += ms;
-        }
-        fe->tv_passes++;
-    }
+    int rc = fe->t_tv.collect();
+    if (rc) return rc;
     const uint8_t* h = fe->tv.h;
-    int rc = VSLAM_OK;
-    for (int j = 0; j < fe->tv_njobs; j++) {
+    for (int j = 0; j < fe->tv_op.jobs; j++) {
         const vslam_fe::TvJobHost& K = fe->tv_jobs[j];
         const int32_t* hdr = (const int32_t*)(h + K.o_hdr);
         vslam_two_view_result& R = results[j];
@@ -398,9 +385,6 @@ extern "C" int vslam_two_view_score(vslam_fe* fe, const vslam_two_view_job* job,
 
 extern "C" int vslam_fe_get_two_view_profile(vslam_fe* fe, double* pairs_ms, double* score_ms, double* select_ms, long* passes) {
     if (!fe) return VSLAM_ERR_INVALID;
-    if (pairs_ms) *pairs_ms = fe->tv_ms[0];
-    if (score_ms) *score_ms = fe->tv_ms[1];
-    if (select_ms) *select_ms = fe->tv_ms[2];
-    if (passes) *passes = fe->tv_passes;
+    fe->t_tv.read({pairs_ms, score_ms, select_ms}, passes);
     return VSLAM_OK;
 }
