@@ -750,7 +750,8 @@ int vslam_fe_get_local_points_profile(vslam_fe* fe, double* frustum_ms, double* 
  * The rig form of SearchByProjection(F, vpMapPoints), right-camera branch included (fmatcher.cpp:321-491), is
  * vslam_search_by_projection_mappoints_rig / vslam_search_local_points_rig below; the rig form of
  * SearchByProjection(CurrentFrame, LastFrame), right-camera branch :2593-2659 included, is vslam_search_by_projection_frame_rig.
- * Not covered: every other matcher's fisheye or right-camera branch (Fuse(.., bRight), SearchForTriangulation, the relocalisation SearchByProjection(CurrentFrame, KeyFrame, ..); SearchByBoW of a rig is vslam_search_by_bow_rig), TriangulateMatches / epipolarConstrain / matchAndtriangulate (cv::SVD), ReconstructWithTwoViews
+ * Fuse(pKF, vpMapPoints, th, bRight) of a fisheye KeyFrame, both cameras of a rig, is vslam_fuse_search_rig.
+ * Not covered: every other matcher's fisheye or right-camera branch (SearchForTriangulation, the relocalisation SearchByProjection(CurrentFrame, KeyFrame, ..), SearchBySim3; SearchByBoW of a rig is vslam_search_by_bow_rig), TriangulateMatches / epipolarConstrain / matchAndtriangulate (cv::SVD), ReconstructWithTwoViews
  * (cv::fisheye::undistortPoints), projectJac, tanf beyond 3*pi/4. */
 typedef struct vslam_kb8_camera {
     float fx, fy, cx, cy; /* mvParameters[0..3] */
@@ -1271,6 +1272,70 @@ int vslam_fuse_search(vslam_fe* fe, const vslam_fuse_params* p, const vslam_fuse
                       const uint8_t* mp_desc_host, int n_points, const vslam_kp* dev_kf_kps,
                       const uint8_t* dev_kf_desc, int n_kf, const float* kf_u_right_host, int32_t* best_idx,
                       int32_t* best_dist);
+
+/* The search half of FMatcher::Fuse(pKF, vpMapPoints, th, bRight) for a fisheye KeyFrame (fmatcher.cpp:1918-2119 with a
+ * KannalaBrandt8 camera; bRight = true and pKF->NLeft != -1: a two-fisheye rig) and of Fuse(pKF, Scw, vpPoints, th,
+ * vpReplacePoint) (:2121-2243) with such a KeyFrame: ONE list of MapPoints against up to 16 (KeyFrame, camera) jobs in one
+ * enqueue.  LocalMapping::SearchInNeighbors (localmapping.cpp:776-782, :809-810) calls Fuse(pKFi, ..) and Fuse(pKFi, .., true)
+ * for every target KeyFrame; the search half reads of a MapPoint its position, normal, distance range, descriptor, isBad() and
+ * IsInKeyFrame(pKF), and an earlier call's map mutation changes only the last two (towards "skip") and the descriptor of the
+ * survivor of a Replace (mappoint.cpp:292).  So the searches of several calls can run before the first mutation; INTEGRATION.md
+ * ("Fuse for a rig") states the walk that makes the caller's result equal to the sequential one.
+ * Restated as written, per job and MapPoint:
+ *   - p3Dc = Rcw * p3Dw + tcw as one gemm; z < 0 rejects, z == 0 goes on.  invz and ur are dead in a rig (below) and not computed
+ *   - uv = pCamera->project(x, y, z): KannalaBrandt8::project with THE JOB'S OWN camera -- mpCamera2 for bRight (:1929), unlike
+ *     the right branch of SearchByProjection(CurrentFrame, LastFrame), which projects through the left model
+ *   - KeyFrame::IsInImage (closed below, open above) over the KeyFrame's integer copy of the grid bounds; cv::norm(p3Dw - Ow)
+ *     within [min_distance, max_distance]; PO.dot(Pn) < 0.5 * dist3D rejects (both accumulated in double); PredictScale; radius
+ *     th * scale[level]
+ *   - KeyFrame::GetFeaturesInArea(u, v, r, bRight) over the side's own grid and keypoints (keyframe.cpp:656-699): columns outer,
+ *     rows inner, ascending index within a cell; level gate [level - 1, level]
+ *   - chi2: a rig's mvuRight is vector<float>(Nleft, -1) (frame.cpp:1160), and so is a monocular fisheye's: every defined entry
+ *     is negative, the monocular branch e2 * invSigma2[kpLevel] > 5.99 rejects.  ODDITY, NOT reproduced: the right call reads
+ *     mvuRight[idx] with the RIGHT-LOCAL index (:2053, before :2079 adds NLeft), i.e. a left feature's entry, or past the end
+ *     of the vector where idx >= Nleft (undefined behaviour); the restatement reads -1 everywhere.  sim3 = 1 has no chi2 gate
+ *   - least distance, `dist < bestDist` from 256: the first of the window order wins a tie and a distance of 256 never wins;
+ *     sim3 = 1 starts from INT_MAX: where nothing is nearer than 256 the first candidate at 256 is reported (best_dist 256)
+ *   - the reported index is the side-local index plus idx_offset (:2079); nothing passes: best_idx -1, best_dist 256.
+ * sim3 = 1 reads pKF->mpCamera and the left keypoints only: camera 0, idx_offset 0, Rcw / tcw / Ow derived from Scw by the
+ * caller as for vslam_fuse_search.  A monocular fisheye KeyFrame (NLeft == -1) is one job with camera 0 and idx_offset 0.
+ * points[i].valid = pMP && !pMP->isBad(); a job's valid_host[i] = !pMP->IsInKeyFrame(pKF) (sim3 = 1: !spAlreadyFound.count).
+ * Of p are read th, log_scale_factor, img_w, img_h and gemm_float; fx, fy, cx, cy, bf, Rcw, tcw, Ow, sim3, Rb and tb are NOT
+ * read (pose and switches are the job's, the intrinsics the cameras').  A KB8 camera must be set (VSLAM_ERR_INVALID
+ * otherwise); rig may be NULL when no job has camera == 1.  The window grid and IsInImage use the context's float grid bounds
+ * or {0, img_w, 0, img_h}, truncated for the KeyFrame as in vslam_fuse_search.  points / mp_desc / points_where: as for
+ * vslam_search_local_points_async (host or DEVICE arrays, untouched until _wait returns).
+ * n_jobs outside 1..16: VSLAM_ERR_INVALID.  n_points > VSLAM_LOCAL_POINTS_MAX or a job with n_kf > 4096:
+ * VSLAM_ERR_UNSUPPORTED.  Nothing is enqueued then, and the blocking form leaves -1 / 256 in every one of its n_jobs * n_points
+ * outputs (for n_jobs > 16 too: the caller sized them by n_jobs; n_jobs < 1 names no outputs).  A job's dev_desc must be
+ * 16-byte aligned (the rows are read 16 bytes at a time; rows [NLeft, ..) of an aligned mDescriptors are) and its dev_kps
+ * 4-byte aligned: VSLAM_ERR_INVALID otherwise.  n_points == 0 and
+ * jobs with n_kf == 0 are ordinary inputs with empty results.  One upload, one launch (k_fuse_rank_rig, grid (ceil(n_points /
+ * 16), n_jobs)), one result copy, no host wait in between; the staging block is the entry's own, so the blocking matchers may
+ * run between _async and _wait.  One search per context may be in flight: a second _async is VSLAM_ERR_INVALID.
+ * _wait: best_idx / best_dist, n_jobs * n_points entries each, job-major. */
+#define VSLAM_FUSE_RIG_MAX_JOBS 16
+typedef struct vslam_fuse_rig_job {   /* one call of Fuse(pKF, vpMapPoints, th, bRight): one camera of one KeyFrame */
+    float Rcw[9], tcw[3], Ow[3];      /* GetRotation / GetTranslation / GetCameraCenter, or the GetRight* ones for bRight */
+    int32_t camera;                   /* 0 = the context's KB8 camera (mpCamera), 1 = rig->cam2 (mpCamera2) */
+    int32_t sim3;                     /* 0: Fuse(pKF, vpMapPoints, th, bRight); 1: Fuse(pKF, Scw, ..) (camera must be 0) */
+    const vslam_kp* dev_kps;          /* mvKeys / mvKeysRight (a rig's mvKeysUn == mvKeys): the side's own array, DEVICE */
+    const uint8_t* dev_desc;          /* the side's descriptor rows, DEVICE, 16-byte aligned: mDescriptors rows [0, NLeft) or [NLeft, NLeft + NRight) */
+    int32_t n_kf;                     /* keypoints of this side, <= 4096 */
+    int32_t idx_offset;               /* added to a reported index: 0, or NLeft for bRight (fmatcher.cpp:2079) */
+    const uint8_t* valid_host;        /* n_points bytes, 0 = IsInKeyFrame(pKF) (or spAlreadyFound); NULL = all 1 */
+} vslam_fuse_rig_job;
+int vslam_fuse_search_rig_async(vslam_fe* fe, const vslam_fuse_params* p, const vslam_kb8_rig* rig,
+                                const vslam_fuse_rig_job* jobs, int n_jobs, const vslam_fuse_point* points,
+                                const uint8_t* mp_desc, int n_points, int points_where);
+int vslam_fuse_search_rig_wait(vslam_fe* fe, int32_t* best_idx, int32_t* best_dist);
+/* _async + _wait */
+int vslam_fuse_search_rig(vslam_fe* fe, const vslam_fuse_params* p, const vslam_kb8_rig* rig, const vslam_fuse_rig_job* jobs,
+                          int n_jobs, const vslam_fuse_point* points, const uint8_t* mp_desc, int n_points, int points_where,
+                          int32_t* best_idx, int32_t* best_dist);
+/* With vslam_fe_set_profiling on: HIP-event time of k_fuse_rank_rig alone, summed over the searches waited for since
+ * profiling was switched on.  Either pointer may be NULL. */
+int vslam_fe_get_fuse_rig_profile(vslam_fe* fe, double* rank_ms, long* passes);
 
 /* Evaluate the device float helpers on host arrays (round trip through HBM): the glibc-exact sinf/cosf
  * used for the rBRIEF rotation (fextractor.cpp:103-104) and cv::fastAtan2 (fextractor.cpp:94). */

@@ -60,6 +60,13 @@ extern "C" int vslamh_search_by_bow_rig(const vslam_kp* kf_kps, const uint8_t* k
                                         const int32_t* f_fv_nodes, const int32_t* f_fv_off, const int32_t* f_fv_feat,
                                         int n_f_nodes, float nnratio, int check_orientation, int32_t* match_f, int* nmatches);
 
+/* the search half of Fuse for a fisheye KeyFrame / a rig over host arrays (a job's dev_kps / dev_desc are HOST pointers here):
+ * the one-point searches that FMatcher::FuseWalk's caller redoes for a MapPoint whose descriptor was recomputed */
+extern "C" int vslamh_fuse_search_rig(const vslam_fuse_params* p, const vslam_kb8_camera* cam, const vslam_kb8_rig* rig,
+                                      const vslam_fuse_rig_job* jobs, int n_jobs, const vslam_fuse_point* points,
+                                      const uint8_t* mp_desc, int n_points, const float* scale_factors, const float* inv_sigma2,
+                                      int nlevels, const float* bounds, int32_t* best_idx, int32_t* best_dist);
+
 namespace VSLAM_SHIM_NAMESPACE {
 namespace geometry {
 
@@ -832,6 +839,103 @@ public:
             pKF2.mFeatVec->feat.data(), (int)pKF2.mFeatVec->nodes.size(), mfNNratio, mbCheckOrientation ? 1 : 0,
             vpMatches12.data(), &nm));
         return nm;
+    }
+
+    /* The search half of FMatcher::Fuse(pKF, vpMapPoints, th, bRight) (fmatcher.cpp:1918-2119) for a fisheye KeyFrame / both
+     * cameras of a two-fisheye rig: ONE list of candidate MapPoints against any number of (KeyFrame, camera) jobs, 16 per
+     * enqueue (more are served in groups of 16).  A job is one call of Fuse -- vslam_fuse_rig_job (include/vslam_fe.h): the
+     * camera's own pose, camera 0 / 1, the side's keypoints and descriptor rows in HBM, idx_offset 0 or NLeft, and one byte per
+     * MapPoint that is 0 where IsInKeyFrame(pKF) holds.  LocalMapping::SearchInNeighbors lists, for every target KeyFrame, its
+     * left job and then its right one.  points[i].valid = pMP && !pMP->isBad().  extractor: the context to run on, with the
+     * KannalaBrandt8 of mpCamera attached; rig (may be NULL when no job has camera 1) carries mpCamera2.
+     * gemmFloat: as vslam_fuse_params::gemm_float (a reference build whose cv::gemm stays in float).  The window grid and IsInImage
+     * use the context's grid bounds while it holds any (SetGridBounds), else {0, imgW, 0, imgH}.
+     * bestIdx / bestDist: jobs.size() * points.size() entries each, job-major; -1 / 256 where nothing passes.  What the
+     * reference does with a result -- Replace / AddObservation + AddMapPoint where bestDist <= TH_LOW -- stays with the caller:
+     * FuseWalk below. */
+    void FuseSearchRig(const FExtractor& extractor, const vslam_kb8_rig* rig, const std::vector<vslam_fuse_rig_job>& jobs,
+                       const std::vector<vslam_fuse_point>& points, const std::vector<uint8_t>& mapPointDescriptors, const float th,
+                       const float logScaleFactor, const int imgW, const int imgH, std::vector<int>& bestIdx,
+                       std::vector<int>& bestDist, const bool gemmFloat = false) {
+        static_assert(sizeof(int) == sizeof(int32_t), "the results are handed over as int32");
+        if (mapPointDescriptors.size() != 32 * points.size())
+            throw std::invalid_argument("FuseSearchRig: one descriptor per MapPoint");
+        const size_t n = points.size();
+        bestIdx.assign(jobs.size() * n, -1);
+        bestDist.assign(jobs.size() * n, 256);
+        vslam_fuse_params p;
+        std::memset(&p, 0, sizeof(p));
+        p.th = th;
+        p.log_scale_factor = logScaleFactor;
+        p.img_w = imgW;
+        p.img_h = imgH;
+        p.gemm_float = gemmFloat ? 1 : 0;
+        for (size_t first = 0; first < jobs.size() && n; first += VSLAM_FUSE_RIG_MAX_JOBS) {
+            const int K = (int)std::min<size_t>(VSLAM_FUSE_RIG_MAX_JOBS, jobs.size() - first);
+            check(vslam_fuse_search_rig(extractor.context(), &p, rig, jobs.data() + first, K, points.data(),
+                                        mapPointDescriptors.data(), (int)n, VSLAM_IMGS_HOST, bestIdx.data() + first * n,
+                                        bestDist.data() + first * n));
+        }
+    }
+
+    /* ONE (job, point) search on the host with the same parameters as FuseSearchRig: what FuseWalk's searchOne calls for a
+     * MapPoint whose descriptor was recomputed.  hostJob: the job with dev_kps / dev_desc pointing at HOST copies of the side's
+     * keypoints and descriptor rows (valid_host is not read: one point, asked about by the walk already); camera: mpCamera's
+     * parameters; descriptor: the MapPoint's 32 bytes of now.  Scale tables and grid bounds come from the extractor's context. */
+    static void FuseSearchOneHost(FExtractor& extractor, const vslam_kb8_camera& camera, const vslam_kb8_rig* rig,
+                                  const vslam_fuse_rig_job& hostJob, const vslam_fuse_point& point, const uint8_t* descriptor,
+                                  const float th, const float logScaleFactor, const int imgW, const int imgH, int& bestIdx,
+                                  int& bestDist, const bool gemmFloat = false) {
+        vslam_fuse_params p;
+        std::memset(&p, 0, sizeof(p));
+        p.th = th;
+        p.log_scale_factor = logScaleFactor;
+        p.img_w = imgW;
+        p.img_h = imgH;
+        p.gemm_float = gemmFloat ? 1 : 0;
+        vslam_fuse_rig_job job = hostJob;
+        job.valid_host = nullptr;
+        const std::vector<float> sf = extractor.GetScaleFactors(), is2 = extractor.GetInverseScaleSigmaSquares();
+        vslam_bounds b;
+        int is_set = 0;
+        check(vslam_fe_get_grid_bounds(extractor.context(), &b, &is_set));
+        const float bounds[4] = {is_set ? b.min_x : 0.0f, is_set ? b.max_x : (float)imgW, is_set ? b.min_y : 0.0f,
+                                 is_set ? b.max_y : (float)imgH};
+        int32_t oi = -1, od = 256;
+        check(vslamh_fuse_search_rig(&p, &camera, rig, &job, 1, &point, descriptor, 1, sf.data(), is2.data(), (int)sf.size(), bounds,
+                                     &oi, &od));
+        bestIdx = oi;
+        bestDist = od;
+    }
+
+    /* The walk over the results of FuseSearchRig that makes the caller's map equal to the one the reference's sequential calls
+     * leave ("Fuse for a rig").  Jobs in the reference's call order (the left job of a KeyFrame before its right
+     * job), points in order.  At each (job, point):
+     *   - isBad(point) or isInKeyFrame(job, point) holds NOW: skip (both only ever flip towards "skip")
+     *   - descriptorRecomputed(point) -- the point survived a Replace earlier in this walk, so ComputeDistinctiveDescriptors ran
+     *     (mappoint.cpp:292): the batch result is stale; searchOne(job, point, idx, dist) redoes this one search with the
+     *     descriptor of now (vslamh_fuse_search_rig with one job and one point, or a one-job device call)
+     *   - bestDist <= TH_LOW: fuse(job, point, bestIdx), the reference's :2093-2112; it may Replace either way
+     * A point that fused in the left job is in the KeyFrame or bad, so the right job of the same KeyFrame skips it: a stale
+     * descriptor only ever matters across KeyFrames.  Returns nFused summed over the jobs. */
+    template <class IsBad, class IsInKeyFrame, class DescriptorRecomputed, class SearchOne, class Fuse>
+    static int FuseWalk(const size_t nJobs, const size_t nPoints, const std::vector<int>& bestIdx, const std::vector<int>& bestDist,
+                        IsBad isBad, IsInKeyFrame isInKeyFrame, DescriptorRecomputed descriptorRecomputed, SearchOne searchOne,
+                        Fuse fuse) {
+        if (bestIdx.size() != nJobs * nPoints || bestDist.size() != nJobs * nPoints)
+            throw std::invalid_argument("FuseWalk: nJobs * nPoints results");
+        const int TH_LOW = 50;
+        int nFused = 0;
+        for (size_t j = 0; j < nJobs; j++)
+            for (size_t i = 0; i < nPoints; i++) {
+                if (isBad(i) || isInKeyFrame(j, i)) continue;
+                int idx = bestIdx[j * nPoints + i], dist = bestDist[j * nPoints + i];
+                if (descriptorRecomputed(i)) searchOne(j, i, idx, dist);
+                if (idx < 0 || dist > TH_LOW) continue;
+                fuse(j, i, idx);
+                nFused++;
+            }
+        return nFused;
     }
 
 protected:

@@ -69,6 +69,7 @@ ABI_SYMBOLS = [
     "vslam_search_by_projection_frame_rig", "vslam_fe_get_frame_rig_profile",
     "vslam_search_by_bow_rig_async", "vslam_search_by_bow_rig_wait", "vslam_search_by_bow_rig",
     "vslam_fe_get_bow_rig_profile", "vslam_search_by_bow_keyframes_rig",
+    "vslam_fuse_search_rig_async", "vslam_fuse_search_rig_wait", "vslam_fuse_search_rig", "vslam_fe_get_fuse_rig_profile",
     "vslam_two_view_score_async", "vslam_two_view_score_wait", "vslam_two_view_score", "vslam_fe_get_two_view_profile",
     "vslam_kfdb_create", "vslam_kfdb_create_ex", "vslam_kfdb_destroy", "vslam_kfdb_add", "vslam_kfdb_erase",
     "vslam_kfdb_clear", "vslam_kfdb_clear_map", "vslam_kfdb_size", "vslam_kfdb_stats", "vslam_kfdb_query_async",
@@ -346,6 +347,76 @@ def rig_frame(dev_kps_left, dev_desc_left, n_left, dev_kps_right, dev_desc_right
     return f
 
 
+FUSE_RIG_MAX_JOBS = 16
+
+
+class _FuseRigJob(C.Structure):  # vslam_fuse_rig_job
+    _fields_ = [("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("Ow", C.c_float * 3), ("camera", C.c_int32),
+                ("sim3", C.c_int32), ("dev_kps", C.c_void_p), ("dev_desc", C.c_void_p), ("n_kf", C.c_int32),
+                ("idx_offset", C.c_int32), ("valid_host", C.c_void_p)]
+
+
+def fuse_rig_job(Rcw, tcw, Ow, kps, desc, n_kf, camera=0, idx_offset=0, valid=None, sim3=False):
+    """vslam_fuse_rig_job: one call of Fuse(pKF, vpMapPoints, th, bRight) -- one camera of one KeyFrame.  Rcw / tcw / Ow: the
+    camera's own pose (GetRight* for bRight); kps / desc: addresses of the side's keypoints and descriptor rows (DEVICE memory
+    for FExtractor.fuse_search_rig, host memory for fuse_search_rig_host); camera 0 = the context's KB8 camera, 1 = rig.cam2;
+    idx_offset: 0, or NLeft for bRight; valid: one byte per MapPoint, 0 = IsInKeyFrame(pKF), or None.  The returned object
+    keeps `valid` alive."""
+    j = _FuseRigJob()
+    j.Rcw[:] = [float(v) for v in np.asarray(Rcw, np.float32).reshape(9)]
+    j.tcw[:] = [float(v) for v in np.asarray(tcw, np.float32).reshape(3)]
+    j.Ow[:] = [float(v) for v in np.asarray(Ow, np.float32).reshape(3)]
+    j.camera, j.sim3, j.n_kf, j.idx_offset = int(camera), int(sim3), int(n_kf), int(idx_offset)
+    j.dev_kps, j.dev_desc = kps or None, desc or None
+    v = None if valid is None else np.ascontiguousarray(valid, np.uint8)
+    j.valid_host = v.ctypes.data if v is not None and len(v) else None
+    j._keep = v
+    return j
+
+
+def _fuse_rig_params(th, log_scale_factor, img_size, gemm_float=False):
+    P = _FuseParams()
+    P.th, P.log_scale_factor, P.img_w, P.img_h = float(th), float(log_scale_factor), int(img_size[0]), int(img_size[1])
+    P.gemm_float = int(gemm_float)
+    return P
+
+
+def _fuse_rig_jobs(jobs, n_points):
+    """the job array of vslam_fuse_search_rig; every job's validity bytes must cover the points"""
+    for j in jobs:
+        if j._keep is not None and len(j._keep) != n_points:
+            raise ValueError("a job's valid array must have one byte per MapPoint")
+    arr = (_FuseRigJob * max(len(jobs), 1))()
+    for k, j in enumerate(jobs):
+        C.memmove(C.byref(arr, k * C.sizeof(_FuseRigJob)), C.byref(j), C.sizeof(_FuseRigJob))
+    return arr
+
+
+def fuse_search_rig_host(cam, rig, jobs, points, mp_desc, th, log_scale_factor, img_size, scale_factors, inv_sigma2,
+                         bounds=None, gemm_float=False, library=None):
+    """vslamh_fuse_search_rig (libvslam_host.so, GPU-free): the search half of Fuse for a fisheye KeyFrame / a rig over host
+    arrays, any number of jobs (fuse_rig_job with host addresses).  cam from kb8_camera(), rig from kb8_rig() or None.
+    -> (best_idx[n_jobs, n_points], best_dist[n_jobs, n_points])"""
+    L = library if library is not None else host_lib()
+    vp, i = C.c_void_p, C.c_int
+    L.vslamh_fuse_search_rig.argtypes = [vp, vp, vp, vp, i, vp, vp, i, vp, vp, i, vp, vp, vp]
+    pts = np.ascontiguousarray(points, FUSE_POINT_DTYPE)
+    md = np.ascontiguousarray(mp_desc, np.uint8).reshape(-1, 32)
+    if len(md) != len(pts):
+        raise ValueError("one descriptor per MapPoint")
+    sf, is2 = np.ascontiguousarray(scale_factors, np.float32), np.ascontiguousarray(inv_sigma2, np.float32)
+    b = np.ascontiguousarray(bounds if bounds is not None else (0, img_size[0], 0, img_size[1]), np.float32)
+    P = _fuse_rig_params(th, log_scale_factor, img_size, gemm_float)
+    arr = _fuse_rig_jobs(jobs, len(pts))
+    n = len(jobs) * len(pts)
+    bi, bd = np.full(max(n, 1), -1, np.int32), np.full(max(n, 1), 256, np.int32)
+    rc = L.vslamh_fuse_search_rig(C.byref(P), C.byref(cam), None if rig is None else C.byref(rig), arr, len(jobs), _p(pts), _p(md),
+                                  len(pts), _p(sf), _p(is2), len(sf), _p(b), _p(bi), _p(bd))
+    if rc:
+        raise VslamError(rc, "vslamh_fuse_search_rig: invalid arguments")
+    return bi[:n].reshape(len(jobs), len(pts)), bd[:n].reshape(len(jobs), len(pts))
+
+
 class _BowRigKf(C.Structure):  # vslam_bow_rig_kf
     _fields_ = [("dev_desc_left", C.c_void_p), ("n_left", C.c_int), ("dev_desc_right", C.c_void_p), ("n_right", C.c_int),
                 ("kps_host", C.c_void_p), ("flags_host", C.c_void_p), ("fv_nodes", C.c_void_p), ("fv_off", C.c_void_p),
@@ -579,6 +650,10 @@ def lib():
                                                         C.c_float, i, vp, vp]
         L.vslam_search_for_triangulation.argtypes = [vp, vp] + [vp, vp, vp, vp, i, vp, vp, vp, i] * 2 + [vp, vp]
         L.vslam_fuse_search.argtypes = [vp, vp, vp, vp, i, vp, vp, i, vp, vp, vp]
+        L.vslam_fuse_search_rig_async.argtypes = [vp, vp, vp, vp, i, vp, vp, i, i]
+        L.vslam_fuse_search_rig_wait.argtypes = [vp, vp, vp]
+        L.vslam_fuse_search_rig.argtypes = [vp, vp, vp, vp, i, vp, vp, i, i, vp, vp]
+        L.vslam_fe_get_fuse_rig_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long)]
         L.vslam_dbg_logf.argtypes = [vp, vp, i, vp]
         L.vslam_dbg_live_memory.argtypes = [vp, vp, vp, vp]
         L.vslam_search_by_projection_sim3.argtypes = [vp, vp, vp, C.c_float, C.c_float, i, vp, vp, vp, vp, vp, vp, i, vp, vp, i,
@@ -1316,6 +1391,62 @@ class FExtractor:
         a, b, n = C.c_double(0), C.c_double(0), C.c_long(0)
         _check(lib().vslam_fe_get_frame_rig_profile(self._h, C.byref(a), C.byref(b), C.byref(n)))
         return a.value, b.value, n.value
+
+    def _fuse_rig_call(self, rig, jobs, points, mp_desc, th, log_scale_factor, img_size, gemm_float, n_points):
+        """the arguments of vslam_fuse_search_rig[_async] up to points_where, what keeps their host arrays alive, and the
+        point count"""
+        on_dev = isinstance(points, int)
+        if on_dev:
+            if n_points is None:
+                raise ValueError("n_points is required with device addresses")
+            keep, pp, dp = (), C.c_void_p(points), C.c_void_p(int(mp_desc))
+        else:
+            keep = (np.ascontiguousarray(points, FUSE_POINT_DTYPE), np.ascontiguousarray(mp_desc, np.uint8).reshape(-1, 32))
+            if len(keep[0]) != len(keep[1]):
+                raise ValueError("one descriptor per MapPoint")
+            n_points = len(keep[0])
+            pp, dp = _p(keep[0]), _p(keep[1])
+        P = _fuse_rig_params(th, log_scale_factor, img_size or (self.width, self.height), gemm_float)
+        arr = _fuse_rig_jobs(jobs, n_points)
+        head = (self._h, C.byref(P), None if rig is None else C.byref(rig), arr, len(jobs), pp, dp, n_points,
+                IMGS_DEVICE if on_dev else IMGS_HOST)
+        return head, (keep, P, arr, list(jobs), rig), n_points
+
+    def fuse_search_rig_async(self, rig, jobs, points, mp_desc, th, log_scale_factor, img_size=None, gemm_float=False,
+                              n_points=None):
+        """Enqueue the search half of FMatcher::Fuse(pKF, vpMapPoints, th, bRight) (fmatcher.cpp:1918-2119) for a fisheye
+        KeyFrame / both cameras of a rig: ONE MapPoint list against up to 16 jobs from fuse_rig_job() (device addresses), and
+        return.  rig from kb8_rig(), or None when no job has camera 1.  points / mp_desc: numpy arrays (FUSE_POINT_DTYPE with
+        valid = pMP && !isBad(), n x 32 uint8), or two device addresses (ints) with n_points given."""
+        head, keep, n = self._fuse_rig_call(rig, jobs, points, mp_desc, th, log_scale_factor, img_size, gemm_float, n_points)
+        _check(lib().vslam_fuse_search_rig_async(*head))
+        self._fsr_keep, self._fsr_shape = keep, (len(jobs), n)
+
+    def fuse_search_rig_wait(self):
+        """-> (best_idx[n_jobs, n_points], best_dist[n_jobs, n_points]); -1 / 256 where nothing passes"""
+        k, n = getattr(self, "_fsr_shape", (0, 0))
+        bi, bd = np.full(max(k * n, 1), -1, np.int32), np.full(max(k * n, 1), 256, np.int32)
+        rc = lib().vslam_fuse_search_rig_wait(self._h, _p(bi), _p(bd))
+        self._fsr_keep = None
+        _check(rc)
+        return bi[:k * n].reshape(k, n), bd[:k * n].reshape(k, n)
+
+    def fuse_search_rig(self, rig, jobs, points, mp_desc, th, log_scale_factor, img_size=None, gemm_float=False,
+                        n_points=None):
+        """fuse_search_rig_async + fuse_search_rig_wait, through the blocking entry point.  What a refused call left in its
+        outputs stays in last_fuse_rig_outputs."""
+        head, keep, n = self._fuse_rig_call(rig, jobs, points, mp_desc, th, log_scale_factor, img_size, gemm_float, n_points)
+        k = len(jobs)
+        bi, bd = np.full(max(k * n, 1), 7, np.int32), np.full(max(k * n, 1), 7, np.int32)
+        self.last_fuse_rig_outputs = (bi[:k * n], bd[:k * n])
+        _check(lib().vslam_fuse_search_rig(*head, _p(bi), _p(bd)))
+        return bi[:k * n].reshape(k, n), bd[:k * n].reshape(k, n)
+
+    def get_fuse_rig_profile(self):
+        """-> (ms in k_fuse_rank_rig, searches) since set_profiling(True)"""
+        a, n = C.c_double(0), C.c_long(0)
+        _check(lib().vslam_fe_get_fuse_rig_profile(self._h, C.byref(a), C.byref(n)))
+        return a.value, n.value
 
     def two_view_score_async(self, jobs):
         """Enqueue MotionEstimator::CheckHomography / CheckFundamental of every hypothesis and the selection of

@@ -207,6 +207,12 @@ struct vslam_fe {
     vslam_pending sbr_op;       /* jobs: keyframe jobs, n: n_left + n_right of the frame */
     size_t sbr_o_m = 0, sbr_o_n = 0;
     vslam_span_timer<2> t_sbr;  /* before k_sbow_nodes_rig | between | behind k_sbow_finish_rig */
+    /* the search half of Fuse for a fisheye KeyFrame / a rig, up to 16 (KeyFrame, camera) jobs (vslam_fuse_search_rig_async,
+     * vslam_fuse_rig.hip): a block of its own for the same reason */
+    vslam_staging fsr;          /* points | descriptors (host points only) | per job: validity bytes | best_idx | best_dist of every job */
+    vslam_pending fsr_op;       /* jobs: the jobs, n: the MapPoints */
+    size_t fsr_o_bi = 0, fsr_o_bd = 0;
+    vslam_span_timer<1> t_fsr;  /* around k_fuse_rank_rig */
 
     /* GPU quadtree distribution */
     bool dev_octree = false;
@@ -237,6 +243,7 @@ struct vslam_fe {
         t_rig.reset();
         t_fr.reset();
         t_sbr.reset();
+        t_fsr.reset();
     }
 
     WorkerPool* pool = nullptr;

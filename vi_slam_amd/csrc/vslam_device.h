@@ -190,6 +190,30 @@ struct FuseArgsDev {
     int32_t *bestIdx, *bestDist;
 };
 
+/* vslam_fuse_search_rig (k_fuse_rank_rig): one (KeyFrame, camera) job over the MapPoint list of the FuseRigArgs around it;
+ * every pointer a DEVICE pointer */
+struct FuseRigJobDev {
+    float Rcw[9], tcw[3], Ow[3];
+    int32_t camera, sim3, nKF, idxOffset;
+    const vslam_kp* kps;
+    const uint8_t* desc;
+    const uint8_t* valid; /* nPoints bytes, or null = all 1 */
+    uint32_t pad[2];
+};
+#define VSLAM_MAX_FUSE_RIG_JOBS 16
+static_assert(sizeof(FuseRigJobDev) == 112, "16 of these travel as one kernel argument");
+struct FuseRigArgs { /* by-value kernel argument (< 4 KB) */
+    FuseRigJobDev job[VSLAM_MAX_FUSE_RIG_JOBS];
+    vslam_kb8_camera cam[2]; /* mpCamera, mpCamera2 */
+    float scale[VSLAM_MAX_LEVELS], invSigma2[VSLAM_MAX_LEVELS];
+    float th, logScaleFactor;
+    SiBounds bnd;
+    int32_t gemmFloat, nlevels, nPoints, pad;
+    const FusePoint* pts;
+    const uint8_t* mpDesc;
+    int32_t *bestIdx, *bestDist; /* [job][nPoints] */
+};
+
 /* One SearchByProjection(CurrentFrame, LastFrame) problem; every pointer is a DEVICE pointer.  nLast / nCur are
  * the counts, or -- when nLastPtr / nCurPtr are set -- capacities with the real counts read from HBM. */
 struct SbpProj;

@@ -1510,6 +1510,79 @@ int vslamh_search_by_projection_frame_rig(const vslam_proj_params* p, const vsla
     return VSLAM_OK;
 }
 
+/* The search half of FMatcher::Fuse(pKF, vpMapPoints, th, bRight) for a fisheye KeyFrame / a two-fisheye rig
+ * (fmatcher.cpp:1918-2119; the Scw overload :2121-2243 as sim3 = 1) as it is written, job after job and point after point:
+ * the statement the device form (vslam_fuse_search_rig) is tested against, and what the shim's walk calls with ONE point to
+ * redo a search whose MapPoint descriptor was recomputed.  Same arguments; every pointer a HOST pointer, a job's dev_kps /
+ * dev_desc included; any number of jobs and points.  cam = mpCamera, rig (may be NULL when no job has camera 1) gives
+ * mpCamera2; scale_factors / inv_sigma2: mvScaleFactors / mvInvLevelSigma2, nlevels entries; bounds: the Frame's float mnMinX,
+ * mnMaxX, mnMinY, mnMaxY, which the KeyFrame truncates for its window origin and IsInImage.  best_idx / best_dist: n_jobs *
+ * n_points entries each, job-major. */
+int vslamh_fuse_search_rig(const vslam_fuse_params* p, const vslam_kb8_camera* cam, const vslam_kb8_rig* rig,
+                           const vslam_fuse_rig_job* jobs, int n_jobs, const vslam_fuse_point* points, const uint8_t* mp_desc,
+                           int n_points, const float* scale_factors, const float* inv_sigma2, int nlevels, const float* bounds,
+                           int32_t* best_idx, int32_t* best_dist) {
+    if (!p || !vslam_kb8::camera_ok(cam) || !jobs || n_jobs < 1 || n_points < 0 || nlevels < 1 || !scale_factors || !inv_sigma2 ||
+        !bounds || (n_points && (!points || !mp_desc || !best_idx || !best_dist)))
+        return VSLAM_ERR_INVALID;
+    for (int j = 0; j < n_jobs; j++) {
+        const vslam_fuse_rig_job& s = jobs[j];
+        if (s.camera < 0 || s.camera > 1 || s.sim3 < 0 || s.sim3 > 1 || (s.sim3 && s.camera) || s.n_kf < 0 ||
+            (s.n_kf && (!s.dev_kps || !s.dev_desc)) || (s.camera == 1 && (!rig || !vslam_kb8::camera_ok(&rig->cam2))))
+            return VSLAM_ERR_INVALID;
+    }
+    const float kb[4] = {(float)(int)bounds[0], (float)(int)bounds[1], (float)(int)bounds[2], (float)(int)bounds[3]};
+    std::vector<int> vIndices;
+    for (int j = 0; j < n_jobs; j++) {
+        const vslam_fuse_rig_job& s = jobs[j];
+        const vslam_kb8_camera& c = s.camera ? rig->cam2 : *cam;
+        RigGrid grid(s.dev_kps, s.n_kf, bounds); /* the Frame's cells and inverses (keyframe.cpp:36, :58-67) .. */
+        grid.minX = kb[0];                       /* .. the window origin from the KeyFrame's integers (:663-675) */
+        grid.minY = kb[2];
+        int32_t* bi = best_idx + (size_t)j * n_points;
+        int32_t* bd = best_dist + (size_t)j * n_points;
+        for (int i = 0; i < n_points; i++) {
+            bi[i] = -1;
+            bd[i] = 256;
+            const vslam_fuse_point& mp = points[i];
+            if (!mp.valid || (s.valid_host && !s.valid_host[i])) continue;
+            float pc[3];
+            for (int r = 0; r < 3; r++) pc[r] = rig_gemm_row(s.Rcw + 3 * r, mp.pos, s.tcw[r], p->gemm_float);
+            if (pc[2] < 0.0f) continue;
+            const vslam_kb8::Uv uv = vslam_kb8::kb8_project(c, pc[0], pc[1], pc[2]);
+            if (!(uv.u >= kb[0] && uv.u < kb[1] && uv.v >= kb[2] && uv.v < kb[3])) continue; /* KeyFrame::IsInImage */
+            const float p0 = mp.pos[0] - s.Ow[0], p1 = mp.pos[1] - s.Ow[1], p2 = mp.pos[2] - s.Ow[2];
+            const float dist3D = vslam_md::norm3(p0, p1, p2);
+            if (dist3D < mp.min_distance || dist3D > mp.max_distance) continue;
+            if (vslam_md::dot3_mat(p0, p1, p2, mp.normal) < 0.5 * (double)dist3D) continue;
+            const int level = vslam_md::predict_level(mp.max_distance, dist3D, p->log_scale_factor, nlevels);
+            const float radius = p->th * scale_factors[level];
+            grid.query(uv.u, uv.v, radius, -1, -1, vIndices);
+            const uint8_t* dMP = mp_desc + (size_t)i * 32;
+            int bestDist = s.sim3 ? INT_MAX : 256, bestIdx = -1;
+            for (int idx : vIndices) {
+                const int kpLevel = s.dev_kps[idx].octave;
+                if (kpLevel < level - 1 || kpLevel > level) continue;
+                if (!s.sim3) { /* mvuRight is -1 throughout: the monocular branch */
+                    const float ex = uv.u - s.dev_kps[idx].x, ey = uv.v - s.dev_kps[idx].y;
+                    const float e2 = ex * ex + ey * ey;
+                    if ((double)(e2 * inv_sigma2[std::min(kpLevel, nlevels - 1)]) > 5.99) continue;
+                }
+                const int dist = rig_hamming(dMP, s.dev_desc + (size_t)idx * 32);
+                if (dist < bestDist) {
+                    bestDist = dist;
+                    bestIdx = idx;
+                }
+            }
+            if (bestIdx >= 0) {
+                bi[i] = bestIdx + s.idx_offset;
+                bd[i] = bestDist;
+            }
+        }
+    }
+    return VSLAM_OK;
+}
+
 /* FMatcher::SearchByBoW(KeyFrame* pKF, Frame& F, vpMapPointMatches) (fmatcher.cpp:546-748) with F.Nleft != -1 as it is
  * written, sequential, for one keyframe: the statement vslam_search_by_bow_rig is tested against, and the shim's fallback
  * beyond the device limits (there are none here).  Descriptor rows and FeatureVector indices of either side run over

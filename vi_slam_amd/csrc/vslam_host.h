@@ -250,4 +250,11 @@ extern "C" int vslamh_search_by_bow_rig(const vslam_kp* kf_kps, const uint8_t* k
                                         const vslam_kp* f_kps_right, const uint8_t* f_desc_right, int n_right,
                                         const int32_t* f_fv_nodes, const int32_t* f_fv_off, const int32_t* f_fv_feat,
                                         int n_f_nodes, float nnratio, int check_orientation, int32_t* match_f, int* nmatches);
+/* vslam_host.cpp: the search half of Fuse for a fisheye KeyFrame / a rig (vslam_fuse_search_rig) over host arrays, a job's
+ * dev_kps / dev_desc included, sequential as the reference writes it; any number of jobs and points (CPU tests, and the shim's
+ * walk for the one-point searches of a MapPoint whose descriptor was recomputed) */
+extern "C" int vslamh_fuse_search_rig(const vslam_fuse_params* p, const vslam_kb8_camera* cam, const vslam_kb8_rig* rig,
+                                      const vslam_fuse_rig_job* jobs, int n_jobs, const vslam_fuse_point* points,
+                                      const uint8_t* mp_desc, int n_points, const float* scale_factors, const float* inv_sigma2,
+                                      int nlevels, const float* bounds, int32_t* best_idx, int32_t* best_dist);
 #endif

@@ -96,6 +96,8 @@ int vk_distinctive_set_max_lds(size_t bytes);
 void vk_distinctive(hipStream_t st, const uint8_t* desc, const int32_t* offsets, int nsets, int maxN, int32_t* best);
 void vk_unproject_stereo(hipStream_t st, const UnprojJobs& U, int njobs);
 void vk_fuse_search(hipStream_t st, const FuseArgsDev& A);
+/* k_fuse_rank_rig: A.nPoints MapPoints against A.job[0 .. njobs); maxKF (the largest job's keypoint count) sizes the LDS */
+void vk_fuse_search_rig(hipStream_t st, const FuseRigArgs& A, int njobs, int maxKF);
 void vk_reset_headers(hipStream_t st, uint8_t* d_cand, size_t cand_stride_bytes, int nimg, int32_t* d_err);
 /* device -> pinned host (or device) range copies / zero fills in one launch; see k_copy_ranges */
 /* returns the number of copy operations put on the stream (runtime copies or one kernel launch) */

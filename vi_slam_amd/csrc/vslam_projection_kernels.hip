@@ -1225,49 +1225,21 @@ k_fuse_rank(FuseArgsDev A) {
                 }
             }
         }
-        if (go) {
-            const SiWindow win = si_window_b(u, v, radius, kbnd, inv);
-            if (!win.empty) {
-                const uint4 da = ((const uint4*)A.mpDesc)[(size_t)q * 2], db = ((const uint4*)A.mpDesc)[(size_t)q * 2 + 1];
-                for (int c = lane; c < A.nKF; c += 64) {
-                    const SbpCand cd = cand[c];
-                    if (cd.cell == 0xFFFF || !si_in_window(cd, win, u, v, radius)) continue;
-                    const int kpLevel = cd.octave;
-                    if (kpLevel < level - 1 || kpLevel > level) continue;
-                    if (!A.sim3) {
-                        /* ex = uv.x - kpx in the reference; only its square is used */
-                        const float is2 = A.invSigma2[min(kpLevel, A.nlevels - 1)];
-                        const float exx = __fsub_rn(u, cd.x), eyy = __fsub_rn(v, cd.y);
-                        if (cd.uRight >= 0.f) {
-                            const float er = __fsub_rn(ur, cd.uRight);
-                            const float e2 = __fadd_rn(__fadd_rn(__fmul_rn(exx, exx), __fmul_rn(eyy, eyy)), __fmul_rn(er, er));
-                            if ((double)__fmul_rn(e2, is2) > 7.8) continue;
-                        } else {
-                            const float e2 = __fadd_rn(__fmul_rn(exx, exx), __fmul_rn(eyy, eyy));
-                            if ((double)__fmul_rn(e2, is2) > 5.99) continue;
-                        }
-                    }
-                    const uint4 ta = ((const uint4*)A.kfDesc)[(size_t)c * 2], tb = ((const uint4*)A.kfDesc)[(size_t)c * 2 + 1];
-                    const uint32_t dist = si_hamming(da, db, ta, tb);
-                    if (dist > 255u) { /* `dist < bestDist`: never from bestDist = 256 (:2039); from INT_MAX (:2203, :2342) it is */
-                        if (A.sim3) far = min(far, ((uint32_t)cd.cell << 12) | (uint32_t)c);
-                        continue;
-                    }
-                    best = min(best, si_key(dist, cd.cell, (uint32_t)c));
-                }
-            }
-        }
-        const uint32_t g = wave_min_u32(best);
-        int32_t idx = g == 0xFFFFFFFFu ? -1 : (int32_t)si_key_index(g);
-        int32_t bd = g == 0xFFFFFFFFu ? 256 : (int32_t)si_key_dist(g);
-        if (g == 0xFFFFFFFFu && A.sim3) { /* wave-uniform: nothing nearer than 256 */
-            const uint32_t f = wave_min_u32(far);
-            if (f != 0xFFFFFFFFu) idx = (int32_t)(f & 0xFFFu);
-        }
-        if (lane == 0) {
-            A.bestIdx[q] = idx;
-            A.bestDist[q] = bd;
-        }
+#define FUSE_NKF A.nKF
+#define FUSE_KF_DESC A.kfDesc
+#define FUSE_SIM3 A.sim3
+#define FUSE_RIG 0
+#define FUSE_OFFSET 0
+#define FUSE_BEST_IDX A.bestIdx
+#define FUSE_BEST_DIST A.bestDist
+#include "vslam_fuse_rank_body.inc"
+#undef FUSE_NKF
+#undef FUSE_KF_DESC
+#undef FUSE_SIM3
+#undef FUSE_RIG
+#undef FUSE_OFFSET
+#undef FUSE_BEST_IDX
+#undef FUSE_BEST_DIST
     }
 }
 
@@ -1276,8 +1248,88 @@ void vk_fuse_search(hipStream_t st, const FuseArgsDev& A) {
     hipLaunchKernelGGL(k_fuse_rank, dim3((A.nPoints + FUSE_QPB - 1) / FUSE_QPB), dim3(256), vk_sbp_rank_lds(A.nKF), st, A);
 }
 
+/* ------------------------------------------------------------------------------------------------
+ * The search half of FMatcher::Fuse(pKF, vpMapPoints, th, bRight) for a fisheye KeyFrame and both cameras of a two-fisheye rig
+ * (fmatcher.cpp:1918-2119 with pKF->NLeft != -1; the Scw overload :2121-2243 as sim3 = 1): k_fuse_rank's sim3 == 0 / 1 gates
+ * with KannalaBrandt8::project of the JOB'S camera in place of Pinhole::project, no invz / ur (a rig's mvuRight is -1
+ * throughout: the monocular chi2 branch alone), the side's own keypoints as the window's grid, and idxOffset (0 or NLeft,
+ * :2079) added to the reported index.  One MapPoint list against up to VSLAM_MAX_FUSE_RIG_JOBS (KeyFrame, camera) jobs: the
+ * job is blockIdx.y, read from the by-value argument block with a uniform index.  A workgroup builds its job's candidate
+ * table in LDS and serves 16 MapPoints, one wave each; the projection is wave-uniform.  Window, level gate, chi2 gate, Hamming
+ * minimum, far rule, reduction and write are k_fuse_rank's own text (vslam_fuse_rank_body.inc).  No workgroup waits for another; every
+ * loop is bounded by nKF or by the 16 points of the block.
+ * ---------------------------------------------------------------------------------------------- */
+__global__ void __launch_bounds__(256)
+k_fuse_rank_rig(FuseRigArgs A) {
+    extern __shared__ __align__(16) uint8_t sbsm[];
+    SbpCand* cand = (SbpCand*)sbsm;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const FuseRigJobDev& J = A.job[blockIdx.y];
+    const vslam_kb8_camera& cam = A.cam[J.camera];
+    const int nKF = J.nKF;
+    const SiBounds bnd = A.bnd;
+    const SiBounds kbnd = si_kf_bounds(bnd);
+    const SiGridInv inv = si_grid_inv(bnd);
+    for (int i = tid; i < nKF; i += 256) cand[i] = sbp_make_cand(J.kps[i], -1.f, bnd, inv);
+    __syncthreads();
+    int32_t* bestIdx = A.bestIdx + (size_t)blockIdx.y * A.nPoints;
+    int32_t* bestDist = A.bestDist + (size_t)blockIdx.y * A.nPoints;
+    for (int q = blockIdx.x * FUSE_QPB + wave; q < min(A.nPoints, (int)(blockIdx.x + 1) * FUSE_QPB); q += 4) {
+        const FusePoint mp = A.pts[q];
+        uint32_t best = 0xFFFFFFFFu;
+        uint32_t far = 0xFFFFFFFFu; /* sim3: cell << 12 | index of the first candidate at distance 256 */
+        bool go = mp.valid != 0 && (!J.valid || J.valid[q] != 0); /* pMP && !isBad(), !IsInKeyFrame(pKF) */
+        float u = 0.f, v = 0.f, radius = 0.f;
+        int level = 0;
+        if (go) { /* wave-uniform */
+            const SbpPoint pc = sbp_transform(J.Rcw, J.tcw, mp.pos[0], mp.pos[1], mp.pos[2], A.gemmFloat);
+            go = !(pc.z < 0.0f);
+            if (go) {
+                const vslam_kb8::Uv uv = vslam_kb8::kb8_project(cam, pc.x, pc.y, pc.z);
+                u = uv.u;
+                v = uv.v;
+                go = u >= kbnd.minX && u < kbnd.maxX && v >= kbnd.minY && v < kbnd.maxY; /* KeyFrame::IsInImage */
+            }
+            if (go) {
+                const float p0 = __fsub_rn(mp.pos[0], J.Ow[0]), p1 = __fsub_rn(mp.pos[1], J.Ow[1]),
+                            p2 = __fsub_rn(mp.pos[2], J.Ow[2]);
+                const float dist3D = vslam_md::norm3(p0, p1, p2);
+                go = !(dist3D < mp.minDistance || dist3D > mp.maxDistance);
+                if (go) go = !(vslam_md::dot3_mat(p0, p1, p2, mp.normal) < __dmul_rn(0.5, (double)dist3D));
+                if (go) {
+                    level = vslam_md::predict_level(mp.maxDistance, dist3D, A.logScaleFactor, A.nlevels);
+                    radius = __fmul_rn(A.th, A.scale[level]);
+                }
+            }
+        }
+#define FUSE_NKF nKF
+#define FUSE_KF_DESC J.desc
+#define FUSE_SIM3 J.sim3
+#define FUSE_RIG 1
+#define FUSE_OFFSET J.idxOffset
+#define FUSE_BEST_IDX bestIdx
+#define FUSE_BEST_DIST bestDist
+#include "vslam_fuse_rank_body.inc"
+#undef FUSE_NKF
+#undef FUSE_KF_DESC
+#undef FUSE_SIM3
+#undef FUSE_RIG
+#undef FUSE_OFFSET
+#undef FUSE_BEST_IDX
+#undef FUSE_BEST_DIST
+    }
+}
+
+void vk_fuse_search_rig(hipStream_t st, const FuseRigArgs& A, int njobs, int maxKF) {
+    if (A.nPoints <= 0 || njobs <= 0) return;
+    hipLaunchKernelGGL(k_fuse_rank_rig, dim3((A.nPoints + FUSE_QPB - 1) / FUSE_QPB, njobs), dim3(256), vk_sbp_rank_lds(maxKF), st,
+                       A);
+}
+
 int vk_sbp_set_max_lds(size_t bytes) {
     int rc = (int)hipFuncSetAttribute((const void*)k_sbp_resolve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (rc) return rc;
+    rc = (int)hipFuncSetAttribute((const void*)k_fuse_rank_rig, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (rc) return rc;
     rc = (int)hipFuncSetAttribute((const void*)k_sbpm_resolve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (rc) return rc;

@@ -7,7 +7,8 @@
  *   rig_ok                                                                 x
  *   kb8_required                                                           x                    x
  *   rig_frame_ptrs_ok                                                                           x                  x
- *   rig_frame_check, rig_frame_stage, rig_jobs                             x                    x                     */
+ *   rig_frame_check, rig_frame_stage, rig_jobs                             x                    x
+ * vslam_fuse_rig uses sbp_prepare (the LDS limit) and kb8_required. */
 #ifndef VSLAM_SBP_HOST_H
 #define VSLAM_SBP_HOST_H
 #include "vslam_ctx.h"
