@@ -751,7 +751,7 @@ int vslam_fe_get_local_points_profile(vslam_fe* fe, double* frustum_ms, double* 
  * vslam_search_by_projection_mappoints_rig / vslam_search_local_points_rig below; the rig form of
  * SearchByProjection(CurrentFrame, LastFrame), right-camera branch :2593-2659 included, is vslam_search_by_projection_frame_rig.
  * Fuse(pKF, vpMapPoints, th, bRight) of a fisheye KeyFrame, both cameras of a rig, is vslam_fuse_search_rig.
- * Not covered: every other matcher's fisheye or right-camera branch (SearchForTriangulation, the relocalisation SearchByProjection(CurrentFrame, KeyFrame, ..), SearchBySim3; SearchByBoW of a rig is vslam_search_by_bow_rig), TriangulateMatches / epipolarConstrain / matchAndtriangulate (cv::SVD), ReconstructWithTwoViews
+ * Not covered: every other matcher's fisheye or right-camera branch (SearchForTriangulation; SearchBySim3 and SearchByProjection(pKF, Scw, vpPoints, vpPointsKFs, ..) project as a pinhole whatever the camera; SearchByBoW of a rig is vslam_search_by_bow_rig, the relocalisation and loop-closing SearchByProjection vslam_search_by_projection_keyframe_kb8 / _sim3_kb8), TriangulateMatches / epipolarConstrain / matchAndtriangulate (cv::SVD), ReconstructWithTwoViews
  * (cv::fisheye::undistortPoints), projectJac, tanf beyond 3*pi/4. */
 typedef struct vslam_kb8_camera {
     float fx, fy, cx, cy; /* mvParameters[0..3] */
@@ -1336,6 +1336,93 @@ int vslam_fuse_search_rig(vslam_fe* fe, const vslam_fuse_params* p, const vslam_
 /* With vslam_fe_set_profiling on: HIP-event time of k_fuse_rank_rig alone, summed over the searches waited for since
  * profiling was switched on.  Either pointer may be NULL. */
 int vslam_fe_get_fuse_rig_profile(vslam_fe* fe, double* rank_ms, long* passes);
+
+/* FMatcher::SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF, sAlreadyFound, th, ORBdist) (fmatcher.cpp:2689-2811) with a
+ * fisheye CurrentFrame: a monocular KB8 frame (Nleft == -1) or the left camera of a two-fisheye rig -- the matcher of
+ * Tracking::Relocalization (tracking.cpp:3570, :3584).  Blocking: Relocalization optimises the pose between its two calls.
+ * The arguments are those of vslam_search_by_projection_keyframe; a KB8 camera must be set (VSLAM_ERR_INVALID otherwise) and
+ * fx, fy, cx, cy of p must equal its intrinsics bit for bit.  Limits as there: 4096 current keypoints, 4096 KeyFrame entries.
+ * Restated as written, per KeyFrame entry i with mp_flags[i] & 1:
+ *   - x3Dc = Rcw * x3Dw + tcw as one gemm (gemm_float as elsewhere); uv = KannalaBrandt8::project(x3Dc)
+ *   - there is NO depth test: a point behind the camera is projected like any other (theta > pi / 2) and, where it lands inside
+ *     the bounds, goes on and can take a keypoint
+ *   - the closed interval over the Frame's float bounds mnMinX..mnMaxY (the context's grid bounds while some are set, else
+ *     {0, img_w, 0, img_h}); dist3D = cv::norm(x3Dw - Ow) within [min, max]; PredictScale; radius = th * scale[level];
+ *     GetFeaturesInArea(u, v, r, level - 1, level + 1)
+ *   - a rig: bRight defaults to false (frame.cpp:678-744), so only the left grid and keypoints_ are searched and only slots
+ *     [0, Nleft) are read or written: n_cur = Nleft, dev_cur_kps / dev_cur_desc the left arrays, and n_kf = NLeft + NRight
+ *     (GetMapPointMatches() has N entries)
+ *   - occupied slots are skipped; `dist < bestDist` from 256: the first of the window order wins a tie; bestDist <= ORBdist;
+ *     a written slot blocks later points; one rotation histogram, ComputeThreeMaxima, nmatches.
+ * ODDITY, NOT reproduced: with mbCheckOrientation :2774 reads pKF->mvKeysUn[i].angle for every i < N, but a rig KeyFrame's
+ * mvKeysUn has only NLeft entries (keyframe.cpp:40 copies F.ukeypoints_, which frame.cpp:764 set to keypoints_), so for a
+ * right-camera MapPoint, i >= NLeft, the reference reads past the end of the vector (undefined behaviour); the restatement
+ * reads the angle of mvKeysRight[i - NLeft].  kf_kps_host is therefore ONE array, mvKeys followed by mvKeysRight, as
+ * vslam_bow_rig_kf takes it. */
+int vslam_search_by_projection_keyframe_kb8(vslam_fe* fe, const vslam_proj_params* p, const float* Ow, float log_scale_factor,
+                                            int orb_dist, const vslam_kp* kf_kps_host, int n_kf, const uint8_t* mp_flags,
+                                            const float* mp_x3dw, const float* mp_min_dist, const float* mp_max_dist,
+                                            const uint8_t* mp_desc_host, const vslam_kp* dev_cur_kps,
+                                            const uint8_t* dev_cur_desc, int n_cur, const uint8_t* cur_occupied_host,
+                                            int32_t* match_cur, int* nmatches);
+
+/* FMatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th, ratioHamming) (fmatcher.cpp:750-863) for fisheye KeyFrames:
+ * ONE list of MapPoints against 1..16 (KeyFrame, Scw) jobs in one enqueue.  LoopClosing::DetectCommonRegionsFromBoW
+ * (loopclosing.cpp:668-684) calls FindMatchesByProjection (:751-803) for up to five covisible KeyFrames with the same
+ * pMostBoWMatchesKF, so with the same vpMapPoints, each with its own Sjw and a fresh vpMatched: jobs that do not interact.
+ * points[i].valid = !pMP->isBad(); a job's valid_host[i] = !spAlreadyFound.count(pMP) (NULL = all), kf_matched_host[idx] =
+ * vpMatched[idx] != NULL on entry (NULL = none); Rcw / tcw / Ow derived from Scw by the caller (:760-764) as for
+ * vslam_search_by_projection_sim3; dev_kps / dev_desc the KeyFrame's LEFT keypoints and descriptor rows.  A KB8 camera must be
+ * set (VSLAM_ERR_INVALID otherwise); a rig KeyFrame's mpCamera is the left one.  points / mp_desc / points_where as for
+ * vslam_fuse_search_rig_async (host or DEVICE arrays), up to VSLAM_LOCAL_POINTS_MAX points.
+ * Restated as written, per job and point in ascending iMP:
+ *   - p3Dc = Rcw * p3Dw + tcw as one gemm; z < 0 rejects, z == 0 goes on; KannalaBrandt8::project with the context's camera
+ *   - KeyFrame::IsInImage over the KeyFrame's integer bounds, closed below and open above; cv::norm(p3Dw - Ow) within the
+ *     range; PO.dot(Pn) < 0.5 * dist rejects (both sides in double); PredictScale; radius = th * scale[level] (th an int)
+ *   - KeyFrame::GetFeaturesInArea(u, v, r) over the left grid: columns outer, rows inner, ascending index within a cell;
+ *     matched keypoints are skipped; level gate [level - 1, level]; `dist < bestDist` from 256; accepted on bestDist <=
+ *     TH_LOW * ratioHamming (the float product floored, capped at 255); vpMatched[bestIdx] = pMP blocks later points; no
+ *     rotation check.
+ * The list is long (the MapPoints of a KeyFrame, of its covisibles and of theirs): a gate pass over (job, point) evaluates
+ * everything up to the radius, an order-preserving compaction hands the 4096-wide matcher only a job's survivors, and the
+ * reported match_kf[idx] is the ORIGINAL iMP.  _wait delivers per job match_kf[j] (n_kf entries), nmatches[j] and n_gated[j]
+ * (the survivors).  A job with more than 4096 survivors gets nmatches -1 and -1 in every entry; the call then returns
+ * VSLAM_ERR_UNSUPPORTED after the other jobs' results are delivered (run that job through the host twin).
+ * n_jobs outside 1..16 or a misaligned pointer (dev_desc and device mp_desc 16 bytes, dev_kps and device points 4):
+ * VSLAM_ERR_INVALID.  n_points > VSLAM_LOCAL_POINTS_MAX or a job with n_kf > 4096: VSLAM_ERR_UNSUPPORTED.  Nothing is enqueued
+ * then, and the blocking form leaves -1 in every output of every job (for n_jobs > 16 too: the caller sized them by n_jobs).
+ * n_points == 0 and jobs with n_kf == 0 are ordinary inputs with empty results.  One upload, no host wait between the launches
+ * (k_s3k_gate, k_s3k_compact, k_sbp_rank_kb8, k_sbp_resolve, k_sbp_replay, k_s3k_finish), one result copy; the staging block
+ * is the entry's own, so the blocking matchers may run between _async and _wait.  One search per context may be in flight: a
+ * second _async is VSLAM_ERR_INVALID. */
+#define VSLAM_SIM3_KB8_MAX_JOBS 16
+typedef struct vslam_sim3_kb8_job {   /* one call of SearchByProjection(pKF, Scw, vpPoints, vpMatched, th, ratioHamming) */
+    float Rcw[9], tcw[3], Ow[3];      /* sRcw / scw, Scw's translation / scw, -Rcw^T tcw (fmatcher.cpp:760-764) */
+    const vslam_kp* dev_kps;          /* pKF's left keypoints (mvKeysUn), DEVICE, 4-byte aligned */
+    const uint8_t* dev_desc;          /* mDescriptors rows [0, n_kf), DEVICE, 16-byte aligned */
+    int32_t n_kf;                     /* <= 4096 */
+    int32_t pad;
+    const uint8_t* kf_matched_host;   /* n_kf bytes: vpMatched[idx] != NULL on entry; NULL = none */
+    const uint8_t* valid_host;        /* n_points bytes: !spAlreadyFound.count(pMP); NULL = all 1 */
+} vslam_sim3_kb8_job;
+typedef struct vslam_sim3_kb8_params {
+    int32_t th;                       /* an int in this overload */
+    float ratio_hamming;
+    float log_scale_factor;           /* pKF->mfLogScaleFactor */
+    int32_t img_w, img_h;             /* the bounds while vslam_fe_set_grid_bounds has set none */
+    int32_t gemm_float;
+} vslam_sim3_kb8_params;
+int vslam_search_by_projection_sim3_kb8_async(vslam_fe* fe, const vslam_sim3_kb8_params* p, const vslam_sim3_kb8_job* jobs,
+                                              int n_jobs, const vslam_fuse_point* points, const uint8_t* mp_desc, int n_points,
+                                              int points_where);
+int vslam_search_by_projection_sim3_kb8_wait(vslam_fe* fe, int32_t* const* match_kf, int* nmatches, int* n_gated);
+/* _async + _wait */
+int vslam_search_by_projection_sim3_kb8(vslam_fe* fe, const vslam_sim3_kb8_params* p, const vslam_sim3_kb8_job* jobs, int n_jobs,
+                                        const vslam_fuse_point* points, const uint8_t* mp_desc, int n_points, int points_where,
+                                        int32_t* const* match_kf, int* nmatches, int* n_gated);
+/* With vslam_fe_set_profiling on: HIP-event time of gate + compaction, of the ranking and of the resolution (k_sbp_resolve,
+ * k_sbp_replay, k_s3k_finish), summed over the searches waited for since.  Any pointer may be NULL. */
+int vslam_fe_get_sim3_kb8_profile(vslam_fe* fe, double* gate_ms, double* rank_ms, double* resolve_ms, long* passes);
 
 /* Evaluate the device float helpers on host arrays (round trip through HBM): the glibc-exact sinf/cosf
  * used for the rBRIEF rotation (fextractor.cpp:103-104) and cv::fastAtan2 (fextractor.cpp:94). */

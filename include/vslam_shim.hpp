@@ -67,6 +67,13 @@ extern "C" int vslamh_fuse_search_rig(const vslam_fuse_params* p, const vslam_kb
                                       const uint8_t* mp_desc, int n_points, const float* scale_factors, const float* inv_sigma2,
                                       int nlevels, const float* bounds, int32_t* best_idx, int32_t* best_dist);
 
+/* the loop-closing SearchByProjection for fisheye KeyFrames over host arrays (a job's dev_kps / dev_desc are HOST pointers here):
+ * what FMatcher::FindMatchesByProjectionKB8 runs for a job whose survivors exceed the device's 4096 */
+extern "C" int vslamh_search_by_projection_sim3_kb8(const vslam_sim3_kb8_params* p, const vslam_kb8_camera* cam,
+                                                    const vslam_sim3_kb8_job* jobs, int n_jobs, const vslam_fuse_point* points,
+                                                    const uint8_t* mp_desc, int n_points, const float* scale_factors, int nlevels,
+                                                    const float* bounds, int32_t* const* match_kf, int* nmatches, int* n_gated);
+
 namespace VSLAM_SHIM_NAMESPACE {
 namespace geometry {
 
@@ -875,6 +882,113 @@ public:
             check(vslam_fuse_search_rig(extractor.context(), &p, rig, jobs.data() + first, K, points.data(),
                                         mapPointDescriptors.data(), (int)n, VSLAM_IMGS_HOST, bestIdx.data() + first * n,
                                         bestDist.data() + first * n));
+        }
+    }
+
+    /* FMatcher::SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF, sAlreadyFound, th, ORBdist) (fmatcher.cpp:2689-2811) with
+     * a fisheye CurrentFrame -- Tracking::Relocalization's matcher for a monocular KB8 frame or the left camera of a two-fisheye
+     * rig.  extractor: the context that extracted the frame (of a rig the LEFT camera's: only keypoints_ and slots [0, Nleft) take
+     * part), with the KannalaBrandt8 of mpCamera attached; camera: its parameters (fx .. cy travel in the projection record).
+     * Tcw: rows [Rcw | tcw] of CurrentFrame.T_w_c_, Ow = -Rcw^T tcw.  Per entry i of pKF->GetMapPointMatches() (N = NLeft +
+     * NRight entries for a rig KeyFrame): keyFrameKeys[i] = mvKeys followed by mvKeysRight (the reference reads mvKeysUn[i].angle
+     * past its end for i >= NLeft; the right keypoint's angle is read instead), mapPointFlags[i] & 1 = pMP && !isBad() &&
+     * !sAlreadyFound.count(pMP), position (3 floats), Get{Min,Max}DistanceInvariance(), descriptor.  occupied (may be NULL): one
+     * byte per current keypoint, CurrentFrame.mvpMapPoints[i2] != NULL.  matchCur[i2] = i or -1; returns nmatches. */
+    int SearchByProjectionKeyFrameKB8(const FExtractor& extractor, const vslam_kb8_camera& camera, const float* Tcw,
+                                      const float* Ow, const float th, const int ORBdist, const float logScaleFactor,
+                                      const int imgW, const int imgH, const std::vector<KeyPoint>& keyFrameKeys,
+                                      const std::vector<uint8_t>& mapPointFlags, const std::vector<float>& x3Dw,
+                                      const std::vector<float>& minDistance, const std::vector<float>& maxDistance,
+                                      const std::vector<uint8_t>& mapPointDescriptors, const std::vector<uint8_t>* occupied,
+                                      std::vector<int>& matchCur, const bool gemmFloat = false) {
+        static_assert(sizeof(int) == sizeof(int32_t), "the results are handed over as int32");
+        const size_t n = keyFrameKeys.size();
+        if (mapPointFlags.size() != n || x3Dw.size() != 3 * n || minDistance.size() != n || maxDistance.size() != n ||
+            mapPointDescriptors.size() != 32 * n)
+            throw std::invalid_argument("SearchByProjectionKeyFrameKB8: one flag, position, range and descriptor per entry");
+        vslam_proj_params p;
+        std::memset(&p, 0, sizeof(p));
+        std::memcpy(p.Tcw, Tcw, sizeof(p.Tcw));
+        p.fx = camera.fx; p.fy = camera.fy; p.cx = camera.cx; p.cy = camera.cy;
+        p.th = th;
+        p.check_orientation = mbCheckOrientation ? 1 : 0;
+        p.img_w = imgW;
+        p.img_h = imgH;
+        p.gemm_float = gemmFloat ? 1 : 0;
+        const vslam_kp* dk = nullptr;
+        const uint8_t* dd = nullptr;
+        int nCur = 0;
+        check(vslam_fe_slot_buffers(extractor.context(), 0, &dk, &dd, &nCur));
+        if (occupied && occupied->size() != (size_t)nCur)
+            throw std::invalid_argument("SearchByProjectionKeyFrameKB8: one occupancy byte per current keypoint");
+        matchCur.assign((size_t)nCur, -1);
+        int nm = 0;
+        check(vslam_search_by_projection_keyframe_kb8(extractor.context(), &p, Ow, logScaleFactor, ORBdist,
+                                                      reinterpret_cast<const vslam_kp*>(keyFrameKeys.data()), (int)n,
+                                                      mapPointFlags.data(), x3Dw.data(), minDistance.data(), maxDistance.data(),
+                                                      mapPointDescriptors.data(), dk, dd, nCur, occupied ? occupied->data() : nullptr,
+                                                      matchCur.data(), &nm));
+        return nm;
+    }
+
+    /* LoopClosing::FindMatchesByProjection's batch (loopclosing.cpp:668-684, :751-803) for fisheye KeyFrames: ONE list of
+     * MapPoints -- those of pMostBoWMatchesKF, of its covisibles and of theirs -- against the covisible KeyFrames as jobs, each
+     * one call of SearchByProjection(pKFj, Sjw, vpMapPoints, vpMatched, th, ratioHamming) (fmatcher.cpp:750-863).  A job is a
+     * vslam_sim3_kb8_job (include/vslam_fe.h): Rcw / tcw / Ow derived from Sjw, pKFj's left keypoints and descriptor rows in HBM,
+     * vpMatched != NULL bytes, !spAlreadyFound bytes.  Any number of jobs: 16 per enqueue.  hostJobs (may be NULL): the same jobs
+     * with dev_kps / dev_desc pointing at HOST copies; a job whose survivors exceed the device's 4096 (nmatches -1) is then run by
+     * the host twin, and without them the refusal is thrown.  camera: mpCamera's parameters, for the twin.
+     * matchKf[j][idx] = iMP (vpMatched[idx] = vpMapPoints[iMP]) or -1; nmatches[j]; nGated[j] = points behind the gates. */
+    void FindMatchesByProjectionKB8(FExtractor& extractor, const vslam_kb8_camera& camera,
+                                    const std::vector<vslam_sim3_kb8_job>& jobs, const std::vector<vslam_sim3_kb8_job>* hostJobs,
+                                    const std::vector<vslam_fuse_point>& points, const std::vector<uint8_t>& mapPointDescriptors,
+                                    const int th, const float ratioHamming, const float logScaleFactor, const int imgW,
+                                    const int imgH, std::vector<std::vector<int>>& matchKf, std::vector<int>& nmatches,
+                                    std::vector<int>& nGated, const bool gemmFloat = false) {
+        static_assert(sizeof(int) == sizeof(int32_t), "the results are handed over as int32");
+        if (mapPointDescriptors.size() != 32 * points.size())
+            throw std::invalid_argument("FindMatchesByProjectionKB8: one descriptor per MapPoint");
+        if (hostJobs && hostJobs->size() != jobs.size())
+            throw std::invalid_argument("FindMatchesByProjectionKB8: one host job per job");
+        vslam_sim3_kb8_params p;
+        std::memset(&p, 0, sizeof(p));
+        p.th = th;
+        p.ratio_hamming = ratioHamming;
+        p.log_scale_factor = logScaleFactor;
+        p.img_w = imgW;
+        p.img_h = imgH;
+        p.gemm_float = gemmFloat ? 1 : 0;
+        matchKf.assign(jobs.size(), std::vector<int>());
+        nmatches.assign(jobs.size(), 0);
+        nGated.assign(jobs.size(), 0);
+        std::vector<int32_t*> out(jobs.size());
+        for (size_t j = 0; j < jobs.size(); j++) {
+            matchKf[j].assign((size_t)std::max(jobs[j].n_kf, 0), -1);
+            out[j] = matchKf[j].data();
+        }
+        for (size_t first = 0; first < jobs.size(); first += VSLAM_SIM3_KB8_MAX_JOBS) {
+            const int K = (int)std::min<size_t>(VSLAM_SIM3_KB8_MAX_JOBS, jobs.size() - first);
+            const int rc = vslam_search_by_projection_sim3_kb8(extractor.context(), &p, jobs.data() + first, K, points.data(),
+                                                               mapPointDescriptors.data(), (int)points.size(), VSLAM_IMGS_HOST,
+                                                               out.data() + first, nmatches.data() + first, nGated.data() + first);
+            if (rc != VSLAM_ERR_UNSUPPORTED || !hostJobs) check(rc);
+            if (rc != VSLAM_ERR_UNSUPPORTED) continue;
+            const std::vector<float> sf = extractor.GetScaleFactors();
+            vslam_bounds b;
+            int is_set = 0;
+            check(vslam_fe_get_grid_bounds(extractor.context(), &b, &is_set));
+            const float bounds[4] = {is_set ? b.min_x : 0.0f, is_set ? b.max_x : (float)imgW, is_set ? b.min_y : 0.0f,
+                                     is_set ? b.max_y : (float)imgH};
+            bool any = false;
+            for (size_t j = first; j < first + (size_t)K; j++) {
+                if (nmatches[j] != -1) continue; /* delivered */
+                any = true;
+                check(vslamh_search_by_projection_sim3_kb8(&p, &camera, hostJobs->data() + j, 1, points.data(),
+                                                           mapPointDescriptors.data(), (int)points.size(), sf.data(),
+                                                           (int)sf.size(), bounds, out.data() + j, nmatches.data() + j,
+                                                           nGated.data() + j));
+            }
+            if (!any) check(rc); /* refused as a whole: a KeyFrame or a list beyond the limits */
         }
     }
 

@@ -70,6 +70,8 @@ ABI_SYMBOLS = [
     "vslam_search_by_bow_rig_async", "vslam_search_by_bow_rig_wait", "vslam_search_by_bow_rig",
     "vslam_fe_get_bow_rig_profile", "vslam_search_by_bow_keyframes_rig",
     "vslam_fuse_search_rig_async", "vslam_fuse_search_rig_wait", "vslam_fuse_search_rig", "vslam_fe_get_fuse_rig_profile",
+    "vslam_search_by_projection_keyframe_kb8", "vslam_search_by_projection_sim3_kb8_async",
+    "vslam_search_by_projection_sim3_kb8_wait", "vslam_search_by_projection_sim3_kb8", "vslam_fe_get_sim3_kb8_profile",
     "vslam_two_view_score_async", "vslam_two_view_score_wait", "vslam_two_view_score", "vslam_fe_get_two_view_profile",
     "vslam_kfdb_create", "vslam_kfdb_create_ex", "vslam_kfdb_destroy", "vslam_kfdb_add", "vslam_kfdb_erase",
     "vslam_kfdb_clear", "vslam_kfdb_clear_map", "vslam_kfdb_size", "vslam_kfdb_stats", "vslam_kfdb_query_async",
@@ -417,6 +419,121 @@ def fuse_search_rig_host(cam, rig, jobs, points, mp_desc, th, log_scale_factor, 
     return bi[:n].reshape(len(jobs), len(pts)), bd[:n].reshape(len(jobs), len(pts))
 
 
+SIM3_KB8_MAX_JOBS = 16
+
+
+class _Sim3Kb8Job(C.Structure):  # vslam_sim3_kb8_job
+    _fields_ = [("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("Ow", C.c_float * 3), ("dev_kps", C.c_void_p),
+                ("dev_desc", C.c_void_p), ("n_kf", C.c_int32), ("pad", C.c_int32), ("kf_matched_host", C.c_void_p),
+                ("valid_host", C.c_void_p)]
+
+
+class _Sim3Kb8Params(C.Structure):  # vslam_sim3_kb8_params
+    _fields_ = [("th", C.c_int32), ("ratio_hamming", C.c_float), ("log_scale_factor", C.c_float), ("img_w", C.c_int32),
+                ("img_h", C.c_int32), ("gemm_float", C.c_int32)]
+
+
+def sim3_kb8_job(Rcw, tcw, Ow, kps, desc, n_kf, matched=None, valid=None):
+    """vslam_sim3_kb8_job: one call of SearchByProjection(pKF, Scw, vpPoints, vpMatched, th, ratioHamming) on a fisheye
+    KeyFrame.  Rcw / tcw / Ow as the function derives them from Scw; kps / desc: addresses of pKF's left keypoints and
+    descriptor rows (DEVICE memory for FExtractor.search_by_projection_sim3_kb8, host memory for the _host twin); matched: one
+    byte per keypoint, vpMatched[idx] != NULL, or None; valid: one byte per MapPoint, !spAlreadyFound.count(pMP), or None.  The
+    returned object keeps both arrays alive."""
+    j = _Sim3Kb8Job()
+    j.Rcw[:] = [float(v) for v in np.asarray(Rcw, np.float32).reshape(9)]
+    j.tcw[:] = [float(v) for v in np.asarray(tcw, np.float32).reshape(3)]
+    j.Ow[:] = [float(v) for v in np.asarray(Ow, np.float32).reshape(3)]
+    j.n_kf = int(n_kf)
+    j.dev_kps, j.dev_desc = kps or None, desc or None
+    m = None if matched is None else np.ascontiguousarray(matched, np.uint8)
+    v = None if valid is None else np.ascontiguousarray(valid, np.uint8)
+    if m is not None and len(m) != j.n_kf:
+        raise ValueError("matched holds one byte per keypoint")
+    j.kf_matched_host = m.ctypes.data if m is not None and len(m) else None
+    j.valid_host = v.ctypes.data if v is not None and len(v) else None
+    j._keep = (m, v)
+    return j
+
+
+def _sim3_kb8_params(th, ratio_hamming, log_scale_factor, img_size, gemm_float=False):
+    P = _Sim3Kb8Params()
+    P.th, P.ratio_hamming, P.log_scale_factor = int(th), float(ratio_hamming), float(log_scale_factor)
+    P.img_w, P.img_h, P.gemm_float = int(img_size[0]), int(img_size[1]), int(gemm_float)
+    return P
+
+
+def _sim3_kb8_jobs(jobs, n_points):
+    """the job array of vslam_search_by_projection_sim3_kb8; every job's validity bytes must cover the points"""
+    for j in jobs:
+        if j._keep[1] is not None and len(j._keep[1]) != n_points:
+            raise ValueError("a job's valid array must have one byte per MapPoint")
+    arr = (_Sim3Kb8Job * max(len(jobs), 1))()
+    for k, j in enumerate(jobs):
+        C.memmove(C.byref(arr, k * C.sizeof(_Sim3Kb8Job)), C.byref(j), C.sizeof(_Sim3Kb8Job))
+    return arr
+
+
+def _sim3_kb8_outputs(jobs, fill=-1):
+    """per job a match_kf array, the pointer array over them, nmatches and n_gated"""
+    ms = [np.full(max(j.n_kf, 1), fill, np.int32) for j in jobs]
+    ptrs = (C.c_void_p * max(len(jobs), 1))(*[m.ctypes.data for m in ms])
+    return ms, ptrs, np.full(max(len(jobs), 1), fill, np.int32), np.full(max(len(jobs), 1), fill, np.int32)
+
+
+def search_by_projection_sim3_kb8_host(cam, jobs, points, mp_desc, th, ratio_hamming, log_scale_factor, img_size,
+                                       scale_factors, bounds=None, gemm_float=False, library=None):
+    """vslamh_search_by_projection_sim3_kb8 (libvslam_host.so, GPU-free): the loop-closing SearchByProjection for fisheye
+    KeyFrames over host arrays, any number of jobs (sim3_kb8_job with host addresses), points and survivors.
+    -> (match_kf: one int32 array per job, nmatches[n_jobs], n_gated[n_jobs])"""
+    L = library if library is not None else host_lib()
+    vp, i = C.c_void_p, C.c_int
+    L.vslamh_search_by_projection_sim3_kb8.argtypes = [vp, vp, vp, i, vp, vp, i, vp, i, vp, vp, vp, vp]
+    pts = np.ascontiguousarray(points, FUSE_POINT_DTYPE)
+    md = np.ascontiguousarray(mp_desc, np.uint8).reshape(-1, 32)
+    if len(md) != len(pts):
+        raise ValueError("one descriptor per MapPoint")
+    sf = np.ascontiguousarray(scale_factors, np.float32)
+    b = np.ascontiguousarray(bounds if bounds is not None else (0, img_size[0], 0, img_size[1]), np.float32)
+    P = _sim3_kb8_params(th, ratio_hamming, log_scale_factor, img_size, gemm_float)
+    arr = _sim3_kb8_jobs(jobs, len(pts))
+    ms, ptrs, nm, ng = _sim3_kb8_outputs(jobs)
+    rc = L.vslamh_search_by_projection_sim3_kb8(C.byref(P), C.byref(cam), arr, len(jobs), _p(pts), _p(md), len(pts), _p(sf),
+                                                len(sf), _p(b), ptrs, _p(nm), _p(ng))
+    if rc:
+        raise VslamError(rc, "vslamh_search_by_projection_sim3_kb8: invalid arguments")
+    return [m[:j.n_kf] for m, j in zip(ms, jobs)], nm[:len(jobs)], ng[:len(jobs)]
+
+
+def search_by_projection_keyframe_kb8_host(cam, Tcw, Ow, th, ORBdist, log_scale_factor, kf_kps, mp_flags, mp_x3dw, mp_min_dist,
+                                           mp_max_dist, mp_desc, cur_kps, cur_desc, img_size, scale_factors, occupied=None,
+                                           bounds=None, check_orientation=True, gemm_float=False, library=None):
+    """vslamh_search_by_projection_keyframe_kb8 (libvslam_host.so, GPU-free): the relocalisation SearchByProjection with a
+    fisheye CurrentFrame over host arrays.  kf_kps: mvKeys followed by mvKeysRight.  -> (nmatches, match_cur[n_cur])"""
+    L = library if library is not None else host_lib()
+    vp, i = C.c_void_p, C.c_int
+    L.vslamh_search_by_projection_keyframe_kb8.argtypes = [vp, vp, vp, C.c_float, i, vp, i, vp, vp, vp, vp, vp, vp, vp, i, vp,
+                                                           vp, i, vp, vp, vp]
+    P = proj_params(Tcw, (cam.fx, cam.fy, cam.cx, cam.cy), th, img_size, check_orientation=check_orientation,
+                    gemm_float=gemm_float)
+    kk, ck = np.ascontiguousarray(kf_kps, KP_DTYPE), np.ascontiguousarray(cur_kps, KP_DTYPE)
+    fl, x = np.ascontiguousarray(mp_flags, np.uint8), np.ascontiguousarray(mp_x3dw, np.float32)
+    mn, mx = np.ascontiguousarray(mp_min_dist, np.float32), np.ascontiguousarray(mp_max_dist, np.float32)
+    md, cd = np.ascontiguousarray(mp_desc, np.uint8), np.ascontiguousarray(cur_desc, np.uint8)
+    oc = None if occupied is None else np.ascontiguousarray(occupied, np.uint8)
+    O = np.ascontiguousarray(Ow, np.float32).reshape(3)
+    sf = np.ascontiguousarray(scale_factors, np.float32)
+    b = np.ascontiguousarray(bounds if bounds is not None else (0, img_size[0], 0, img_size[1]), np.float32)
+    m = np.full(max(len(ck), 1), -1, np.int32)
+    nm = C.c_int(0)
+    rc = L.vslamh_search_by_projection_keyframe_kb8(C.byref(P), C.byref(cam), _p(O), C.c_float(log_scale_factor), int(ORBdist),
+                                                    _p(kk), len(kk), _p(fl), _p(x), _p(mn), _p(mx), _p(md), _p(ck), _p(cd),
+                                                    len(ck), _p(oc) if oc is not None else None, _p(sf), len(sf), _p(b), _p(m),
+                                                    C.byref(nm))
+    if rc:
+        raise VslamError(rc, "vslamh_search_by_projection_keyframe_kb8: invalid arguments")
+    return nm.value, m[:len(ck)]
+
+
 class _BowRigKf(C.Structure):  # vslam_bow_rig_kf
     _fields_ = [("dev_desc_left", C.c_void_p), ("n_left", C.c_int), ("dev_desc_right", C.c_void_p), ("n_right", C.c_int),
                 ("kps_host", C.c_void_p), ("flags_host", C.c_void_p), ("fv_nodes", C.c_void_p), ("fv_off", C.c_void_p),
@@ -660,6 +777,12 @@ def lib():
                                                       vp, vp, vp]
         L.vslam_search_by_projection_keyframe.argtypes = [vp, vp, vp, C.c_float, i, vp, i, vp, vp, vp, vp, vp, vp, vp, i, vp,
                                                           vp, vp]
+        L.vslam_search_by_projection_keyframe_kb8.argtypes = L.vslam_search_by_projection_keyframe.argtypes
+        L.vslam_search_by_projection_sim3_kb8_async.argtypes = [vp, vp, vp, i, vp, vp, i, i]
+        L.vslam_search_by_projection_sim3_kb8_wait.argtypes = [vp, vp, vp, vp]
+        L.vslam_search_by_projection_sim3_kb8.argtypes = [vp, vp, vp, i, vp, vp, i, i, vp, vp, vp]
+        L.vslam_fe_get_sim3_kb8_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                    C.POINTER(C.c_long)]
         L.vslam_search_by_projection_dev_async.argtypes = [vp, i, vp]
         L.vslam_search_by_projection_dev_wait.argtypes = [vp, vp, vp, vp]
         L.vslam_stereo_points_dev_async.argtypes = [vp, i, vp, C.c_float, C.c_float, C.c_float, C.c_float, i, i]
@@ -1448,6 +1571,69 @@ class FExtractor:
         _check(lib().vslam_fe_get_fuse_rig_profile(self._h, C.byref(a), C.byref(n)))
         return a.value, n.value
 
+    def _sim3_kb8_call(self, jobs, points, mp_desc, th, ratio_hamming, log_scale_factor, img_size, gemm_float, n_points):
+        """the arguments of vslam_search_by_projection_sim3_kb8[_async] up to points_where, and what keeps their host arrays
+        alive"""
+        on_dev = isinstance(points, int)
+        if on_dev:
+            if n_points is None:
+                raise ValueError("n_points is required with device addresses")
+            keep, pp, dp = (), C.c_void_p(points), C.c_void_p(int(mp_desc))
+        else:
+            keep = (np.ascontiguousarray(points, FUSE_POINT_DTYPE), np.ascontiguousarray(mp_desc, np.uint8).reshape(-1, 32))
+            if len(keep[0]) != len(keep[1]):
+                raise ValueError("one descriptor per MapPoint")
+            n_points = len(keep[0])
+            pp, dp = _p(keep[0]), _p(keep[1])
+        P = _sim3_kb8_params(th, ratio_hamming, log_scale_factor, img_size or (self.width, self.height), gemm_float)
+        arr = _sim3_kb8_jobs(jobs, n_points)
+        head = (self._h, C.byref(P), arr, len(jobs), pp, dp, n_points, IMGS_DEVICE if on_dev else IMGS_HOST)
+        return head, (keep, P, arr, list(jobs))
+
+    def search_by_projection_sim3_kb8_async(self, jobs, points, mp_desc, th, ratio_hamming, log_scale_factor, img_size=None,
+                                            gemm_float=False, n_points=None):
+        """Enqueue FMatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th, ratioHamming) (fmatcher.cpp:750-863) for
+        fisheye KeyFrames: ONE MapPoint list against up to 16 jobs from sim3_kb8_job() (device addresses), and return.
+        points / mp_desc: numpy arrays (FUSE_POINT_DTYPE with valid = !isBad(), n x 32 uint8), or two device addresses (ints)
+        with n_points given."""
+        head, keep = self._sim3_kb8_call(jobs, points, mp_desc, th, ratio_hamming, log_scale_factor, img_size, gemm_float,
+                                         n_points)
+        _check(lib().vslam_search_by_projection_sim3_kb8_async(*head))
+        self._s3k_keep = keep
+
+    def search_by_projection_sim3_kb8_wait(self):
+        """-> (match_kf: per job an int32 array, match_kf[idx] = iMP or -1; nmatches[n_jobs]; n_gated[n_jobs]).  A job with
+        more than 4096 points behind its gates has nmatches -1; the call then raises ERR_UNSUPPORTED, and what was delivered
+        stays in last_sim3_kb8_outputs."""
+        keep = getattr(self, "_s3k_keep", None)
+        jobs = keep[3] if keep else []  # nothing enqueued: the library says so
+        ms, ptrs, nm, ng = _sim3_kb8_outputs(jobs)
+        rc = lib().vslam_search_by_projection_sim3_kb8_wait(self._h, ptrs, _p(nm), _p(ng))
+        self._s3k_keep = None
+        out = ([m[:j.n_kf] for m, j in zip(ms, jobs)], nm[:len(jobs)], ng[:len(jobs)])
+        self.last_sim3_kb8_outputs = out
+        _check(rc)
+        return out
+
+    def search_by_projection_sim3_kb8(self, jobs, points, mp_desc, th, ratio_hamming, log_scale_factor, img_size=None,
+                                      gemm_float=False, n_points=None):
+        """search_by_projection_sim3_kb8_async + _wait, through the blocking entry point.  What a refused call left in its
+        outputs stays in last_sim3_kb8_outputs."""
+        head, keep = self._sim3_kb8_call(jobs, points, mp_desc, th, ratio_hamming, log_scale_factor, img_size, gemm_float,
+                                         n_points)
+        ms, ptrs, nm, ng = _sim3_kb8_outputs(jobs, fill=7)
+        out = ([m[:j.n_kf] for m, j in zip(ms, jobs)], nm[:len(jobs)], ng[:len(jobs)])
+        self.last_sim3_kb8_outputs = out
+        _check(lib().vslam_search_by_projection_sim3_kb8(*head, ptrs, _p(nm), _p(ng)))
+        return out
+
+    def get_sim3_kb8_profile(self):
+        """-> (ms in k_s3k_gate + k_s3k_compact, ms in k_sbp_rank_kb8, ms in the resolution, searches) since
+        set_profiling(True)"""
+        a, b, c, n = C.c_double(0), C.c_double(0), C.c_double(0), C.c_long(0)
+        _check(lib().vslam_fe_get_sim3_kb8_profile(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(n)))
+        return a.value, b.value, c.value, n.value
+
     def two_view_score_async(self, jobs):
         """Enqueue MotionEstimator::CheckHomography / CheckFundamental of every hypothesis and the selection of
         FindHomography / FindFundamental (motion_estimation.cpp:2096-2195, 2277-2440) for up to 32 frame pairs and return.
@@ -1917,6 +2103,31 @@ class FMatcher:
         m = np.full(max(n_cur, 1), -1, np.int32)
         nm = C.c_int(0)
         _check(lib().vslam_search_by_projection_keyframe(
+            self.fe._h, C.byref(P), _p(O), C.c_float(log_scale_factor), int(ORBdist), _p(kk), len(kk), _p(fl), _p(x), _p(mn),
+            _p(mx), _p(md), C.c_void_p(dev_cur_kps), C.c_void_p(dev_cur_desc), n_cur, _p(oc) if oc is not None else None,
+            _p(m), C.byref(nm)))
+        return nm.value, m[:n_cur]
+
+    def SearchByProjectionKeyFrameKB8(self, Tcw, Ow, cam, th, ORBdist, log_scale_factor, kf_kps, mp_flags, mp_x3dw,
+                                      mp_min_dist, mp_max_dist, mp_desc, dev_cur_kps, dev_cur_desc, n_cur, occupied=None,
+                                      img_size=None, gemm_float=False):
+        """FMatcher::SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (fmatcher.cpp:2689-2811) with a fisheye
+        CurrentFrame: a monocular KB8 frame or the left camera of a rig (n_cur = Nleft).  cam = (fx, fy, cx, cy) of the KB8
+        camera set on the extractor; kf_kps: mvKeys followed by mvKeysRight (n_kf = NLeft + NRight entries).
+        -> (nmatches, match_cur[n_cur] = pKF entry index or -1)."""
+        kk = np.ascontiguousarray(kf_kps, KP_DTYPE)
+        fl = np.ascontiguousarray(mp_flags, np.uint8)
+        x = np.ascontiguousarray(mp_x3dw, np.float32)
+        mn = np.ascontiguousarray(mp_min_dist, np.float32)
+        mx = np.ascontiguousarray(mp_max_dist, np.float32)
+        md = np.ascontiguousarray(mp_desc, np.uint8)
+        oc = None if occupied is None else np.ascontiguousarray(occupied, np.uint8)
+        O = np.ascontiguousarray(Ow, np.float32).reshape(3)
+        P = proj_params(Tcw, cam, th, img_size or (self.fe.width, self.fe.height),
+                        check_orientation=self.mbCheckOrientation, gemm_float=gemm_float)
+        m = np.full(max(n_cur, 1), -1, np.int32)
+        nm = C.c_int(0)
+        _check(lib().vslam_search_by_projection_keyframe_kb8(
             self.fe._h, C.byref(P), _p(O), C.c_float(log_scale_factor), int(ORBdist), _p(kk), len(kk), _p(fl), _p(x), _p(mn),
             _p(mx), _p(md), C.c_void_p(dev_cur_kps), C.c_void_p(dev_cur_desc), n_cur, _p(oc) if oc is not None else None,
             _p(m), C.byref(nm)))

@@ -213,6 +213,14 @@ struct vslam_fe {
     vslam_pending fsr_op;       /* jobs: the jobs, n: the MapPoints */
     size_t fsr_o_bi = 0, fsr_o_bd = 0;
     vslam_span_timer<1> t_fsr;  /* around k_fuse_rank_rig */
+    /* SearchByProjection(pKF, Scw, ..) for fisheye KeyFrames, up to 16 (KeyFrame, Scw) jobs over one MapPoint list
+     * (vslam_search_by_projection_sim3_kb8_async, vslam_sim3_kb8.hip): a block of its own for the same reason */
+    vslam_staging s3k;          /* points | descriptors (host points only) | per job: validity bytes | per job: vpMatched bytes | per job: match_kf | nmatches, n_gated */
+    vslam_dbuf<uint8_t> d_s3k;  /* HBM only: gate records | chunk counts | counts | needSeq | per job: matcher scratch, compacted arrays */
+    vslam_pending s3k_op;       /* jobs: the jobs, n: the MapPoints */
+    int s3k_nkf[16] = {};       /* keypoints per job: what _wait sizes match_kf by */
+    size_t s3k_o_m[16] = {}, s3k_o_res = 0;
+    vslam_span_timer<3> t_s3k;  /* before k_s3k_gate | behind k_s3k_compact | behind k_sbp_rank_kb8 | behind k_s3k_finish */
 
     /* GPU quadtree distribution */
     bool dev_octree = false;
@@ -244,6 +252,7 @@ struct vslam_fe {
         t_fr.reset();
         t_sbr.reset();
         t_fsr.reset();
+        t_s3k.reset();
     }
 
     WorkerPool* pool = nullptr;

@@ -294,6 +294,36 @@ struct RigFrameDev {
     int32_t* fallbacks;       /* diagnostics: full re-scans, may be null */
 };
 
+/* vslam_search_by_projection_sim3_kb8 (k_s3k_gate, k_s3k_compact, k_s3k_finish): what the jobs of the SbpJobs beside it do not
+ * hold -- the pose of every job, the MapPoint list they share and the compaction of each job's survivors.  Job j ranks and
+ * resolves its survivors through JS.job[j] (mode 3, nLastPtr = counts + 4 * j + 1); every pointer a DEVICE pointer */
+struct Sim3Kb8JobDev {
+    float Rcw[9], tcw[3], Ow[3];
+    int32_t nKF;
+    const uint8_t* valid; /* nPoints bytes, or null = all 1 */
+    uint8_t* descC;       /* cap x 32: the survivors' descriptors, in list order */
+    uint8_t* flagsC;      /* cap: 3 = a query that blocks the keypoint it takes */
+    int32_t* indexC;      /* cap: the survivor's iMP */
+    SbpProj* projC;       /* cap: the survivors' projection records = JS.job[j].proj */
+    int32_t* matchKf;     /* nKF = JS.job[j].matchCur: survivor positions from the resolver, then iMP */
+};
+#define VSLAM_MAX_SIM3_KB8_JOBS 16
+static_assert(sizeof(Sim3Kb8JobDev) == 112, "16 of these travel as one kernel argument");
+struct Sim3Kb8Args { /* by-value kernel argument (< 4 KB) */
+    Sim3Kb8JobDev job[VSLAM_MAX_SIM3_KB8_JOBS];
+    vslam_kb8_camera cam; /* pKF->mpCamera: a rig KeyFrame's is the left one */
+    float scale[VSLAM_MAX_LEVELS];
+    float th, logScaleFactor;
+    SiBounds bnd;
+    int32_t gemmFloat, nlevels, nPoints, cap, nchunks, pad;
+    const FusePoint* pts;
+    const uint8_t* mpDesc;
+    SbpProj* gate;       /* [job][nPoints]: the projection record of every (job, point), valid = passed every gate */
+    int32_t* chunkKeep;  /* [job][nchunks] */
+    int32_t* counts;     /* [job][4]: survivors, survivors handed to the matcher (0 where there are more than cap), -, - */
+    int32_t* result;     /* [job][2]: nmatches (= JS.job[j].nmatches; -1: refused), n_gated */
+};
+
 /* k_unproject_stereo: one stereo pair's left keypoints -> world points (Frame::UnprojectStereo) */
 struct UnprojJob {
     float Twc[12]; /* rows [mRwc | mOw] */

@@ -1583,6 +1583,151 @@ int vslamh_fuse_search_rig(const vslam_fuse_params* p, const vslam_kb8_camera* c
     return VSLAM_OK;
 }
 
+/* FMatcher::SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF, sAlreadyFound, th, ORBdist) (fmatcher.cpp:2689-2811) with a
+ * fisheye CurrentFrame as it is written, sequential: the statement vslam_search_by_projection_keyframe_kb8 is tested against.
+ * Same arguments with host keypoints; cam = CurrentFrame.mpCamera; cur_kps / cur_desc: keypoints_ and the descriptor rows
+ * [0, n_cur), of a rig the LEFT camera's (bRight defaults to false); kf_kps: mvKeys followed by mvKeysRight -- the reference
+ * reads pKF->mvKeysUn[i].angle past the end for i >= NLeft, the restatement the right keypoint's angle. */
+int vslamh_search_by_projection_keyframe_kb8(const vslam_proj_params* p, const vslam_kb8_camera* cam, const float* Ow,
+                                             float log_scale_factor, int orb_dist, const vslam_kp* kf_kps, int n_kf,
+                                             const uint8_t* mp_flags, const float* mp_x3dw, const float* mp_min_dist,
+                                             const float* mp_max_dist, const uint8_t* mp_desc, const vslam_kp* cur_kps,
+                                             const uint8_t* cur_desc, int n_cur, const uint8_t* cur_occupied,
+                                             const float* scale_factors, int nlevels, const float* bounds, int32_t* match_cur,
+                                             int* nmatches) {
+    if (!p || !vslam_kb8::camera_ok(cam) || !Ow || n_kf < 0 || n_cur < 0 || nlevels < 1 || !scale_factors || !bounds || !nmatches ||
+        orb_dist < 1 || orb_dist > 255 ||
+        (n_kf && (!kf_kps || !mp_flags || !mp_x3dw || !mp_min_dist || !mp_max_dist || !mp_desc)) ||
+        (n_cur && (!cur_kps || !cur_desc || !match_cur)))
+        return VSLAM_ERR_INVALID;
+    if (vslamh_frame_rig_camera_check(p, cam)) return VSLAM_ERR_INVALID;
+    const int L = VSLAM_HISTO_LENGTH;
+    std::vector<uint8_t> occ((size_t)n_cur, 0);
+    for (int i = 0; i < n_cur; i++) {
+        match_cur[i] = -1;
+        if (cur_occupied) occ[i] = cur_occupied[i] != 0;
+    }
+    const RigGrid grid(cur_kps, n_cur, bounds);
+    std::vector<int> vIndices2;
+    std::vector<int> rotHist[VSLAM_HISTO_LENGTH];
+    int nm = 0;
+    for (int i = 0; i < n_kf; i++) {
+        if (!(mp_flags[i] & 1)) continue; /* pMP && !pMP->isBad() && !sAlreadyFound.count(pMP) */
+        const float* x3Dw = mp_x3dw + 3 * i;
+        float x3Dc[3];
+        rig_transform(p->Tcw, x3Dw, p->gemm_float, x3Dc);
+        const vslam_kb8::Uv uv = vslam_kb8::kb8_project(*cam, x3Dc[0], x3Dc[1], x3Dc[2]); /* no depth test */
+        if (uv.u < bounds[0] || uv.u > bounds[1]) continue;
+        if (uv.v < bounds[2] || uv.v > bounds[3]) continue;
+        const float dist3D = vslam_md::norm3(x3Dw[0] - Ow[0], x3Dw[1] - Ow[1], x3Dw[2] - Ow[2]);
+        if (dist3D < mp_min_dist[i] || dist3D > mp_max_dist[i]) continue;
+        const int level = vslam_md::predict_level(mp_max_dist[i], dist3D, log_scale_factor, nlevels);
+        const float radius = p->th * scale_factors[level];
+        grid.query(uv.u, uv.v, radius, level - 1, level + 1, vIndices2);
+        if (vIndices2.empty()) continue;
+        const uint8_t* dMP = mp_desc + (size_t)i * 32;
+        int bestDist = 256, bestIdx2 = -1;
+        for (int i2 : vIndices2) {
+            if (occ[i2]) continue;
+            const int dist = rig_hamming(dMP, cur_desc + (size_t)i2 * 32);
+            if (dist < bestDist) {
+                bestDist = dist;
+                bestIdx2 = i2;
+            }
+        }
+        if (bestDist <= orb_dist) {
+            match_cur[bestIdx2] = i;
+            occ[bestIdx2] = 1;
+            nm++;
+            if (p->check_orientation) rotHist[vslam_md::rot_bin(kf_kps[i].angle, cur_kps[bestIdx2].angle, L)].push_back(bestIdx2);
+        }
+    }
+    if (p->check_orientation) {
+        int histo[VSLAM_HISTO_LENGTH];
+        for (int b = 0; b < L; b++) histo[b] = (int)rotHist[b].size();
+        const vslam_md::ThreeMaxima mx = vslam_md::three_maxima(histo, L);
+        for (int b = 0; b < L; b++)
+            if (!vslam_md::keeps_bin(mx, b))
+                for (int s : rotHist[b]) {
+                    match_cur[s] = -1;
+                    nm--;
+                }
+    }
+    *nmatches = nm;
+    return VSLAM_OK;
+}
+
+/* FMatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th, ratioHamming) (fmatcher.cpp:750-863) for fisheye KeyFrames as
+ * it is written, job after job and point after point: the statement vslam_search_by_projection_sim3_kb8 is tested against, and
+ * what the shim runs for a job the device refused.  Same arguments; every pointer a HOST pointer, a job's dev_kps / dev_desc
+ * included; any number of jobs, points and survivors.  n_gated[j] (may be NULL): the points that pass every gate up to the
+ * radius.  bounds: the Frame's float mnMinX, mnMaxX, mnMinY, mnMaxY, truncated for the KeyFrame. */
+int vslamh_search_by_projection_sim3_kb8(const vslam_sim3_kb8_params* p, const vslam_kb8_camera* cam,
+                                         const vslam_sim3_kb8_job* jobs, int n_jobs, const vslam_fuse_point* points,
+                                         const uint8_t* mp_desc, int n_points, const float* scale_factors, int nlevels,
+                                         const float* bounds, int32_t* const* match_kf, int* nmatches, int* n_gated) {
+    if (!p || !vslam_kb8::camera_ok(cam) || !jobs || n_jobs < 1 || n_points < 0 || nlevels < 1 || !scale_factors || !bounds ||
+        !match_kf || !nmatches || (n_points && (!points || !mp_desc)) || p->th < 0 || !(p->ratio_hamming >= 0.0f))
+        return VSLAM_ERR_INVALID;
+    for (int j = 0; j < n_jobs; j++)
+        if (jobs[j].n_kf < 0 || (jobs[j].n_kf && (!jobs[j].dev_kps || !jobs[j].dev_desc || !match_kf[j]))) return VSLAM_ERR_INVALID;
+    const float kb[4] = {(float)(int)bounds[0], (float)(int)bounds[1], (float)(int)bounds[2], (float)(int)bounds[3]};
+    const float lim = 50 * p->ratio_hamming; /* bestDist <= TH_LOW * ratioHamming with an integer bestDist */
+    const int thr = lim >= 255.0f ? 255 : std::max(0, (int)floorf(lim));
+    const float th = (float)p->th;
+    std::vector<int> vIndices;
+    for (int j = 0; j < n_jobs; j++) {
+        const vslam_sim3_kb8_job& s = jobs[j];
+        RigGrid grid(s.dev_kps, s.n_kf, bounds); /* the Frame's cells and inverses, the KeyFrame's integer window origin */
+        grid.minX = kb[0];
+        grid.minY = kb[2];
+        std::vector<uint8_t> matched((size_t)s.n_kf, 0);
+        for (int c = 0; c < s.n_kf; c++) {
+            match_kf[j][c] = -1;
+            if (s.kf_matched_host) matched[c] = s.kf_matched_host[c] != 0;
+        }
+        int nm = 0, gated = 0;
+        for (int iMP = 0; iMP < n_points; iMP++) {
+            const vslam_fuse_point& mp = points[iMP];
+            if (!mp.valid || (s.valid_host && !s.valid_host[iMP])) continue;
+            float pc[3];
+            for (int r = 0; r < 3; r++) pc[r] = rig_gemm_row(s.Rcw + 3 * r, mp.pos, s.tcw[r], p->gemm_float);
+            if (pc[2] < 0.0f) continue;
+            const vslam_kb8::Uv uv = vslam_kb8::kb8_project(*cam, pc[0], pc[1], pc[2]);
+            if (!(uv.u >= kb[0] && uv.u < kb[1] && uv.v >= kb[2] && uv.v < kb[3])) continue; /* KeyFrame::IsInImage */
+            const float p0 = mp.pos[0] - s.Ow[0], p1 = mp.pos[1] - s.Ow[1], p2 = mp.pos[2] - s.Ow[2];
+            const float dist = vslam_md::norm3(p0, p1, p2);
+            if (dist < mp.min_distance || dist > mp.max_distance) continue;
+            if (vslam_md::dot3_mat(p0, p1, p2, mp.normal) < 0.5 * (double)dist) continue;
+            const int level = vslam_md::predict_level(mp.max_distance, dist, p->log_scale_factor, nlevels);
+            const float radius = th * scale_factors[level];
+            gated++;
+            grid.query(uv.u, uv.v, radius, -1, -1, vIndices);
+            if (vIndices.empty()) continue;
+            const uint8_t* dMP = mp_desc + (size_t)iMP * 32;
+            int bestDist = 256, bestIdx = -1;
+            for (int idx : vIndices) {
+                if (matched[idx]) continue;
+                const int kpLevel = s.dev_kps[idx].octave;
+                if (kpLevel < level - 1 || kpLevel > level) continue;
+                const int d = rig_hamming(dMP, s.dev_desc + (size_t)idx * 32);
+                if (d < bestDist) {
+                    bestDist = d;
+                    bestIdx = idx;
+                }
+            }
+            if (bestDist <= thr) {
+                match_kf[j][bestIdx] = iMP;
+                matched[bestIdx] = 1;
+                nm++;
+            }
+        }
+        nmatches[j] = nm;
+        if (n_gated) n_gated[j] = gated;
+    }
+    return VSLAM_OK;
+}
+
 /* FMatcher::SearchByBoW(KeyFrame* pKF, Frame& F, vpMapPointMatches) (fmatcher.cpp:546-748) with F.Nleft != -1 as it is
  * written, sequential, for one keyframe: the statement vslam_search_by_bow_rig is tested against, and the shim's fallback
  * beyond the device limits (there are none here).  Descriptor rows and FeatureVector indices of either side run over

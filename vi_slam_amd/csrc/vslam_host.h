@@ -257,4 +257,18 @@ extern "C" int vslamh_fuse_search_rig(const vslam_fuse_params* p, const vslam_kb
                                       const vslam_fuse_rig_job* jobs, int n_jobs, const vslam_fuse_point* points,
                                       const uint8_t* mp_desc, int n_points, const float* scale_factors, const float* inv_sigma2,
                                       int nlevels, const float* bounds, int32_t* best_idx, int32_t* best_dist);
+/* vslam_host.cpp: the relocalisation and loop-closing SearchByProjection for fisheye cameras
+ * (vslam_search_by_projection_keyframe_kb8, vslam_search_by_projection_sim3_kb8) over host arrays, sequential as the reference
+ * writes them; the second takes any number of jobs, points and survivors (CPU tests, the shim's fallback for a refused job) */
+extern "C" int vslamh_search_by_projection_keyframe_kb8(const vslam_proj_params* p, const vslam_kb8_camera* cam, const float* Ow,
+                                                        float log_scale_factor, int orb_dist, const vslam_kp* kf_kps, int n_kf,
+                                                        const uint8_t* mp_flags, const float* mp_x3dw, const float* mp_min_dist,
+                                                        const float* mp_max_dist, const uint8_t* mp_desc, const vslam_kp* cur_kps,
+                                                        const uint8_t* cur_desc, int n_cur, const uint8_t* cur_occupied,
+                                                        const float* scale_factors, int nlevels, const float* bounds,
+                                                        int32_t* match_cur, int* nmatches);
+extern "C" int vslamh_search_by_projection_sim3_kb8(const vslam_sim3_kb8_params* p, const vslam_kb8_camera* cam,
+                                                    const vslam_sim3_kb8_job* jobs, int n_jobs, const vslam_fuse_point* points,
+                                                    const uint8_t* mp_desc, int n_points, const float* scale_factors, int nlevels,
+                                                    const float* bounds, int32_t* const* match_kf, int* nmatches, int* n_gated);
 #endif

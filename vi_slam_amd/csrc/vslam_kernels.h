@@ -92,6 +92,16 @@ size_t vk_sbp_rig_replay_lds(int nSlots, int nLast);
 void vk_search_frame_rig(hipStream_t st, const SbpJobs& JS, const RigFrameDev& R, int nLast, hipEvent_t between = nullptr);
 void vk_search_by_projection(hipStream_t st, const SbpJobs& JS, int njobs, int maxLast, int maxCur, int* fallbacks,
                              int forceSeq);
+/* the same behind k_sbp_rank_kb8: modes 2 and 3 of a fisheye frame / KeyFrame; `between` (may be null) is recorded behind the
+ * ranking */
+void vk_search_by_projection_kb8(hipStream_t st, const SbpJobs& JS, int njobs, int maxLast, int maxCur, int* fallbacks,
+                                 int forceSeq, const vslam_kb8_camera& cam, hipEvent_t between = nullptr);
+/* SearchByProjection(pKF, Scw, ..) for fisheye KeyFrames: k_s3k_gate, k_s3k_compact, then the above over every job's
+ * survivors (A.cap sizes the ranking grid, maxKF the LDS), then k_s3k_finish; the events (may be null) are recorded behind the
+ * compaction and behind the ranking */
+struct Sim3Kb8Args;
+void vk_search_sim3_kb8(hipStream_t st, const Sim3Kb8Args& A, const SbpJobs& JS, int njobs, int maxKF, int* fallbacks,
+                        int forceSeq, hipEvent_t after_compact = nullptr, hipEvent_t after_rank = nullptr);
 int vk_distinctive_set_max_lds(size_t bytes);
 void vk_distinctive(hipStream_t st, const uint8_t* desc, const int32_t* offsets, int nsets, int maxN, int32_t* best);
 void vk_unproject_stereo(hipStream_t st, const UnprojJobs& U, int njobs);

@@ -46,9 +46,11 @@ static int kb8_refuse(const vslam_fe* fe) {
 /* One job in fe->proj to its end: launch, [o_m, end) -- the match table, then at o_n nmatches | needSeq -- to the mirror,
  * wait, hand out. */
 static int sbp_run_single(vslam_fe* fe, const SbpJobs& JS, int n_last, int n_cur, size_t o_m, size_t o_n, size_t end,
-                          int32_t* match_cur, int* nmatches) {
+                          int32_t* match_cur, int* nmatches, bool kb8 = false) {
     hipStream_t st = fe->stream;
-    vk_search_by_projection(st, JS, 1, n_last, n_cur, fe->d_init_fb, fe->tune.sbp_sequential == 1 /* cross-check path */);
+    const int force_seq = fe->tune.sbp_sequential == 1; /* cross-check path */
+    if (kb8) vk_search_by_projection_kb8(st, JS, 1, n_last, n_cur, fe->d_init_fb, force_seq, fe->kb8);
+    else vk_search_by_projection(st, JS, 1, n_last, n_cur, fe->d_init_fb, force_seq);
     HIPCHK(hipGetLastError());
     fe->proj.down(st, o_m, end - o_m);
     HIPCHK(hipGetLastError());
@@ -65,6 +67,7 @@ struct SbpKfExtras {
     int orb_dist;
     const float* normals = nullptr; /* non-null: the Scw overloads (mode 3) */
     int proj_kind = 0;
+    bool kb8 = false; /* mode 2 of a fisheye CurrentFrame: KannalaBrandt8::project with the context's camera (k_sbp_rank_kb8) */
 };
 
 static int sbp_frame_impl(vslam_fe* fe, const vslam_proj_params* p, const vslam_kp* last_kps_host, int n_last,
@@ -77,7 +80,15 @@ static int sbp_frame_impl(vslam_fe* fe, const vslam_proj_params* p, const vslam_
         g_err = "invalid arguments";
         return VSLAM_ERR_INVALID;
     }
-    if (int rc = kb8_refuse(fe)) return rc;
+    if (kf && kf->kb8) {
+        if (int rc = kb8_required(fe)) return rc;
+        if (vslamh_frame_rig_camera_check(p, &fe->kb8)) {
+            g_err = "fx, fy, cx, cy of the projection parameters differ from the KB8 camera's (vslam_fe_set_kb8_camera)";
+            return VSLAM_ERR_INVALID;
+        }
+    } else if (int rc = kb8_refuse(fe)) {
+        return rc;
+    }
     *nmatches = 0;
     if (n_cur == 0 || n_last == 0) {
         for (int i = 0; i < n_cur; i++) match_cur[i] = -1;
@@ -143,7 +154,7 @@ static int sbp_frame_impl(vslam_fe* fe, const vslam_proj_params* p, const vslam_
         JS.kf.maxDist = (const float*)(d + o_mx);
         for (int i = 0; i < 3; i++) JS.kf.ow[i] = kf->ow[i];
     }
-    return sbp_run_single(fe, JS, n_last, n_cur, o_m, o_n, total, match_cur, nmatches);
+    return sbp_run_single(fe, JS, n_last, n_cur, o_m, o_n, total, match_cur, nmatches, kf && kf->kb8);
 }
 
 extern "C" int vslam_search_by_projection_frame(vslam_fe* fe, const vslam_proj_params* p,
@@ -218,6 +229,35 @@ extern "C" int vslam_search_by_projection_keyframe(vslam_fe* fe, const vslam_pro
     for (int i = 0; i < 3; i++) kf.ow[i] = Ow[i];
     kf.log_scale_factor = log_scale_factor;
     kf.orb_dist = orb_dist;
+    return sbp_frame_impl(fe, p, kf_kps_host, n_kf, mp_flags, mp_x3dw, mp_desc_host, dev_cur_kps, dev_cur_desc, n_cur, nullptr,
+                          cur_occupied_host, &kf, match_cur, nmatches);
+}
+
+/* The same matcher with a fisheye CurrentFrame -- a monocular KB8 frame or the left camera of a two-fisheye rig, whose bRight
+ * defaults to false (frame.cpp:678-744): k_sbp_rank_kb8 in front of the same resolution.  Rules, and the oddity of the
+ * reference's angle read for a rig KeyFrame, in include/vslam_fe.h */
+extern "C" int vslam_search_by_projection_keyframe_kb8(vslam_fe* fe, const vslam_proj_params* p, const float* Ow,
+                                                       float log_scale_factor, int orb_dist, const vslam_kp* kf_kps_host,
+                                                       int n_kf, const uint8_t* mp_flags, const float* mp_x3dw,
+                                                       const float* mp_min_dist, const float* mp_max_dist,
+                                                       const uint8_t* mp_desc_host, const vslam_kp* dev_cur_kps,
+                                                       const uint8_t* dev_cur_desc, int n_cur,
+                                                       const uint8_t* cur_occupied_host, int32_t* match_cur, int* nmatches) {
+    if (!Ow || (n_kf > 0 && (!mp_min_dist || !mp_max_dist)) || orb_dist < 1 || orb_dist > 255) {
+        g_err = "invalid arguments";
+        return VSLAM_ERR_INVALID;
+    }
+    if (n_kf > 4096) {
+        g_err = "SearchByProjection on the device supports at most 4096 KeyFrame entries";
+        return VSLAM_ERR_UNSUPPORTED;
+    }
+    SbpKfExtras kf;
+    kf.min_dist = mp_min_dist;
+    kf.max_dist = mp_max_dist;
+    for (int i = 0; i < 3; i++) kf.ow[i] = Ow[i];
+    kf.log_scale_factor = log_scale_factor;
+    kf.orb_dist = orb_dist;
+    kf.kb8 = true;
     return sbp_frame_impl(fe, p, kf_kps_host, n_kf, mp_flags, mp_x3dw, mp_desc_host, dev_cur_kps, dev_cur_desc, n_cur, nullptr,
                           cur_occupied_host, &kf, match_cur, nmatches);
 }

@@ -35,6 +35,7 @@ struct SbpProj { /* projection record of one last-frame keypoint (k_sbp_rank -> 
     float u, v, radius, ur;
     int32_t minLevel, maxLevel, valid, pad;
 };
+static_assert(sizeof(SbpProj) == 32, "k_s3k_compact moves a record as two uint4");
 
 __device__ __forceinline__ bool sbp_level_ok(int octave, int minLevel, int maxLevel) { /* frame.cpp:712-728 */
     const bool bCheckLevels = (minLevel > 0) || (maxLevel >= 0);
@@ -204,8 +205,22 @@ __device__ __forceinline__ SbpProj sbp_proj_rig(const SbpJobs& JS, const SbpJobD
     return pr;
 }
 
-/* one body, two kernels (vslam_sbp_rank_body.inc): the rig kernel adds query mode 4 and the struct it reads, and the kernel the
- * pinhole matchers launch keeps its argument list and its code */
+/* mode 2 with a fisheye CurrentFrame (fmatcher.cpp:2705-2743 with KannalaBrandt8::project at :2718): as sbp_proj_keyframe.
+ * There is no depth test: a point behind the camera is projected like any other (theta > pi / 2) and goes on where it lands
+ * inside the bounds */
+__device__ __forceinline__ SbpProj sbp_proj_keyframe_kb8(const SbpJobs& JS, const SbpJobDev& J, const vslam_kb8_camera& cam,
+                                                         int q, const SbpPoint& pc, float X, float Y, float Z,
+                                                         const SiBounds& bnd) {
+    const vslam_kb8::Uv o = vslam_kb8::kb8_project(cam, pc.x, pc.y, pc.z);
+    const float2 uv = make_float2(o.u, o.v);
+    if (!sbp_in_frame(uv, bnd)) return SbpProj{};
+    const SbpDist d = sbp_dist(JS.kf, q, X, Y, Z);
+    if (!d.inRange) return SbpProj{};
+    return sbp_proj_level(JS, J.th, uv, d, /* maxLevel = level + */ 1);
+}
+
+/* one body, three kernels (vslam_sbp_rank_body.inc): the rig kernel adds query mode 4 and the struct it reads, the KB8 kernel
+ * reads modes 2 and 3 as their fisheye forms, and the kernel the pinhole matchers launch keeps its argument list and its code */
 __global__ void __launch_bounds__(256)
 k_sbp_rank(SbpJobs JS) {
 #define SBP_RANK_RIG 0
@@ -215,6 +230,14 @@ k_sbp_rank(SbpJobs JS) {
 __global__ void __launch_bounds__(256)
 k_sbp_rank_rig(SbpJobs JS, RigFrameDev R) {
 #define SBP_RANK_RIG 1
+#include "vslam_sbp_rank_body.inc"
+#undef SBP_RANK_RIG
+}
+/* SearchByProjection(CurrentFrame, pKF, ..) with a fisheye CurrentFrame (mode 2), and the ranking of the survivors of
+ * k_s3k_gate (mode 3: SearchByProjection(pKF, Scw, ..) with a fisheye KeyFrame) */
+__global__ void __launch_bounds__(256)
+k_sbp_rank_kb8(SbpJobs JS, vslam_kb8_camera cam) {
+#define SBP_RANK_RIG 2
 #include "vslam_sbp_rank_body.inc"
 #undef SBP_RANK_RIG
 }
@@ -657,6 +680,140 @@ void vk_search_by_projection(hipStream_t st, const SbpJobs& JS, int njobs, int m
     }
     hipLaunchKernelGGL(k_sbp_resolve, dim3(njobs), dim3(SBP_RT), vk_sbp_resolve_lds(maxCur), st, JS, forceSeq);
     hipLaunchKernelGGL(k_sbp_replay, dim3(njobs), dim3(64), vk_sbp_replay_lds(maxCur, maxLast), st, JS, fallbacks);
+}
+
+/* the same with k_sbp_rank_kb8 in front: modes 2 and 3 of a fisheye frame / KeyFrame.  `between` (may be null) is recorded
+ * behind the ranking */
+void vk_search_by_projection_kb8(hipStream_t st, const SbpJobs& JS, int njobs, int maxLast, int maxCur, int* fallbacks,
+                                 int forceSeq, const vslam_kb8_camera& cam, hipEvent_t between) {
+    if (njobs <= 0) return;
+    if (maxLast > 0)
+        hipLaunchKernelGGL(k_sbp_rank_kb8, dim3((maxLast + SBP_QPB - 1) / SBP_QPB, njobs), dim3(256),
+                           vk_sbp_rank_lds(maxCur), st, JS, cam);
+    if (between) (void)hipEventRecord(between, st);
+    hipLaunchKernelGGL(k_sbp_resolve, dim3(njobs), dim3(SBP_RT), vk_sbp_resolve_lds(maxCur), st, JS, forceSeq);
+    hipLaunchKernelGGL(k_sbp_replay, dim3(njobs), dim3(64), vk_sbp_replay_lds(maxCur, maxLast), st, JS, fallbacks);
+}
+
+/* ------------------------------------------------------------------------------------------------
+ * FMatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th, ratioHamming) (fmatcher.cpp:750-863) for fisheye KeyFrames:
+ * ONE MapPoint list against up to 16 (KeyFrame, Scw) jobs.  The list is long (the MapPoints of a KeyFrame, of its covisibles
+ * and of theirs) and the matcher behind takes 4096 queries, so the gates come first, as in SearchLocalPoints:
+ *   k_s3k_gate     one thread per (job, point): everything up to the radius -- validity, Rcw * p + tcw as one gemm, z < 0,
+ *                  KannalaBrandt8::project, KeyFrame::IsInImage over the integer bounds, the distance range, the viewing angle
+ *                  (both sides in double), PredictScale -- into a projection record, and the survivors per chunk of 256 points
+ *   k_s3k_compact  k_rig_compact's ranks: ballot / popcount over a running base of chunk counts, the list order kept; a job's
+ *                  survivors get their record, descriptor, flags (3: every accepted point blocks its keypoint) and iMP.  A job
+ *                  with more than `cap` survivors hands the matcher none
+ *   k_sbp_rank_kb8 (mode 3), k_sbp_resolve, k_sbp_replay: one job each over its survivors
+ *   k_s3k_finish   match_kf[idx]: the survivor's position -> its iMP; nmatches (-1: refused) and n_gated
+ * ---------------------------------------------------------------------------------------------- */
+#define S3K_CHUNK 256
+__global__ void __launch_bounds__(S3K_CHUNK)
+k_s3k_gate(Sim3Kb8Args A) {
+    __shared__ int s_keep[4];
+    const Sim3Kb8JobDev& J = A.job[blockIdx.y];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int i = blockIdx.x * S3K_CHUNK + tid;
+    SbpProj pr = {};
+    if (i < A.nPoints) {
+        const FusePoint mp = A.pts[i];
+        bool ok = mp.valid != 0 && (!J.valid || J.valid[i]); /* !pMP->isBad() && !spAlreadyFound.count(pMP) */
+        const SbpPoint pc = sbp_transform(J.Rcw, J.tcw, mp.pos[0], mp.pos[1], mp.pos[2], A.gemmFloat);
+        ok = ok && !(pc.z < 0.0f);
+        const vslam_kb8::Uv uv = vslam_kb8::kb8_project(A.cam, pc.x, pc.y, pc.z);
+        const SiBounds wb = si_kf_bounds(A.bnd);
+        ok = ok && uv.u >= wb.minX && uv.u < wb.maxX && uv.v >= wb.minY && uv.v < wb.maxY; /* KeyFrame::IsInImage */
+        const float p0 = __fsub_rn(mp.pos[0], J.Ow[0]), p1 = __fsub_rn(mp.pos[1], J.Ow[1]), p2 = __fsub_rn(mp.pos[2], J.Ow[2]);
+        const float dist = vslam_md::norm3(p0, p1, p2);
+        ok = ok && !(dist < mp.minDistance || dist > mp.maxDistance);
+        ok = ok && !(vslam_md::dot3_mat(p0, p1, p2, mp.normal) < __dmul_rn(0.5, (double)dist));
+        if (ok) {
+            const int level = vslam_md::predict_level(mp.maxDistance, dist, A.logScaleFactor, A.nlevels);
+            pr.u = uv.u;
+            pr.v = uv.v;
+            pr.radius = __fmul_rn(A.th, A.scale[level]);
+            pr.minLevel = level - 1;
+            pr.maxLevel = level;
+            pr.valid = 1;
+        }
+        A.gate[(size_t)blockIdx.y * A.nPoints + i] = pr;
+    }
+    const unsigned long long bk = __ballot(pr.valid != 0);
+    if (lane == 0) s_keep[wave] = __popcll(bk);
+    __syncthreads();
+    if (tid == 0) A.chunkKeep[blockIdx.y * A.nchunks + blockIdx.x] = s_keep[0] + s_keep[1] + s_keep[2] + s_keep[3];
+}
+
+__global__ void __launch_bounds__(S3K_CHUNK)
+k_s3k_compact(Sim3Kb8Args A) {
+    __shared__ int s_before[4], s_wave[4];
+    const Sim3Kb8JobDev& J = A.job[blockIdx.y];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.x;
+    /* chunk counts: thread t holds chunk t (nchunks <= 256) */
+    int before = tid < b ? A.chunkKeep[blockIdx.y * A.nchunks + tid] : 0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) before += __shfl_xor(before, o, 64);
+    const int i = b * S3K_CHUNK + tid;
+    uint4 r0 = make_uint4(0, 0, 0, 0), r1 = r0; /* the record as two 16-byte words: u, v, radius, ur | minLevel, maxLevel, valid, - */
+    if (i < A.nPoints) {
+        const uint4* g = (const uint4*)(A.gate + (size_t)blockIdx.y * A.nPoints + i);
+        r0 = g[0];
+        r1 = g[1];
+    }
+    const bool keep = r1.z != 0;
+    const unsigned long long bk = __ballot(keep);
+    const int rank = __popcll(bk & ((1ull << lane) - 1ull));
+    if (lane == 0) {
+        s_before[wave] = before;
+        s_wave[wave] = __popcll(bk);
+    }
+    __syncthreads();
+    const int base = s_before[0] + s_before[1] + s_before[2] + s_before[3];
+    int woff = 0;
+    for (int w = 0; w < wave; w++) woff += s_wave[w];
+    const int pos = base + woff + rank;
+    if (keep && pos < A.cap) {
+        ((uint4*)(J.projC + pos))[0] = r0;
+        ((uint4*)(J.projC + pos))[1] = r1;
+        const uint4* src = (const uint4*)(A.mpDesc + (size_t)i * 32);
+        uint4* dst = (uint4*)(J.descC + (size_t)pos * 32);
+        dst[0] = src[0];
+        dst[1] = src[1];
+        J.flagsC[pos] = 3; /* bit 0: a query; bit 1: vpMatched[bestIdx] = pMP blocks later points */
+        J.indexC[pos] = i;
+    }
+    if (b == (int)gridDim.x - 1 && tid == 0) {
+        const int kept = base + s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+        A.counts[blockIdx.y * 4] = kept;
+        A.counts[blockIdx.y * 4 + 1] = kept > A.cap ? 0 : kept;
+    }
+}
+
+__global__ void __launch_bounds__(256)
+k_s3k_finish(Sim3Kb8Args A) {
+    const Sim3Kb8JobDev& J = A.job[blockIdx.x];
+    const int kept = A.counts[blockIdx.x * 4];
+    const bool refused = kept > A.cap;
+    for (int c = threadIdx.x; c < J.nKF; c += 256) {
+        const int m = J.matchKf[c];
+        J.matchKf[c] = (refused || m < 0) ? -1 : J.indexC[m];
+    }
+    if (threadIdx.x == 0) {
+        if (refused) A.result[blockIdx.x * 2] = -1;
+        A.result[blockIdx.x * 2 + 1] = kept;
+    }
+}
+
+void vk_search_sim3_kb8(hipStream_t st, const Sim3Kb8Args& A, const SbpJobs& JS, int njobs, int maxKF, int* fallbacks,
+                        int forceSeq, hipEvent_t after_compact, hipEvent_t after_rank) {
+    if (njobs <= 0 || A.nPoints <= 0) return;
+    hipLaunchKernelGGL(k_s3k_gate, dim3(A.nchunks, njobs), dim3(S3K_CHUNK), 0, st, A);
+    hipLaunchKernelGGL(k_s3k_compact, dim3(A.nchunks, njobs), dim3(S3K_CHUNK), 0, st, A);
+    if (after_compact) (void)hipEventRecord(after_compact, st);
+    vk_search_by_projection_kb8(st, JS, njobs, A.cap, maxKF, fallbacks, forceSeq, A.cam, after_rank);
+    hipLaunchKernelGGL(k_s3k_finish, dim3(njobs), dim3(256), 0, st, A);
 }
 
 /* ------------------------------------------------------------------------------------------------
@@ -1344,6 +1501,8 @@ int vk_sbp_set_max_lds(size_t bytes) {
     rc = (int)hipFuncSetAttribute((const void*)k_sbp_rig_resolve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (rc) return rc;
     rc = (int)hipFuncSetAttribute((const void*)k_sbp_rig_replay, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (rc) return rc;
+    rc = (int)hipFuncSetAttribute((const void*)k_sbp_rank_kb8, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (rc) return rc;
     return (int)hipFuncSetAttribute((const void*)k_sbp_replay, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }

@@ -1,7 +1,7 @@
-/* vslam_sbp_rank_body.inc -- the body of k_sbp_rank and of k_sbp_rank_rig (vslam_projection_kernels.hip), included once in each
- * with SBP_RANK_RIG 0 / 1.  Text and not a template over the mode set: behind a `template <bool>` body the compiler gave the
+/* vslam_sbp_rank_body.inc -- the body of k_sbp_rank, of k_sbp_rank_rig and of k_sbp_rank_kb8 (vslam_projection_kernels.hip),
+ * included once in each with SBP_RANK_RIG 0 / 1 / 2.  Text and not a template over the mode set: behind a `template <bool>` body the compiler gave the
  * pinhole kernel 87 VGPRs where it has 74 as a kernel of its own (occupancy 5 instead of 6); as text its code is what it was.
- * Names from the kernel: JS, and with SBP_RANK_RIG the RigFrameDev R. */
+ * Names from the kernel: JS, with SBP_RANK_RIG 1 the RigFrameDev R, with SBP_RANK_RIG 2 the vslam_kb8_camera cam. */
     extern __shared__ __align__(16) uint8_t sbsm[];
     SbpCand* cand = (SbpCand*)sbsm; /* nCur */
     const SbpJobDev& J = JS.job[blockIdx.y];
@@ -21,10 +21,18 @@
     __syncthreads();
     for (int q = blockIdx.x * SBP_QPB + wave; q < min(nLast, (int)(blockIdx.x + 1) * SBP_QPB); q += 4) {
         SbpProj pr = {};
-#if SBP_RANK_RIG
+#if SBP_RANK_RIG == 1
         if (J.flags[q] & 1) { /* mode 4; blockIdx.y: job 0 is the left branch, job 1 the right one */
             const SbpPoint pc = sbp_transform(J.Tcw, J.x3Dw[3 * q], J.x3Dw[3 * q + 1], J.x3Dw[3 * q + 2], J.gemmFloat);
             pr = sbp_proj_rig(JS, J, R, (int)blockIdx.y, pc, lastKps[q].octave, bnd);
+        }
+#elif SBP_RANK_RIG == 2
+        (void)lastKps; /* neither mode reads a keypoint of the query side */
+        if (J.mode == 3) { /* a survivor of k_s3k_gate: its record is made, k_s3k_compact put it here */
+            pr = J.proj[q];
+        } else if (J.flags[q] & 1) { /* mode 2 through KannalaBrandt8::project */
+            const float X = J.x3Dw[3 * q], Y = J.x3Dw[3 * q + 1], Z = J.x3Dw[3 * q + 2];
+            pr = sbp_proj_keyframe_kb8(JS, J, cam, q, sbp_transform(J.Tcw, X, Y, Z, J.gemmFloat), X, Y, Z, bnd);
         }
 #else
         if (J.mode == 1) {
