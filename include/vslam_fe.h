@@ -1126,6 +1126,140 @@ int vslam_kfdb_select_nbest(const int64_t* hit_kf, const int32_t* hit_map, const
                             vslam_kfdb_neighbours_fn neighbours_fn, void* user, int64_t* loop_kf, int* n_loop,
                             int64_t* merge_kf, int* n_merge);
 
+/* ---------------------------------------------------------------- Covisibility (the observation graph and its counts)
+ *
+ * A mirror of MapPoint::mObservations / nObs / mbBad and of the keyframes' id, map and mbBad in HBM, with a host shadow.
+ * The caller calls the mirror's twin wherever the reference calls the original; the mutators change the shadow only
+ * (after waiting for a query of this mirror that is still in flight), and a query uploads what changed on the
+ * context's stream before its kernels.  Keyframes, MapPoints and maps are ids (KeyFrame::mnId, MapPoint::id_,
+ * Map::GetId()).  Unknown ids, duplicate adds and out-of-range arguments return VSLAM_ERR_INVALID and change nothing;
+ * an id that was erased may be added again.
+ *
+ * order_key stands for the KeyFrame* value: every std::map<KeyFrame*, ..> and every sort of pair<int, KeyFrame*> of the
+ * reference orders by pointer, so the key is an input; (uintptr_t)pKF reproduces the reference's orders.  Keys are
+ * unique among the live keyframes.
+ *
+ *   add_keyframe / add_keyframes          one keyframe / n keyframes (all or none)
+ *   set_keyframe_bad                      mbBad as isBad() reads it, nothing else
+ *   set_keyframe_map                      KeyFrame::UpdateMap
+ *   erase_keyframe                        forgets the slot; VSLAM_ERR_INVALID while a MapPoint still observes it
+ *   add_point                             a MapPoint without observations, nObs = 0, not bad
+ *   add_observation (mappoint.cpp:137-162)  sets the left (is_right = 0) or right index of the keyframe's entry and that
+ *                                         side's level (keypoint octave, 0..63); nObs += stereo ? 2 : 1 -- stereo is the
+ *                                         caller's `!pKF->mpCamera2 && mvuRight[idx] >= 0`, kept with the left side.  A
+ *                                         second call for a side overwrites it and increments nObs again, as there
+ *   erase_observation (:164-197)          no entry: nothing happens.  nObs goes down per side as stored, the entry is
+ *                                         dropped, and with nObs <= 2 the point becomes bad and loses every observation
+ *                                         (:211-220); *became_bad (may be NULL) says so
+ *   clear_point                           the first block of SetBadFlag and of Replace: bad, observations cleared; nObs
+ *                                         stays as it is, as there
+ *   erase_point                           forgets the MapPoint
+ *   clear_map                             forgets the keyframes of the map and every MapPoint that one of them observes
+ *   clear                                 forgets everything
+ *   size                                  live keyframes, live points, observation entries
+ *   stats                                 pool capacity and records handed out, growths, compactions
+ *   get_point                             nObs, bad flag and the entries in ascending order_key; *n_records is always
+ *                                         set, VSLAM_ERR_CAPACITY when it exceeds cap (nothing is written then)
+ *
+ * The pool holds 4096 observation records at first (initial_entries, 0 = that default).  A point's records lie in one
+ * segment of 4, 8, 16, .. records; a full segment moves to one of twice the size at the pool's end, a full pool doubles,
+ * and the pool is compacted when abandoned segments exceed half of what was handed out.
+ *
+ * Queries: up to VSLAM_COVIS_MAX_JOBS jobs per enqueue, one query per mirror in flight (a second _async returns
+ * VSLAM_ERR_INVALID); results stay readable until the next enqueue on the mirror.  mp_ids is mvpMapPoints, index
+ * aligned, -1 for NULL, at most VSLAM_COVIS_MAX_LIST entries; an id listed twice counts twice; a point that is bad in
+ * the mirror is skipped.  result.error: bit 0 an mp_id the mirror does not know, bit 1 an unknown self_kf / kf_id
+ * (CONNECTIONS and culling); the job's other outputs are zero then.
+ *
+ * connections, mode VSLAM_COVIS_CONNECTIONS = KeyFrame::UpdateConnections (keyframe.cpp:363-427): the counter runs over
+ * every observer except self_kf, bad keyframes and keyframes of a map other than map_id.  n_counter entries (kf, count)
+ * in ascending order_key = mConnectedKeyFrameWeights; kf_max / n_max by `>` along that order (:402); n_ordered entries
+ * = mvpOrderedConnectedKeyFrames / mvOrderedWeights: those with count >= 15, or the single (n_max, kf_max), in
+ * descending (count, order_key).  n_counter = 0: the caller returns as :385.
+ * Mode VSLAM_COVIS_VOTE = Tracking::UpdateLocalKeyFrames (tracking.cpp:3309-3376): every observer counts; delivered
+ * are the keyframes that are not bad, in ascending order_key, and kf_max among them; n_ordered = 0.
+ * Both: n_tracked = KeyFrame::TrackedMapPoints(min_obs) (:320-339) over the list.
+ * connections_lists copies the lists of job j of the query delivered last; any pointer may be NULL.
+ *
+ * culling = LocalMapping::KeyFrameCulling (localmapping.cpp:990-1052): mp_ids[i] = -1 for NULL and for a point the depth
+ * gate :1003-1007 rejects, levels[i] = scaleLevel of :1012-1014.  n_mps = nMPs, n_redundant = nRedundantObservations
+ * with thObs = th_obs (3 there).  The results of one enqueue hold up to and including the first job whose keyframe
+ * the caller culls: SetBadFlag erases its observations and changes the later counts. */
+#define VSLAM_COVIS_MAX_JOBS 128
+#define VSLAM_COVIS_MAX_LIST 8192
+#define VSLAM_COVIS_CONNECTIONS 0
+#define VSLAM_COVIS_VOTE 1
+typedef struct vslam_covis vslam_covis;
+typedef struct vslam_covis_obs {
+    int64_t kf_id;
+    int32_t left_idx, right_idx;     /* -1: that side does not observe */
+    int32_t left_level, right_level; /* -1 likewise */
+    int32_t stereo;
+    int32_t reserved;
+} vslam_covis_obs;
+typedef struct vslam_covis_job {
+    int32_t mode;
+    int32_t map_id;
+    int64_t self_kf;
+    int32_t min_obs;
+    int32_t n;
+    const int64_t* mp_ids;
+} vslam_covis_job;
+typedef struct vslam_covis_result {
+    int32_t error;
+    int32_t n_counter;
+    int32_t n_ordered;
+    int32_t n_max;
+    int64_t kf_max; /* -1: none */
+    int32_t n_tracked;
+    int32_t reserved;
+} vslam_covis_result;
+typedef struct vslam_covis_cull_job {
+    int64_t kf_id;
+    int32_t n;
+    int32_t reserved;
+    const int64_t* mp_ids;
+    const int32_t* levels;
+} vslam_covis_cull_job;
+typedef struct vslam_covis_cull_result {
+    int32_t error;
+    int32_t n_mps;
+    int32_t n_redundant;
+    int32_t reserved;
+} vslam_covis_cull_result;
+int vslam_covis_create(int device, int initial_entries, vslam_covis** out);
+void vslam_covis_destroy(vslam_covis* c);
+/* jobs per enqueue, list entries per job, and the number of live keyframes up to which the kernels keep the
+ * histogram in LDS (above it: a global scratch array per job) */
+int vslam_covis_limits(int* max_jobs, int* max_list, int* lds_slots);
+int vslam_covis_add_keyframe(vslam_covis* c, int64_t kf_id, int32_t map_id, uint64_t order_key);
+int vslam_covis_add_keyframes(vslam_covis* c, int n, const int64_t* kf_ids, const int32_t* map_ids, const uint64_t* order_keys);
+int vslam_covis_set_keyframe_bad(vslam_covis* c, int64_t kf_id);
+int vslam_covis_set_keyframe_map(vslam_covis* c, int64_t kf_id, int32_t map_id);
+int vslam_covis_erase_keyframe(vslam_covis* c, int64_t kf_id);
+int vslam_covis_add_point(vslam_covis* c, int64_t mp_id);
+int vslam_covis_add_observation(vslam_covis* c, int64_t mp_id, int64_t kf_id, int32_t idx, int is_right, int level, int stereo);
+int vslam_covis_erase_observation(vslam_covis* c, int64_t mp_id, int64_t kf_id, int* became_bad);
+int vslam_covis_clear_point(vslam_covis* c, int64_t mp_id);
+int vslam_covis_erase_point(vslam_covis* c, int64_t mp_id);
+int vslam_covis_clear_map(vslam_covis* c, int32_t map_id);
+int vslam_covis_clear(vslam_covis* c);
+int vslam_covis_size(vslam_covis* c, int* n_keyframes, int* n_points, long long* n_observations);
+int vslam_covis_stats(vslam_covis* c, long long* capacity, long long* used, int* n_growths, int* n_compactions);
+int vslam_covis_get_point(vslam_covis* c, int64_t mp_id, int cap, int* n_obs, int* bad, vslam_covis_obs* obs, int* n_records);
+int vslam_covis_connections_async(vslam_covis* c, vslam_fe* fe, int n_jobs, const vslam_covis_job* jobs);
+int vslam_covis_connections_wait(vslam_covis* c, vslam_fe* fe, vslam_covis_result* results /* [n_jobs] */);
+int vslam_covis_connections(vslam_covis* c, vslam_fe* fe, int n_jobs, const vslam_covis_job* jobs, vslam_covis_result* results);
+int vslam_covis_connections_lists(vslam_covis* c, int job, int64_t* counter_kf, int32_t* counter_n /* [n_counter] */,
+                                  int64_t* ordered_kf, int32_t* ordered_w /* [n_ordered] */);
+int vslam_covis_culling_async(vslam_covis* c, vslam_fe* fe, int n_jobs, const vslam_covis_cull_job* jobs, int th_obs);
+int vslam_covis_culling_wait(vslam_covis* c, vslam_fe* fe, vslam_covis_cull_result* results /* [n_jobs] */);
+int vslam_covis_culling(vslam_covis* c, vslam_fe* fe, int n_jobs, const vslam_covis_cull_job* jobs, int th_obs,
+                        vslam_covis_cull_result* results);
+/* HIP-event spans summed over the queries waited for while vslam_fe_set_profiling is on: the upload's scatter kernel,
+ * the query kernel; bytes uploaded by those queries */
+int vslam_covis_get_profile(vslam_covis* c, double* apply_ms, double* query_ms, long long* upload_bytes, long* passes);
+
 /* FMatcher::SearchByBoW(KeyFrame* pKF, Frame& F, vector<MapPoint*>& vpMapPointMatches) (fmatcher.cpp:546-748,
  * pinhole frames).  FeatureVectors as produced by vslam_bow_assemble (ascending node ids, offsets, feature
  * indices); kf_flags[i] != 0 iff pKF's i-th keypoint has a MapPoint that is not bad; keypoints only contribute

@@ -1724,6 +1724,184 @@ private:
     std::map<long long, float> reloc_, place_;
 };
 
+/* ---------------------------------------------------------------------------------------------------
+ * The observation graph and the covisibility counts over it (include/vslam_fe.h, Covisibility): MapPoint::mObservations,
+ * nObs and mbBad, the keyframes' map and mbBad, behind ids.  The caller calls the twin wherever the reference calls the
+ * original: AddObservation / EraseObservation / SetBadFlag / Replace of a MapPoint, SetBadFlag / UpdateMap of a KeyFrame.
+ * order_key stands for the KeyFrame* value, by which the reference orders its maps and sorts: pass (uintptr_t)pKF.
+ * UpdateConnections answers KeyFrame::UpdateConnections (keyframe.cpp:363-427), the vote of
+ * Tracking::UpdateLocalKeyFrames (tracking.cpp:3309-3376) and TrackedMapPoints for up to 128 keyframes / frames in one
+ * enqueue; KeyFrameCulling walks LocalMapping::KeyFrameCulling's loop (localmapping.cpp:983-1100) by the walk rule.
+ * ------------------------------------------------------------------------------------------------- */
+class CovisibilityMap {
+public:
+    enum Mode { CONNECTIONS = VSLAM_COVIS_CONNECTIONS, VOTE = VSLAM_COVIS_VOTE };
+    struct ConnectionsJob {
+        int mode;
+        long long self_kf; /* mnId; unused by VOTE */
+        int map_id;
+        int min_obs;                   /* TrackedMapPoints(minObs) */
+        std::vector<long long> mp_ids; /* mvpMapPoints, -1 = NULL */
+    };
+    struct Connections {
+        int error;
+        std::vector<long long> counter_kf; /* mConnectedKeyFrameWeights in ascending order_key */
+        std::vector<int> counter_n;
+        long long kf_max;
+        int n_max;
+        std::vector<long long> ordered_kf; /* mvpOrderedConnectedKeyFrames */
+        std::vector<int> ordered_w;        /* mvOrderedWeights */
+        int n_tracked;
+    };
+    struct CullingJob {
+        long long kf_id;
+        std::vector<long long> mp_ids; /* -1 = NULL or rejected by the depth gate (localmapping.cpp:1003-1007) */
+        std::vector<int32_t> levels;   /* scaleLevel of :1012-1014 */
+    };
+    struct CullingResult {
+        int error, nMPs, nRedundantObservations;
+    };
+
+    explicit CovisibilityMap(int device = 0, int initial_entries = 0) { check(vslam_covis_create(device, initial_entries, &c_)); }
+    ~CovisibilityMap() { vslam_covis_destroy(c_); }
+    CovisibilityMap(const CovisibilityMap&) = delete;
+    CovisibilityMap& operator=(const CovisibilityMap&) = delete;
+
+    void AddKeyFrame(long long kf_id, int map_id, unsigned long long order_key) { check(vslam_covis_add_keyframe(c_, kf_id, map_id, order_key)); }
+    void SetKeyFrameBad(long long kf_id) { check(vslam_covis_set_keyframe_bad(c_, kf_id)); }
+    void UpdateMap(long long kf_id, int map_id) { check(vslam_covis_set_keyframe_map(c_, kf_id, map_id)); }
+    void EraseKeyFrame(long long kf_id) {
+        check(vslam_covis_erase_keyframe(c_, kf_id));
+        ordered_.erase(kf_id);
+    }
+    void AddMapPoint(long long mp_id) { check(vslam_covis_add_point(c_, mp_id)); }
+    /* MapPoint::AddObservation: stereo = !pKF->mpCamera2 && pKF->mvuRight[idx] >= 0, is_right = pKF->NLeft != -1 && idx >= NLeft */
+    void AddObservation(long long mp_id, long long kf_id, int idx, bool is_right, int octave, bool stereo) {
+        check(vslam_covis_add_observation(c_, mp_id, kf_id, idx, is_right, octave, stereo));
+    }
+    /* MapPoint::EraseObservation -> whether the point became bad (SetBadFlag ran) */
+    bool EraseObservation(long long mp_id, long long kf_id) {
+        int bad = 0;
+        check(vslam_covis_erase_observation(c_, mp_id, kf_id, &bad));
+        return bad != 0;
+    }
+    /* the first block of MapPoint::SetBadFlag and of MapPoint::Replace */
+    void ClearMapPoint(long long mp_id) { check(vslam_covis_clear_point(c_, mp_id)); }
+    void EraseMapPoint(long long mp_id) { check(vslam_covis_erase_point(c_, mp_id)); }
+    void clearMap(int map_id) {
+        check(vslam_covis_clear_map(c_, map_id));
+        ordered_.clear();
+    }
+    void clear() {
+        check(vslam_covis_clear(c_));
+        ordered_.clear();
+    }
+    /* KeyFrame::SetBadFlag as far as the graph goes (keyframe.cpp:553, :629) */
+    void SetBadFlag(long long kf_id, const std::vector<long long>& mvpMapPoints) {
+        for (long long m : mvpMapPoints)
+            if (m != -1) EraseObservation(m, kf_id);
+        SetKeyFrameBad(kf_id);
+    }
+
+    std::vector<Connections> UpdateConnections(const FExtractor& extractor, const std::vector<ConnectionsJob>& jobs) {
+        std::vector<std::vector<int64_t> > ids(jobs.size());
+        std::vector<vslam_covis_job> J(jobs.size());
+        for (size_t j = 0; j < jobs.size(); j++) {
+            ids[j].assign(jobs[j].mp_ids.begin(), jobs[j].mp_ids.end());
+            J[j] = vslam_covis_job{jobs[j].mode, jobs[j].map_id, jobs[j].self_kf, jobs[j].min_obs, (int32_t)ids[j].size(), ids[j].data()};
+        }
+        std::vector<vslam_covis_result> R(jobs.size() + 1);
+        check(vslam_covis_connections(c_, context_of(extractor), (int)jobs.size(), J.data(), R.data()));
+        std::vector<Connections> out(jobs.size());
+        for (size_t j = 0; j < jobs.size(); j++) {
+            const vslam_covis_result& r = R[j];
+            std::vector<int64_t> ck((size_t)r.n_counter + 1), ok((size_t)r.n_ordered + 1);
+            std::vector<int32_t> cn((size_t)r.n_counter + 1), ow((size_t)r.n_ordered + 1);
+            check(vslam_covis_connections_lists(c_, (int)j, ck.data(), cn.data(), ok.data(), ow.data()));
+            Connections& o = out[j];
+            o.error = r.error;
+            o.counter_kf.assign(ck.begin(), ck.begin() + r.n_counter);
+            o.counter_n.assign(cn.begin(), cn.begin() + r.n_counter);
+            o.kf_max = r.kf_max;
+            o.n_max = r.n_max;
+            o.ordered_kf.assign(ok.begin(), ok.begin() + r.n_ordered);
+            o.ordered_w.assign(ow.begin(), ow.begin() + r.n_ordered);
+            o.n_tracked = r.n_tracked;
+            /* what GetBestCovisibilityKeyFrames reads; an empty counter leaves the lists as they were (keyframe.cpp:385) */
+            if (jobs[j].mode == CONNECTIONS && !r.error && r.n_counter) ordered_[jobs[j].self_kf] = o.ordered_kf;
+        }
+        return out;
+    }
+
+    std::vector<CullingResult> Culling(const FExtractor& extractor, const std::vector<CullingJob>& jobs, size_t first = 0, int thObs = 3) {
+        std::vector<std::vector<int64_t> > ids(jobs.size());
+        std::vector<vslam_covis_cull_job> J;
+        for (size_t j = first; j < jobs.size(); j++) {
+            if (jobs[j].levels.size() != jobs[j].mp_ids.size()) throw std::invalid_argument("CovisibilityMap::Culling: one level per MapPoint");
+            ids[j].assign(jobs[j].mp_ids.begin(), jobs[j].mp_ids.end());
+            J.push_back(vslam_covis_cull_job{jobs[j].kf_id, (int32_t)ids[j].size(), 0, ids[j].data(), jobs[j].levels.data()});
+        }
+        std::vector<vslam_covis_cull_result> R(J.size() + 1);
+        check(vslam_covis_culling(c_, context_of(extractor), (int)J.size(), J.data(), thObs, R.data()));
+        std::vector<CullingResult> out(J.size());
+        for (size_t j = 0; j < J.size(); j++) out[j] = CullingResult{R[j].error, R[j].n_mps, R[j].n_redundant};
+        return out;
+    }
+
+    /* The walk rule.  SetBadFlag on a culled keyframe erases its observations and changes the counts of the keyframes
+     * behind it, so the results of one enqueue hold up to and including the first job whose keyframe is culled: the walk
+     * takes the jobs in order, asks shouldCull(job, result) -- `nRedundantObservations > redundant_th * nMPs` and the
+     * inertial conditions of localmapping.cpp:1054-1096 -- lets applyCull(job) call the mutators (SetBadFlag above), and
+     * enqueues the jobs behind it again.  Returns every job's result as the sequential loop sees it. */
+    template <class ShouldCull, class ApplyCull>
+    std::vector<CullingResult> KeyFrameCulling(const FExtractor& extractor, const std::vector<CullingJob>& jobs, ShouldCull shouldCull,
+                                               ApplyCull applyCull, int thObs = 3) {
+        std::vector<CullingResult> out;
+        size_t at = 0;
+        while (at < jobs.size()) {
+            const std::vector<CullingResult> res = Culling(extractor, jobs, at, thObs);
+            for (size_t i = 0; i < res.size(); i++) {
+                out.push_back(res[i]);
+                const CullingJob& job = jobs[at++];
+                if (!res[i].error && shouldCull(job, res[i])) {
+                    applyCull(job);
+                    break;
+                }
+            }
+        }
+        return out;
+    }
+
+    /* GetBestCovisibilityKeyFrames(10) from the ordered list of the last CONNECTIONS result of the keyframe: as a
+     * vslam_kfdb_neighbours_fn (user = the CovisibilityMap) and as KeyFrameDatabase::Neighbours */
+    static int neighbours(void* user, int64_t kf_id, int64_t* out_ids) {
+        const CovisibilityMap* self = (const CovisibilityMap*)user;
+        const auto it = self->ordered_.find(kf_id);
+        if (it == self->ordered_.end()) return 0;
+        const int n = it->second.size() < 10 ? (int)it->second.size() : 10;
+        for (int i = 0; i < n; i++) out_ids[i] = it->second[(size_t)i];
+        return n;
+    }
+    KeyFrameDatabase::Neighbours neighbours() const {
+        return [this](long long kf_id) {
+            int64_t ids[10];
+            const int n = neighbours((void*)this, kf_id, ids);
+            return std::vector<long long>(ids, ids + n);
+        };
+    }
+
+    void size(int& keyframes, int& points, long long& observations) const { check(vslam_covis_size(c_, &keyframes, &points, &observations)); }
+    vslam_covis* handle() const { return c_; }
+
+private:
+    static vslam_fe* context_of(const FExtractor& extractor) {
+        if (!extractor.context()) throw std::runtime_error("CovisibilityMap: the extractor has not processed an image yet");
+        return extractor.context();
+    }
+    vslam_covis* c_ = nullptr;
+    std::map<long long, std::vector<long long> > ordered_;
+};
+
 } /* namespace geometry */
 
 /* ---------------------------------------------------------------------------------------------------

@@ -76,6 +76,12 @@ ABI_SYMBOLS = [
     "vslam_kfdb_create", "vslam_kfdb_create_ex", "vslam_kfdb_destroy", "vslam_kfdb_add", "vslam_kfdb_erase",
     "vslam_kfdb_clear", "vslam_kfdb_clear_map", "vslam_kfdb_size", "vslam_kfdb_stats", "vslam_kfdb_query_async",
     "vslam_kfdb_query_wait", "vslam_kfdb_select_relocalization", "vslam_kfdb_select_nbest",
+    "vslam_covis_create", "vslam_covis_destroy", "vslam_covis_limits", "vslam_covis_add_keyframe", "vslam_covis_add_keyframes",
+    "vslam_covis_set_keyframe_bad", "vslam_covis_set_keyframe_map", "vslam_covis_erase_keyframe", "vslam_covis_add_point",
+    "vslam_covis_add_observation", "vslam_covis_erase_observation", "vslam_covis_clear_point", "vslam_covis_erase_point",
+    "vslam_covis_clear_map", "vslam_covis_clear", "vslam_covis_size", "vslam_covis_stats", "vslam_covis_get_point",
+    "vslam_covis_connections_async", "vslam_covis_connections_wait", "vslam_covis_connections", "vslam_covis_connections_lists",
+    "vslam_covis_culling_async", "vslam_covis_culling_wait", "vslam_covis_culling", "vslam_covis_get_profile",
     "vslam_dbg_live_memory",
 ]
 
@@ -636,14 +642,84 @@ def bind_kfdb_select(L):
     return L
 
 
+class _CovisJob(C.Structure):  # vslam_covis_job
+    _fields_ = [("mode", C.c_int32), ("map_id", C.c_int32), ("self_kf", C.c_int64), ("min_obs", C.c_int32), ("n", C.c_int32),
+                ("mp_ids", C.c_void_p)]
+
+
+class _CovisResult(C.Structure):  # vslam_covis_result
+    _fields_ = [("error", C.c_int32), ("n_counter", C.c_int32), ("n_ordered", C.c_int32), ("n_max", C.c_int32),
+                ("kf_max", C.c_int64), ("n_tracked", C.c_int32), ("reserved", C.c_int32)]
+
+
+class _CovisCullJob(C.Structure):  # vslam_covis_cull_job
+    _fields_ = [("kf_id", C.c_int64), ("n", C.c_int32), ("reserved", C.c_int32), ("mp_ids", C.c_void_p),
+                ("levels", C.c_void_p)]
+
+
+class _CovisCullResult(C.Structure):  # vslam_covis_cull_result
+    _fields_ = [("error", C.c_int32), ("n_mps", C.c_int32), ("n_redundant", C.c_int32), ("reserved", C.c_int32)]
+
+
+#: vslam_covis_obs: one entry of MapPoint::mObservations
+COVIS_OBS_DTYPE = np.dtype([("kf_id", "<i8"), ("left_idx", "<i4"), ("right_idx", "<i4"), ("left_level", "<i4"),
+                            ("right_level", "<i4"), ("stereo", "<i4"), ("reserved", "<i4")])
+COVIS_MAX_JOBS, COVIS_MAX_LIST = 128, 8192
+COVIS_CONNECTIONS, COVIS_VOTE = 0, 1
+
+
+def bind_covis(L, prefix):
+    """ctypes signatures of the covisibility mirror: prefix vslam_covis_ (libvslam_fe.so) or vslamh_covis_ (the GPU-free
+    twin over the same bookkeeping, in both libraries)"""
+    vp, i, i64, i32 = C.c_void_p, C.c_int, C.c_int64, C.c_int32
+    g = lambda name: getattr(L, prefix + name)
+    g("destroy").argtypes = [vp]
+    g("destroy").restype = None
+    g("add_keyframe").argtypes = [vp, i64, i32, C.c_uint64]
+    g("add_keyframes").argtypes = [vp, i, vp, vp, vp]
+    g("set_keyframe_bad").argtypes = [vp, i64]
+    g("set_keyframe_map").argtypes = [vp, i64, i32]
+    g("erase_keyframe").argtypes = [vp, i64]
+    g("add_point").argtypes = [vp, i64]
+    g("add_observation").argtypes = [vp, i64, i64, i32, i, i, i]
+    g("erase_observation").argtypes = [vp, i64, i64, C.POINTER(i)]
+    g("clear_point").argtypes = [vp, i64]
+    g("erase_point").argtypes = [vp, i64]
+    g("clear_map").argtypes = [vp, i32]
+    g("clear").argtypes = [vp]
+    g("size").argtypes = [vp, C.POINTER(i), C.POINTER(i), C.POINTER(C.c_longlong)]
+    g("stats").argtypes = [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(i), C.POINTER(i)]
+    g("get_point").argtypes = [vp, i64, i, C.POINTER(i), C.POINTER(i), vp, C.POINTER(i)]
+    g("connections_lists").argtypes = [vp, i, vp, vp, vp, vp]
+    if prefix == "vslamh_covis_":
+        g("create").argtypes = [i]
+        g("create").restype = vp
+        g("last_error").argtypes = [vp]
+        g("last_error").restype = C.c_char_p
+        g("connections").argtypes = [vp, i, C.POINTER(_CovisJob), C.POINTER(_CovisResult)]
+        g("culling").argtypes = [vp, i, C.POINTER(_CovisCullJob), i, C.POINTER(_CovisCullResult)]
+    else:
+        g("create").argtypes = [i, i, C.POINTER(vp)]
+        g("limits").argtypes = [C.POINTER(i)] * 3
+        g("connections_async").argtypes = [vp, vp, i, C.POINTER(_CovisJob)]
+        g("connections_wait").argtypes = [vp, vp, C.POINTER(_CovisResult)]
+        g("connections").argtypes = [vp, vp, i, C.POINTER(_CovisJob), C.POINTER(_CovisResult)]
+        g("culling_async").argtypes = [vp, vp, i, C.POINTER(_CovisCullJob), i]
+        g("culling_wait").argtypes = [vp, vp, C.POINTER(_CovisCullResult)]
+        g("culling").argtypes = [vp, vp, i, C.POINTER(_CovisCullJob), i, C.POINTER(_CovisCullResult)]
+        g("get_profile").argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_longlong),
+                                     C.POINTER(C.c_long)]
+    return L
+
+
 _host_lib = None
 
 
 def host_lib():
-    """libvslam_host.so: the GPU-free host logic (selection stages, file readers)."""
+    """libvslam_host.so: the GPU-free host logic (selection stages, file readers, the covisibility twin)."""
     global _host_lib
     if _host_lib is None:
-        _host_lib = bind_voc_file(bind_kfdb_select(C.CDLL(HOST_LIB_PATH)))
+        _host_lib = bind_covis(bind_voc_file(bind_kfdb_select(C.CDLL(HOST_LIB_PATH))), "vslamh_covis_")
     return _host_lib
 
 
@@ -886,6 +962,7 @@ def lib():
         L.vslam_kfdb_query_async.argtypes = [vp, vp, i, vp, vp, vp]
         L.vslam_kfdb_query_wait.argtypes = [vp, vp, i, i, vp, vp, vp, vp, vp, C.POINTER(i)]
         bind_kfdb_select(L)
+        bind_covis(L, "vslam_covis_")
         _lib = L
     return _lib
 
@@ -2663,6 +2740,229 @@ class KeyFrameDatabase:
         return self._select(hits, self.place_score,
                             lambda io: kfdb_select_nbest(hits, io, map_id, connected, neighbours, n, bad_maps,
                                                          library=lib()))
+
+
+def _covis_ids(mp_ids):
+    """mvpMapPoints as ids: a sequence with None or -1 for NULL -> contiguous int64"""
+    if isinstance(mp_ids, np.ndarray):
+        return np.ascontiguousarray(mp_ids, np.int64)
+    return np.array([-1 if v is None else v for v in mp_ids], np.int64)
+
+
+class _CovisBase:
+    """The observation graph (MapPoint::mObservations, nObs, mbBad; the keyframes' map and mbBad) behind ids, and the
+    covisibility counts over it.  One mutator per call of the reference (include/vslam_fe.h, Covisibility)."""
+    _prefix = None
+
+    def _fn(self, name):
+        return getattr(self._L, self._prefix + name)
+
+    def _call(self, name, *args):
+        rc = self._fn(name)(self._h, *args)
+        if rc != VSLAM_OK:
+            self._raise(rc)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._fn("destroy")(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add_keyframe(self, kf_id, map_id, order_key):
+        self._call("add_keyframe", kf_id, map_id, order_key)
+
+    def add_keyframes(self, kf_ids, map_ids, order_keys):
+        kf, mp = np.ascontiguousarray(kf_ids, np.int64), np.ascontiguousarray(map_ids, np.int32)
+        key = np.ascontiguousarray(order_keys, np.uint64)
+        if not (len(kf) == len(mp) == len(key)):
+            raise ValueError("add_keyframes: three arrays of one length")
+        self._call("add_keyframes", len(kf), _p(kf), _p(mp), _p(key))
+
+    def set_keyframe_bad(self, kf_id):
+        self._call("set_keyframe_bad", kf_id)
+
+    def set_keyframe_map(self, kf_id, map_id):
+        self._call("set_keyframe_map", kf_id, map_id)
+
+    def erase_keyframe(self, kf_id):
+        self._call("erase_keyframe", kf_id)
+
+    def add_point(self, mp_id):
+        self._call("add_point", mp_id)
+
+    def add_observation(self, mp_id, kf_id, idx, is_right=False, level=0, stereo=False):
+        self._call("add_observation", mp_id, kf_id, idx, int(bool(is_right)), level, int(bool(stereo)))
+
+    def erase_observation(self, mp_id, kf_id):
+        """-> True when the point became bad (nObs <= 2) and lost its observations"""
+        bad = C.c_int()
+        self._call("erase_observation", mp_id, kf_id, C.byref(bad))
+        return bool(bad.value)
+
+    def clear_point(self, mp_id):
+        self._call("clear_point", mp_id)
+
+    def erase_point(self, mp_id):
+        self._call("erase_point", mp_id)
+
+    def clear_map(self, map_id):
+        self._call("clear_map", map_id)
+
+    def clear(self):
+        self._call("clear")
+
+    def size(self):
+        """(live keyframes, live points, observation entries)"""
+        k, m, o = C.c_int(), C.c_int(), C.c_longlong()
+        self._call("size", C.byref(k), C.byref(m), C.byref(o))
+        return k.value, m.value, o.value
+
+    def stats(self):
+        cap, used, ng, nc = C.c_longlong(), C.c_longlong(), C.c_int(), C.c_int()
+        self._call("stats", C.byref(cap), C.byref(used), C.byref(ng), C.byref(nc))
+        return dict(capacity=cap.value, used=used.value, growths=ng.value, compactions=nc.value)
+
+    def get_point(self, mp_id):
+        """-> (nObs, bad, entries as COVIS_OBS_DTYPE in ascending order_key)"""
+        nobs, bad, n = C.c_int(), C.c_int(), C.c_int()
+        self._call("get_point", mp_id, 0, C.byref(nobs), C.byref(bad), None, C.byref(n))
+        obs = np.zeros(n.value, COVIS_OBS_DTYPE)
+        if n.value:
+            self._call("get_point", mp_id, n.value, C.byref(nobs), C.byref(bad), _p(obs), C.byref(n))
+        return nobs.value, bool(bad.value), obs
+
+    @staticmethod
+    def _jobs(jobs):
+        """dicts(mode, self_kf, map_id, min_obs, mp_ids) -> (vslam_covis_job array, the id arrays it points into)"""
+        arr, keep = (_CovisJob * max(len(jobs), 1))(), []
+        for k, j in enumerate(jobs):
+            ids = _covis_ids(j["mp_ids"])
+            keep.append(ids)
+            arr[k] = _CovisJob(j.get("mode", COVIS_CONNECTIONS), j.get("map_id", 0), j.get("self_kf", -1), j.get("min_obs", 0),
+                               len(ids), ids.ctypes.data)
+        return arr, keep
+
+    @staticmethod
+    def _cull_jobs(jobs):
+        arr, keep = (_CovisCullJob * max(len(jobs), 1))(), []
+        for k, j in enumerate(jobs):
+            ids, lv = _covis_ids(j["mp_ids"]), np.ascontiguousarray(j["levels"], np.int32)
+            if len(ids) != len(lv):
+                raise ValueError("a culling job has one level per MapPoint")
+            keep += [ids, lv]
+            arr[k] = _CovisCullJob(j["kf_id"], len(ids), 0, ids.ctypes.data, lv.ctypes.data)
+        return arr, keep
+
+    def _deliver(self, res, n_jobs):
+        out = []
+        for j in range(n_jobs):
+            r = res[j]
+            ck, cn = np.zeros(r.n_counter, np.int64), np.zeros(r.n_counter, np.int32)
+            ok, ow = np.zeros(r.n_ordered, np.int64), np.zeros(r.n_ordered, np.int32)
+            self._call("connections_lists", j, _p(ck), _p(cn), _p(ok), _p(ow))
+            out.append(dict(error=r.error, counter_kf=ck, counter_n=cn, kf_max=r.kf_max, n_max=r.n_max, ordered_kf=ok,
+                            ordered_w=ow, n_tracked=r.n_tracked))
+        return out
+
+    @staticmethod
+    def _deliver_cull(res, n_jobs):
+        return [dict(error=res[j].error, n_mps=res[j].n_mps, n_redundant=res[j].n_redundant) for j in range(n_jobs)]
+
+
+class CovisibilityMap(_CovisBase):
+    """The mirror in HBM.  Queries run on the stream of an FExtractor context; up to COVIS_MAX_JOBS jobs per enqueue.
+    connections(fe, jobs): jobs are dicts(mode=COVIS_CONNECTIONS | COVIS_VOTE, self_kf, map_id, min_obs, mp_ids) -> per
+    job dict(error, counter_kf, counter_n, kf_max, n_max, ordered_kf, ordered_w, n_tracked).  culling(fe, jobs): dicts
+    (kf_id, mp_ids, levels) -> dict(error, n_mps, n_redundant)."""
+    _prefix = "vslam_covis_"
+
+    def __init__(self, device=0, initial_entries=0):
+        self._L = lib()
+        h = C.c_void_p()
+        _check(self._L.vslam_covis_create(device, initial_entries, C.byref(h)))
+        self._h = h
+        self._pending = None
+
+    def _raise(self, rc):
+        _check(rc)
+
+    @staticmethod
+    def limits():
+        a, b, c = C.c_int(), C.c_int(), C.c_int()
+        _check(lib().vslam_covis_limits(C.byref(a), C.byref(b), C.byref(c)))
+        return dict(max_jobs=a.value, max_list=b.value, lds_slots=c.value)
+
+    def connections_async(self, fe, jobs):
+        arr, keep = self._jobs(jobs)
+        self._call("connections_async", fe._h, len(jobs), arr)
+        self._pending = (fe, len(jobs))
+
+    def connections_wait(self):
+        if self._pending is None:
+            self._call("connections_wait", None, (_CovisResult * 1)())
+        fe, n = self._pending
+        res = (_CovisResult * max(n, 1))()
+        self._pending = None
+        self._call("connections_wait", fe._h, res)
+        return self._deliver(res, n)
+
+    def connections(self, fe, jobs):
+        self.connections_async(fe, jobs)
+        return self.connections_wait()
+
+    def culling_async(self, fe, jobs, th_obs=3):
+        arr, keep = self._cull_jobs(jobs)
+        self._call("culling_async", fe._h, len(jobs), arr, th_obs)
+        self._pending = (fe, len(jobs))
+
+    def culling_wait(self):
+        if self._pending is None:
+            self._call("culling_wait", None, (_CovisCullResult * 1)())
+        fe, n = self._pending
+        res = (_CovisCullResult * max(n, 1))()
+        self._pending = None
+        self._call("culling_wait", fe._h, res)
+        return self._deliver_cull(res, n)
+
+    def culling(self, fe, jobs, th_obs=3):
+        self.culling_async(fe, jobs, th_obs)
+        return self.culling_wait()
+
+    def profile(self):
+        a, q, b, n = C.c_double(), C.c_double(), C.c_longlong(), C.c_long()
+        self._call("get_profile", C.byref(a), C.byref(q), C.byref(b), C.byref(n))
+        return dict(apply_ms=a.value, query_ms=q.value, upload_bytes=b.value, passes=n.value)
+
+
+class CovisibilityMapHost(_CovisBase):
+    """The GPU-free twin over the same bookkeeping (libvslam_host.so): the CPU tests and demos; not a fallback."""
+    _prefix = "vslamh_covis_"
+
+    def __init__(self, initial_entries=0, library=None):
+        self._L = library if library is not None else host_lib()
+        self._h = C.c_void_p(self._L.vslamh_covis_create(initial_entries))
+        if not self._h:
+            raise VslamError(ERR_INVALID, "vslamh_covis_create")
+
+    def _raise(self, rc):
+        raise VslamError(rc, self._L.vslamh_covis_last_error(self._h).decode())
+
+    def connections(self, jobs):
+        arr, keep = self._jobs(jobs)
+        res = (_CovisResult * max(len(jobs), 1))()
+        self._call("connections", len(jobs), arr, res)
+        return self._deliver(res, len(jobs))
+
+    def culling(self, jobs, th_obs=3):
+        arr, keep = self._cull_jobs(jobs)
+        res = (_CovisCullResult * max(len(jobs), 1))()
+        self._call("culling", len(jobs), arr, th_obs, res)
+        return self._deliver_cull(res, len(jobs))
 
 
 def ComputeDistinctiveDescriptors(fe, desc, offsets):
