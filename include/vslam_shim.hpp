@@ -40,9 +40,9 @@
 #define VSLAM_SHIM_NAMESPACE vi_slam_amd
 #endif
 
-/* libvslam_fe.so, the host side (vi_slam_amd/csrc/vslam_host.h): SearchByProjection(CurrentFrame, LastFrame) of a two-fisheye
- * rig as the reference's sequential loop over host arrays -- what FMatcher::SearchByProjection(RigFrameView, ..) falls back on
- * beyond the device's limits */
+/* libvslam_fe.so, the host side (declared in vi_slam_amd/csrc/vslam_host.h, defined in vslam_match_host.cpp):
+ * SearchByProjection(CurrentFrame, LastFrame) of a two-fisheye rig as the reference's sequential loop over host arrays -- what
+ * FMatcher::SearchByProjection(RigFrameView, ..) falls back on beyond the device's limits */
 extern "C" int vslamh_search_by_projection_frame_rig(const vslam_proj_params* p, const vslam_kb8_camera* cam, const float* Trl,
                                                      const vslam_kp* last_kps, int n_last, const uint8_t* last_flags,
                                                      const float* last_x3dw, const uint8_t* mp_desc, const vslam_kp* kps_left,

@@ -290,6 +290,37 @@ def hand():
     return c
 
 
+# ------------------------------------------------------------------------------------------------ the KeyFrame's window origin
+def keyframe_origin():
+    """-> the smallest case that tells the KeyFrame's integer window origin from the Frame's float one; NOT one of cases()
+    (those share BOUNDS, whole numbers, where the two origins are one): it brings its own "bounds".  The cells come from the
+    float bounds (0.9, 60.9, 0.9, 45.9) and are 0.94 px wide, the KeyFrame places its window from (0, 0): 0.96 cell to the left.
+    One Scw job (no chi-square test), two points at level 0 (radius 3), each with ONE keypoint at Hamming distance 1:
+      0  u = 40.6, keypoint 2.9 px left of it, cell column 39; the window starts at column floor(37.6 * 64 / 60) = 40 -- not found
+         (from the float origin it would start at column 39 and find it);
+      1  u = 20, keypoint 0.5 px right of it -- found either way"""
+    if "origin" in _cache:
+        return _cache["origin"]
+    g = golden()
+    rng = np.random.default_rng(75)
+    job = dict(keyframe_jobs(np.hstack([np.eye(3), np.zeros((3, 1))]), None, None, None, None)[0], sim3=True)
+    pts, desc, keys = [], [], []
+    for px, dx in (((40.6, 20.0), -2.9), ((20.0, 20.0), 0.5)):
+        d = rng.integers(0, 256, 32).astype(np.uint8)
+        pos = world_point(job, px, 3.0)
+        u, v = project(job, pos)
+        pts.append(fuse_point(job, pos, 0))
+        desc.append(d)
+        keys.append((u + F32(dx), v + F32(0.25), flip(d, 1)))
+    k = np.zeros(len(keys), g["kl"].dtype)
+    k["x"], k["y"], k["size"] = [r[0] for r in keys], [r[1] for r in keys], 31.0
+    job.update(kps=k, desc=np.array([r[2] for r in keys], np.uint8))
+    c = dict(jobs=[job], pts=np.array(pts, orbo.FUSE_POINT_DTYPE), desc=np.array(desc, np.uint8), th=TH, gf=False, refuse=None,
+             bounds=(0.9, 60.9, 0.9, 45.9))
+    _cache["origin"] = c
+    return c
+
+
 # ------------------------------------------------------------------------------------------------ all cases
 def _first(c, n, jobs):
     jobs = [dict(j, valid=None if j["valid"] is None else j["valid"][:n]) for j in jobs]

@@ -20,13 +20,13 @@ Blur classes, from k_blur7_v2 (vi_slam_amd/csrc/vslam_image_kernels.hip:63-170) 
     (contexts of one or two images) or R = 32 (batches): only a blur_rows override of at least a level's height reaches it,
     and test_gpu_stages.py carries one.  Every other height class is required for both R = 8 and R = 32.
 
-FAST classes, from vslam::build_cells / build_bands / pack_bands (vslam_host.cpp:343-405, :602-632), which feed both
+FAST classes, from vslam::build_cells / build_bands / pack_bands (vslam_host.cpp), which feed both
 k_fast_cells_v3 (one workgroup per cell) and k_fast_bands (one per band):
   - one cell row / one cell column on a level (30 <= side - 32 < 60);
-  - the last cell of a row / column narrower or shorter than the others (clipped at the border, :359 / :364);
+  - the last cell of a row / column narrower or shorter than the others (clipped at the border, in build_cells);
   - a band of four cells; a band cut short because a fourth (or third ...) interior would pass 128 px, i.e. a cell row of
-    pitch > 32 with more cells than 128 / pitch (:389);
-  - a level with more than one column-table class (pitch, interior width) among its bands (:613-617);
+    pitch > 32 with more cells than 128 / pitch (build_bands);
+  - a level with more than one column-table class (pitch, interior width) among its bands (pack_bands);
   - the smallest candidate segment ceil(iw / 2) * ceil(ih / 2) of a cell (vslam_context.hip:204).  The clipped last cell
     of a row is narrowest where the level is just too narrow for one more column; among levels of at most 520 x 300 px
     that is 10 x 18 px (a level of 513 x 273), found by smallest_segment() below rather than written down;
@@ -64,7 +64,7 @@ def frame_id(f):
 
 
 def level_sizes(w, h, nlevels, scale):
-    """[(lw, lh)] as vslam::build_tables / level_size have them (vslam_host.cpp:32-46, :82-86): the scale factors are floats
+    """[(lw, lh)] as vslam::build_tables / level_size have them (vslam_host.cpp): the scale factors are floats
     multiplied up in double, the inverse is a float division, the size is cvRound (to nearest, ties to even) of a float
     product."""
     s = np.float32(1.0)

@@ -20,6 +20,7 @@ import pytest
 import fuse_rig_cases as FC
 import fuse_rig_ref as FR
 import fuse_rig_walk as FW
+from host_sources import host_sources
 import kb8_ref as KR
 import matcher_gate_cases as G
 import vi_slam_amd as V
@@ -141,6 +142,19 @@ def test_host_twin_equals_the_restatement(name):
     assert len(bad) == 0, (name, bad[:5])
 
 
+def test_host_twin_places_the_window_from_the_keyframes_integer_origin():
+    """FC.keyframe_origin(): bounds with fractions over cells narrower than a pixel, where the KeyFrame's truncated window origin
+    leaves out a keypoint within the radius that the Frame's float origin would reach"""
+    c, g = FC.keyframe_origin(), FC.golden()
+    args = (c["jobs"], c["pts"], c["desc"], g["cams"], c["th"], FC.LSF, g["sf"], g["is2"], c["bounds"])
+    want = FR.fuse_search_rig(*args)
+    assert want[0].tolist() == [[-1, 1]] and want[1].tolist() == [[256, 1]]
+    jobs, keep = _host_jobs(c)
+    got = V.fuse_search_rig_host(V.kb8_camera(*FC.CAM1), None, jobs, c["pts"], c["desc"], c["th"], FC.LSF, FC.IMG, g["sf"], g["is2"],
+                                 bounds=c["bounds"])
+    assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]), (got, want)
+
+
 def test_host_twin_refuses_bad_jobs():
     c = FC.cases()["np1"]
     for change in (dict(camera=2), dict(sim3=True, camera=1)):
@@ -152,12 +166,10 @@ def test_stand_alone_host_check_runs_clean_under_sanitizers(tmp_path):
     """tests/tools/fuse_rig_host_check.cpp and the host sources as ONE program with -fsanitize=address,undefined, over every
     exported case"""
     exe = str(tmp_path / "fuse_rig_host_check")
-    src = os.path.join(ROOT, "vi_slam_amd", "csrc")
     # -O0: half the build time of -O1
     cmd = ["g++", "-std=c++17", "-O0", "-g1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off",
            "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "tools", "fuse_rig_host_check.cpp"),
-           os.path.join(src, "vslam_host.cpp"), os.path.join(src, "vslam_voc_file.cpp"),
-           os.path.join(src, "vslam_voc_train_host.cpp"), "-o", exe]
+           *host_sources(), "-o", exe]
     r = subprocess.run(cmd, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     out = str(tmp_path / "cases")

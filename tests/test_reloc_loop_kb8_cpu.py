@@ -17,6 +17,7 @@ import sys
 import numpy as np
 import pytest
 
+from host_sources import host_sources
 import kb8_ref as KR
 import matcher_gate_cases as G
 import reloc_loop_kb8_cases as RC
@@ -247,12 +248,10 @@ def test_stand_alone_host_check_runs_clean_under_sanitizers(tmp_path):
     """tests/tools/reloc_loop_kb8_host_check.cpp and the host sources as ONE program with -fsanitize=address,undefined, over
     every exported case"""
     exe = str(tmp_path / "reloc_loop_kb8_host_check")
-    src = os.path.join(ROOT, "vi_slam_amd", "csrc")
     # -O0: half the build time of -O1
     cmd = ["g++", "-std=c++17", "-O0", "-g1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off",
            "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "tools", "reloc_loop_kb8_host_check.cpp"),
-           os.path.join(src, "vslam_host.cpp"), os.path.join(src, "vslam_voc_file.cpp"),
-           os.path.join(src, "vslam_voc_train_host.cpp"), "-o", exe]
+           *host_sources(), "-o", exe]
     r = subprocess.run(cmd, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     out = str(tmp_path / "cases")

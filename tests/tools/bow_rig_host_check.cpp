@@ -1,8 +1,8 @@
-/* The host twin of the rig SearchByBoW (vslamh_search_by_bow_rig, vi_slam_amd/csrc/vslam_host.cpp) as a program of its own, for a
- * sanitizer build on the CPU:
+/* The host twin of the rig SearchByBoW (vslamh_search_by_bow_rig, vi_slam_amd/csrc/vslam_match_host.cpp) as a program of its
+ * own, for a sanitizer build on the CPU:
  *   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -ffp-contract=off -I include \
- *       tests/tools/bow_rig_host_check.cpp vi_slam_amd/csrc/vslam_host.cpp vi_slam_amd/csrc/vslam_voc_file.cpp \
- *       vi_slam_amd/csrc/vslam_voc_train_host.cpp -o bow_rig_host_check
+ *       tests/tools/bow_rig_host_check.cpp \
+ *       $(make -s -C vi_slam_amd/csrc print-host-srcs P=vi_slam_amd/csrc/) -o bow_rig_host_check
  *   bow_rig_host_check case.bin ..      (written by tests/tools/dump_bow_rig_cases.py)
  * case.bin: int32 n_kf, kf_n_left, n_kf_nodes, n_kf_feat, n_f, n_left, n_f_nodes, n_f_feat, check_orientation; float nnratio; then
  * the KeyFrame's keypoints, descriptors, flags, nodes, offsets, features; the frame's keypoints, descriptors, nodes, offsets,

@@ -1,8 +1,8 @@
-/* The host twin of the rig motion-model matcher (vslamh_search_by_projection_frame_rig, vi_slam_amd/csrc/vslam_host.cpp) as a
- * program of its own, for a sanitizer build on the CPU:
+/* The host twin of the rig motion-model matcher (vslamh_search_by_projection_frame_rig, vi_slam_amd/csrc/vslam_match_host.cpp) as
+ * a program of its own, for a sanitizer build on the CPU:
  *   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -ffp-contract=off -I include \
- *       tests/tools/frame_rig_host_check.cpp vi_slam_amd/csrc/vslam_host.cpp vi_slam_amd/csrc/vslam_voc_file.cpp \
- *       vi_slam_amd/csrc/vslam_voc_train_host.cpp -o frame_rig_host_check
+ *       tests/tools/frame_rig_host_check.cpp \
+ *       $(make -s -C vi_slam_amd/csrc print-host-srcs P=vi_slam_amd/csrc/) -o frame_rig_host_check
  *   frame_rig_host_check case.bin      (written by tests/tools/dump_frame_rig_case.py)
  * case.bin: int32 n_last, n_left, n_right, has_occ, nlevels; one vslam_proj_params; one vslam_kb8_camera; float Trl[12],
  * bounds[4], scale[nlevels]; then last-frame keypoints, flags, positions, descriptors, left keypoints, left descriptors, right

@@ -1,8 +1,8 @@
-/* The host twin of the rig Fuse search (vslamh_fuse_search_rig, vi_slam_amd/csrc/vslam_host.cpp) as a program of its own, for a
- * sanitizer build on the CPU:
+/* The host twin of the rig Fuse search (vslamh_fuse_search_rig, vi_slam_amd/csrc/vslam_match_host.cpp) as a program of its
+ * own, for a sanitizer build on the CPU:
  *   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -ffp-contract=off -I include \
- *       tests/tools/fuse_rig_host_check.cpp vi_slam_amd/csrc/vslam_host.cpp vi_slam_amd/csrc/vslam_voc_file.cpp \
- *       vi_slam_amd/csrc/vslam_voc_train_host.cpp -o fuse_rig_host_check
+ *       tests/tools/fuse_rig_host_check.cpp \
+ *       $(make -s -C vi_slam_amd/csrc print-host-srcs P=vi_slam_amd/csrc/) -o fuse_rig_host_check
  *   fuse_rig_host_check case.bin ..      (written by tests/tools/dump_fuse_rig_cases.py)
  * case.bin: int32 n_jobs, n_points, nlevels, gemm_float; float th, log_scale_factor, bounds[4]; the two cameras (9 floats each);
  * Tlr, Trl (12 floats each); scale factors and inverse sigma2 (nlevels each); the points (vslam_fuse_point) and their

@@ -1,8 +1,8 @@
-/* The host twin of the rig matcher (vslamh_search_by_projection_mappoints_rig, vi_slam_amd/csrc/vslam_host.cpp) as a program of
- * its own, for a sanitizer build on the CPU:
+/* The host twin of the rig matcher (vslamh_search_by_projection_mappoints_rig, vi_slam_amd/csrc/vslam_match_host.cpp) as a
+ * program of its own, for a sanitizer build on the CPU:
  *   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -ffp-contract=off -I include \
- *       tests/tools/local_points_rig_host_check.cpp vi_slam_amd/csrc/vslam_host.cpp vi_slam_amd/csrc/vslam_voc_file.cpp \
- *       vi_slam_amd/csrc/vslam_voc_train_host.cpp -o rig_host_check
+ *       tests/tools/local_points_rig_host_check.cpp \
+ *       $(make -s -C vi_slam_amd/csrc print-host-srcs P=vi_slam_amd/csrc/) -o rig_host_check
  *   rig_host_check case.bin      (written by tests/tools/dump_local_points_rig_case.py)
  * case.bin: int32 n_mp, n_left, n_right, has_occ, nlevels; float th, nnratio, bounds[4], scale[nlevels]; then left records, right
  * records, descriptors, left keypoints, left descriptors, right keypoints, right descriptors, L2R, R2L, [occupied], and the

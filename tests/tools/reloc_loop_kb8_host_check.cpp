@@ -1,9 +1,9 @@
 /* The host twins of the relocalisation and the loop-closing SearchByProjection for fisheye cameras
- * (vslamh_search_by_projection_keyframe_kb8, vslamh_search_by_projection_sim3_kb8, vi_slam_amd/csrc/vslam_host.cpp) as a program
- * of its own, for a sanitizer build on the CPU:
+ * (vslamh_search_by_projection_keyframe_kb8, vslamh_search_by_projection_sim3_kb8, vi_slam_amd/csrc/vslam_match_host.cpp) as a
+ * program of its own, for a sanitizer build on the CPU:
  *   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -ffp-contract=off -I include \
- *       tests/tools/reloc_loop_kb8_host_check.cpp vi_slam_amd/csrc/vslam_host.cpp vi_slam_amd/csrc/vslam_voc_file.cpp \
- *       vi_slam_amd/csrc/vslam_voc_train_host.cpp -o reloc_loop_kb8_host_check
+ *       tests/tools/reloc_loop_kb8_host_check.cpp \
+ *       $(make -s -C vi_slam_amd/csrc print-host-srcs P=vi_slam_amd/csrc/) -o reloc_loop_kb8_host_check
  *   reloc_loop_kb8_host_check case.bin ..      (written by tests/tools/dump_reloc_loop_kb8_cases.py)
  * case.bin starts with eight int32, the first of them 0 (A) or 1 (B), and six floats.
  *   A: 0, n_kf, n_cur, nlevels, gemm_float, check_orientation, orb_dist, has_occupied; th, log_scale_factor, bounds[4]; the

@@ -5,7 +5,7 @@
  * ties" -- runs on the GPU: 16 lanes per feature (one child per lane, k = 10 for the ORB vocabulary), 4 features per
  * wave, the arg-min as a 4-step shuffle reduction on dist << 20 | child position.  What is left (accumulating the
  * word weights in a std::map in feature order, the L1/L2 normalisation in double, grouping feature indices by node)
- * is order-dependent double arithmetic on ~2000 items and stays on the host: vslam_bow_assemble (vslam_host.cpp).
+ * is order-dependent double arithmetic on ~2000 items and stays on the host: vslam_bow_assemble (vslam_kfdb_host.cpp).
  */
 #include "vslam_ctx.h"
 #include "vslam_kernels.h"

@@ -1,6 +1,6 @@
 /* vslam_featuretracker.hip -- the pyramidal Lucas-Kanade feature tracker, vilib::FeatureTrackerGPU
  * (include/vslam_featuretracker.h): the two kernels, the per-frame sequence and the C ABI.  The bookkeeping (track list,
- * buffer ids, feature list, occupancy, best-N) is vslam_host.cpp's vslam_ftbook; pyramid and detector: vslam_griddet.h.
+ * buffer ids, feature list, occupancy, best-N) is vslam_ftbook.cpp's vslam_ftbook; pyramid and detector: vslam_griddet.h.
  *
  * What the reference runs (CUDA, warp = 32, thirdparty/vilib/visual_lib/src/feature_tracker/feature_tracker_cuda_tools.cu):
  *   K10 update_tracks_kernel    :624-690  3 candidates per block; the int template patches with a 1-px rim and the inverse of

@@ -1,6 +1,6 @@
 /* vslam_frustum.h -- Frame::isInFrustum (frame.cpp:529-595, the pinhole branch Nleft == -1) and MapPoint::PredictScale
  * (mappoint.cpp:523-538) for one MapPoint, written once for the device (k_frustum, vslam_frustum.hip) and the host
- * (vslamh_in_frustum in vslam_host.cpp: CPU tests and the stand-alone demo, not a fallback of the product).
+ * (vslamh_in_frustum in vslam_camera_host.cpp: CPU tests and the stand-alone demo, not a fallback of the product).
  * The same test with the fisheye projection (mpCamera = KannalaBrandt8) and the two-camera branch Nleft != -1
  * (isInFrustumChecks) are in vslam_kb8.h, built from the pieces of this header.
  *

@@ -2,7 +2,7 @@
  * cameras of a two-fisheye rig (fmatcher.cpp:1918-2119 with pKF->NLeft != -1; the Scw overload :2121-2243 as sim3 = 1): one
  * MapPoint list against up to 16 (KeyFrame, camera) jobs in one enqueue.  The rules are stated in include/vslam_fe.h above
  * vslam_fuse_rig_job; the kernel is k_fuse_rank_rig (vslam_projection_kernels.hip), the host twin vslamh_fuse_search_rig
- * (vslam_host.cpp).  The staging block fe->fsr is this entry's own: the blocking matchers, which fill fe->proj on the host at
+ * (vslam_match_host.cpp).  The staging block fe->fsr is this entry's own: the blocking matchers, which fill fe->proj on the host at
  * once, can run while a search is in flight. */
 #include "vslam_sbp_host.h"
 

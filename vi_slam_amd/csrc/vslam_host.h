@@ -2,6 +2,9 @@
  * resize coefficient tables, the FAST cell list, the sequential quadtree distribution and the
  * order-dependent matcher replays.  Plain C++17; built into libvslam_fe.so (with the kernels) and into
  * libvslam_host.so (g++, no HIP) so the CPU test-suite can exercise it without a GPU.
+ * namespace vslam is vslam_host.cpp; the C declarations at the end are grouped by the file that defines them
+ * (vslam_match_host.cpp, vslam_camera_host.cpp).  vslam_kfdb_host.cpp and vslam_ftbook.cpp define what include/vslam_fe.h and
+ * include/vslam_featuretracker.h declare.
  */
 #ifndef VSLAM_HOST_H
 #define VSLAM_HOST_H
@@ -15,6 +18,9 @@
 
 /* EDGE_THRESHOLD-3: the FAST cell grid starts 16 px inside the level (fextractor.cpp:764-767) */
 #define VSLAM_FAST_BORDER 16
+
+/* shared between the host files of one library, not exported from it */
+#define VSLAM_HOST_INTERNAL __attribute__((visibility("hidden")))
 
 namespace vslam {
 
@@ -188,6 +194,9 @@ struct FrameGrid {
     int n;
     void build(const vslam_kp* k, int n_, int imgW, int imgH); /* bounds {0, imgW, 0, imgH} */
     void build(const vslam_kp* k, int n_, const float bounds[4]); /* minX, maxX, minY, maxY (ComputeImageBounds) */
+    /* A KeyFrame's grid: the cells and inverses are the Frame's, made from its float bounds (keyframe.cpp:36, :58-67), while
+     * KeyFrame::GetFeaturesInArea (:663-675) places its window from the integer mnMinX / mnMinY the KeyFrame truncated them to */
+    VSLAM_HOST_INTERNAL void build_keyframe(const vslam_kp* k, int n_, const float bounds[4]);
     void query(float x, float y, float r, int minLevel, int maxLevel, std::vector<int>& out) const;
 };
 
@@ -199,6 +208,12 @@ int search_for_initialization_replay(const vslam_kp* kps1, int n1, const vslam_k
                                      const uint8_t* dmat, const int* row_of_i1, const int* col_of_i2,
                                      int ncols, const float bounds[4], float* prevMatched, int32_t* matches12,
                                      int windowSize, float nnratio, bool checkOri);
+
+/* The end of every matcher's orientation check: the three fullest bins of the rotation histogram stay
+ * (vslam_md::three_maxima / keeps_bin, the kernels' text), the entries of every other bin are returned, bin after bin in the
+ * order they were pushed.  The caller clears them by its own rule: SearchForInitialization counts a loser only if it still
+ * holds a match (fmatcher.cpp:1082-1086), the other matchers count every one. */
+VSLAM_HOST_INTERNAL std::vector<int> rotation_losers(const std::vector<int>* rotHist /* 30 = FMatcher::HISTO_LENGTH bins */);
 
 /* Carving of one staging block (vslam_staging.h): part 0 starts at 0 and part i at the end of part i - 1 rounded up to
  * `align` (a power of two), so a part of no bytes takes no room.  off[0 .. n) receives the starts; returns the rounded
@@ -214,24 +229,20 @@ std::array<size_t, N + 1> layout(size_t align, const size_t (&sizes)[N]) {
 
 } // namespace vslam
 
-/* vslam_host.cpp: layout_parts for the CPU suite (off: n entries); returns the total */
+/* ---- vslam_host.cpp (its other vslamh_* hooks serve the CPU suite alone, which declares them where it calls them) */
+/* layout_parts for the CPU suite (off: n entries); returns the total */
 extern "C" uint64_t vslamh_layout(uint64_t align, const uint64_t* sizes, int n, uint64_t* off);
-/* vslam_host.cpp: index map-back and over-capacity decision of vslam_search_local_points_wait */
+
+/* ---- vslam_match_host.cpp: the matchers on the host */
+/* index map-back and over-capacity decision of vslam_search_local_points_wait */
 extern "C" int vslamh_local_points_finish(const int32_t* match_compact, int n_cur, const int32_t* orig_index, int n_kept,
                                           int capacity, int32_t* match_cur);
-/* vslam_host.cpp: the range check of a rig frame's mvLeftToRightMatch / mvRightToLeftMatch (each entry -1 or an index of the
+/* the range check of a rig frame's mvLeftToRightMatch / mvRightToLeftMatch (each entry -1 or an index of the
  * other side), as vslam_search_by_projection_mappoints_rig makes it before anything is enqueued */
 extern "C" int vslamh_rig_maps_check(const int32_t* left_to_right, int n_left, const int32_t* right_to_left, int n_right);
-/* vslam_host.cpp: vslam_two_view_score over host arrays by the shared vslam_two_view.h code (CPU tests, the demo) */
+/* vslam_two_view_score over host arrays by the shared vslam_two_view.h code (CPU tests, the demo) */
 extern "C" int vslamh_two_view_score(const vslam_two_view_job* job, vslam_two_view_result* result);
-/* vslam_host.cpp: the decisions around a KB8 camera, as the entry points take them (each returns a VSLAM_* code):
- * _exclusive: setting a KB8 camera beside a pinhole camera with that k1, or a pinhole camera with that k1 beside a KB8 camera
- * (other_set: the other kind is set); _frustum_check: the frustum parameters against the camera (NULL: pinhole, nothing to check); _projecting_entry:
- * an entry point that projects with intrinsics of its own */
-extern "C" int vslamh_kb8_exclusive(int other_set, float k1);
-extern "C" int vslamh_kb8_frustum_check(const vslam_frustum_params* p, const vslam_kb8_camera* cam);
-extern "C" int vslamh_kb8_projecting_entry(int has_kb8);
-/* vslam_host.cpp: vslam_search_by_projection_frame_rig's intrinsics test (p's fx, fy, cx, cy against the KB8 camera, bit for
+/* vslam_search_by_projection_frame_rig's intrinsics test (p's fx, fy, cx, cy against the KB8 camera, bit for
  * bit), and the function itself over host arrays, sequential as the reference writes it (CPU tests, the shim's fallback) */
 extern "C" int vslamh_frame_rig_camera_check(const vslam_proj_params* p, const vslam_kb8_camera* cam);
 extern "C" int vslamh_search_by_projection_frame_rig(const vslam_proj_params* p, const vslam_kb8_camera* cam, const float* Trl,
@@ -241,7 +252,7 @@ extern "C" int vslamh_search_by_projection_frame_rig(const vslam_proj_params* p,
                                                      const uint8_t* desc_right, int n_right, const uint8_t* occupied,
                                                      const float* scale_factors, int nlevels, const float* bounds,
                                                      int32_t* match_cur, int* nmatches);
-/* vslam_host.cpp: SearchByBoW(KeyFrame, Frame) of a rig (fmatcher.cpp:546-748, F.Nleft != -1) over host arrays for one keyframe,
+/* SearchByBoW(KeyFrame, Frame) of a rig (fmatcher.cpp:546-748, F.Nleft != -1) over host arrays for one keyframe,
  * sequential as the reference writes it (CPU tests, the shim's fallback beyond the device limits) */
 extern "C" int vslamh_search_by_bow_rig(const vslam_kp* kf_kps, const uint8_t* kf_desc_left, int kf_n_left,
                                         const uint8_t* kf_desc_right, int kf_n_right, const uint8_t* kf_flags,
@@ -250,14 +261,14 @@ extern "C" int vslamh_search_by_bow_rig(const vslam_kp* kf_kps, const uint8_t* k
                                         const vslam_kp* f_kps_right, const uint8_t* f_desc_right, int n_right,
                                         const int32_t* f_fv_nodes, const int32_t* f_fv_off, const int32_t* f_fv_feat,
                                         int n_f_nodes, float nnratio, int check_orientation, int32_t* match_f, int* nmatches);
-/* vslam_host.cpp: the search half of Fuse for a fisheye KeyFrame / a rig (vslam_fuse_search_rig) over host arrays, a job's
+/* the search half of Fuse for a fisheye KeyFrame / a rig (vslam_fuse_search_rig) over host arrays, a job's
  * dev_kps / dev_desc included, sequential as the reference writes it; any number of jobs and points (CPU tests, and the shim's
  * walk for the one-point searches of a MapPoint whose descriptor was recomputed) */
 extern "C" int vslamh_fuse_search_rig(const vslam_fuse_params* p, const vslam_kb8_camera* cam, const vslam_kb8_rig* rig,
                                       const vslam_fuse_rig_job* jobs, int n_jobs, const vslam_fuse_point* points,
                                       const uint8_t* mp_desc, int n_points, const float* scale_factors, const float* inv_sigma2,
                                       int nlevels, const float* bounds, int32_t* best_idx, int32_t* best_dist);
-/* vslam_host.cpp: the relocalisation and loop-closing SearchByProjection for fisheye cameras
+/* the relocalisation and loop-closing SearchByProjection for fisheye cameras
  * (vslam_search_by_projection_keyframe_kb8, vslam_search_by_projection_sim3_kb8) over host arrays, sequential as the reference
  * writes them; the second takes any number of jobs, points and survivors (CPU tests, the shim's fallback for a refused job) */
 extern "C" int vslamh_search_by_projection_keyframe_kb8(const vslam_proj_params* p, const vslam_kb8_camera* cam, const float* Ow,
@@ -271,4 +282,13 @@ extern "C" int vslamh_search_by_projection_sim3_kb8(const vslam_sim3_kb8_params*
                                                     const vslam_sim3_kb8_job* jobs, int n_jobs, const vslam_fuse_point* points,
                                                     const uint8_t* mp_desc, int n_points, const float* scale_factors, int nlevels,
                                                     const float* bounds, int32_t* const* match_kf, int* nmatches, int* n_gated);
+
+/* ---- vslam_camera_host.cpp: the camera models on the host */
+/* the decisions around a KB8 camera, as the entry points take them (each returns a VSLAM_* code):
+ * _exclusive: setting a KB8 camera beside a pinhole camera with that k1, or a pinhole camera with that k1 beside a KB8 camera
+ * (other_set: the other kind is set); _frustum_check: the frustum parameters against the camera (NULL: pinhole, nothing to check); _projecting_entry:
+ * an entry point that projects with intrinsics of its own */
+extern "C" int vslamh_kb8_exclusive(int other_set, float k1);
+extern "C" int vslamh_kb8_frustum_check(const vslam_frustum_params* p, const vslam_kb8_camera* cam);
+extern "C" int vslamh_kb8_projecting_entry(int has_kb8);
 #endif

@@ -1,6 +1,6 @@
 /* vslam_kb8.h -- the KannalaBrandt8 fisheye camera (kannalabrandt8.cpp:11-27 project, :82-109 unproject) and the frustum
  * test of a fisheye Frame (frame.cpp:529-595 with the virtual camera; :596-606 and isInFrustumChecks :1191-1271 for a
- * two-camera rig), written once for the device (vslam_kb8.hip) and the host (the vslamh_* twins of vslam_host.cpp: CPU tests
+ * two-camera rig), written once for the device (vslam_kb8.hip) and the host (the vslamh_* twins of vslam_camera_host.cpp: CPU tests
  * and the stand-alone demo, not a fallback of the product).
  *
  * The reference calls the host libm: atan2f, sqrtf, std::cos(float), std::sin(float), std::tan(float).  Device libm is not
@@ -355,7 +355,7 @@ VSLAM_HD bool in_frustum_check(const vslam_fr::Frame& F, const float* T, const f
     return true;
 }
 
-/* what the host checks before a launch; shared with the CPU tests through vslamh_kb8_* (vslam_host.cpp) */
+/* what the host checks before a launch; shared with the CPU tests through vslamh_kb8_* (vslam_camera_host.cpp) */
 static inline bool camera_ok(const vslam_kb8_camera* c) {
     if (!c) return false;
     const float v[9] = {c->fx, c->fy, c->cx, c->cy, c->k[0], c->k[1], c->k[2], c->k[3], c->precision};

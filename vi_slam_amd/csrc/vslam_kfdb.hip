@@ -9,7 +9,7 @@
  * number stands for it: the reference meets the keyframes sharing words with a query in the order (smallest common
  * word, slot).  What follows the hit list -- exclusion of connected keyframes, minCommonWords, covisibility
  * accumulation, the candidate lists -- is order-dependent work on a few hundred items and lives on the host:
- * vslam_kfdb_select_* (vslam_host.cpp).
+ * vslam_kfdb_select_* (vslam_kfdb_host.cpp).
  */
 #include <unordered_map>
 

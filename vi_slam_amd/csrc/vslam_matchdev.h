@@ -1,8 +1,8 @@
 /* vslam_matchdev.h -- the reference arithmetic that the matchers share, each thing once.
  *
  * The first part is host/device text (VSLAM_HD): the rotation histogram of every FMatcher search, cv::norm / cv::Mat::dot
- * of a 3-vector and MapPoint::PredictScale.  The kernels, vslam_frustum.h and the host replay of vslam_host.cpp (CPU
- * tests) run the same lines.  The second part is device only: the Frame grid window, the match key, and the pieces of
+ * of a 3-vector and MapPoint::PredictScale.  The kernels, vslam_frustum.h, the host replay of vslam_host.cpp and the
+ * matcher twins of vslam_match_host.cpp (CPU tests) run the same lines.  The second part is device only: the Frame grid window, the match key, and the pieces of
  * the SearchByProjection family that more than one kernel file or kernel needs.
  *
  * Contraction: on the device every operation goes through the _rn intrinsics; host builds rely on -ffp-contract=off

@@ -2,7 +2,7 @@
  * fisheye KeyFrames: ONE MapPoint list against up to 16 (KeyFrame, Scw) jobs in one enqueue, the shape of
  * LoopClosing::FindMatchesByProjection's callers.  The rules are stated in include/vslam_fe.h above vslam_sim3_kb8_job; the
  * kernels are k_s3k_gate / k_s3k_compact / k_sbp_rank_kb8 / k_sbp_resolve / k_sbp_replay / k_s3k_finish
- * (vslam_projection_kernels.hip), the host twin vslamh_search_by_projection_sim3_kb8 (vslam_host.cpp).  The staging block
+ * (vslam_projection_kernels.hip), the host twin vslamh_search_by_projection_sim3_kb8 (vslam_match_host.cpp).  The staging block
  * fe->s3k is this entry's own: the blocking matchers, which fill fe->proj on the host at once, can run while a search is in
  * flight.  What only the kernels touch (gate records, compacted arrays, the matcher's scratch) lives in fe->d_s3k. */
 #include <vector>

@@ -1,6 +1,6 @@
 /* vslam_two_view.h -- MotionEstimator::CheckHomography (motion_estimation.cpp:2277-2360) and CheckFundamental (:2362-2440)
  * for one pair under one hypothesis, and the selection of FindHomography / FindFundamental (:2120-2143, :2171-2194), written
- * once for the device (k_tv_score, k_tv_select in vslam_two_view.hip) and the host (vslamh_two_view_score in vslam_host.cpp:
+ * once for the device (k_tv_score, k_tv_select in vslam_two_view.hip) and the host (vslamh_two_view_score in vslam_match_host.cpp:
  * CPU tests and the stand-alone demo, not a fallback of the product).
  *
  * What the reference evaluates per pair (u1, v1) = mvKeys1[i].pt, (u2, v2) = mvKeys2[j].pt, in its order:

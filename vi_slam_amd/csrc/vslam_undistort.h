@@ -1,5 +1,5 @@
 /* vslam_undistort.h -- cv::undistortPoints(src, dst, K, D, noArray(), K) of OpenCV 4.2 for one point, written once for
- * the device (k_undistort_kps, vslam_undistort.hip) and the host (vslam_host.cpp, image bounds, CPU tests).
+ * the device (k_undistort_kps, vslam_undistort.hip) and the host (vslam_camera_host.cpp, image bounds, CPU tests).
  *
  * What the reference calls (frame.cpp:758-790 UndistortKeyPoints, :793-821 ComputeImageBounds) lands in
  * cvUndistortPointsInternal with TermCriteria(MAX_ITER, 5, 0.01): exactly five fixed-point iterations, no EPS test,
