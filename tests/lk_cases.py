@@ -81,18 +81,23 @@ def summary(tracker, counts):
                 disparity=u32(np.array([tracker.book.disparity(0.5)], np.float32)))
 
 
-@functools.lru_cache(None)
-def run_ref(name):
-    """-> (the lk_ref.Tracker after the case's last frame, summary, per-frame summaries)"""
-    kind, opts, get = cases()[name]
-    seq = get()
+def run_case(kind, opts, seq, border=BORDER):
+    """one case (detector, options, frames) through the yardstick -> (the lk_ref.Tracker after the last frame, summary,
+    per-frame summaries); tests/lk_edge_cases.py runs its table through this too"""
     nc, nr = grid(seq[0])
-    T = lk.Tracker(lk.Options(**opts), ref_detector(kind), nc, nr, CELL, CELL)
+    T = lk.Tracker(lk.Options(**opts), ref_detector(kind, border), nc, nr, CELL, CELL)
     counts, per_frame = [], []
     for img in seq:
         counts.append(T.track(img))
         per_frame.append(summary(T, counts))
     return T, per_frame[-1], per_frame
+
+
+@functools.lru_cache(None)
+def run_ref(name):
+    """-> (the lk_ref.Tracker after the case's last frame, summary, per-frame summaries)"""
+    kind, opts, get = cases()[name]
+    return run_case(kind, opts, get())
 
 
 def templates(T):

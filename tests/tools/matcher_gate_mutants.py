@@ -4,29 +4,15 @@
 Each mutant is a one-line change of the device code: a comparison operator, a literal or a literal's type; none removes a
 clamp or touches an index (the tie-key mutant mirrors the index field in the encoder AND the decoder, so every index it
 yields is the one that went in).  The old text must occur exactly once in its file or the tool stops.
+Build, run and report are tests/tools/mutant_driver.py's (its docstring describes them); the report is
+profiles/matcher_gate_mutants.txt.
 
-  build   every mutant is applied to a copy of vi_slam_amd/csrc (with include/) in a temporary directory OUTSIDE the tree
-          and built there with `make -j N` (N <= 16; hipcc cross-compiles without a GPU); its libvslam_fe.so is copied to
-          --libs DIR/<name>.so.
-  run     per mutant one fresh child process per group of pytest files, under its own `timeout`, with VSLAM_FE_LIB naming
-          the mutant's library: the new gate module, and (with --parent) the files that owned these gates before it.
-          Exit status 0 = the files passed, the mutant SURVIVED them; 1 = noticed.  Any other status stops the tool.
-  report  --out FILE (profiles/matcher_gate_mutants.txt)
-
-    python tests/tools/matcher_gate_mutants.py build --libs DIR [--jobs 16] [--only NAME ...]
+    python tests/tools/matcher_gate_mutants.py build --libs DIR [--jobs 16] [--parallel 1] [--only NAME ...]
     python tests/tools/matcher_gate_mutants.py run --libs DIR [--parent] [--out FILE] [--only NAME ...]
                                                    [--json FILE --resume --limit N]   (a run split over several calls)
 """
-import argparse
-import json
-import os
-import shutil
-import subprocess
-import sys
-import tempfile
-import time
+import mutant_driver
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 PK, PJ, MD, BW = ("vslam_projection_kernels.hip", "vslam_projection.hip", "vslam_matchdev.h", "vslam_bow.hip")
 NEW = ["tests/test_gpu_matcher_gates.py"]
 PARENT = ["tests/test_gpu_projection.py", "tests/test_gpu_projection_bounds.py", "tests/test_gpu_mapping.py",
@@ -101,124 +87,8 @@ MUTANTS = [
 ]
 
 
-def apply_edits(src_dir, edits):
-    for fname, old, new in edits:
-        path = os.path.join(src_dir, fname)
-        with open(path) as f:
-            text = f.read()
-        if text.count(old) != 1:
-            sys.exit("mutant text occurs %d times in %s (must be once): %r" % (text.count(old), fname, old))
-        with open(path, "w") as f:
-            f.write(text.replace(old, new))
-
-
-def build(args):
-    jobs = min(int(args.jobs), 16)
-    os.makedirs(args.libs, exist_ok=True)
-    work = tempfile.mkdtemp(prefix="gate_mutants_")
-    try:
-        for name, edits, _ in MUTANTS:
-            if args.only and name not in args.only:
-                continue
-            top = os.path.join(work, name)
-            shutil.copytree(os.path.join(ROOT, "vi_slam_amd", "csrc"), os.path.join(top, "vi_slam_amd", "csrc"))
-            shutil.copytree(os.path.join(ROOT, "include"), os.path.join(top, "include"))
-            csrc = os.path.join(top, "vi_slam_amd", "csrc")
-            apply_edits(csrc, edits)
-            t0 = time.time()
-            subprocess.check_call(["make", "-s", "-C", csrc, "-j%d" % jobs, "../libvslam_fe.so"])
-            shutil.copy(os.path.join(top, "vi_slam_amd", "libvslam_fe.so"), os.path.join(args.libs, name + ".so"))
-            print("built %-32s %5.1f s" % (name, time.time() - t0), flush=True)
-            shutil.rmtree(top)
-    finally:
-        shutil.rmtree(work, ignore_errors=True)
-
-
-def run_files(lib, files, limit):
-    """one fresh child under its own time limit -> exit status"""
-    env = dict(os.environ, VSLAM_FE_LIB=os.path.abspath(lib))
-    cmd = ["timeout", "-k", "10", str(limit), sys.executable, "-m", "pytest", "-m", "gpu", "-q", "-x", "-p", "no:cacheprovider"] + files
-    return subprocess.call(cmd, cwd=ROOT, env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-
-
-def run(args):
-    rows = []
-    if args.resume and args.json and os.path.exists(args.json):  # a run split over several calls: keep what is there
-        with open(args.json) as f:
-            rows = json.load(f)
-    done = {r["name"] for r in rows}
-    verdict = {0: "survived", 1: "noticed"}
-    for name, edits, equivalent in MUTANTS:
-        if (args.only and name not in args.only) or name in done:
-            continue
-        if args.limit and len(rows) - len(done) >= args.limit:
-            break
-        lib = os.path.join(args.libs, name + ".so")
-        if not os.path.exists(lib):
-            sys.exit("no library for mutant %s in %s: run `build` first" % (name, args.libs))
-        rec = dict(name=name, equivalent=equivalent, edits=[(f, o, n) for f, o, n in edits])
-        groups = [("new", NEW, 300)] + ([("parent", PARENT, 900)] if args.parent else [])
-        for key, files, limit in groups:
-            t0 = time.time()
-            rc = run_files(lib, files, limit)
-            rec[key] = verdict.get(rc, "status %d" % rc)
-            rec[key + "_s"] = round(time.time() - t0, 1)
-            print("%-32s %-7s %-9s %6.1f s" % (name, key, rec[key], rec[key + "_s"]), flush=True)
-            if rc not in (0, 1):
-                rows.append(rec)
-                write(args, rows)
-                sys.exit("mutant %s: exit status %d from %s -- stopping" % (name, rc, " ".join(files)))
-        rows.append(rec)
-    write(args, rows)
-
-
-def write(args, rows):
-    if args.json:
-        with open(args.json, "w") as f:
-            json.dump(rows, f, indent=1)
-    if not args.out:
-        return
-    live = [r for r in rows if not r["equivalent"]]
-    with open(args.out, "w") as f:
-        f.write("Mutants of the projecting matchers' gates (tests/tools/matcher_gate_mutants.py), one library per mutant,\n"
-                "one fresh pytest process per mutant and file group on an MI355X.\n"
-                "  new    = tests/test_gpu_matcher_gates.py\n"
-                "  parent = %s\n" % ", ".join(os.path.basename(p) for p in PARENT))
-        f.write("noticed = the files failed on the mutant; survived = they passed.\n\n")
-        f.write("%-30s %-10s %-10s  change\n" % ("mutant", "parent", "new"))
-        for r in rows:
-            f.write("%-30s %-10s %-10s  " % (r["name"], r.get("parent", "-"), r["new"] + ("*" if r["equivalent"] else "")))
-            f.write("; ".join("%s: %s -> %s" % (fn, " ".join(o.split())[-60:], " ".join(n.split())[-60:]) for fn, o, n in r["edits"]))
-            f.write("\n")
-        f.write("\n* equivalent mutants, not counted:\n")
-        for r in rows:
-            if r["equivalent"]:
-                f.write("  %s: %s\n" % (r["name"], r["equivalent"]))
-        f.write("\ncounted mutants: %d; noticed by the new module: %d; noticed by the parent's files: %s\n" % (
-            len(live), sum(r["new"] == "noticed" for r in live),
-            sum(r.get("parent") == "noticed" for r in live) if any("parent" in r for r in live) else "not run"))
-
-
-def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("what", choices=["build", "run", "list"])
-    ap.add_argument("--libs", default=None, help="directory of the mutant libraries")
-    ap.add_argument("--jobs", default=16)
-    ap.add_argument("--only", nargs="*")
-    ap.add_argument("--parent", action="store_true", help="also run the files that owned these gates before")
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--json", default=None)
-    ap.add_argument("--resume", action="store_true", help="skip the mutants --json already lists")
-    ap.add_argument("--limit", type=int, default=0, help="run at most this many mutants in this call")
-    args = ap.parse_args()
-    if args.what == "list":
-        for name, edits, eq in MUTANTS:
-            print(name, "(equivalent)" if eq else "")
-        return
-    if not args.libs:
-        sys.exit("--libs DIR is required")
-    build(args) if args.what == "build" else run(args)
-
+SPEC = mutant_driver.Spec(MUTANTS, NEW, PARENT, "Mutants of the projecting matchers' gates (tests/tools/matcher_gate_mutants.py)",
+                          "gate_mutants_", 300, 900)
 
 if __name__ == "__main__":
-    main()
+    mutant_driver.main(SPEC, __doc__)
